@@ -15,7 +15,11 @@ value  : algorithmic bytes (12 nnz + 4 (n+1) + 16 n per iteration, 
          ranks' blocks) x iterations / max-over-ranks wall time of the K timed iterations; inputs
          resident in HBM.
 
-Run: python bench.py [--gpus N --steps K --warmup W].  N>1 runs one rank per GPU: either launched
+Run: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full].  A plain run sets
+up, warms up, times the K steps and prints the line; --dump-outputs DIR then also writes what the
+timed steps computed as DIR/<name>.npy (same arguments: same inputs, so two builds compare output
+for output); --full adds the measured HBM ceilings, the extras and the CPU baselines to the line
+(N = 1; --no-extras / --no-cpu-baseline drop either again).  N>1 runs one rank per GPU: either launched
 by torch.distributed.run (WORLD_SIZE set), or, when started directly, bench.py starts the N ranks
 itself as a child torch.distributed.run over 127.0.0.1 before importing torch and relays rank 0's
 line and exit code.
@@ -54,10 +58,20 @@ def parse():
     p.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                    help="strong: one global matrix split over the ranks (BASELINE config 4); "
                         "weak: a full-size block per rank")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline run, also measure what the line reports beside it: the STREAM-like "
+                        "HBM ceilings, the extras (configs 1, 2, 3, 5, other precisions and sizes) and the CPU "
+                        "baselines (N = 1 only).  Off by default: a plain run sets up, warms up, times the steps "
+                        "and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what they computed (eigenvalue estimate, iteration count, "
+                        "iterate) as DIR/<name>.npy in float64; an iterate above the size cap is written as a "
+                        "fixed seeded sample of its entries")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
     p.add_argument("--no-extras", action="store_true",
-                   help="skip configs 2 (QR 4096^2), 3 (1M x 16 CSR) and 5 (shifted inverse, 1M complex)")
+                   help="with --full: skip configs 2 (QR 4096^2), 3 (1M x 16 CSR) and 5 (shifted inverse, "
+                        "1M complex)")
     p.add_argument("--check", action="store_true",
                    help="after the timed region, run the power method to convergence (tol 1e-12, at most 300 "
                         "iterations) on the same sharded matrix and report lambda / iterations in the line")
@@ -681,6 +695,28 @@ def run_config5_general(E, S, ctx, torch, stream):
     return out
 
 
+DUMP_MAX_ENTRIES = 4_000_000   # float64 entries of the iterate over all ranks (32 MB of the 64 MB cap)
+DUMP_SEED = 20251226
+
+
+def dump_outputs(path, res, rank, world):
+    """--dump-outputs: what a caller of the timed path receives after its last step (the session's
+    finish(): Rayleigh-quotient estimate, iteration count, normalised iterate), as float64 .npy
+    files.  Every rank writes its own row block of the iterate (eigenvector.npy at N = 1, else
+    eigenvector_rank<r>.npy); a block above its share of DUMP_MAX_ENTRIES is written as the entries
+    at a sorted index sample drawn from default_rng([DUMP_SEED, rank]), the same from run to run."""
+    os.makedirs(path, exist_ok=True)
+    x = np.asarray(res.eigenvector, dtype=np.float64)
+    cap = max(1, DUMP_MAX_ENTRIES // world)
+    if x.size > cap:
+        idx = np.sort(np.random.default_rng([DUMP_SEED, rank]).choice(x.size, size=cap, replace=False))
+        x = x[idx]
+    np.save(os.path.join(path, "eigenvector.npy" if world == 1 else f"eigenvector_rank{rank}.npy"), x)
+    if rank == 0:
+        np.save(os.path.join(path, "eigenvalue.npy"), np.array([float(res.eigenvalue)], dtype=np.float64))
+        np.save(os.path.join(path, "iterations.npy"), np.array([float(res.iterations)], dtype=np.float64))
+
+
 def launcher_cmd(argv, n, port, python=None):
     """The child command that starts N ranks of this script, one per GPU of this node (the
     contract's own form: torch.distributed.run over 127.0.0.1, arguments forwarded unchanged)."""
@@ -782,9 +818,14 @@ def main():
     x0 = S.start_vector(rows, np.float64, row0=row0)
     transport = sess.transport()
     opts = E.SolverOptions(2**31 - 1, -1.0)   # tol < 0: the reference loop never stops early
+    # --dump-outputs: finish() hands out results only once the reference loop has ended, so its
+    # iteration budget is set to end with the last timed launch: reference iteration k completes
+    # with launch k + 1 (its second product is the next iteration's first), so W + K launches are
+    # W + K - 1 iterations; the launches themselves are the same, and the one after them only decides
+    head_opts = E.SolverOptions(max(1, args.warmup + args.steps - 1), -1.0) if args.dump_outputs else opts
 
     def warm(s):
-        s.begin(opts, x0)
+        s.begin(head_opts, x0)
         s.step(args.warmup)
         torch.cuda.synchronize()
         s.query()   # raises on a peer-wait fault (bounded waits: every rank gets here)
@@ -842,6 +883,17 @@ def main():
     if world > 1:
         transports = [None] * world
         dist.all_gather_object(transports, transport_names[transport])
+    if args.dump_outputs:
+        # untimed: the state the timed steps left (every rank downloads its own row block); one more
+        # launch sees the budget used up and ends the loop without iterating (a run of fewer than
+        # two launches in all is topped up to the one iteration a result needs)
+        for _ in range(3):
+            sess.step(1)
+            if sess.query()[0]:
+                break
+        else:
+            raise SystemExit("--dump-outputs: the loop did not end after the timed steps")
+        dump_outputs(args.dump_outputs, sess.finish(), rank, world)
     check = None
     if args.check:
         # untimed: the same session run to convergence (every rank takes part: the exchange is per
@@ -941,7 +993,7 @@ def main():
                 "kind": {0: "none (one GPU)", 1: "RCCL communicator", 2: "loopback", 3: "host all-gather + peer inboxes"}[ck.value],
                 "note": "from eigsol_ctx_info: the ranks the library itself exchanges with (no 8-GPU run of "
                         "this line has been recorded by the builder; the driver's SCALE record is the measurement)"}
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         out["roofline"]["measured_hbm"] = measured_hbm(torch, torch_stream, ctx)
         t = out["roofline"].get("traffic")
         kr = out["roofline"]["measured_hbm"].get("kernel_read_GBps")
@@ -952,7 +1004,7 @@ def main():
             km = out["roofline"]["measured_hbm"].get("kernel_mix12_GBps")
             if km:
                 out["roofline"]["actual_over_kernel_mix12_ceiling"] = round(actual / km, 4)
-    if not args.no_extras and world == 1:
+    if args.full and not args.no_extras and world == 1:
         out["extras"] = {
             "config3_csr_1Mx16": run_config3(E, S, ctx, torch, torch_stream, opts),
             "config4_uniform10m": run_uniform10m(E, S, ctx, torch, torch_stream, opts),
@@ -971,7 +1023,7 @@ def main():
     A.close()
     ctx.close()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             mat = gen(kind, n_global, k, 0, n_global)
             out["cpu_baseline"] = cpu_baseline(kind, k, args.cpu_seconds, n_global, mat)
             out["cpu_baseline"]["host"] = host_cpu()

@@ -104,3 +104,32 @@ def test_device_map_for_shared_gpus(monkeypatch):
     import pytest
     with pytest.raises(SystemExit):
         bench.device_map(2)
+
+
+def test_dump_outputs_writes_float64_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: eigenvalue / iterations / eigenvector as float64 .npy; an iterate above the
+    cap is the entries at a sorted sample drawn from default_rng([DUMP_SEED, rank]), the same on
+    every call; a short one is written whole; rank r > 0 writes only its own block, under its
+    share of the cap."""
+    from types import SimpleNamespace
+
+    import numpy as np
+
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_ENTRIES", 1000)
+    x = np.random.default_rng(1).standard_normal(5000)
+    res = SimpleNamespace(eigenvalue=2.5, eigenvector=x, iterations=7)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), res, 0, 1)
+    assert sorted(os.listdir(tmp_path / "a")) == ["eigenvalue.npy", "eigenvector.npy", "iterations.npy"]
+    got = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["eigenvalue.npy"].tolist() == [2.5] and got["iterations.npy"].tolist() == [7.0]
+    idx = np.sort(np.random.default_rng([bench.DUMP_SEED, 0]).choice(5000, size=1000, replace=False))
+    assert np.array_equal(got["eigenvector.npy"], x[idx])
+    assert all(np.array_equal(got[f], np.load(tmp_path / "b" / f)) for f in got)
+    bench.dump_outputs(str(tmp_path / "c"), SimpleNamespace(eigenvalue=1.0, eigenvector=x[:10], iterations=1), 0, 1)
+    assert np.array_equal(np.load(tmp_path / "c" / "eigenvector.npy"), x[:10])
+    bench.dump_outputs(str(tmp_path / "r"), res, 1, 2)
+    assert os.listdir(tmp_path / "r") == ["eigenvector_rank1.npy"]
+    assert np.load(tmp_path / "r" / "eigenvector_rank1.npy").shape == (500,)

@@ -99,3 +99,33 @@ def test_bench_rccl_bootstrap_failure_falls_back_to_host():
     assert d["config"]["bootstrap"] == "host (RCCL bootstrap failed)"
     assert d["config"]["communicator"]["transport_per_rank"] == ["peer", "peer"]
     assert d["value"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_timed_state(tmp_path):
+    """A plain run prints the headline line only (HBM probes, extras and CPU baselines are --full's),
+    and --dump-outputs writes the state its W + K launches left: W + K - 1 reference iterations
+    (iteration k completes with launch k + 1), within the file's parity bound of the unsharded
+    reference loop stopped after as many iterations (tol < 0)."""
+    import numpy as np
+    steps, warm = 4, 2
+    out = tmp_path / "dump"
+    r, _ = _bench(["--workload", "band1m", "--steps", str(steps), "--warmup", str(warm), "--dump-outputs", str(out)],
+                  "0")
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [s for s in r.stdout.splitlines() if s.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["warmup"] == warm and d["ms_per_step"] > 0 and d["value"] > 0
+    assert "extras" not in d and "cpu_allcores" not in d and d["cpu_baseline"] is None
+    assert "measured_hbm" not in d["roofline"]
+    assert sorted(os.listdir(out)) == ["eigenvalue.npy", "eigenvector.npy", "iterations.npy"]
+    lam, x, it = (np.load(out / f) for f in ("eigenvalue.npy", "eigenvector.npy", "iterations.npy"))
+    assert lam.dtype == x.dtype == it.dtype == np.float64
+    n = 1_000_000
+    assert x.shape == (n,) and it.tolist() == [steps + warm - 1]
+    rp, ci, v = S.band(n, 16)
+    cp, ri, vv = O.csr_to_csc(rp, ci, v, n)
+    ref = O.power_csc(cp, ri, vv, S.start_vector(n), steps + warm - 1, -1.0)
+    assert ref["iterations"] == steps + warm - 1 and not ref["converged"]
+    assert abs(lam[0] - ref["eigenvalue"]) <= 1e-10 * (1 + abs(ref["eigenvalue"]))
+    assert abs(abs(np.vdot(x, ref["eigenvector"])) - 1) <= 1e-10

@@ -10,7 +10,7 @@ mkdir -p $OUT
 part=${1:-a}
 if [ "$part" = a ]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > $OUT/gputest.log 2>&1 || { echo "gpu tests failed"; exit 1; }
-  timeout -k 10 400 python -u bench.py > $OUT/bench.log 2>&1 || { echo "bench failed"; exit 1; }
+  timeout -k 10 400 python -u bench.py --full > $OUT/bench.log 2>&1 || { echo "bench failed"; exit 1; }
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/headline -o run -- python3 $R/bench.py --no-extras --no-cpu-baseline > $OUT/headline.log 2>&1 || { echo "headline profile failed"; exit 1; }
   echo "part a ok"
