@@ -188,7 +188,10 @@ int eigsol_power_kernel_name(eigsol_power* s, char* buf, size_t capacity);
  *               (tiles = refinement steps of the last solve, bytes = all of its passes);
  *          18 = shifted inverse, general sparse: GMRES preconditioned by the exact sparse LU of
  *               A - sigma I (symbolic fill without pivoting, used when the filled pattern holds at most
- *               EIGSOL_LU_FILL_CAP x nnz entries; tiles and bytes as for 7) */
+ *               EIGSOL_LU_FILL_CAP x nnz entries; tiles and bytes as for 7);
+ *          20 = shifted inverse, dense LU substitution by triangles: chosen at set-up instead of 4's
+ *               products with inverted 64 x 64 diagonal blocks when a block of L or U is ill
+ *               conditioned (Skeel condition number above 1e6), or by EIGSOL_DENSE_TRSV=1 */
 
 /* ---------------------------------------------------------------- shifted inverse iteration
  * shiftedInversePowerMethod<S>(M, ShiftedSolverOptions<S>{sigma, maxIter, tol})

@@ -386,7 +386,10 @@ class PowerSession:
                  18: "GMRES over the exact sparse LU (complete fill, no pivoting; tiles = Arnoldi "
                      "steps of the last solve)",
                  19: "GMRES over the nested-dissection multifrontal LU (dense fronts, pivoting inside each "
-                     "front; tiles = Arnoldi steps of the last solve)"}
+                     "front; tiles = Arnoldi steps of the last solve)",
+                 20: "dense LU substitution by triangles (dense_trsv_kernel: 64-row block rows, 64-step "
+                     "triangles, epoch flags; chosen for a factor whose diagonal blocks are too ill "
+                     "conditioned for products with their inverses, or by EIGSOL_DENSE_TRSV=1)"}
         return {"bytes_per_iteration": b.value, "grid": g.value, "tiles": t.value,
                 "variant": v.value, "kernel": names.get(v.value, "?"),
                 "iterations_per_launch": v.value - 10 if 12 <= v.value <= 14 else 1}

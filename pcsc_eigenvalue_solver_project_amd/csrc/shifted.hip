@@ -134,7 +134,8 @@ struct ShiftFactor {
     void* zf = nullptr;
     void* tinv = nullptr;         // [nblk][2] inverted diagonal blocks inv(L_kk), inv(U_kk), 64 x 64 column-major
     void* tmul = nullptr;         // [nblk][2] premultiplied next-to-diagonal tiles (dense_tmul_kernel)
-    int dense_v = 2;              // substitution kernel: 2 = dense_trsv2_kernel, 1 = dense_trsv_kernel (EIGSOL_DENSE_TRSV=1)
+    int dense_v = 2;              // substitution kernel: 2 = dense_trsv2_kernel, 1 = dense_trsv_kernel (ill-conditioned
+                                  // diagonal blocks, or EIGSOL_DENSE_TRSV=1; see dense_lu_factor)
 };
 
 namespace dev {
@@ -1594,6 +1595,39 @@ __global__ __launch_bounds__(256) void dense_tinv_kernel(const S* lu, int64_t n,
     for (int t = 0; t < 16; ++t) out[(16 * wv + t) * kDB + lane] = v[t];
 }
 
+// Skeel condition number || |inv(T)| |T| ||_inf of every inverted diagonal block (T = L_kk with its unit
+// diagonal, or U_kk; the identity past a partial last block), from dense_tinv_kernel's output: a product
+// with inv(T) has a backward error of that many roundoffs where the substitution with T has one, so
+// dense_lu_factor keeps dense_trsv2_kernel only while the largest stays small.  One wave per block and
+// triangle, lane = row; a NaN (singular block) is kept as the result.
+template <class S>
+__global__ __launch_bounds__(64) void dense_tcond_kernel(const S* lu, const S* tinv, int64_t n, double* cond) {
+    __shared__ double w[kDB];
+    const int k = blockIdx.x, upper = blockIdx.y, lane = threadIdx.x;
+    const int64_t r0 = (int64_t)k * kDB;
+    const int rn = (int)min<int64_t>(kDB, n - r0);
+    double s = 1.0;   // row sum of |T|: the unit diagonal of L_kk, or the identity's row
+    if (lane < rn) {
+        if (upper) s = 0.0;
+        const int j0 = upper ? lane : 0, j1 = upper ? rn : lane;
+        for (int j = j0; j < j1; ++j) s += score(lu[(r0 + lane) + (r0 + j) * n]);
+    }
+    w[lane] = s;
+    __syncthreads();
+    const S* ti = tinv + (int64_t)(2 * k + upper) * kDB * kDB;
+    double c = 0.0;
+    for (int j = 0; j < kDB; ++j) c += score(ti[lane + j * kDB]) * w[j];
+    __syncthreads();
+    w[lane] = c;
+    __syncthreads();
+    if (lane == 0) {
+        double m = 0.0;
+        for (int i = 0; i < kDB; ++i)
+            if (w[i] > m || w[i] != w[i]) m = w[i];   // once NaN, m stays NaN
+        cond[2 * k + upper] = m;
+    }
+}
+
 // The premultiplied next-to-diagonal tiles of dense_trsv2_kernel's dense_pf 2: tmul + 4096 (2 r) =
 // inv(L_rr) L_{r,r-1} (r >= 1), tmul + 4096 (2 r + 1) = inv(U_rr) U_{r,r+1} (r <= nblk - 2), 64 x 64
 // column-major, rows past a partial last block and columns past a partial next block zero.  Thread =
@@ -2249,6 +2283,12 @@ static int64_t kDenseSingleMax() {
     return 64;
 }
 
+// Largest Skeel condition number || |inv(T)| |T| ||_inf of a 64 x 64 diagonal block of L or U for which
+// the factor keeps dense_trsv2_kernel: Gaussian, A / sqrt(n) + diag and planted-spectrum
+// factors up to n = 16384 measure <= 9.4e2 in all four scalar types, the adversarial factors of
+// tests/test_gpu_dense_lu_edges.py >= 5e8.
+constexpr double kDenseBlockCondMax = 1e6;
+
 template <class S>
 static int dense_lu_factor(ShiftFactor* f, bool from_sparse) {
     hipStream_t st = f->ctx->stream;
@@ -2319,19 +2359,47 @@ static int dense_lu_factor(ShiftFactor* f, bool from_sparse) {
         EIGSOL_HIP(hipMemsetAsync(f->flag_b, 0, sizeof(int32_t) * nblk, st));
         EIGSOL_HIP(hipMemsetAsync(f->work, 0, 64, st));
         EIGSOL_HIP(hipMemsetAsync(f->err, 0, 64, st));
-        // EIGSOL_DENSE_TRSV=1: round 5's substitution (64-step triangles on one wave, 32 workgroups)
+        // dense_trsv2_kernel applies the diagonal blocks as products with their inverses, which is backward
+        // stable only while the blocks are well conditioned (partial pivoting bounds |l_ij| <= 1, not
+        // inv(L_kk): entries near -1 give an inverse near 2^62).  So the blocks' Skeel condition numbers are
+        // measured once here, and a factor with one above kDenseBlockCondMax (or singular: NaN) is solved by
+        // the triangle substitution dense_trsv_kernel (64-step triangles on one wave, 32 workgroups), which
+        // is backward stable whatever L and U hold, like PartialPivLU::solve.  EIGSOL_DENSE_TRSV=1 / 2 force
+        // dense_trsv_kernel / dense_trsv2_kernel (A/B).
         const char* dv = std::getenv("EIGSOL_DENSE_TRSV");
-        f->dense_v = (dv && std::atoi(dv) == 1) ? 1 : 2;
+        const int forced = dv ? std::atoi(dv) : 0;
+        f->dense_v = forced == 1 ? 1 : 2;
+        if (f->dense_v == 2) {
+            EIGSOL_HIP(hipMalloc(&f->tinv, sizeof(S) * (size_t)nblk * 2 * dev::kDB * dev::kDB));
+            hipLaunchKernelGGL((dev::dense_tinv_kernel<S>), dim3(nblk, 2), dim3(256), 0, st, static_cast<const S*>(f->lu),
+                               n, static_cast<S*>(f->tinv));
+            EIGSOL_HIP(hipGetLastError());
+        }
+        if (f->dense_v == 2 && forced != 2) {
+            double* dcond = nullptr;
+            EIGSOL_HIP(hipMalloc(&dcond, sizeof(double) * 2 * nblk));
+            hipLaunchKernelGGL((dev::dense_tcond_kernel<S>), dim3(nblk, 2), dim3(64), 0, st, static_cast<const S*>(f->lu),
+                               static_cast<const S*>(f->tinv), n, dcond);
+            std::vector<double> hc(2 * (size_t)nblk);
+            const hipError_t ce = hipMemcpyAsync(hc.data(), dcond, sizeof(double) * hc.size(), hipMemcpyDeviceToHost, st);
+            const hipError_t se = hipStreamSynchronize(st);
+            hipFree(dcond);
+            EIGSOL_HIP(ce);
+            EIGSOL_HIP(se);
+            bool ok = true;
+            for (double c : hc) ok = ok && c <= kDenseBlockCondMax;   // false for a NaN
+            if (!ok) {
+                f->dense_v = 1;
+                hipFree(f->tinv);
+                f->tinv = nullptr;
+            }
+        }
         if (f->dense_v == 2) {
             // value buffers [z | z' | y | y'] (dense_trsv2_kernel), all unsolved
             hipFree(f->zf);
             f->zf = nullptr;
             EIGSOL_HIP(hipMalloc(&f->zf, sizeof(S) * 4 * n));
             EIGSOL_HIP(hipMemsetD32Async(static_cast<hipDeviceptr_t>(f->zf), 0x7FF4DEADu, sizeof(S) * n, st));
-            EIGSOL_HIP(hipMalloc(&f->tinv, sizeof(S) * (size_t)nblk * 2 * dev::kDB * dev::kDB));
-            hipLaunchKernelGGL((dev::dense_tinv_kernel<S>), dim3(nblk, 2), dim3(256), 0, st, static_cast<const S*>(f->lu),
-                               n, static_cast<S*>(f->tinv));
-            EIGSOL_HIP(hipGetLastError());
             EIGSOL_HIP(hipMalloc(&f->tmul, sizeof(S) * (size_t)nblk * 2 * dev::kDB * dev::kDB));
             hipLaunchKernelGGL((dev::dense_tmul_kernel<S>), dim3(nblk, 2), dim3(256), 0, st, static_cast<const S*>(f->lu),
                                static_cast<const S*>(f->tinv), n, nblk, static_cast<S*>(f->tmul));
@@ -3836,7 +3904,7 @@ void shift_info(const ShiftFactor* f, double* bytes, int32_t* variant, int32_t* 
         if (tiles) *tiles = f->nlevels;
     } else {
         if (bytes) *bytes = sb * n * n + 2.0 * sb * n;
-        if (variant) *variant = 4;
+        if (variant) *variant = (f->dense_multi && f->dense_v == 1) ? 20 : 4;   // 20: dense_trsv_kernel
         if (tiles) *tiles = 0;
     }
 }

@@ -335,6 +335,12 @@ def test_dense_trsv2_matches_round5_substitution(ctx, dtype, grid, monkeypatch):
     if grid:
         monkeypatch.setenv("EIGSOL_DENSE_TRSV_GRID", grid)
     x2 = E.solve_shifted(E.DenseMatrix(ctx, A), sigma, b)
+    if not grid:
+        # well-conditioned diagonal blocks: the factor keeps dense_trsv2_kernel (kernel_info variant 4; 20 is
+        # dense_trsv_kernel, chosen at set-up for ill-conditioned blocks - tests/test_gpu_dense_lu_edges.py)
+        sess = E.ShiftedSession(E.DenseMatrix(ctx, A), sigma)
+        assert sess.kernel_info()["variant"] == 4
+        sess.close()
     monkeypatch.setenv("EIGSOL_DENSE_TRSV", "1")
     x1 = E.solve_shifted(E.DenseMatrix(ctx, A), sigma, b)
     M = A - sigma * np.eye(n)
