@@ -249,6 +249,14 @@ int eigsol_solve_shifted_dense(eigsol_dense* A, const void* sigma, const void* b
  *     matrix, then every eigenvalue refined in double-double by Newton's method on det(H - mu I)
  *     (Hyman's recurrence, n <= 8192); eig_re_or_c receives n dd (real parts) / n cdd values, and
  *     for EIGSOL_DD eig_im (optional) the imaginary parts as n {hi, lo} pairs (2n doubles).
+ *     fp64 eigenvalues within 1e-8 (1 + |lambda|) of each other are refined as a group, each
+ *     Newton step deflated against the group's values already refined (so a cluster far tighter
+ *     than the fp64 error still yields one value per eigenvalue), at most 16 steps each.  A value
+ *     is refined when a step reached 2^-104 |mu| or the contraction of the steps shows the next
+ *     one there.  It is NOT refined when it ran out of steps (the last iterate is returned), when
+ *     the refinement moved it by more than 1e-8 (1 + |lambda|) or no step was usable (the fp64
+ *     value is returned), or when it ended on another value's root (the later one gets its fp64
+ *     value back): `converged` does not report these, eigsol_qr_refine_info does.
  * n == 0: iterations 0, converged 1 (qr_eigenvalues.hpp:55-57). */
 #define EIGSOL_QR_FRANCIS 0
 #define EIGSOL_QR_UNSHIFTED 1
@@ -260,6 +268,18 @@ int eigsol_qr_eigenvalues_dense(eigsol_ctx* ctx, int dtype, int64_t n, const voi
                                 const eigsol_solver_options* opts, int variant,
                                 void* eig_re_or_c, double* eig_im, int32_t* iterations,
                                 int32_t* converged);
+/* The refinement of the context's last EIGSOL_DD / EIGSOL_CDD Francis call: how many of its
+ * eigenvalues are not refined to the double-double floor (rules above; 0 before any such call) and
+ * the most Newton steps one took.  Either pointer may be null. */
+int eigsol_qr_refine_info(eigsol_ctx* ctx, int64_t* unrefined, int32_t* max_newton_steps);
+/* Diagnostic: that refinement alone.  H_colmajor: a host upper-Hessenberg matrix of order n <= 8192
+ * in the dtype's wire format (EIGSOL_DD / EIGSOL_CDD; entries below the subdiagonal are not
+ * read); starts: `count` values as cdd (4 doubles each: re.hi, re.lo, im.hi, im.lo).  Runs what the
+ * Francis variant runs on its fp64 eigenvalues: the same kernel instance for n, grouping,
+ * deflation, discard and collision rules.  refined: `count` cdd values; steps: per value the
+ * Newton steps taken, or -1 when it is not refined. */
+int eigsol_hyman_refine(eigsol_ctx* ctx, int dtype, int64_t n, const void* H_colmajor, int64_t count,
+                        const double* starts, double* refined, int32_t* steps);
 
 /* ---------------------------------------------------------------- row-sharded power iteration
  * One process per GPU; RCCL over xGMI (the reference has no distribution: SURVEY.md §2.1).

@@ -495,12 +495,15 @@ def solve_shifted(matrix, shift, b) -> np.ndarray:
 class QRResult:
     """``EigSol::QRResult<S>`` (src/result/qr_result.hpp:25-43).  For the Francis variant on a
     real matrix, ``eigenvalues`` holds the real parts (the diagonal of the standardised real Schur
-    form) and ``eigenvalues_complex`` the full complex eigenvalues."""
+    form) and ``eigenvalues_complex`` the full complex eigenvalues.  ``unrefined`` (long double
+    Francis only, else 0) counts the eigenvalues the double-double refinement did not bring to its
+    floor (``eigsol_qr_refine_info``): those are fp64-grade, whatever ``converged`` says."""
 
     eigenvalues: np.ndarray
     iterations: int
     converged: bool
     eigenvalues_complex: Optional[np.ndarray] = None
+    unrefined: int = 0
 
 
 def _square_dense(A, who: str) -> np.ndarray:
@@ -566,7 +569,10 @@ def qr_eigenvalues(ctx: Context, A, opts: SolverOptions = SolverOptions(), varia
             full = ev.astype(np.clongdouble)
             if eim is not None:
                 full = full + np.clongdouble(1j) * from_wire(eim, np.longdouble)[:n]
-        return QRResult(ev, int(it.value), bool(conv.value), full)
+        unref = C.c_int64(0)
+        if v == 0 and n:
+            call("eigsol_qr_refine_info", ctx.handle, C.byref(unref), None)
+        return QRResult(ev, int(it.value), bool(conv.value), full, int(unref.value))
     if v == 0 and A.dtype in (np.float32, np.complex64):
         # single precision: the multishift sweeps are double kernels (as in the C++ facade, the
         # matrix is promoted and the eigenvalues rounded back); "unshifted" runs natively in float
@@ -588,3 +594,30 @@ def qr_eigenvalues(ctx: Context, A, opts: SolverOptions = SolverOptions(), varia
     elif v == 0 and A.dtype == np.complex128:
         full = eig.copy()
     return QRResult(eig, int(it.value), bool(conv.value), full)
+
+
+def hyman_refine(ctx: Context, H, starts):
+    """Diagnostic (``eigsol_hyman_refine``): the long double Francis variant's refinement alone, on
+    the upper-Hessenberg long double / complex long double matrix ``H`` from the values ``starts``.
+    A float64 / complex128 ``H`` is taken as the long double matrix of the same values (low parts
+    zero).  Returns (refined values as clongdouble, Newton steps per value with -1 = not refined)."""
+    H = _square_dense(H, "hyman_refine")
+    n = H.shape[0]
+    if is_wide(H.dtype):
+        code, Hw = _dtype_code(H.dtype), to_wire(H.ravel(order="F"), H.dtype)
+    elif H.dtype in (np.float64, np.complex128):
+        cx = H.dtype == np.complex128
+        code = EIGSOL_CDD if cx else EIGSOL_DD
+        Hw = np.zeros((n * n, 4 if cx else 2))
+        Hw[:, 0] = H.real.ravel(order="F")
+        if cx:
+            Hw[:, 2] = H.imag.ravel(order="F")
+    else:
+        raise EigSolError(3, "hyman_refine: H must be (complex) long double or double")
+    st = np.ascontiguousarray(starts, dtype=np.clongdouble).reshape(-1)
+    cnt = len(st)
+    out = wire_buffer(np.clongdouble, max(cnt, 1))
+    steps = np.zeros(max(cnt, 1), dtype=np.int32)
+    call("eigsol_hyman_refine", ctx.handle, code, n, _ptr(Hw), cnt, _ptr(to_wire(st, np.clongdouble)), _ptr(out),
+         _ptr(steps))
+    return from_wire(out, np.clongdouble)[:cnt], steps[:cnt]

@@ -233,6 +233,9 @@ struct eigsol_ctx {
     void* hcoll_user = nullptr;
     int rank = 0;
     int nranks = 1;
+    // the last long double Francis call's refinement (eigsol_qr_refine_info)
+    int64_t wide_unrefined = 0;
+    int32_t wide_newton_max = 0;
 };
 
 struct eigsol_csr {

@@ -739,6 +739,8 @@ int wide_hessenberg(eigsol_ctx* ctx, int dtype, int64_t n, const void* A, void* 
 int wide_qr_decompose(eigsol_ctx* ctx, int dtype, int64_t m, int64_t n, const void* A, void* Q, void* R);
 int wide_qr_eigenvalues(eigsol_ctx* ctx, int dtype, int64_t n, const void* A, const eigsol_solver_options* opts,
                         int variant, void* eig, double* eig_im, int32_t* iters, int32_t* conv);
+int wide_hyman_refine(eigsol_ctx* ctx, int dtype, int64_t n, const void* H, int64_t count, const double* starts,
+                      double* refined, int32_t* steps);
 
 }  // namespace eigsol
 
@@ -815,6 +817,22 @@ int eigsol_qr_eigenvalues_dense(eigsol_ctx* ctx, int dtype, int64_t n, const voi
                                    static_cast<double*>(eig_re_or_c), wi.data(), iterations, converged);
     if (rc == EIGSOL_OK && eig_im) std::memcpy(eig_im, wi.data(), n * sizeof(double));
     return rc;
+}
+
+int eigsol_qr_refine_info(eigsol_ctx* ctx, int64_t* unrefined, int32_t* max_newton_steps) {
+    if (!ctx) return fail(EIGSOL_E_INVALID, "eigsol_qr_refine_info: null ctx");
+    if (unrefined) *unrefined = ctx->wide_unrefined;
+    if (max_newton_steps) *max_newton_steps = ctx->wide_newton_max;
+    return EIGSOL_OK;
+}
+
+int eigsol_hyman_refine(eigsol_ctx* ctx, int dtype, int64_t n, const void* H_colmajor, int64_t count,
+                        const double* starts, double* refined, int32_t* steps) {
+    if (!ctx || n <= 0 || count < 0 || !H_colmajor || (count && (!starts || !refined || !steps)))
+        return fail(EIGSOL_E_INVALID, "eigsol_hyman_refine: bad arguments");
+    if (!dtype_wide(dtype)) return fail(EIGSOL_E_INVALID, "eigsol_hyman_refine: dtype must be EIGSOL_DD or EIGSOL_CDD");
+    EIGSOL_HIP(hipSetDevice(ctx->device));
+    return wide_hyman_refine(ctx, dtype, n, H_colmajor, count, starts, refined, steps);
 }
 
 }  // extern "C"

@@ -1207,8 +1207,26 @@ int wqr_unshifted_host(eigsol_ctx* ctx, int64_t n, const void* A, int max_iter, 
 // Exact zeros on the subdiagonal split H into blocks; each block has its own recurrence and the
 // eigenvalue is refined on the block whose Newton step from the fp64 value is the smallest.  x and
 // its derivative are rescaled by powers of two when they leave [2^-300, 2^300] (the ratio c / c'
-// is scale-invariant).  A refinement that moves the eigenvalue by more than 1e-8 (1 + |lambda|)
-// (a Newton step that left the fp64 eigenvalue's basin) is discarded and the fp64 value kept.
+// is scale-invariant).
+//
+// Clusters.  Starts within 1e-8 (1 + |lambda|) of each other (chained) form a group, refined by
+// one workgroup member after member; a member's step is deflated against the members already
+// refined on the same diagonal block (Maehly): delta = c / (c' - c sum_j 1 / (mu - mu_j)), so two
+// starts nearest the same root end on different roots and Newton stays quadratic inside a cluster
+// whose gap is far below the fp64 error.  A well-separated eigenvalue is a group of one and costs
+// what it did without the grouping.  Groups of more than kHyMaxGroup starts (a long run of equal
+// eigenvalues, e.g. a multiple of the identity) are not deflated: their members run alone.
+//
+// Exit.  Newton stops, and the value counts as refined, after a step |delta_k| <= 2^-104 |mu|, or
+// when the steps contract and the next one predicted from them, |delta_k| (|delta_k| /
+// |delta_k-1|)^2 (quadratic convergence with the constant the last two steps show), is below that
+// floor: the iterate is then at the floor and the confirming pass is not run.  At most
+// kHyMaxNewton steps (a double root's linear phase from an fp64 start takes about ten).  A value
+// is NOT refined, and reported so (steps < 0), when it ran out of steps without meeting that rule
+// (its last iterate is still returned), when no block gave a usable step, when the refinement
+// moved it by more than 1e-8 (1 + |lambda|) (it left the fp64 eigenvalue's basin: the fp64 value
+// is kept), or when after all that it coincides (to 2^-96) with another value refined on the same
+// block: the later one keeps its fp64 start, so the results stay one-to-one with the starts.
 namespace wqdev {
 
 template <class T> __device__ __forceinline__ cdd as_cdd(const T& a);
@@ -1217,131 +1235,167 @@ template <> __device__ __forceinline__ cdd as_cdd<cdd>(const cdd& a) { return a;
 
 __device__ __forceinline__ double cdd_maxhi(const cdd& a) { return fmax(fabs(a.re.hi), fabs(a.im.hi)); }
 
-constexpr int kHyT = 1024;   // threads of the refinement (one workgroup per eigenvalue)
+constexpr int kHyT = 1024;        // threads of the refinement (one workgroup per group of starts)
+constexpr int kHyMaxNewton = 16;  // Newton steps per eigenvalue
+constexpr int kHyMaxGroup = 16;   // starts deflated against each other
 
-// One workgroup per eigenvalue; thread t owns rows t + kHyT k, k < R (n <= kHyT R).  Per column j
+// One workgroup per group (members gmem[gptr[b] .. gptr[b + 1]), indices into lam0, refined in that
+// order); thread t owns rows t + kHyT k, k < R (n <= kHyT R).  Per column j
 // (descending): every owned row i <= j adds (h(i, j) - mu [i = j]) x_j to r_i and the same with
 // x'_j (minus x_j at i = j) to r'_i; the owner of row j then forms x_{j-1} = -r_j / h(j, j-1) (and
 // x'_{j-1}), or closes the block at a zero subdiagonal.  One barrier per column, two LDS slots
-// alternating by column parity.
+// alternating by column parity.  steps_out: the Newton steps taken, or -1 - steps when the value is
+// not refined; blk_out: the upper end of the diagonal block it was refined on.
 template <class T, int R>
 __global__ __launch_bounds__(kHyT) void hyman_newton_kernel(const T* __restrict__ H, int n, const cdd* __restrict__ lam0,
-                                                            cdd* __restrict__ lam_out, int32_t* __restrict__ steps_out,
-                                                            int max_newton) {
+                                                            const int32_t* __restrict__ gptr,
+                                                            const int32_t* __restrict__ gmem, cdd* __restrict__ lam_out,
+                                                            int32_t* __restrict__ steps_out,
+                                                            int32_t* __restrict__ blk_out, int max_newton) {
     EIGSOL_EXACT
     __shared__ cdd sx[2][2];      // [parity] {x_j, x'_j}
     __shared__ int sflag[2][2];   // [parity] {reset rows < j+1 (block closed), scale exponent}
     __shared__ cdd s_delta;       // Newton step of the selected block
     __shared__ double s_best;     // |step| of the best block (first pass)
     __shared__ int s_hi, s_cur_hi, s_done, s_upd;
+    __shared__ cdd s_defl[kHyMaxGroup];   // the group's members refined so far ...
+    __shared__ int s_dblk[kHyMaxGroup];   // ... and the block each was refined on
+    __shared__ int s_ndefl;
     const int t = threadIdx.x;
     const int64_t ld = n;
     const cdd zero = cdd{dd{0.0, 0.0}, dd{0.0, 0.0}};
     const cdd one = cdd{dd{1.0, 0.0}, dd{0.0, 0.0}};
-    const cdd l0 = lam0[blockIdx.x];
-    cdd mu = l0;
-    int steps = 0;
-    if (t == 0) { s_hi = -1; s_done = 0; }
-    for (int it = 0; it < max_newton; ++it) {
-        cdd r[R], rp[R];
+    const int g0 = gptr[blockIdx.x], g1 = gptr[blockIdx.x + 1];
+    if (t == 0) s_ndefl = 0;
+    for (int gm = g0; gm < g1; ++gm) {
+        const int id = gmem[gm];
+        const cdd l0 = lam0[id];
+        cdd mu = l0;
+        int steps = 0;
+        bool refined = false;   // thread 0: the stop rule was met
+        double prev = -1.0;     // thread 0: |step| of the pass before
+        if (t == 0) { s_hi = -1; s_done = 0; }
+        for (int it = 0; it < max_newton; ++it) {
+            cdd r[R], rp[R];
 #pragma unroll
-        for (int k = 0; k < R; ++k) { r[k] = zero; rp[k] = zero; }
-        if (t == 0) {
-            sx[(n - 1) & 1][0] = one;
-            sx[(n - 1) & 1][1] = zero;
-            sflag[(n - 1) & 1][0] = 0;
-            sflag[(n - 1) & 1][1] = 0;
-            s_cur_hi = n;
-            s_best = -1.0;
-        }
-        __syncthreads();
-        for (int j = n - 1; j >= 0; --j) {
-            const int par = j & 1;
-            const cdd xj = sx[par][0], xpj = sx[par][1];
-            const int reset = sflag[par][0], esc = sflag[par][1];
-#pragma unroll
-            for (int k = 0; k < R; ++k) {
-                const int i = t + kHyT * k;
-                if (i <= j) {
-                    if (reset) { r[k] = zero; rp[k] = zero; }   // rows of the next block start afresh
-                    else if (esc) { r[k] = cdd_ldexp(r[k], esc); rp[k] = cdd_ldexp(rp[k], esc); }
-                    cdd a = as_cdd<T>(H[i + (int64_t)j * ld]);
-                    if (i == j) a = cdd_sub(a, mu);
-                    r[k] = cdd_add(r[k], cdd_mul(a, xj));
-                    rp[k] = cdd_add(rp[k], cdd_mul(a, xpj));
-                    if (i == j) rp[k] = cdd_sub(rp[k], xj);
-                }
+            for (int k = 0; k < R; ++k) { r[k] = zero; rp[k] = zero; }
+            if (t == 0) {
+                sx[(n - 1) & 1][0] = one;
+                sx[(n - 1) & 1][1] = zero;
+                sflag[(n - 1) & 1][0] = 0;
+                sflag[(n - 1) & 1][1] = 0;
+                s_cur_hi = n;
+                s_best = -1.0;
             }
-            // the owner of row j: next x, or the block [j, cur_hi) closes
-            if (t == (j % kHyT)) {
-                const int k = j / kHyT;
-                cdd rj = r[0], rpj = rp[0];
+            __syncthreads();
+            for (int j = n - 1; j >= 0; --j) {
+                const int par = j & 1;
+                const cdd xj = sx[par][0], xpj = sx[par][1];
+                const int reset = sflag[par][0], esc = sflag[par][1];
 #pragma unroll
-                for (int q = 1; q < R; ++q)
-                    if (q == k) { rj = r[q]; rpj = rp[q]; }
-                const cdd sub_h = j > 0 ? as_cdd<T>(H[j + (int64_t)(j - 1) * ld]) : zero;
-                const int np = (j - 1) & 1;
-                if (j == 0 || cdd_is_zero(sub_h)) {
-                    // block [j, cur_hi): c = r_j, c' = r'_j, Newton step c / c'
-                    const cdd d = cdd_div(rj, rpj);
-                    const double ad = cdd_maxhi(d);
-                    const bool ok = ad == ad && ad <= 1.7976931348623157e308;
-                    if (it == 0) {
-                        if (ok && (s_best < 0.0 || ad < s_best)) { s_best = ad; s_delta = d; s_hi = s_cur_hi; }
-                    } else if (s_cur_hi == s_hi) {
-                        s_delta = ok ? d : zero;
-                        s_best = ok ? ad : -1.0;
+                for (int k = 0; k < R; ++k) {
+                    const int i = t + kHyT * k;
+                    if (i <= j) {
+                        if (reset) { r[k] = zero; rp[k] = zero; }   // rows of the next block start afresh
+                        else if (esc) { r[k] = cdd_ldexp(r[k], esc); rp[k] = cdd_ldexp(rp[k], esc); }
+                        cdd a = as_cdd<T>(H[i + (int64_t)j * ld]);
+                        if (i == j) a = cdd_sub(a, mu);
+                        r[k] = cdd_add(r[k], cdd_mul(a, xj));
+                        rp[k] = cdd_add(rp[k], cdd_mul(a, xpj));
+                        if (i == j) rp[k] = cdd_sub(rp[k], xj);
                     }
-                    if (j > 0) {
-                        sx[np][0] = one;
-                        sx[np][1] = zero;
-                        sflag[np][0] = 1;
-                        sflag[np][1] = 0;
-                        s_cur_hi = j;
+                }
+                // the owner of row j: next x, or the block [j, cur_hi) closes
+                if (t == (j % kHyT)) {
+                    const int k = j / kHyT;
+                    cdd rj = r[0], rpj = rp[0];
+#pragma unroll
+                    for (int q = 1; q < R; ++q)
+                        if (q == k) { rj = r[q]; rpj = rp[q]; }
+                    const cdd sub_h = j > 0 ? as_cdd<T>(H[j + (int64_t)(j - 1) * ld]) : zero;
+                    const int np = (j - 1) & 1;
+                    if (j == 0 || cdd_is_zero(sub_h)) {
+                        // block [j, cur_hi): c = r_j, c' = r'_j, Newton step c / c', deflated against
+                        // the group's members already refined on this block
+                        cdd den = rpj;
+                        for (int q = 0; q < s_ndefl; ++q)
+                            if (s_dblk[q] == s_cur_hi) den = cdd_sub(den, cdd_mul(rj, cdd_div(one, cdd_sub(mu, s_defl[q]))));
+                        const cdd d = cdd_div(rj, den);
+                        const double ad = cdd_maxhi(d);
+                        const bool ok = ad == ad && ad <= 1.7976931348623157e308;
+                        if (it == 0) {
+                            if (ok && (s_best < 0.0 || ad < s_best)) { s_best = ad; s_delta = d; s_hi = s_cur_hi; }
+                        } else if (s_cur_hi == s_hi) {
+                            s_delta = ok ? d : zero;
+                            s_best = ok ? ad : -1.0;
+                        }
+                        if (j > 0) {
+                            sx[np][0] = one;
+                            sx[np][1] = zero;
+                            sflag[np][0] = 1;
+                            sflag[np][1] = 0;
+                            s_cur_hi = j;
+                        }
+                    } else {
+                        cdd xn = cdd_neg(cdd_div(rj, sub_h));
+                        cdd xpn = cdd_neg(cdd_div(rpj, sub_h));
+                        const double m = fmax(cdd_maxhi(xn), cdd_maxhi(xpn));
+                        int e = 0;
+                        if (m > 0x1p300 || (m > 0.0 && m < 0x1p-300)) e = -ilogb(m);
+                        if (e) { xn = cdd_ldexp(xn, e); xpn = cdd_ldexp(xpn, e); }
+                        sx[np][0] = xn;
+                        sx[np][1] = xpn;
+                        sflag[np][0] = 0;
+                        sflag[np][1] = e;
                     }
+                }
+                __syncthreads();
+            }
+            // Newton update (thread 0 decides, everyone reads mu): mu <- mu - delta of the selected
+            // block; stop after a step at the double-double floor or one that predicts the next there
+            // (refined), or without a usable step or out of steps (not refined)
+            if (t == 0) {
+                s_upd = 0;
+                if (s_best < 0.0) {
+                    s_done = 1;
                 } else {
-                    cdd xn = cdd_neg(cdd_div(rj, sub_h));
-                    cdd xpn = cdd_neg(cdd_div(rpj, sub_h));
-                    const double m = fmax(cdd_maxhi(xn), cdd_maxhi(xpn));
-                    int e = 0;
-                    if (m > 0x1p300 || (m > 0.0 && m < 0x1p-300)) e = -ilogb(m);
-                    if (e) { xn = cdd_ldexp(xn, e); xpn = cdd_ldexp(xpn, e); }
-                    sx[np][0] = xn;
-                    sx[np][1] = xpn;
-                    sflag[np][0] = 0;
-                    sflag[np][1] = e;
+                    const cdd mn = cdd_sub(mu, s_delta);
+                    ++steps;
+                    const double floor_mu = 0x1p-104 * fmax(cdd_maxhi(mn), 1e-300);
+                    refined = s_best <= floor_mu;
+                    if (!refined && prev > 0.0 && s_best <= prev) {
+                        const double q = s_best / prev;
+                        refined = s_best * q * q <= floor_mu;
+                    }
+                    prev = s_best;
+                    if (refined || it + 1 == max_newton) s_done = 1;
+                    sx[0][0] = mn;   // hand mu over through LDS (slot free until the next pass starts)
+                    s_upd = 1;
                 }
             }
             __syncthreads();
+            if (s_upd) mu = sx[0][0];
+            const int done = s_done;
+            __syncthreads();
+            if (done) break;
         }
-        // Newton update (thread 0 decides, everyone reads mu): mu <- mu - c / c' of the selected
-        // block; stop after a step at the double-double floor, or without a usable step
         if (t == 0) {
-            s_upd = 0;
-            if (s_best < 0.0) {
-                s_done = 1;
-            } else {
-                const cdd mn = cdd_sub(mu, s_delta);
-                ++steps;
-                const double am = fmax(cdd_maxhi(mn), 1e-300);
-                if (s_best <= 0x1p-104 * am || it + 1 == max_newton) s_done = 1;
-                sx[0][0] = mn;   // hand mu over through LDS (slot free until the next pass starts)
-                s_upd = 1;
+            // discard a refinement that left the fp64 eigenvalue's neighbourhood
+            const cdd dm = cdd_sub(mu, l0);
+            const double move = cdd_maxhi(dm), scale = 1.0 + cdd_maxhi(l0);
+            const bool keep = steps > 0 && move == move && move <= 1e-8 * scale;
+            lam_out[id] = keep ? mu : l0;
+            steps_out[id] = keep && refined ? steps : -1 - steps;
+            blk_out[id] = s_hi;
+            // later members step away from this one (also from an iterate that ran out of steps: it
+            // is close enough to its root to take it out of their way)
+            if (keep && gm + 1 < g1 && s_ndefl < kHyMaxGroup) {
+                s_defl[s_ndefl] = mu;
+                s_dblk[s_ndefl] = s_hi;
+                ++s_ndefl;
             }
         }
         __syncthreads();
-        if (s_upd) mu = sx[0][0];
-        const int done = s_done;
-        __syncthreads();
-        if (done) break;
-    }
-    if (t == 0) {
-        // discard a refinement that left the fp64 eigenvalue's neighbourhood
-        const cdd dm = cdd_sub(mu, l0);
-        const double move = cdd_maxhi(dm), scale = 1.0 + cdd_maxhi(l0);
-        const bool keep = move == move && move <= 1e-8 * scale;
-        lam_out[blockIdx.x] = keep ? mu : l0;
-        steps_out[blockIdx.x] = keep ? steps : -1;
     }
 }
 
@@ -1383,9 +1437,115 @@ namespace {
 constexpr int kHyMaxRows = 8;   // refinement: n <= kHyT * 8 = 8192
 
 template <class T, int R>
-static void hyman_launch(hipStream_t st, const T* H, int n, const cdd* l0, cdd* l1, int32_t* steps, int64_t count) {
-    hipLaunchKernelGGL((wqdev::hyman_newton_kernel<T, R>), dim3((unsigned)count), dim3(wqdev::kHyT), 0, st, H, n, l0,
-                       l1, steps, 4);
+static void hyman_launch(hipStream_t st, const T* H, int n, const cdd* l0, const int32_t* gptr, const int32_t* gmem,
+                         cdd* l1, int32_t* steps, int32_t* blk, int64_t groups) {
+    hipLaunchKernelGGL((wqdev::hyman_newton_kernel<T, R>), dim3((unsigned)groups), dim3(wqdev::kHyT), 0, st, H, n, l0,
+                       gptr, gmem, l1, steps, blk, wqdev::kHyMaxNewton);
+}
+
+static double cdd_dist(const cdd& a, const cdd& b) {
+    return std::fmax(std::fabs((a.re.hi - b.re.hi) + (a.re.lo - b.re.lo)),
+                     std::fabs((a.im.hi - b.im.hi) + (a.im.lo - b.im.lo)));
+}
+static double cdd_mag(const cdd& a) { return std::fmax(std::fabs(a.re.hi), std::fabs(a.im.hi)); }
+
+// Pairs (i, j) of v within rel (1 + |v_i|) of each other, found on the values sorted by real part.
+template <class F>
+static void near_pairs(const cdd* v, int64_t count, double rel, F&& visit) {
+    std::vector<int32_t> ord(count);
+    for (int64_t i = 0; i < count; ++i) ord[i] = (int32_t)i;
+    auto key = [&](int32_t i) { return v[i].re.hi == v[i].re.hi ? v[i].re.hi : HUGE_VAL; };   // NaN last
+    std::sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) { return key(a) < key(b); });
+    for (int64_t a = 0; a < count; ++a) {
+        const cdd& va = v[ord[a]];
+        const double thr = rel * (1.0 + cdd_mag(va));
+        if (!(thr == thr)) continue;
+        for (int64_t b = a + 1; b < count && v[ord[b]].re.hi - va.re.hi <= thr; ++b)
+            if (cdd_dist(va, v[ord[b]]) <= thr) visit(std::min(ord[a], ord[b]), std::max(ord[a], ord[b]));
+    }
+}
+
+// The refinement's groups: starts chained by distances <= 1e-8 (1 + |lambda|), each group's members in
+// index order; a chain of more than kHyMaxGroup starts is left as groups of one.
+static void hyman_groups(const cdd* l0, int64_t count, std::vector<int32_t>& gptr, std::vector<int32_t>& gmem) {
+    std::vector<int32_t> root(count), size(count, 1);
+    for (int64_t i = 0; i < count; ++i) root[i] = (int32_t)i;
+    auto find = [&](int32_t i) {
+        while (root[i] != i) i = root[i] = root[root[i]];
+        return i;
+    };
+    near_pairs(l0, count, 1e-8, [&](int32_t i, int32_t j) {
+        const int32_t a = find(i), b = find(j);
+        if (a == b) return;
+        root[std::max(a, b)] = std::min(a, b);   // the root is the group's lowest index
+        size[std::min(a, b)] += size[std::max(a, b)];
+    });
+    // members gathered behind their root in index order (a root precedes its members)
+    std::vector<int32_t> slot(count, -1), fill;
+    gptr.assign(1, 0);
+    gmem.assign(count, 0);
+    for (int64_t i = 0; i < count; ++i) {
+        const int32_t r = find((int32_t)i);
+        if (size[r] > wqdev::kHyMaxGroup || size[r] == 1) {
+            gmem[gptr.back()] = (int32_t)i;
+            gptr.push_back(gptr.back() + 1);
+        } else if (r == i) {
+            slot[r] = (int32_t)fill.size();
+            fill.push_back(gptr.back() + 1);
+            gmem[gptr.back()] = (int32_t)i;
+            gptr.push_back(gptr.back() + size[r]);
+        } else {
+            gmem[fill[slot[r]]++] = (int32_t)i;
+        }
+    }
+}
+
+// The shipped refinement of `count` starts l0 (host) on the device Hessenberg matrix H of order n:
+// l1 = the refined values, steps = Newton steps taken, or -1 - steps for a value that is not
+// refined (see the rules above wqdev).  The instance (rows per thread) follows n.
+template <class T>
+static int hyman_refine(hipStream_t st, const T* H, int64_t n, const cdd* l0, int64_t count, cdd* l1, int32_t* steps) {
+    if (count == 0) return EIGSOL_OK;
+    std::vector<int32_t> gptr, gmem, blk(count);
+    hyman_groups(l0, count, gptr, gmem);
+    const int64_t groups = (int64_t)gptr.size() - 1;
+    cdd *dl0 = nullptr, *dl1 = nullptr;
+    int32_t* di = nullptr;   // steps | blocks | group pointers | group members
+    int rc = EIGSOL_OK;
+    if (hipMalloc(&dl0, count * sizeof(cdd)) != hipSuccess || hipMalloc(&dl1, count * sizeof(cdd)) != hipSuccess ||
+        hipMalloc(&di, (3 * count + groups + 1) * sizeof(int32_t)) != hipSuccess)
+        rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: hipMalloc (refinement)");
+    int32_t *dsteps = di, *dblk = di + count, *dgptr = di + 2 * count, *dgmem = di + 2 * count + groups + 1;
+    if (rc == EIGSOL_OK &&
+        (hipMemcpyAsync(dl0, l0, count * sizeof(cdd), hipMemcpyHostToDevice, st) != hipSuccess ||
+         hipMemcpyAsync(dgptr, gptr.data(), (groups + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess ||
+         hipMemcpyAsync(dgmem, gmem.data(), count * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess))
+        rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: upload eigenvalues");
+    if (rc == EIGSOL_OK) {
+        const int R = (int)((n + wqdev::kHyT - 1) / wqdev::kHyT);
+        const int ni = (int)n;
+        if (R <= 1) hyman_launch<T, 1>(st, H, ni, dl0, dgptr, dgmem, dl1, dsteps, dblk, groups);
+        else if (R <= 2) hyman_launch<T, 2>(st, H, ni, dl0, dgptr, dgmem, dl1, dsteps, dblk, groups);
+        else if (R <= 4) hyman_launch<T, 4>(st, H, ni, dl0, dgptr, dgmem, dl1, dsteps, dblk, groups);
+        else hyman_launch<T, 8>(st, H, ni, dl0, dgptr, dgmem, dl1, dsteps, dblk, groups);
+        if (hipGetLastError() != hipSuccess ||
+            hipMemcpyAsync(l1, dl1, count * sizeof(cdd), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipMemcpyAsync(steps, dsteps, count * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipMemcpyAsync(blk.data(), dblk, count * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            stream_wait(st) != hipSuccess)
+            rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: double-double refinement");
+    }
+    for (void* p : {(void*)dl0, (void*)dl1, (void*)di})
+        if (p) (void)hipFree(p);
+    if (rc != EIGSOL_OK) return rc;
+    // no silent collisions: of two values that ended on the same root of the same block, the later
+    // keeps its start (a value that already kept it has nothing to give back)
+    near_pairs(l1, count, 0x1p-96, [&](int32_t i, int32_t j) {
+        if (blk[i] != blk[j] || cdd_dist(l1[j], l0[j]) == 0.0) return;
+        l1[j] = l0[j];
+        if (steps[j] >= 0) steps[j] = -1 - steps[j];
+    });
+    return EIGSOL_OK;
 }
 
 // eig: n scalars of T (DD: the real parts); eig_im (DD only, may be null): n dd imaginary parts
@@ -1398,13 +1558,10 @@ int wqr_francis_host(eigsol_ctx* ctx, int64_t n, const void* A, int max_iter, vo
     hipStream_t st = ctx->stream;
     T* H = nullptr;
     double* H64 = nullptr;
-    cdd *dl0 = nullptr, *dl1 = nullptr;
-    int32_t* dsteps = nullptr;
     unsigned long long* damax = nullptr;
     int rc = EIGSOL_OK;
     if (hipMalloc(&H, n * n * sizeof(T)) != hipSuccess || hipMalloc(&H64, n * n * (cx ? 16 : 8)) != hipSuccess ||
-        hipMalloc(&dl0, n * sizeof(cdd)) != hipSuccess || hipMalloc(&dl1, n * sizeof(cdd)) != hipSuccess ||
-        hipMalloc(&dsteps, n * sizeof(int32_t)) != hipSuccess || hipMalloc(&damax, 64) != hipSuccess)
+        hipMalloc(&damax, 64) != hipSuccess)
         rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: hipMalloc");
     WQr<T> w;
     if (rc == EIGSOL_OK) rc = wqr_alloc(w, n);
@@ -1448,28 +1605,15 @@ int wqr_francis_host(eigsol_ctx* ctx, int64_t n, const void* A, int max_iter, vo
     }
     std::vector<cdd> l1(n);
     std::vector<int32_t> steps(n, 0);
-    if (rc == EIGSOL_OK && hipMemcpyAsync(dl0, l0.data(), n * sizeof(cdd), hipMemcpyHostToDevice, st) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: upload eigenvalues");
+    if (rc == EIGSOL_OK) rc = hyman_refine<T>(st, H, n, l0.data(), n, l1.data(), steps.data());
     if (rc == EIGSOL_OK) {
-        const int R = (int)((n + wqdev::kHyT - 1) / wqdev::kHyT);
-        const int ni = (int)n;
-        if (R <= 1) hyman_launch<T, 1>(st, H, ni, dl0, dl1, dsteps, n);
-        else if (R <= 2) hyman_launch<T, 2>(st, H, ni, dl0, dl1, dsteps, n);
-        else if (R <= 4) hyman_launch<T, 4>(st, H, ni, dl0, dl1, dsteps, n);
-        else hyman_launch<T, 8>(st, H, ni, dl0, dl1, dsteps, n);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(l1.data(), dl1, n * sizeof(cdd), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipMemcpyAsync(steps.data(), dsteps, n * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            stream_wait(st) != hipSuccess)
-            rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: double-double refinement");
-    }
-    if (rc == EIGSOL_OK) {
-        if (std::getenv("EIGSOL_WIDE_QR_DEBUG")) {
-            int kept = 0, mx = 0;
-            for (int32_t s : steps) { kept += s < 0; mx = std::max(mx, s); }
-            std::fprintf(stderr, "[wide-qr] n %lld sweeps %d refinement: %d kept fp64, max Newton steps %d\n",
-                         (long long)n, sweeps, kept, mx);
-        }
+        int32_t unrefined = 0, mx = 0;
+        for (int32_t s : steps) { unrefined += s < 0; mx = std::max(mx, s < 0 ? -1 - s : s); }
+        ctx->wide_unrefined = unrefined;
+        ctx->wide_newton_max = mx;
+        if (std::getenv("EIGSOL_WIDE_QR_DEBUG"))
+            std::fprintf(stderr, "[wide-qr] n %lld sweeps %d refinement: %d not refined, max Newton steps %d\n",
+                         (long long)n, sweeps, unrefined, mx);
         for (int64_t i = 0; i < n; ++i) {
             if constexpr (cx) {
                 static_cast<cdd*>(eig)[i] = l1[i];
@@ -1485,13 +1629,43 @@ int wqr_francis_host(eigsol_ctx* ctx, int64_t n, const void* A, int max_iter, vo
     if (iters) *iters = sweeps;
     if (conv) *conv = failed ? 0 : 1;
     wqr_free(w);
-    for (void* p : {(void*)H, (void*)H64, (void*)dl0, (void*)dl1, (void*)dsteps, (void*)damax})
+    for (void* p : {(void*)H, (void*)H64, (void*)damax})
         if (p) (void)hipFree(p);
+    return rc;
+}
+
+// eigsol_hyman_refine: the refinement alone, on a host Hessenberg matrix (entries below the
+// subdiagonal are not read)
+template <class T>
+int hyman_refine_host(eigsol_ctx* ctx, int64_t n, const void* Hh, int64_t count, const cdd* starts, cdd* refined,
+                      int32_t* steps) {
+    if (n > (int64_t)wqdev::kHyT * kHyMaxRows)
+        return fail(EIGSOL_E_UNSUPPORTED, "eigsol_hyman_refine: the double-double refinement handles n <= 8192");
+    hipStream_t st = ctx->stream;
+    T* H = nullptr;
+    int rc = EIGSOL_OK;
+    if (hipMalloc(&H, n * n * sizeof(T)) != hipSuccess) rc = fail(EIGSOL_E_HIP, "eigsol_hyman_refine: hipMalloc");
+    if (rc == EIGSOL_OK && hipMemcpyAsync(H, Hh, n * n * sizeof(T), hipMemcpyHostToDevice, st) != hipSuccess)
+        rc = fail(EIGSOL_E_HIP, "eigsol_hyman_refine: upload");
+    if (rc == EIGSOL_OK) rc = hyman_refine<T>(st, H, n, starts, count, refined, steps);
+    for (int64_t i = 0; i < count && rc == EIGSOL_OK; ++i)
+        if (steps[i] < 0) steps[i] = -1;
+    if (H) (void)hipFree(H);
     return rc;
 }
 
 }  // namespace
 
+int wide_hyman_refine(eigsol_ctx* ctx, int dtype, int64_t n, const void* H, int64_t count, const double* starts,
+                      double* refined, int32_t* steps) {
+    std::vector<cdd> l0(count), l1(count);   // the caller's doubles need not have cdd's alignment
+    std::memcpy(l0.data(), starts, count * sizeof(cdd));
+    const int rc = by_wide(dtype, [&](auto tag) {
+        return hyman_refine_host<decltype(tag)>(ctx, n, H, count, l0.data(), l1.data(), steps);
+    });
+    if (rc == EIGSOL_OK) std::memcpy(refined, l1.data(), count * sizeof(cdd));
+    return rc;
+}
 int wide_hessenberg(eigsol_ctx* ctx, int dtype, int64_t n, const void* A, void* H) {
     return by_wide(dtype, [&](auto tag) { return whessenberg_host<decltype(tag)>(ctx, n, A, H); });
 }
