@@ -520,6 +520,26 @@ struct EigenResult {
         : eigenvalue(lambda), eigenvector(vec), iterations(iters), converged(conv) {}
 };
 
+// Block subspace iteration (subspaceIteration, solvers.hpp; no counterpart in the reference): the
+// nev eigenpairs of largest modulus from a block of `block` >= nev vectors (0: min(n, 32, 2 nev)).
+// residualTolerance > 0 adds ||A x - theta x|| / ||x|| <= residualTolerance (1 + |theta|) to the
+// eigenvalue test.  A cut between nev and nev + 1 through eigenvalues of equal modulus (a conjugate
+// pair split by nev = block) may end with converged = false.
+struct SubspaceOptions : public SolverOptions {
+    int nev = 1;
+    int block = 0;
+    double residualTolerance = 0;
+};
+
+template <typename S>
+struct SubspaceResult {
+    std::vector<std::complex<double>> eigenvalues;       // |.| descending, a conjugate pair +imag first
+    DenseMatrix<std::complex<double>> eigenvectors;      // n x nev, unit columns
+    std::vector<double> residuals;                       // ||A x - theta x||_2
+    int iterations = 0;                                  // products A Q
+    bool converged = false;
+};
+
 template <typename S>
 struct QRResult {
     Vector<S> eigenvalues;

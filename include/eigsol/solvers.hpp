@@ -7,6 +7,7 @@
 //   to_hessenberg<S> / _dense      src/qr_method/to_hessenberg.hpp:23-119
 //   qr_decompose<S> / _dense       src/qr_method/qr_decompose.hpp:25-132
 //   qr_eigenvalues<S> / _dense     src/qr_method/qr_eigenvalues.hpp:40-147
+//   subspaceIteration<S>           new: nev dominant eigenpairs of a sparse matrix (eigsol_subspace_csr)
 //
 // Scalars: double and std::complex<double> natively; float and std::complex<float> natively for the
 // power method and the triangular-CSR shifted inverse, promoted to fp64 for the other solvers
@@ -232,6 +233,69 @@ EigenResult<S> shiftedInversePowerMethod(const Matrix& M,
 template <ScalarConcept S>
 EigenResult<S> shiftedInversePowerMethod(const Matrix& M, const ShiftedSolverOptions<S>& opts, const Vector<S>& x0) {
     return detail::power_like<S>(M, opts, &x0, &opts.shift, "shiftedInversePowerMethod");
+}
+
+// ------------------------------------------------------------------------- block subspace iteration
+// The opts.nev eigenpairs of largest modulus of a sparse matrix (eigsol_subspace_csr: orthogonal
+// iteration with Rayleigh-Ritz on opts.block vectors).  S = double and std::complex<double>; the
+// default start block is drawn with random_vector<S> (column by column), so set_random_seed governs it.
+namespace detail {
+template <typename S>
+SubspaceResult<S> subspace_run(const Matrix& M, const SubspaceOptions& opts, const DenseMatrix<S>* X0) {
+    const char* who = "subspaceIteration";
+    if (M.scalar_type() != typeid(S)) throw std::runtime_error(std::string(who) + ": scalar type mismatch");
+    const std::int64_t n = M.rows();
+    if (n != M.cols()) throw std::runtime_error(std::string(who) + ": matrix must be square");
+    if (n == 0) throw std::runtime_error(std::string(who) + ": matrix has zero size");
+    if (M.isDense()) throw std::runtime_error(std::string(who) + ": only sparse matrices are supported");
+    SubspaceResult<S> res;
+    if constexpr (!DeviceScalar<S>) {
+        throw std::runtime_error(std::string(who) + ": scalar type not supported by the device path "
+                                                    "(double, std::complex<double>)");
+    } else {
+        eigsol_subspace_options o;
+        o.max_iterations = opts.maxIterations;
+        o.tolerance = opts.tolerance;
+        o.residual_tolerance = opts.residualTolerance;
+        o.nev = opts.nev;
+        if (opts.block > 0) o.block = opts.block;
+        else if (X0) o.block = static_cast<int>(X0->cols());
+        else o.block = static_cast<int>(std::min<std::int64_t>({n, 32, 2 * static_cast<std::int64_t>(opts.nev)}));
+        DenseMatrix<S> start;
+        if (X0) {
+            if (X0->rows() != n || X0->cols() != o.block)
+                throw std::runtime_error(std::string(who) + ": start block size mismatch");
+        } else {
+            start = DenseMatrix<S>(n, std::max(o.block, 0));
+            start.setRandom();
+            X0 = &start;
+        }
+        const std::size_t k = static_cast<std::size_t>(std::max(opts.nev, 0));
+        res.eigenvalues.assign(std::max<std::size_t>(k, 1), {});
+        res.residuals.assign(std::max<std::size_t>(k, 1), 0.0);
+        res.eigenvectors = DenseMatrix<std::complex<double>>(n, static_cast<std::int64_t>(k));
+        std::int32_t it = 0, conv = 0;
+        const int st = eigsol_subspace_csr(M.device<S>().csr(), &o, X0->data(),
+                                           reinterpret_cast<double*>(res.eigenvalues.data()),
+                                           k ? reinterpret_cast<double*>(res.eigenvectors.data()) : nullptr,
+                                           res.residuals.data(), &it, &conv);
+        check(st, who);
+        res.eigenvalues.resize(k);
+        res.residuals.resize(k);
+        res.iterations = it;
+        res.converged = conv != 0;
+    }
+    return res;
+}
+}  // namespace detail
+
+template <ScalarConcept S>
+SubspaceResult<S> subspaceIteration(const Matrix& M, const SubspaceOptions& opts = SubspaceOptions{}) {
+    return detail::subspace_run<S>(M, opts, nullptr);
+}
+template <ScalarConcept S>
+SubspaceResult<S> subspaceIteration(const Matrix& M, const SubspaceOptions& opts, const DenseMatrix<S>& X0) {
+    return detail::subspace_run<S>(M, opts, &X0);
 }
 
 // --------------------------------------------------------------------------------- solve_shifted

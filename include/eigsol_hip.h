@@ -193,6 +193,49 @@ int eigsol_power_kernel_name(eigsol_power* s, char* buf, size_t capacity);
  *               products with inverted 64 x 64 diagonal blocks when a block of L or U is ill
  *               conditioned (Skeel condition number above 1e6), or by EIGSOL_DENSE_TRSV=1 */
 
+/* ---------------------------------------------------------------- block subspace iteration
+ * The k = nev eigenpairs of largest modulus of a sparse matrix by orthogonal iteration with
+ * Rayleigh-Ritz on a block of m = block >= k vectors (csrc/subspace.hip; the reference has no
+ * counterpart).  Block vectors on the device are row-major interleaved: n x m with the vector
+ * index fastest, X[i * m + j].
+ *   Q = cholqr2(X0); repeat: Z = A Q; B = Q^H Z; (theta, Y) = eig(B), sorted by |theta| descending
+ *   (moduli equal to 1e-12 relative: the larger imaginary part first); stop when every wanted theta
+ *   is within tolerance (1 + |theta|) of its nearest not-yet-matched wanted value of the previous
+ *   iteration (|a-b| <= tol (1+|a|), a the new value) and, with residual_tolerance > 0, every wanted
+ *   ||Z y - theta Q y|| / ||Q y|| <= residual_tolerance (1 + |theta|); else Q = cholqr2(Z).
+ * iterations counts the products Z = A Q; max_iterations = 1 returns iterations = 1, converged = 0.
+ * One host wait per iteration (B and the factorisations' error words; one more on an iteration
+ * whose eigenvalue test passed and whose residuals are then formed); the Cholesky factorisations
+ * and R^-1 stay on the device.  A factorisation that meets a pivot that is not positive or below
+ * m 2^-52 max diag fails with EIGSOL_E_SOLVER ("subspace_iteration: block lost rank at column j"):
+ * a rank-deficient X0, or A Q of rank below m (A of rank below m).  A cut between k and k + 1
+ * through eigenvalues of equal modulus (a conjugate pair split by k = m, say) may never settle
+ * and end with converged = 0.
+ * Status: EIGSOL_E_INVALID (null pointers; nev < 1; block < nev; block > 32; block > n;
+ * max_iterations < 1; m outside 1..32 for spmm), EIGSOL_E_NOT_SQUARE, EIGSOL_E_ZERO_SIZE,
+ * EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD matrices and row-sharded matrices, spmm too); all of
+ * these are decided before any device call.
+ * Out of scope: dense matrices, single precision, double-double, row-sharded matrices and a
+ * session / step form. */
+typedef struct eigsol_subspace_options {
+    int32_t max_iterations;      /* 1000 */
+    double  tolerance;           /* 1e-10; < 0: never converges */
+    double  residual_tolerance;  /* 0: off */
+    int32_t nev;                 /* k >= 1 */
+    int32_t block;               /* m: nev <= m <= 32, m <= n */
+} eigsol_subspace_options;
+
+/* Y = A X on device buffers, row-major interleaved blocks (X: ncols x m, Y: nrows x m),
+ * stream-ordered.  Column j of Y is bitwise eigsol_csr_spmv of column j of X. */
+int eigsol_csr_spmm(eigsol_csr* A, int32_t m, const void* X_dev, void* Y_dev);
+
+/* X0: host, column-major n x m, matrix dtype.  eigenvalues: 2k doubles (re, im).  eigenvectors
+ * (optional): n x k complex, column-major (2nk doubles), unit 2-norm.  residuals (optional): k
+ * doubles, ||A x_j - theta_j x_j||_2 of the returned pairs (from Z = A Q of the last product). */
+int eigsol_subspace_csr(eigsol_csr* A, const eigsol_subspace_options* opts, const void* X0,
+                        double* eigenvalues, double* eigenvectors, double* residuals,
+                        int32_t* iterations, int32_t* converged);
+
 /* ---------------------------------------------------------------- shifted inverse iteration
  * shiftedInversePowerMethod<S>(M, ShiftedSolverOptions<S>{sigma, maxIter, tol})
  * (shifted_inverse_power_solver.hpp:112-125, impl :21-79).  A - sigma I is factored ONCE at

@@ -15,11 +15,12 @@ from typing import Optional
 import numpy as np
 
 from ._capi import (EIGSOL_C64, EIGSOL_C128, EIGSOL_CDD, EIGSOL_DD, EIGSOL_E_INVALID, EIGSOL_E_SIZE_MISMATCH, EIGSOL_E_UNSUPPORTED, EIGSOL_F32,
-                    EIGSOL_F64, EigSolError, SolverOptionsC, call, check, last_error, lib)
+                    EIGSOL_F64, EigSolError, SolverOptionsC, SubspaceOptionsC, call, check, last_error, lib)
 
 __all__ = [
     "EigSolError", "SolverOptions", "EigenResult", "Context", "CsrMatrix", "DenseMatrix",
     "PowerSession", "power_method", "device_count", "lib", "last_error",
+    "SubspaceOptions", "SubspaceResult", "subspace_iteration", "spmm",
 ]
 
 
@@ -267,6 +268,10 @@ class CsrMatrix:
     def spmv(self, x_dev: int, y_dev: int) -> None:
         call("eigsol_csr_spmv", self.handle, C.c_void_p(x_dev), C.c_void_p(y_dev))
 
+    def spmm(self, x_dev: int, y_dev: int, m: int) -> None:
+        """Y = A X on row-major interleaved device blocks (X: ncols x m, Y: nrows x m)."""
+        call("eigsol_csr_spmm", self.handle, int(m), C.c_void_p(x_dev), C.c_void_p(y_dev))
+
     def close(self) -> None:
         if getattr(self, "handle", None):
             lib().eigsol_csr_destroy(self.handle)
@@ -428,6 +433,82 @@ def power_method(matrix, opts: SolverOptions = SolverOptions(), x0=None) -> Eige
     call(fn, matrix.handle, C.byref(o), _ptr(x0), _ptr(lam), _ptr(x), C.byref(it), C.byref(conv))
     ev = _scalar(from_wire(lam, matrix.dtype)[0], matrix.dtype)
     return EigenResult(ev, from_wire(x, matrix.dtype), int(it.value), bool(conv.value))
+
+
+# ------------------------------------------------------------------------ block subspace iteration
+def spmm(matrix: CsrMatrix, X) -> np.ndarray:
+    """``A @ X`` for a host block X (ncols x m, 1 <= m <= 32) through ``eigsol_csr_spmm``: column j of
+    the result is bitwise ``CsrMatrix.spmv`` of column j."""
+    X = np.asarray(X)
+    nrows, ncols = matrix.shape
+    if X.ndim != 2 or X.shape[0] != ncols:
+        raise EigSolError(EIGSOL_E_SIZE_MISMATCH, f"X has shape {X.shape}, the matrix has {ncols} columns")
+    m = X.shape[1]
+    Xr = np.ascontiguousarray(X, dtype=matrix.dtype)      # row-major = interleaved
+    Y = np.empty((nrows, m), dtype=matrix.dtype)
+    ctx = matrix.ctx
+    dx, dy = ctx.malloc(max(Xr.nbytes, 16)), ctx.malloc(max(Y.nbytes, 16))
+    try:
+        if Xr.nbytes:
+            ctx.h2d(dx, Xr)
+        matrix.spmm(dx, dy, m)
+        if Y.nbytes:
+            ctx.d2h(Y, dy)
+    finally:
+        ctx.free(dx)
+        ctx.free(dy)
+    return Y
+
+
+@dataclass
+class SubspaceOptions:
+    """Options of :func:`subspace_iteration` (``eigsol_subspace_options`` without nev / block)."""
+
+    max_iterations: int = 1000
+    tolerance: float = 1e-10          # < 0: never converges
+    residual_tolerance: float = 0.0   # 0: the eigenvalue test alone decides
+
+
+@dataclass
+class SubspaceResult:
+    eigenvalues: np.ndarray    # k complex, |.| descending, a conjugate pair +imag first
+    eigenvectors: np.ndarray   # n x k complex, unit columns
+    residuals: np.ndarray      # k: ||A x - theta x||_2
+    iterations: int            # products Z = A Q
+    converged: bool
+
+
+def subspace_iteration(matrix, nev: int, opts: SubspaceOptions = SubspaceOptions(), block: Optional[int] = None,
+                       X0=None, seed: int = 0) -> SubspaceResult:
+    """The ``nev`` eigenpairs of largest modulus of a device-resident CSR matrix by block subspace
+    iteration with Rayleigh-Ritz (``eigsol_subspace_csr``).  ``block`` (default min(n, 32, 2 nev))
+    vectors are iterated; ``X0`` (n x block) defaults to uniform(-1, 1) entries from
+    ``numpy.random.default_rng(seed)``.  A cut between nev and nev + 1 through eigenvalues of equal
+    modulus (a conjugate pair split by nev = block) may end with ``converged`` false."""
+    n = matrix.shape[0]
+    nev = int(nev)
+    m = min(n, 32, 2 * nev) if block is None else int(block)
+    if X0 is None:
+        rng = np.random.default_rng(seed)
+        X0 = rng.uniform(-1, 1, (n, max(m, 0)))
+        if np.issubdtype(matrix.dtype, np.complexfloating):
+            X0 = X0 + 1j * rng.uniform(-1, 1, (n, max(m, 0)))
+    X0 = np.asarray(X0)
+    if X0.ndim != 2 or X0.shape != (n, m):
+        raise EigSolError(EIGSOL_E_SIZE_MISMATCH, f"X0 has shape {X0.shape}, expected ({n}, {m})")
+    if is_wide(matrix.dtype):
+        raise EigSolError(EIGSOL_E_UNSUPPORTED, "subspace_iteration: long double matrices are not supported")
+    Xf = np.asfortranarray(X0, dtype=matrix.dtype)         # column-major n x m
+    k = max(nev, 0)
+    ev = np.zeros(max(k, 1), dtype=np.complex128)
+    vec = np.zeros((n, k), dtype=np.complex128, order="F")
+    res = np.zeros(max(k, 1))
+    it, conv = C.c_int32(0), C.c_int32(0)
+    o = SubspaceOptionsC(int(opts.max_iterations), float(opts.tolerance), float(opts.residual_tolerance), nev, m)
+    pd = C.POINTER(C.c_double)
+    call("eigsol_subspace_csr", matrix.handle, C.byref(o), _ptr(Xf), ev.ctypes.data_as(pd),
+         vec.ctypes.data_as(pd) if vec.size else None, res.ctypes.data_as(pd), C.byref(it), C.byref(conv))
+    return SubspaceResult(ev[:k], vec, res[:k], int(it.value), bool(conv.value))
 
 
 @dataclass

@@ -56,6 +56,11 @@ class SolverOptionsC(C.Structure):
     _fields_ = [("max_iterations", C.c_int32), ("tolerance", C.c_double)]
 
 
+class SubspaceOptionsC(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("tolerance", C.c_double), ("residual_tolerance", C.c_double),
+                ("nev", C.c_int32), ("block", C.c_int32)]
+
+
 _vp = C.c_void_p
 _i32 = C.c_int32
 _i64 = C.c_int64
@@ -87,6 +92,8 @@ SIGNATURES = {
     "eigsol_csr_destroy": [_vp],
     "eigsol_csr_info": [_vp, _pi64, _pi64, _pi64, _pint],
     "eigsol_csr_spmv": [_vp, _vp, _vp],
+    "eigsol_csr_spmm": [_vp, _i32, _vp, _vp],
+    "eigsol_subspace_csr": [_vp, C.POINTER(SubspaceOptionsC), _vp, _pd, _pd, _pd, _pi32, _pi32],
     "eigsol_dense_create": [_vp, C.c_int, _i64, _i64, _vp, _ppv],
     "eigsol_dense_destroy": [_vp],
     "eigsol_dense_gemv": [_vp, _vp, _vp],
