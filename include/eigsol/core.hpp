@@ -540,6 +540,29 @@ struct SubspaceResult {
     bool converged = false;
 };
 
+// Krylov-Schur (krylovSchur, solvers.hpp; no counterpart in the reference): nev eigenpairs from a
+// Krylov basis of ncv vectors (0: min(n, 64, max(2 nev + 1, 20))), of largest modulus, or nearest
+// `shift` when shiftInvert is set (one factorisation of A - shift I, one solve per step).
+template <typename S>
+struct KrylovOptions {
+    int maxRestarts = 300;
+    double tolerance = 1e-10;   // < 0: never converges
+    int nev = 1;
+    int ncv = 0;
+    bool shiftInvert = false;
+    S shift = S(0);
+};
+
+template <typename S>
+struct KrylovResult {
+    std::vector<std::complex<double>> eigenvalues;       // largest modulus first, or nearest the shift first
+    DenseMatrix<std::complex<double>> eigenvectors;      // n x nev, unit columns
+    std::vector<double> residuals;                       // ||A x - lambda x||_2
+    int restarts = 0;                                    // restart cycles run
+    int applications = 0;                                // products A v, or solves with A - shift I
+    bool converged = false;
+};
+
 template <typename S>
 struct QRResult {
     Vector<S> eigenvalues;

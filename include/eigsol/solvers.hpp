@@ -8,6 +8,7 @@
 //   qr_decompose<S> / _dense       src/qr_method/qr_decompose.hpp:25-132
 //   qr_eigenvalues<S> / _dense     src/qr_method/qr_eigenvalues.hpp:40-147
 //   subspaceIteration<S>           new: nev dominant eigenpairs of a sparse matrix (eigsol_subspace_csr)
+//   krylovSchur<S>                 new: nev eigenpairs, dominant or nearest a shift (eigsol_krylov_csr)
 //
 // Scalars: double and std::complex<double> natively; float and std::complex<float> natively for the
 // power method and the triangular-CSR shifted inverse, promoted to fp64 for the other solvers
@@ -296,6 +297,70 @@ SubspaceResult<S> subspaceIteration(const Matrix& M, const SubspaceOptions& opts
 template <ScalarConcept S>
 SubspaceResult<S> subspaceIteration(const Matrix& M, const SubspaceOptions& opts, const DenseMatrix<S>& X0) {
     return detail::subspace_run<S>(M, opts, &X0);
+}
+
+// ----------------------------------------------------------------------------------- Krylov-Schur
+// opts.nev eigenpairs of a sparse matrix by thick-restart Arnoldi (eigsol_krylov_csr): of largest
+// modulus, or nearest opts.shift with opts.shiftInvert.  S = double and std::complex<double>; the
+// default start vector is drawn with random_vector<S>, so set_random_seed governs it.
+namespace detail {
+template <typename S>
+KrylovResult<S> krylov_run(const Matrix& M, const KrylovOptions<S>& opts, const Vector<S>* v0) {
+    const char* who = "krylovSchur";
+    if (M.scalar_type() != typeid(S)) throw std::runtime_error(std::string(who) + ": scalar type mismatch");
+    const std::int64_t n = M.rows();
+    if (n != M.cols()) throw std::runtime_error(std::string(who) + ": matrix must be square");
+    if (n == 0) throw std::runtime_error(std::string(who) + ": matrix has zero size");
+    if (M.isDense()) throw std::runtime_error(std::string(who) + ": only sparse matrices are supported");
+    KrylovResult<S> res;
+    if constexpr (!DeviceScalar<S>) {
+        throw std::runtime_error(std::string(who) + ": scalar type not supported by the device path "
+                                                    "(double, std::complex<double>)");
+    } else {
+        eigsol_krylov_options o;
+        o.max_restarts = opts.maxRestarts;
+        o.tolerance = opts.tolerance;
+        o.nev = opts.nev;
+        o.ncv = opts.ncv > 0 ? opts.ncv
+                             : static_cast<int>(std::min<std::int64_t>(
+                                   {n, 64, std::max<std::int64_t>(2 * static_cast<std::int64_t>(opts.nev) + 1, 20)}));
+        o.mode = opts.shiftInvert ? EIGSOL_KRYLOV_SHIFT_INVERT : EIGSOL_KRYLOV_LM;
+        Vector<S> start;
+        if (v0) {
+            if (static_cast<std::int64_t>(v0->size()) != n)
+                throw std::runtime_error(std::string(who) + ": start vector size mismatch");
+        } else {
+            start = random_vector<S>(static_cast<std::size_t>(n));
+            v0 = &start;
+        }
+        const std::size_t k = static_cast<std::size_t>(std::max(opts.nev, 0));
+        res.eigenvalues.assign(std::max<std::size_t>(k, 1), {});
+        res.residuals.assign(std::max<std::size_t>(k, 1), 0.0);
+        res.eigenvectors = DenseMatrix<std::complex<double>>(n, static_cast<std::int64_t>(k));
+        std::int32_t rs = 0, ap = 0, conv = 0;
+        const S shift = opts.shift;
+        const int st = eigsol_krylov_csr(M.device<S>().csr(), &o, &shift, v0->data(),
+                                         reinterpret_cast<double*>(res.eigenvalues.data()),
+                                         k ? reinterpret_cast<double*>(res.eigenvectors.data()) : nullptr,
+                                         res.residuals.data(), &rs, &ap, &conv);
+        check(st, who);
+        res.eigenvalues.resize(k);
+        res.residuals.resize(k);
+        res.restarts = rs;
+        res.applications = ap;
+        res.converged = conv != 0;
+    }
+    return res;
+}
+}  // namespace detail
+
+template <ScalarConcept S>
+KrylovResult<S> krylovSchur(const Matrix& M, const KrylovOptions<S>& opts = KrylovOptions<S>{}) {
+    return detail::krylov_run<S>(M, opts, nullptr);
+}
+template <ScalarConcept S>
+KrylovResult<S> krylovSchur(const Matrix& M, const KrylovOptions<S>& opts, const Vector<S>& v0) {
+    return detail::krylov_run<S>(M, opts, &v0);
 }
 
 // --------------------------------------------------------------------------------- solve_shifted

@@ -236,6 +236,79 @@ int eigsol_subspace_csr(eigsol_csr* A, const eigsol_subspace_options* opts, cons
                         double* eigenvalues, double* eigenvectors, double* residuals,
                         int32_t* iterations, int32_t* converged);
 
+/* ---------------------------------------------------------------- Krylov-Schur (thick-restart Arnoldi)
+ * k = nev eigenpairs of a sparse matrix from a Krylov basis of m = ncv vectors (csrc/krylov.hip; the
+ * reference has no counterpart), in two modes:
+ *   EIGSOL_KRYLOV_LM            Op = A: the eigenvalues of largest modulus (the product runs on the
+ *                               single-vector layout the eigsol_csr selected at upload);
+ *   EIGSOL_KRYLOV_SHIFT_INVERT  Op = (A - sigma I)^-1: the eigenvalues nearest sigma.  A - sigma I is
+ *                               factored once (the factors of the shifted inverse iteration below) and
+ *                               solved once per step; a factor failure (a singular A - sigma I, say)
+ *                               returns with that path's own status and message.
+ * V is n x (m + 1) on the device, column-major, in the matrix dtype; S is the (m + 1) x m Rayleigh
+ * matrix, B = S[:m, :m], b^T = S[m, :m].
+ *   v_0 = v0 / ||v0||, p = 0; cycle 1 .. max_restarts:
+ *     steps j = p .. m-1, enqueued without a host wait: w = Op v_j; twice { c = V_j^H w; w -= V_j c;
+ *       h += c } (V_j = V[:, :j+1], classical Gram-Schmidt with one reorthogonalisation); beta = ||w||;
+ *       S[:j+1, j] = h, S[j+1, j] = beta, v_{j+1} = w / beta;
+ *     one host wait (S, the breakdown word, the factor's error word);
+ *     (theta, Y) = eig(B), ordered by |theta| descending (moduli equal to 1e-12 relative: the larger
+ *       imaginary part first), est_i = |b^T y_i|; converged when est_i <= tolerance max(eps^(2/3),
+ *       |theta_i|) for every i < k (ARPACK's test);
+ *     else restart: p = k, or k + 1 for a real matrix when theta_{k-1} and theta_k are a conjugate
+ *       pair; Q = an orthonormal basis (matrix dtype, m x p; for a real matrix of [Re Y_p, Im Y_p]) of
+ *       the invariant subspace of B of theta_0 .. theta_{p-1}; V[:, :p] = V[:, :m] Q, v_p = v_m,
+ *       S = 0, S[:p, :p] = Q^H B Q, S[p, :p] = b^T Q.
+ *   lambda_i = theta_i (LM) or sigma + 1 / theta_i (shift-invert); x_i = V[:, :m] y_i scaled to unit
+ *   2-norm; residual_i = ||A x_i - lambda_i x_i||_2 formed with A on the device.
+ * Output order: that of theta, so largest |lambda| first (LM) or nearest sigma first (shift-invert).
+ * Of a conjugate pair of a real matrix the member with the positive imaginary part comes first in
+ * LM, the one with the negative imaginary part in shift-invert (Im 1/theta = -Im theta / |theta|^2).
+ * Breakdown: a step with beta <= m 2^-52 ||Op v_j|| (the norm before orthogonalisation) found an
+ * invariant subspace of dimension d = j + 1: it stores v_{j+1} = 0 and 1 + j in a device word.  At
+ * the cycle's wait the host truncates to that subspace: d >= nev returns its Ritz pairs with
+ * converged = 1 and applications counted up to the breakdown; d < nev fails with EIGSOL_E_SOLVER
+ * ("krylov_schur: invariant subspace of dimension d < nev").  No restart with a fresh vector.
+ * restarts counts the cycles run (max_restarts = 1: restarts = 1, applications = ncv); applications
+ * counts w = Op v.
+ * Status, all decided before any device call: EIGSOL_E_INVALID (null pointers; nev < 1;
+ * ncv < nev + 2; ncv > 64; ncv > n; max_restarts < 1; unknown mode), EIGSOL_E_NOT_SQUARE,
+ * EIGSOL_E_ZERO_SIZE, EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD matrices, row-sharded matrices).
+ * Out of scope: dense matrices, single precision, double-double, row-sharded matrices, a session /
+ * step form, generalised problems and selections other than these two. */
+#define EIGSOL_KRYLOV_LM 0
+#define EIGSOL_KRYLOV_SHIFT_INVERT 1
+typedef struct eigsol_krylov_options {
+    int32_t max_restarts; /* 300 */
+    double  tolerance;    /* 1e-10; < 0: never converges */
+    int32_t nev;          /* k >= 1 */
+    int32_t ncv;          /* m: nev + 2 <= m <= 64, m <= n */
+    int32_t mode;         /* EIGSOL_KRYLOV_LM / EIGSOL_KRYLOV_SHIFT_INVERT */
+} eigsol_krylov_options;
+
+/* sigma: one scalar of the matrix dtype, read only in shift-invert (may be NULL otherwise).  v0:
+ * host, n scalars of the matrix dtype.  eigenvalues: 2k doubles (re, im).  eigenvectors (optional):
+ * n x k complex, column-major (2nk doubles), unit 2-norm.  residuals (optional): k doubles.
+ * restarts / applications / converged: optional. */
+int eigsol_krylov_csr(eigsol_csr* A, const eigsol_krylov_options* opts, const void* sigma, const void* v0,
+                      double* eigenvalues, double* eigenvectors, double* residuals, int32_t* restarts,
+                      int32_t* applications, int32_t* converged);
+
+/* The solver's two kernel groups on device buffers (dtype EIGSOL_F64 / EIGSOL_C128), enqueued on the
+ * context's stream.
+ * eigsol_krylov_orth: one orthogonalisation step of w (n scalars) against the j orthonormal columns
+ * of V (n x j, column-major, leading dimension ldv >= n), 1 <= j <= 64: twice { c = V^H w;
+ * w -= V c; h += c }, then w /= beta.  h_out (host, 2j doubles: re, im), beta_out (host: ||w|| after
+ * the two passes) and wnorm_out (host: ||w|| before them) are optional; the call waits for the
+ * stream when one of them is given.  A step with beta <= 64 2^-52 wnorm leaves w = 0 (breakdown).
+ * eigsol_krylov_rotate: V[:, :p] <- V[:, :m] Q in place (V: n x m, column-major, ldv >= n; Q: host,
+ * m x p column-major, of the dtype; 1 <= p <= m <= 64); columns p .. m-1 are left as they are.  Q
+ * is copied before the call returns. */
+int eigsol_krylov_orth(eigsol_ctx* ctx, int dtype, int64_t n, int32_t j, const void* V_dev, int64_t ldv,
+                       void* w_dev, double* h_out, double* beta_out, double* wnorm_out);
+int eigsol_krylov_rotate(eigsol_ctx* ctx, int dtype, int64_t n, int32_t m, int32_t p, void* V_dev,
+                         int64_t ldv, const void* Q);
+
 /* ---------------------------------------------------------------- shifted inverse iteration
  * shiftedInversePowerMethod<S>(M, ShiftedSolverOptions<S>{sigma, maxIter, tol})
  * (shifted_inverse_power_solver.hpp:112-125, impl :21-79).  A - sigma I is factored ONCE at

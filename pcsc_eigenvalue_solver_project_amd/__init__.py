@@ -15,12 +15,14 @@ from typing import Optional
 import numpy as np
 
 from ._capi import (EIGSOL_C64, EIGSOL_C128, EIGSOL_CDD, EIGSOL_DD, EIGSOL_E_INVALID, EIGSOL_E_SIZE_MISMATCH, EIGSOL_E_UNSUPPORTED, EIGSOL_F32,
-                    EIGSOL_F64, EigSolError, SolverOptionsC, SubspaceOptionsC, call, check, last_error, lib)
+                    EIGSOL_F64, EIGSOL_KRYLOV_LM, EIGSOL_KRYLOV_SHIFT_INVERT, EigSolError, KrylovOptionsC, SolverOptionsC,
+                    SubspaceOptionsC, call, check, last_error, lib)
 
 __all__ = [
     "EigSolError", "SolverOptions", "EigenResult", "Context", "CsrMatrix", "DenseMatrix",
     "PowerSession", "power_method", "device_count", "lib", "last_error",
     "SubspaceOptions", "SubspaceResult", "subspace_iteration", "spmm",
+    "KrylovOptions", "KrylovResult", "krylov_schur", "krylov_orth", "krylov_rotate",
 ]
 
 
@@ -509,6 +511,105 @@ def subspace_iteration(matrix, nev: int, opts: SubspaceOptions = SubspaceOptions
     call("eigsol_subspace_csr", matrix.handle, C.byref(o), _ptr(Xf), ev.ctypes.data_as(pd),
          vec.ctypes.data_as(pd) if vec.size else None, res.ctypes.data_as(pd), C.byref(it), C.byref(conv))
     return SubspaceResult(ev[:k], vec, res[:k], int(it.value), bool(conv.value))
+
+
+# ------------------------------------------------------------------------------------ Krylov-Schur
+@dataclass
+class KrylovOptions:
+    """Options of :func:`krylov_schur` (``eigsol_krylov_options`` without nev / ncv / mode)."""
+
+    max_restarts: int = 300
+    tolerance: float = 1e-10          # < 0: never converges
+
+
+@dataclass
+class KrylovResult:
+    eigenvalues: np.ndarray    # k complex: largest modulus first, or nearest sigma first
+    eigenvectors: np.ndarray   # n x k complex, unit columns
+    residuals: np.ndarray      # k: ||A x - lambda x||_2
+    restarts: int              # restart cycles run
+    applications: int          # products A v, or solves with A - sigma I
+    converged: bool
+
+
+def default_ncv(n: int, nev: int) -> int:
+    return min(n, 64, max(2 * nev + 1, 20))
+
+
+def krylov_schur(matrix, nev: int, opts: KrylovOptions = KrylovOptions(), sigma=None, ncv: Optional[int] = None,
+                 v0=None, seed: int = 0) -> KrylovResult:
+    """``nev`` eigenpairs of a device-resident CSR matrix by the Krylov-Schur method
+    (``eigsol_krylov_csr``): those of largest modulus (``sigma is None``), or those nearest ``sigma``
+    through one factorisation of A - sigma I.  ``ncv`` basis vectors (default
+    min(n, 64, max(2 nev + 1, 20))); ``v0`` defaults to uniform(-1, 1) entries from
+    ``numpy.random.default_rng(seed)`` (complex for complex matrices)."""
+    n = matrix.shape[0]
+    nev = int(nev)
+    m = default_ncv(n, nev) if ncv is None else int(ncv)
+    if v0 is None:
+        rng = np.random.default_rng(seed)
+        v0 = rng.uniform(-1, 1, n)
+        if np.issubdtype(matrix.dtype, np.complexfloating):
+            v0 = v0 + 1j * rng.uniform(-1, 1, n)
+    if is_wide(matrix.dtype):
+        raise EigSolError(EIGSOL_E_UNSUPPORTED, "krylov_schur: long double matrices are not supported")
+    v0 = _vector(v0, matrix.dtype, n, "v0")
+    k = max(nev, 0)
+    ev = np.zeros(max(k, 1), dtype=np.complex128)
+    vec = np.zeros((n, k), dtype=np.complex128, order="F")
+    res = np.zeros(max(k, 1))
+    rs, ap, conv = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    o = KrylovOptionsC(int(opts.max_restarts), float(opts.tolerance), nev, m,
+                       EIGSOL_KRYLOV_LM if sigma is None else EIGSOL_KRYLOV_SHIFT_INVERT)
+    sg = None if sigma is None else _sigma(sigma, matrix.dtype)
+    pd = C.POINTER(C.c_double)
+    call("eigsol_krylov_csr", matrix.handle, C.byref(o), None if sg is None else _ptr(sg), _ptr(v0),
+         ev.ctypes.data_as(pd), vec.ctypes.data_as(pd) if vec.size else None, res.ctypes.data_as(pd), C.byref(rs),
+         C.byref(ap), C.byref(conv))
+    return KrylovResult(ev[:k], vec, res[:k], int(rs.value), int(ap.value), bool(conv.value))
+
+
+def krylov_orth(ctx: Context, V, w):
+    """One orthogonalisation step of the Krylov-Schur solver (``eigsol_krylov_orth``) on host arrays:
+    w (n) against the orthonormal columns of V (n x j), two Gram-Schmidt passes, then normalised.
+    Returns (w_out, h, beta, wnorm)."""
+    V = np.asfortranarray(V)
+    if V.ndim != 2 or np.shape(w) != (V.shape[0],):
+        raise EigSolError(EIGSOL_E_SIZE_MISMATCH, f"V has shape {V.shape}, w has shape {np.shape(w)}")
+    n, j = V.shape
+    w = np.ascontiguousarray(w, dtype=V.dtype)
+    code = _dtype_code(V.dtype)
+    h = np.zeros(max(j, 1), dtype=np.complex128)
+    beta, wn = C.c_double(0), C.c_double(0)
+    dv, dw = ctx.malloc(max(V.nbytes, 16)), ctx.malloc(max(w.nbytes, 16))
+    try:
+        ctx.h2d(dv, V.ravel(order="F"))                     # column-major, ld = n
+        ctx.h2d(dw, w)
+        call("eigsol_krylov_orth", ctx.handle, code, n, j, C.c_void_p(dv), n, C.c_void_p(dw),
+             h.ctypes.data_as(C.POINTER(C.c_double)), C.byref(beta), C.byref(wn))
+        out = ctx.d2h(np.empty(n, dtype=V.dtype), dw)
+    finally:
+        ctx.free(dv)
+        ctx.free(dw)
+    return out, (h[:j] if np.iscomplexobj(V) else h[:j].real.copy()), beta.value, wn.value
+
+
+def krylov_rotate(ctx: Context, V, Q) -> np.ndarray:
+    """``V[:, :p] <- V[:, :m] Q`` in place on the device (``eigsol_krylov_rotate``) for host arrays
+    V (n x m) and Q (m x p); returns the n x m result (columns p .. m-1 unchanged)."""
+    V = np.asfortranarray(V)
+    Q = np.asfortranarray(Q, dtype=V.dtype)
+    if V.ndim != 2 or Q.ndim != 2 or Q.shape[0] != V.shape[1]:
+        raise EigSolError(EIGSOL_E_SIZE_MISMATCH, f"V has shape {V.shape}, Q has shape {Q.shape}")
+    n, m = V.shape
+    dv = ctx.malloc(max(V.nbytes, 16))
+    try:
+        ctx.h2d(dv, V.ravel(order="F"))                     # column-major, ld = n
+        call("eigsol_krylov_rotate", ctx.handle, _dtype_code(V.dtype), n, m, Q.shape[1], C.c_void_p(dv), n, _ptr(Q))
+        out = ctx.d2h(np.empty(n * m, dtype=V.dtype), dv).reshape((n, m), order="F")
+    finally:
+        ctx.free(dv)
+    return out
 
 
 @dataclass

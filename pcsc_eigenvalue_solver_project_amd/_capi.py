@@ -61,6 +61,15 @@ class SubspaceOptionsC(C.Structure):
                 ("nev", C.c_int32), ("block", C.c_int32)]
 
 
+EIGSOL_KRYLOV_LM = 0
+EIGSOL_KRYLOV_SHIFT_INVERT = 1
+
+
+class KrylovOptionsC(C.Structure):
+    _fields_ = [("max_restarts", C.c_int32), ("tolerance", C.c_double), ("nev", C.c_int32), ("ncv", C.c_int32),
+                ("mode", C.c_int32)]
+
+
 _vp = C.c_void_p
 _i32 = C.c_int32
 _i64 = C.c_int64
@@ -94,6 +103,9 @@ SIGNATURES = {
     "eigsol_csr_spmv": [_vp, _vp, _vp],
     "eigsol_csr_spmm": [_vp, _i32, _vp, _vp],
     "eigsol_subspace_csr": [_vp, C.POINTER(SubspaceOptionsC), _vp, _pd, _pd, _pd, _pi32, _pi32],
+    "eigsol_krylov_csr": [_vp, C.POINTER(KrylovOptionsC), _vp, _vp, _pd, _pd, _pd, _pi32, _pi32, _pi32],
+    "eigsol_krylov_orth": [_vp, C.c_int, _i64, _i32, _vp, _i64, _vp, _pd, _pd, _pd],
+    "eigsol_krylov_rotate": [_vp, C.c_int, _i64, _i32, _i32, _vp, _i64, _vp],
     "eigsol_dense_create": [_vp, C.c_int, _i64, _i64, _vp, _ppv],
     "eigsol_dense_destroy": [_vp],
     "eigsol_dense_gemv": [_vp, _vp, _vp],
