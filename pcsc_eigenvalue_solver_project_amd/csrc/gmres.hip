@@ -40,21 +40,13 @@
 #include <thread>
 #include <vector>
 
+#include "gmres.hpp"
 #include "kernels_common.hpp"
 #include "multifrontal.hpp"
+#include "shifted.hpp"
 
 namespace eigsol {
 
-struct ShiftFactor;
-int shift_factor_tri(eigsol_ctx* ctx, int dtype, int64_t n, std::vector<int32_t>& rp, std::vector<int32_t>& ci,
-                     const void* vals, bool up, ShiftFactor** out);
-int shift_factor_tri_dev(eigsol_ctx* ctx, int dtype, int64_t n, int32_t* rp, int32_t* ci, void* vals, int64_t nnz,
-                         bool up, ShiftFactor** out);
-hipError_t tri_exclusive_scan(hipStream_t st, const int32_t* in, int32_t* out, int64_t n);
-int shift_solve_launch(ShiftFactor* f, const void* b_dev, void* y_dev);
-int shift_error(ShiftFactor* f);
-void shift_factor_free(ShiftFactor* f);
-void shift_info(const ShiftFactor* f, double* bytes, int32_t* variant, int32_t* tiles);
 int csr_upload(eigsol_ctx* ctx, int dtype, int64_t nrows, int64_t ncols, int64_t nnz, const int32_t* rowptr,
                const int32_t* colidx, const void* values, eigsol_csr** out, int64_t xoff);
 

@@ -27,15 +27,10 @@
 #include <complex>
 
 #include "kernels_common.hpp"
+#include "shifted.hpp"
 #include "small_eig.hpp"
 
 namespace eigsol {
-
-struct ShiftFactor;
-int shift_factor_csr(eigsol_csr* A, const void* sigma, ShiftFactor** out);
-void shift_factor_free(ShiftFactor* f);
-int shift_error(ShiftFactor* f);
-int shift_solve_launch(ShiftFactor* f, const void* b_dev, void* y_dev);
 
 namespace dev {
 namespace ks {

@@ -17,6 +17,7 @@
 #include <cxxabi.h>
 
 #include "kernels_common.hpp"
+#include "shifted.hpp"
 
 namespace eigsol {
 int csr_grid(eigsol_csr* A, int* grid, bool peer = false);
@@ -39,18 +40,6 @@ int norm_partial_launch(eigsol_ctx* ctx, int dtype, const void* x, int64_t n, Po
                         void* blk_part, void* out, int grid);
 int scale_out_launch(eigsol_ctx* ctx, int dtype, const void* src, double nrm, void* dst, int64_t n);
 int dist_exchange(eigsol_csr* A, void* y, void* rank_part);
-struct ShiftFactor;
-int shift_factor_csr(eigsol_csr* A, const void* sigma, ShiftFactor** out);
-int shift_factor_dense(eigsol_dense* A, const void* sigma, ShiftFactor** out);
-void shift_factor_free(ShiftFactor* f);
-int shift_grid(const ShiftFactor* f);
-void* shift_aux(const ShiftFactor* f, int j);
-int shift_error(ShiftFactor* f);
-void shift_lag_reset(ShiftFactor* f);
-int shift_iter_launch(ShiftFactor* f, void* buf0, void* buf1, PowerCtl* ctl, const void* rank_part,
-                      void* my_part, void* trace, int parity, int first);
-int shift_solve_launch(ShiftFactor* f, const void* b_dev, void* y_dev);
-void shift_info(const ShiftFactor* f, double* bytes, int32_t* variant, int32_t* tiles);
 // extended precision (EIGSOL_DD / EIGSOL_CDD, wide.hip): the same session interface, host-driven
 struct WideSession;
 int wide_session_create(eigsol_ctx* ctx, eigsol_csr* csr, eigsol_dense* dense, const void* sigma, int32_t trace_cap,

@@ -18,6 +18,11 @@
 //     update on the fp64 matrix cores; Eigen's PartialPivLU is blocked too), then a
 //     single-workgroup forward/back substitution per iteration with the vector in LDS.
 // Non-triangular sparse matrices too large to densify are reported as EIGSOL_E_UNSUPPORTED.
+//
+// This file holds the solve kernels, the launch paths, the dense LU and the general-sparse dispatch.
+// The triangular factor's analysis and layout (level order, head / tail plan, host and device builds,
+// tri_build) live in tri_factor.hip; shift_factor.hpp is what the two files share, shifted.hpp what
+// the other modules see.
 #include <algorithm>
 #include <cmath>
 #include <complex>
@@ -25,130 +30,16 @@
 #include <cstring>
 #include <vector>
 
-#include "band_lu.hpp"
-#include "kernels_common.hpp"
 #include "mfma_rankk.hpp"
+#include "shift_factor.hpp"
 
 namespace eigsol {
 
-struct GmresSolver;
-// Adev: the device matrix A itself (same dtype and order), used for the products with M = A - sigma I
-int gmres_create(eigsol_ctx* ctx, int dtype, int64_t n, const int32_t* rp, const int32_t* ci, const void* v,
-                 double sre, double sim, GmresSolver** out, eigsol_csr* Adev = nullptr);
-void gmres_free(GmresSolver* g);
-int gmres_solve(GmresSolver* g, const void* b_dev, double bdiv, void* y_dev, const double* guess = nullptr);
-int gmres_can_lag(const GmresSolver* g);
-int gmres_solve_lag(GmresSolver* g, const void* b_dev, double bdiv, void* y_dev);
-int gmres_lag_verdict(GmresSolver* g);
-void gmres_lag_reset(GmresSolver* g);
-void gmres_info(const GmresSolver* g, double* bytes, int32_t* steps);
-int gmres_complete(const GmresSolver* g);
-
-namespace dev {
-constexpr int kMaxMulti = 4;      // solves per multi-solve launch (one head wave each)
-}
 static constexpr int kMultiDefault = 4;   // EIGSOL_TRSV_MULTI (config 5 per iteration: K = 1 0.674, 2 0.502, 3 0.439, 4 0.414 ms)
 
-constexpr size_t kPinBytes = 256;   // ShiftFactor::hpin
-
-struct ShiftFactor {
-    eigsol_ctx* ctx = nullptr;
-    int dtype = EIGSOL_F64;
-    int64_t n = 0;
-    int kind = 0;                 // 0 triangular CSR, 1 dense LU, 2 ILU(0)-preconditioned GMRES, 3 band LU
-    GmresSolver* gm = nullptr;    // kind 2 (gmres.hip)
-    bool lag_prev = false;        // kind 2 iteration: the previous launch's solve check is still to be read
-    double lag_bdiv = 0.0;        // ... and that solve's divisor (||y_{t-1}||)
-    void* promo = nullptr;        // kind 2 in single precision: [2][n] double-precision right-hand side and
-                                  // solution of the GMRES family's solve (its factors are built in double)
-    BandFactor* band = nullptr;   // kind 3 (band_lu.hip)
-    void* hpin = nullptr;         // pinned host scratch for per-solve readbacks (pageable copies sleep ~1 ms)
-    eigsol_csr* src = nullptr;    // kind 2: A, retained for the densified-LU fallback
-    int fell_back = 0;            // kind 1 reached through the GMRES fallback
-    double sig_re = 0.0, sig_im = 0.0;
-    // triangular: everything indexed by solve position (rows sorted by level, levels padded)
-    int upper = 1;
-    int64_t nnz_total = 0;        // nonzeros of A (diagonal included), for roofline accounting
-    int64_t nnz_off = 0;
-    int32_t* order = nullptr;     // head position -> row (-1: level padding)
-    void* z[2] = {nullptr, nullptr};   // solve values polled by readers; sentinel = not yet solved
-    int32_t npos = 0, nchunks = 0, nlevels = 0;
-    void* hval = nullptr;         // head, pass-major entries / columns / pivots
-    int32_t* hcol = nullptr;
-    void* hpiv = nullptr;
-    int2* passes = nullptr;       // head passes {first position, end | barrier}
-    int32_t npass = 0, hpos = 0, hlevels = 0;
-    int wave_head = 1;            // head kernel: 1 one-wave (sptrsv_whead_kernel), 0 one workgroup
-    void* wval = nullptr;         // one-wave head, pass-major (see sptrsv_whead_kernel)
-    int32_t* wcol = nullptr;
-    void* wrp = nullptr;
-    int32_t* wdst = nullptr;
-    int32_t nwpass = 0;
-    int red_grid = 0;             // blocks of the partials reduction
-    int2* smeta = nullptr;        // tail slices (see sptrsv_slice_kernel)
-    int32_t* trow = nullptr;
-    void* tpiv = nullptr;
-    int32_t* tcol = nullptr;
-    void* tval = nullptr;
-    int32_t nslices = 0;
-    int slice_b = 16;             // entries per lane held in registers (4, 8 or 16)
-    int tail_chunks = 0;          // tail variant: 1 chunk kernel, 0 slice kernel
-    int chunk_two = 0;            // chunk kernel with two entries per lane (tail rows longer than 16)
-    int32_t* porder = nullptr;    // chunk variant (see sptrsv_chunk_kernel)
-    int32_t* pptr = nullptr;
-    int32_t* pcol = nullptr;
-    void* pval = nullptr;
-    void* ppiv = nullptr;
-    int32_t chunk0 = 0;
-    // tail polls without back-off (EIGSOL_TRSV_POLL_FAST, low 16 bits) and the back-off schedule
-    // (EIGSOL_TRSV_POLL_SLOW, bits 16-18; poll_backoff).  Round 6 (tools/r06_trsv_backoff_ab.sh,
-    // profiles/r06_trsv_backoff_ab.log, config 5 at K = 4): sleeps of 2 / 8 / 32 x 64 cycles
-    // (growing with the spins) 0.4127-0.4134 ms per iteration; a constant 4 / 6 / 8 / 12 / 16:
-    // 0.4072-0.4083 (the long sleeps woke late); 32: 0.415.  Default: a constant 8
-    int poll_fast = 4 << 16;
-    int poll_mode = 2;            // EIGSOL_TRSV_POLL_MODE (bit 0: slice tail, one re-poll per lane; bit 1: chunk tails, the second chunk's first polls after the first chunk: config 5 0.698 -> 0.674 ms, K = 4 0.419 -> 0.414)
-    // multi-solve launches (sptrsv_chunk_role_kernel; EIGSOL_TRSV_MULTI=K, 1 disables): K reference
-    // iterations per launch, solve j one dependency round behind solve j - 1
-    int multi = 1;
-    int grid_multi = 0;
-    int hconc = 0;                // multi head: every solve's values fit the LDS (sptrsv_whead_kernel)
-    void* aux[dev::kMaxMulti - 1] = {};           // w_0 .. w_{K-2} (n scalars each)
-    void* zm[dev::kMaxMulti][2] = {};             // solve j >= 1: polled values (zm[0] unused: z)
-    int32_t epoch_m = 0;
-    void* kpart = nullptr;        // part4 per solve j >= 1: {||w_j||^2, w_{j-1}^H w_j}
-    void* kblk = nullptr;         // part4 per block of those reductions
-    uint32_t* work = nullptr;     // [2]: last-arriver ticket of the partials reduction
-    int32_t* err = nullptr;
-    void* wave_part = nullptr;    // part4 per wave
-    int32_t epoch = 0;
-    int grid = 0;
-    // dense
-    void* lu = nullptr;           // column-major n x n, L (unit) below, U on and above the diagonal
-    int32_t* perm = nullptr;      // P b: b_perm[i] = b[perm[i]]
-    int32_t* zero_pivot = nullptr;
-    size_t lds_bytes = 0;
-    // dense, multi-CU substitution (large n): epoch flags per block row, forward results
-    int dense_multi = 0;
-    int32_t* flag_f = nullptr;
-    int32_t* flag_b = nullptr;
-    void* zf = nullptr;
-    void* tinv = nullptr;         // [nblk][2] inverted diagonal blocks inv(L_kk), inv(U_kk), 64 x 64 column-major
-    void* tmul = nullptr;         // [nblk][2] premultiplied next-to-diagonal tiles (dense_tmul_kernel)
-    int dense_v = 2;              // substitution kernel: 2 = dense_trsv2_kernel, 1 = dense_trsv_kernel (ill-conditioned
-                                  // diagonal blocks, or EIGSOL_DENSE_TRSV=1; see dense_lu_factor)
-};
-
 namespace dev {
 
-#ifndef EIGSOL_TRSV_ROW_LANES
-#define EIGSOL_TRSV_ROW_LANES 16
-#endif
-constexpr int kRowLanes = EIGSOL_TRSV_ROW_LANES;   // lanes per row: one row per 16-lane group
-constexpr int kWaveRows = 64 / kRowLanes;          // positions per wave round (one chunk): levels are padded to this
 constexpr int kSpinLimit = 1 << 20;   // polls (with back-off) before the wait is declared broken
-// An unsolved entry of z holds this NaN in every 8-byte word.  A solved value never does: the
-// producer maps it to the default quiet NaN (sanitize), so the value itself is the ready flag.
-constexpr unsigned long long kSent = 0x7FF4DEAD7FF4DEADull;
 
 template <class S>
 struct TriArgs {
@@ -368,10 +259,6 @@ __device__ __forceinline__ S wait_value(const S* z, int j, int32_t* err) {
 // arithmetic latency, not a memory round trip.  zl starts as the scaled right-hand side.
 // Padding entries read the zero slot zl[hpos] with value zero; the pass count is padded to a
 // multiple of the ring depth with empty passes, so the ring loop is straight-line code.
-constexpr int kHeadThreads = 1024;
-constexpr int kHeadRows = kHeadThreads / kRowLanes;    // rows per pass
-constexpr int kHeadDepth = 8;                          // passes in flight
-constexpr int32_t kPassBarrier = 1 << 30;
 
 template <class S, bool kIter>
 __global__ __launch_bounds__(kHeadThreads) void sptrsv_head_kernel(TriArgs<S> a, int parity) {
@@ -450,8 +337,6 @@ __global__ __launch_bounds__(kHeadThreads) void sptrsv_head_kernel(TriArgs<S> a,
 // in a register ring.  The other waves only help to stage the right-hand side into LDS and to
 // publish the solved values.
 constexpr int kWHeadThreads = 256;
-constexpr int kWHeadDepth = 8;
-constexpr int kWHeadRows = 16;   // rows per pass
 constexpr int kDppQuad2301 = 0x4E;
 __device__ __forceinline__ double quad_sum(double v) {
     v += dpp_f64<kDppQuad1032>(v);
@@ -1973,220 +1858,6 @@ __global__ void shift_diag_kernel(S* a, int64_t n, S sigma) {
     if (i < n) a[i * n + i] = sub(a[i * n + i], sigma);
 }
 
-// ---- on-device analysis of a triangular CSR (factor_tri_device): the same level order and the same
-// position-indexed chunk layout the host build produces, without moving the matrix off the device.
-
-// Per row: pivot d_i - sigma (the diagonal entries summed in stored order, 0 where there is none),
-// off-diagonal count, and the triangularity / zero-pivot flags (flags[0]: an entry left of the
-// diagonal, [1]: right of it, [2]: a zero pivot), one atomic per wave.
-template <class S>
-__global__ __launch_bounds__(256) void tri_rows_kernel(const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
-                                                       const S* __restrict__ val, int64_t n, S sig,
-                                                       S* __restrict__ pv, int32_t* __restrict__ offlen,
-                                                       int32_t* __restrict__ flags) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    bool lo = false, hi = false, zp = false;
-    if (i < n) {
-        S d = s_zero<S>();
-        int32_t off = 0;
-        for (int32_t e = rp[i]; e < rp[i + 1]; ++e) {
-            const int32_t c = ci[e];
-            if (c == i) d = add(d, val[e]);
-            else {
-                ++off;
-                lo |= c < i;
-                hi |= c > i;
-            }
-        }
-        const S p = sub(d, sig);
-        pv[i] = p;
-        offlen[i] = off;
-        if constexpr (std::is_same_v<S, double> || std::is_same_v<S, float>) zp = p == 0;
-        else zp = p.re == 0 && p.im == 0;
-    }
-    const uint64_t bl = __ballot(lo), bh = __ballot(hi), bz = __ballot(zp);
-    if ((threadIdx.x & 63) == 0) {
-        if (bl) atomicOr(flags + 0, 1);
-        if (bh) atomicOr(flags + 1, 1);
-        if (bz) atomicOr(flags + 2, 1);
-    }
-}
-
-// Dependency levels, sync-free: level(i) = 1 + max level of the rows row i reads (0 for none).
-// Rows are claimed in dependency order through a ticket (upper: row n-1 first), four rows per wave
-// (16 lanes per row); a row's dependencies always hold smaller tickets, claimed by waves that are
-// already running, so every wait ends.  A wave re-polls its unfinished rows' dependencies
-// (agent-scope loads, -1 = not yet known) and publishes a row as soon as all of them are known,
-// inside the loop (a divergent group must never wait on a row its own wave publishes after the
-// loop).  Per level: row count and longest row (atomics); maxlev = the deepest level.  A wait past
-// ~2 s of the 100 MHz constant clock sets err and publishes level 0, so a broken analysis ends
-// (the host then builds on the CPU).
-__global__ __launch_bounds__(256) void tri_level_kernel(const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
-                                                        const int32_t* __restrict__ offlen, int64_t n, int upper,
-                                                        int32_t* lev, uint32_t* ticket, int32_t* lcnt,
-                                                        int32_t* lmax, int32_t* maxlev, int32_t* err) {
-    const int lane = threadIdx.x & (kRowLanes - 1);
-    const int grp = (threadIdx.x & 63) / kRowLanes;
-    for (;;) {
-        uint32_t t0 = 0;
-        if ((threadIdx.x & 63) == 0) t0 = atomicAdd(ticket, (uint32_t)kWaveRows);
-        t0 = __shfl(t0, 0, 64);
-        if ((int64_t)t0 >= n) return;
-        const int64_t t = (int64_t)t0 + grp;
-        const bool live = t < n;
-        const int64_t i = live ? (upper ? n - 1 - t : t) : 0;
-        const int32_t e0 = live ? rp[i] : 0, e1 = live ? rp[i + 1] : 0;
-        bool done = !live;
-        const long long t_start = wall_clock64();
-        for (;;) {
-            int32_t m = -1;
-            bool ready = true;
-            if (!done)
-                for (int32_t e = e0 + lane; e < e1; e += kRowLanes) {
-                    const int32_t c = ci[e];
-                    if (c == i) continue;
-                    const int32_t l = __hip_atomic_load(lev + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (l < 0) ready = false;
-                    m = max(m, l);
-                }
-            // the row's 16 lanes: all ready (ballot), and the largest dependency level (every lane
-            // shuffles: a shuffle under a divergent mask would read inactive lanes' stale registers)
-#pragma unroll
-            for (int off = kRowLanes / 2; off > 0; off >>= 1) m = max(m, __shfl_xor(m, off, 64));
-            const uint64_t unready = __ballot(!ready);
-            ready = ((unready >> (grp * kRowLanes)) & ((1ull << kRowLanes) - 1)) == 0;
-            bool timeout = false;
-            if (!done && !ready && wall_clock64() - t_start > 200000000ll) {
-                timeout = true;
-                ready = true;
-                m = -1;
-            }
-            if (!done && ready) {
-                if (lane == 0) {
-                    if (timeout) atomicOr(err, 1);
-                    const int32_t l = m + 1;
-                    __hip_atomic_store(lev + i, l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    atomicAdd(lcnt + l, 1);
-                    atomicMax(lmax + l, offlen[i]);
-                    atomicMax(maxlev, l);
-                }
-                done = true;
-            }
-            if (__ballot(!done) == 0) break;
-            __builtin_amdgcn_s_sleep(1);
-        }
-    }
-}
-
-// position -> row: the rows sorted by level (stable: ascending row inside a level) placed at their
-// level's padded start; padding positions stay -1
-__global__ __launch_bounds__(256) void tri_order_kernel(const int32_t* __restrict__ lev_sorted,
-                                                        const int32_t* __restrict__ rows_sorted, int64_t n,
-                                                        const int32_t* __restrict__ ustart,
-                                                        const int32_t* __restrict__ pstart, int32_t* __restrict__ order) {
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) return;
-    const int32_t l = lev_sorted[k];
-    order[pstart[l] + (k - ustart[l])] = rows_sorted[k];
-}
-
-// per position: its row's off-diagonal count (plen[npos] = 0 closes the scan) and its pivot
-template <class S>
-__global__ __launch_bounds__(256) void tri_poslen_kernel(const int32_t* __restrict__ order, int64_t npos,
-                                                         const int32_t* __restrict__ offlen, const S* __restrict__ pv,
-                                                         S one, int32_t* __restrict__ plen, S* __restrict__ ppiv) {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p > npos) return;
-    if (p == npos) {
-        plen[p] = 0;
-        return;
-    }
-    const int32_t i = order[p];
-    plen[p] = i >= 0 ? offlen[i] : 0;
-    ppiv[p] = i >= 0 ? pv[i] : one;
-}
-
-// the position-ordered off-diagonal CSR: 16 lanes per position copy its row's entries (diagonal
-// skipped, stored order kept) to pptr[p]
-template <class S>
-__global__ __launch_bounds__(256) void tri_gather_kernel(const int32_t* __restrict__ order, int64_t npos,
-                                                         const int32_t* __restrict__ pptr,
-                                                         const int32_t* __restrict__ rp, const int32_t* __restrict__ ci,
-                                                         const S* __restrict__ val, const int32_t* __restrict__ offlen,
-                                                         int32_t* __restrict__ pcol, S* __restrict__ pval) {
-    const int64_t p = ((int64_t)blockIdx.x * 256 + threadIdx.x) / kRowLanes;
-    const int lane = threadIdx.x & (kRowLanes - 1);
-    if (p >= npos) return;
-    const int32_t i = order[p];
-    if (i < 0) return;
-    const int32_t e0 = rp[i], len = rp[i + 1] - e0, nd = len - offlen[i], base = pptr[p];
-    for (int32_t k = lane; k < len; k += kRowLanes) {
-        const int32_t c = ci[e0 + k];
-        if (c == i) continue;
-        const int32_t o = base + (c < i ? k : k - nd);
-        pcol[o] = c;
-        pval[o] = val[e0 + k];
-    }
-}
-
-// head rows: row -> head position (their columns become LDS positions)
-__global__ __launch_bounds__(256) void tri_rowpos_kernel(const int32_t* __restrict__ order, int32_t hpos,
-                                                         int32_t* __restrict__ rowpos) {
-    const int32_t p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= hpos) return;
-    const int32_t i = order[p];
-    if (i >= 0) rowpos[i] = p;
-}
-
-// 1 / pivot as the host build forms it (complex: in double, no contraction), for bitwise-equal heads
-__device__ __forceinline__ double head_recip(double p) { return 1.0 / p; }
-__device__ __forceinline__ float head_recip(float p) { return 1.0f / p; }
-__device__ __forceinline__ cplx head_recip(cplx p) {
-#pragma clang fp contract(off)
-    const double d = p.re * p.re + p.im * p.im;
-    return cplx{p.re / d, -p.im / d};
-}
-__device__ __forceinline__ cplxf head_recip(cplxf p) {
-#pragma clang fp contract(off)
-    const double re = p.re, im = p.im;
-    const double d = re * re + im * im;
-    return cplxf{(float)(re / d), (float)(-im / d)};
-}
-
-// one-wave head, pass-major (see sptrsv_whead_kernel): thread (q, u) fills row u of pass q; the
-// arrays arrive pre-filled with the padding (values 0, columns hpos, pivots 1, targets -1)
-template <class S>
-__global__ __launch_bounds__(256) void tri_whead_kernel(const int2* __restrict__ ptab, int32_t nreal,
-                                                        const int32_t* __restrict__ order, const int32_t* __restrict__ rp,
-                                                        const int32_t* __restrict__ ci, const S* __restrict__ val,
-                                                        const S* __restrict__ pv, const int32_t* __restrict__ rowpos,
-                                                        S* __restrict__ wval, int32_t* __restrict__ wcol,
-                                                        S* __restrict__ wrp, int32_t* __restrict__ wdst) {
-    const int32_t g = blockIdx.x * 256 + threadIdx.x;
-    const int32_t q = g / kWHeadRows, u = g % kWHeadRows;
-    if (q >= nreal) return;
-    const int2 pt = ptab[q];   // {first position, rows}
-    if (u >= pt.y) return;
-    const int32_t p = pt.x + u;
-    const int32_t i = order[p];
-    wrp[(size_t)q * kWHeadRows + u] = head_recip(pv[i]);
-    wdst[(size_t)q * kWHeadRows + u] = p;
-    int32_t idx = 0;
-    for (int32_t e = rp[i]; e < rp[i + 1]; ++e) {
-        const int32_t c = ci[e];
-        if (c == i) continue;
-        const size_t slot = ((size_t)q * 4 + (size_t)(idx % 4)) * 64 + (size_t)(4 * u + idx / 4);
-        wcol[slot] = rowpos[c];
-        wval[slot] = val[e];
-        ++idx;
-    }
-}
-
-template <class T>
-__global__ __launch_bounds__(256) void fill_kernel(T* __restrict__ a, int64_t n, T v) {
-    for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (int64_t)gridDim.x * 256) a[k] = v;
-}
-
 template <class S, class W>
 __global__ __launch_bounds__(256) void convert_kernel(const S* __restrict__ in, W* __restrict__ out, int64_t n) {
     for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -2226,27 +1897,6 @@ template <class S> inline constexpr bool kGmres = std::is_same_v<S, double> || s
 template <class S> using GmresScalar = std::conditional_t<is_real_v<S>, double, cplx>;
 int resident_blocks(eigsol_ctx* ctx, const void* kernel, int threads, size_t dyn_lds, int* grid);
 
-template <class S>
-static S make_sigma(double re, double im) {
-    if constexpr (std::is_same_v<S, double>) { (void)im; return re; }
-    else if constexpr (std::is_same_v<S, cplx>) return cplx{re, im};
-    else if constexpr (std::is_same_v<S, float>) { (void)im; return (float)re; }
-    else return cplxf{(float)re, (float)im};
-}
-// host arithmetic of the factor set-up (pivots d_i - sigma) in the scalar's own precision
-template <class S> static S h_add(S a, S b) {
-    if constexpr (is_real_v<S>) return a + b;
-    else return S{a.re + b.re, a.im + b.im};
-}
-template <class S> static S h_sub(S a, S b) {
-    if constexpr (is_real_v<S>) return a - b;
-    else return S{a.re - b.re, a.im - b.im};
-}
-template <class S> static bool h_zero(S a) {
-    if constexpr (is_real_v<S>) return a == 0;
-    else return a.re == 0 && a.im == 0;
-}
-
 static void shift_free(ShiftFactor* f) {
     if (!f) return;
     if (f->gm) gmres_free(f->gm);
@@ -2273,6 +1923,19 @@ static void shift_free(ShiftFactor* f) {
 }
 
 void shift_factor_free(ShiftFactor* f) { shift_free(f); }
+
+// an empty factor of A - sigma I (A: n x n, nnz stored entries) holding a reference to its context
+ShiftFactor* shift_factor_new(eigsol_ctx* ctx, int dtype, int64_t n, double sre, double sim, int64_t nnz) {
+    auto* f = new ShiftFactor();
+    f->ctx = ctx;
+    ctx_retain(f->ctx);
+    f->dtype = dtype;
+    f->n = n;
+    f->sig_re = sre;
+    f->sig_im = sim;
+    f->nnz_total = nnz;
+    return f;
+}
 
 template <class S>
 static int64_t kDenseSingleMax() {
@@ -2467,58 +2130,6 @@ int shift_factor_dense(eigsol_dense* A, const void* sigma, ShiftFactor** out) {
     }
 }
 
-// Level analysis of a triangular pattern (host, once per matrix): level(i) = 1 + max level of
-// the rows it reads; positions sorted by level, each level padded to a multiple of kWaveRows.
-static void level_order(const std::vector<int32_t>& rp, const std::vector<int32_t>& ci, int64_t n,
-                        bool upper, std::vector<int32_t>& order, int32_t& nlevels,
-                        std::vector<int64_t>& lstart, std::vector<int64_t>& lcount) {
-    std::vector<int32_t> lev(n, 0);
-    int32_t maxl = 0;
-    auto visit = [&](int64_t i) {
-        int32_t l = 0;
-        for (int32_t e = rp[i]; e < rp[i + 1]; ++e) l = std::max(l, lev[ci[e]] + 1);
-        lev[i] = l;
-        maxl = std::max(maxl, l);
-    };
-    if (upper) for (int64_t i = n - 1; i >= 0; --i) visit(i);
-    else for (int64_t i = 0; i < n; ++i) visit(i);
-    nlevels = maxl + 1;
-    std::vector<int64_t> cnt(nlevels + 1, 0);
-    for (int64_t i = 0; i < n; ++i) ++cnt[lev[i] + 1];
-    std::vector<int64_t> start(nlevels + 1, 0);
-    constexpr int64_t W = dev::kWaveRows;
-    for (int32_t l = 0; l < nlevels; ++l) start[l + 1] = start[l] + ((cnt[l + 1] + W - 1) / W) * W;
-    order.assign(start[nlevels], -1);
-    std::vector<int64_t> fill(start.begin(), start.end() - 1);
-    for (int64_t i = 0; i < n; ++i) order[fill[lev[i]]++] = (int32_t)i;
-    lstart = start;
-    lcount.assign(cnt.begin() + 1, cnt.end());
-}
-
-// Head of the level order solved by one workgroup from LDS: the longest prefix of levels whose
-// positions fit the LDS budget and whose levels are narrow (a wide level is cheaper spread over
-// the whole GPU).  EIGSOL_TRSV_HEAD_ROWS / EIGSOL_TRSV_HEAD_WIDTH override (0 rows: no head).
-template <class S>
-static int32_t head_levels(const std::vector<int64_t>& lstart, const std::vector<int64_t>& lcount,
-                           const std::vector<int32_t>& lmaxlen, int32_t nlevels, bool wave_head) {
-    int64_t cap = (int64_t)(150 * 1024) / (int64_t)sizeof(S);
-    // widest head level.  One-workgroup head: config 5 256 -> 0.861 ms, 1024 -> 0.872 ms per solve.
-    // One-wave head (16 rows per pass, ~0.26 us a pass): 64 -> 0.833 ms, 256 -> 0.879 ms (a wider
-    // level is cheaper in the tail, ~1.7 us a level)
-    int64_t width = wave_head ? 64 : 256;
-    if (const char* e = std::getenv("EIGSOL_TRSV_HEAD_ROWS")) cap = std::min<int64_t>(cap, std::atoll(e));
-    if (const char* e = std::getenv("EIGSOL_TRSV_HEAD_WIDTH")) width = std::atoll(e);
-    int32_t h = 0;
-    int64_t npass = 0;   // the pass table shares the LDS budget (8 bytes a pass)
-    while (h < nlevels && lcount[h] <= width && lmaxlen[h] <= dev::kRowLanes) {
-        const int64_t np = npass + (lcount[h] + dev::kHeadRows - 1) / dev::kHeadRows;
-        if ((lstart[h + 1] + 1) * (int64_t)sizeof(S) + (np + dev::kHeadDepth) * 8 > cap * (int64_t)sizeof(S)) break;
-        npass = np;
-        ++h;
-    }
-    return h;
-}
-
 template <class S>
 static const void* slice_kernel_ptr(int b, bool iter) {
     if (b == 4) return iter ? reinterpret_cast<const void*>(dev::sptrsv_slice_kernel<S, 4, true>)
@@ -2637,45 +2248,18 @@ static int gmres_dense_fallback(ShiftFactor* f, int rc_gmres) {
 }
 
 template <class S>
-static int factor_tri_host(eigsol_ctx* ctx, int dtype, int64_t n, std::vector<int32_t>& rp,
-                           std::vector<int32_t>& ci, std::vector<S>& v, bool up, double sre, double sim,
-                           ShiftFactor** out);
-
-template <class S>
-static int factor_tri_device(eigsol_csr* A, double sre, double sim, ShiftFactor** out, bool& declined);
-
-template <class S>
 static int factor_csr_t(eigsol_csr* A, double sre, double sim, ShiftFactor** out) {
     hipStream_t st = A->ctx->stream;
     const int64_t n = A->nrows, nnz = A->nnz;
-    // triangular matrices: analysis and layout on the device (EIGSOL_TRSV_HOST=1: the host build)
-    const char* host_env = std::getenv("EIGSOL_TRSV_HOST");
-    if (n > 0 && !(host_env && std::atoi(host_env))) {
-        bool declined = false;
-        const int rc = factor_tri_device<S>(A, sre, sim, out, declined);
-        if (!declined) return rc;
-    }
-    std::vector<int32_t> rp(n + 1), ci(nnz);
-    std::vector<S> v(nnz);
-    EIGSOL_HIP(hipMemcpyAsync(rp.data(), A->rowptr, (n + 1) * 4, hipMemcpyDeviceToHost, st));
-    EIGSOL_HIP(hipMemcpyAsync(ci.data(), A->col, nnz * 4, hipMemcpyDeviceToHost, st));
-    EIGSOL_HIP(hipMemcpyAsync(v.data(), A->val, nnz * sizeof(S), hipMemcpyDeviceToHost, st));
-    EIGSOL_HIP(hipStreamSynchronize(st));
-    bool up = true, lo = true;
-    for (int64_t i = 0; i < n && (up || lo); ++i)
-        for (int32_t e = rp[i]; e < rp[i + 1]; ++e) {
-            if (ci[e] < i) up = false;
-            if (ci[e] > i) lo = false;
-        }
-    if (up || lo) return factor_tri_host<S>(A->ctx, A->dtype, n, rp, ci, v, up, sre, sim, out);
-    auto* f = new ShiftFactor();
-    f->ctx = A->ctx;
-    ctx_retain(f->ctx);
-    f->dtype = A->dtype;
-    f->n = n;
-    f->sig_re = sre;
-    f->sig_im = sim;
-    f->nnz_total = nnz;
+    // triangular matrices: the level-ordered factor (tri_factor.hip); any other pattern comes back
+    // downloaded, for the dispatch below
+    TriHostCsr<S> h;
+    *out = nullptr;
+    EIGSOL_TRY(tri_build<S>(TriCsrView{A->ctx, A->dtype, n, nnz, A->rowptr, A->col, A->val}, sre, sim, -1, h, out));
+    if (*out) return EIGSOL_OK;
+    const std::vector<int32_t>&rp = h.rp_own, &ci = h.ci_own;
+    const std::vector<S>& v = h.v_own;
+    ShiftFactor* f = shift_factor_new(A->ctx, A->dtype, n, sre, sim, nnz);
     int rc = EIGSOL_OK;
     {
         if constexpr (!kDenseLU<S>) {
@@ -2748,14 +2332,7 @@ static int factor_csr_t(eigsol_csr* A, double sre, double sim, ShiftFactor** out
                 BandPlan bp;
                 band_plan(A->dtype, n, rp.data(), ci.data(), bp);
                 if (bp.ok) {
-                    auto* fb = new ShiftFactor();
-                    fb->ctx = A->ctx;
-                    ctx_retain(fb->ctx);
-                    fb->dtype = A->dtype;
-                    fb->n = n;
-                    fb->sig_re = sre;
-                    fb->sig_im = sim;
-                    fb->nnz_total = nnz;
+                    ShiftFactor* fb = shift_factor_new(A->ctx, A->dtype, n, sre, sim, nnz);
                     if (band_create(A->ctx, A->dtype, n, rp.data(), ci.data(), v.data(), sre, sim, bp, &fb->band) ==
                         EIGSOL_OK) {
                         fb->kind = 3;
@@ -2790,20 +2367,11 @@ static int factor_csr_t(eigsol_csr* A, double sre, double sim, ShiftFactor** out
     }
 }
 
-template <class S>
-static void tri_dump(const ShiftFactor* f);
-
-static int dev_upload(hipStream_t st, void** dst, const void* src, size_t bytes) {
-    EIGSOL_HIP(hipMalloc(dst, std::max<size_t>(bytes, 16)));
-    if (bytes && src) EIGSOL_HIP(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, st));
-    return EIGSOL_OK;
-}
-
 // Launch geometry of a level-ordered triangular factor (host- or device-built): the tail grid (one
 // residency round, cooperative launch), the multi-solve set-up and the partials grid.  Needs the
 // layout fields (tail variant, chunk_two, slice_b, head, chunks / slices) already set.
 template <class S>
-static int tri_launch_setup(ShiftFactor* f) {
+static int tri_launch_setup_t(ShiftFactor* f) {
     int rc = EIGSOL_OK;
     // tail grid: one residency round (cooperative launch), capped at EIGSOL_TRSV_BLOCKS_PER_CU
     // blocks per CU and by the work
@@ -2863,652 +2431,16 @@ static int tri_launch_setup(ShiftFactor* f) {
     return rc;
 }
 
-// Solve state of a triangular factor: the two polled value buffers (every row unsolved: the
-// sentinel; the zero slot z[n] stays 0 for good), the ticket / error words and the wave partials.
-template <class S>
-static int tri_state_alloc(ShiftFactor* f) {
-    hipStream_t st = f->ctx->stream;
-    const int64_t n = f->n;
-    EIGSOL_TRY(dev_upload(st, &f->z[0], nullptr, (n + 1) * sizeof(S)));
-    EIGSOL_TRY(dev_upload(st, &f->z[1], nullptr, (n + 1) * sizeof(S)));
-    EIGSOL_TRY(dev_upload(st, (void**)&f->work, nullptr, 64));
-    EIGSOL_TRY(dev_upload(st, (void**)&f->err, nullptr, 64));
-    EIGSOL_TRY(dev_upload(st, &f->wave_part, nullptr, (size_t)f->grid * dev::kWaves * sizeof(dev::part4)));
-    const uint32_t sent = (uint32_t)(dev::kSent & 0xffffffffu);
-    for (void* zb : f->z) {
-        hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(zb), (int)sent, n * sizeof(S) / 4, st);
-        hipMemsetAsync(static_cast<char*>(zb) + n * sizeof(S), 0, sizeof(S), st);
-    }
-    hipMemsetAsync(f->work, 0, 64, st);
-    hipMemsetAsync(f->err, 0, 64, st);
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(EIGSOL_E_HIP, "factor upload");
-    return EIGSOL_OK;
-}
-
-// Triangular CSR (host arrays, columns ascending per row) -> level-ordered factor of A - sigma I.
-template <class S>
-static int factor_tri_host(eigsol_ctx* ctx, int dtype, int64_t n, std::vector<int32_t>& rp,
-                           std::vector<int32_t>& ci, std::vector<S>& v, bool up, double sre, double sim,
-                           ShiftFactor** out) {
-    hipStream_t st = ctx->stream;
-    const int64_t nnz = rp[n];
-    auto* f = new ShiftFactor();
-    f->ctx = ctx;
-    ctx_retain(f->ctx);
-    f->dtype = dtype;
-    f->n = n;
-    f->sig_re = sre;
-    f->sig_im = sim;
-    f->nnz_total = nnz;
-    int rc = EIGSOL_OK;
-    f->upper = up ? 1 : 0;
-    // split diagonal / off-diagonal; pivots d_i - sigma (missing diagonal: 0 - sigma)
-    const S sig = make_sigma<S>(sre, sim);
-    std::vector<int32_t> orp(n + 1, 0), oci;
-    std::vector<S> ov, pv(n);
-    oci.reserve(nnz);
-    ov.reserve(nnz);
-    for (int64_t i = 0; i < n; ++i) {
-        S d = s_zero<S>();
-        for (int32_t e = rp[i]; e < rp[i + 1]; ++e) {
-            if (ci[e] == i) {
-                d = h_add(d, v[e]);
-            } else {
-                oci.push_back(ci[e]);
-                ov.push_back(v[e]);
-            }
-        }
-        pv[i] = h_sub(d, sig);
-        if (h_zero(pv[i])) {
-            shift_free(f);
-            return fail(EIGSOL_E_SOLVER, "solve_shifted: SparseLU factorization failed");
-        }
-        orp[i + 1] = (int32_t)oci.size();
-    }
-    f->nnz_off = (int64_t)oci.size();
-    std::vector<int32_t> order;
-    std::vector<int64_t> lstart, lcount;
-    level_order(orp, oci, n, up, order, f->nlevels, lstart, lcount);
-    f->npos = (int32_t)order.size();
-    std::vector<int32_t> lmaxlen(f->nlevels, 0);   // longest row (off-diagonal entries) per level
-    for (int32_t l = 0; l < f->nlevels; ++l)
-        for (int64_t p = lstart[l]; p < lstart[l] + lcount[l]; ++p)
-            lmaxlen[l] = std::max(lmaxlen[l], orp[order[p] + 1] - orp[order[p]]);
-    if (const char* e = std::getenv("EIGSOL_TRSV_HEAD")) f->wave_head = std::strcmp(e, "block") ? 1 : 0;
-    f->hlevels = head_levels<S>(lstart, lcount, lmaxlen, f->nlevels, f->wave_head != 0);
-    if (const char* e = std::getenv("EIGSOL_TRSV_POLL_FAST"))
-        f->poll_fast = (f->poll_fast & ~0xffff) | std::min(0xffff, std::max(0, std::atoi(e)));
-    if (const char* e = std::getenv("EIGSOL_TRSV_POLL_SLOW"))
-        f->poll_fast = (f->poll_fast & 0xffff) | (std::min(7, std::max(0, std::atoi(e))) << 16);
-    if (const char* e = std::getenv("EIGSOL_TRSV_POLL_MODE")) f->poll_mode = std::atoi(e);
-    f->hpos = (int32_t)lstart[f->hlevels];
-    std::vector<int2> passes;
-    for (int32_t l = 0; l < f->hlevels; ++l) {
-        const int32_t p0 = (int32_t)lstart[l], p1 = (int32_t)(lstart[l] + lcount[l]);
-        for (int32_t p = p0; p < p1; p += dev::kHeadRows) {
-            const int32_t e = std::min(p1, p + dev::kHeadRows);
-            passes.push_back(make_int2(p, e | (e == p1 ? dev::kPassBarrier : 0)));
-        }
-    }
-    while (!passes.empty() && passes.size() % dev::kHeadDepth) passes.push_back(make_int2(0, 0));   // empty
-    f->npass = (int32_t)passes.size();
-    std::vector<int32_t> rowpos;
-    if (f->hpos > 0) {
-        rowpos.assign(n, -1);
-        for (int32_t p = 0; p < f->hpos; ++p)
-            if (order[p] >= 0) rowpos[order[p]] = p;
-    }
-    // head, pass-major (see sptrsv_head_kernel): columns are LDS positions of earlier head rows
-    const size_t hslots = (size_t)f->npass * dev::kHeadThreads;
-    std::vector<int32_t> hcol(hslots, f->hpos);   // padding: the zero slot
-    std::vector<S> hval(hslots, s_zero<S>()), hpiv((size_t)f->npass * dev::kHeadRows, make_sigma<S>(1.0, 0.0));
-    for (int32_t q = 0; q < f->npass; ++q) {
-        const int32_t p0 = passes[q].x, p1 = passes[q].y & ~dev::kPassBarrier;
-        for (int32_t p = p0; p < p1; ++p) {
-            const size_t g = (size_t)q * dev::kHeadRows + (p - p0);
-            const int32_t i = order[p];
-            hpiv[g] = pv[i];
-            for (int32_t e = orp[i]; e < orp[i + 1]; ++e) {
-                hcol[g * dev::kRowLanes + (e - orp[i])] = rowpos[oci[e]];
-                hval[g * dev::kRowLanes + (e - orp[i])] = ov[e];
-            }
-        }
-    }
-    // one-wave head (see sptrsv_whead_kernel): passes of <= 16 rows inside a level, 4 lanes per row,
-    // entry idx of a row at lane 4 g + idx / 4, slot idx % 4; reciprocal pivots.
-    // EIGSOL_TRSV_HEAD=block selects the one-workgroup head.
-    std::vector<S> wval, wrp;
-    std::vector<int32_t> wcol, wdst;
-    if (f->hpos > 0) {
-        auto recip = [](S p) -> S {
-            if constexpr (is_real_v<S>) return (S)1 / p;
-            else {
-                const double d = (double)p.re * (double)p.re + (double)p.im * (double)p.im;
-                S r;
-                r.re = (decltype(p.re))((double)p.re / d);
-                r.im = (decltype(p.im))(-(double)p.im / d);
-                return r;
-            }
-        };
-        int32_t q = 0;
-        for (int32_t l = 0; l < f->hlevels; ++l) {
-            const int32_t p0 = (int32_t)lstart[l], p1 = (int32_t)(lstart[l] + lcount[l]);
-            for (int32_t p = p0; p < p1; p += dev::kWHeadRows, ++q) {
-                wval.resize((size_t)(q + 1) * 256, s_zero<S>());
-                wcol.resize((size_t)(q + 1) * 256, f->hpos);
-                wrp.resize((size_t)(q + 1) * dev::kWHeadRows, make_sigma<S>(1.0, 0.0));
-                wdst.resize((size_t)(q + 1) * dev::kWHeadRows, -1);
-                for (int32_t u = 0; u < std::min(dev::kWHeadRows, p1 - p); ++u) {
-                    const int32_t i = order[p + u];
-                    wrp[(size_t)q * dev::kWHeadRows + u] = recip(pv[i]);
-                    wdst[(size_t)q * dev::kWHeadRows + u] = p + u;
-                    for (int32_t e = orp[i]; e < orp[i + 1]; ++e) {
-                        const int32_t idx = e - orp[i];
-                        const size_t slot = ((size_t)q * 4 + (size_t)(idx % 4)) * 64 + (size_t)(4 * u + idx / 4);
-                        wcol[slot] = rowpos[oci[e]];
-                        wval[slot] = ov[e];
-                    }
-                }
-            }
-        }
-        while (q % dev::kWHeadDepth) {   // empty passes: the ring loop is straight-line code
-            ++q;
-            wval.resize((size_t)q * 256, s_zero<S>());
-            wcol.resize((size_t)q * 256, f->hpos);
-            wrp.resize((size_t)q * dev::kWHeadRows, make_sigma<S>(1.0, 0.0));
-            wdst.resize((size_t)q * dev::kWHeadRows, -1);
-        }
-        f->nwpass = q;
-    }
-    // tail variant: slices (row per lane) for few, very wide levels; chunks (16 lanes per row)
-    // otherwise.  EIGSOL_TRSV_TAIL=slice|chunk overrides.
-    {
-        // slices when most tail rows sit in levels of >= 64k rows (a wave's 64 rows then rarely
-        // wait); measured: one 1M-row level 74 vs 195 us, config 5 (widest level 21k) 1.3 vs 0.86 ms
-        int64_t trows = 0, wide = 0;
-        for (int32_t l = f->hlevels; l < f->nlevels; ++l) {
-            trows += lcount[l];
-            if (lcount[l] >= 65536) wide += lcount[l];
-        }
-        f->tail_chunks = (trows > 0 && 2 * wide < trows) ? 1 : 0;
-        if (const char* e = std::getenv("EIGSOL_TRSV_TAIL")) f->tail_chunks = std::strcmp(e, "slice") ? 1 : 0;
-    }
-    std::vector<int32_t> porder, pptr, pcol;
-    std::vector<S> pval, ppiv;
-    if (f->tail_chunks) {   // position-indexed copies: no dependent metadata loads in the kernel
-        f->chunk0 = f->hpos / dev::kWaveRows;
-        f->nchunks = f->npos / dev::kWaveRows;
-        porder = order;
-        pptr.assign((size_t)f->npos + 1, 0);
-        ppiv.assign((size_t)f->npos, make_sigma<S>(1.0, 0.0));
-        pcol.reserve(oci.size());
-        pval.reserve(oci.size());
-        int32_t longest = 0;
-        for (int32_t p = 0; p < f->npos; ++p) {
-            const int32_t i = order[p];
-            if (i >= 0) {
-                if (p >= f->hpos) longest = std::max(longest, orp[i + 1] - orp[i]);
-                for (int32_t e = orp[i]; e < orp[i + 1]; ++e) {
-                    pcol.push_back(oci[e]);
-                    pval.push_back(ov[e]);
-                }
-                ppiv[p] = pv[i];
-            }
-            pptr[p + 1] = (int32_t)pcol.size();
-        }
-        // rows past 16 entries: the second entry of every lane is polled with the first
-        // (EIGSOL_TRSV_TWO=0|1 overrides; round 4, the exact LU's U of config 5 made general)
-        f->chunk_two = longest > dev::kRowLanes ? 1 : 0;
-        if (const char* e = std::getenv("EIGSOL_TRSV_TWO")) f->chunk_two = std::atoi(e) != 0;
-    }
-    // tail slices (see sptrsv_slice_kernel): 64 rows of one level each; B = the smallest of
-    // 4 / 8 / 16 that holds the entries of at least 95 % of the slices (longer slices loop)
-    std::vector<int32_t> slen;   // longest row per slice
-    std::vector<int64_t> sfirst;
-    std::vector<int32_t> scount;
-    for (int32_t l = f->tail_chunks ? f->nlevels : f->hlevels; l < f->nlevels; ++l)
-        for (int64_t p = lstart[l]; p < lstart[l] + lcount[l]; p += 64) {
-            const int32_t c = (int32_t)std::min<int64_t>(64, lstart[l] + lcount[l] - p);
-            int32_t K = 0;
-            for (int32_t u = 0; u < c; ++u) K = std::max(K, orp[order[p + u] + 1] - orp[order[p + u]]);
-            sfirst.push_back(p);
-            scount.push_back(c);
-            slen.push_back(K);
-        }
-    f->nslices = (int32_t)slen.size();
-    {
-        std::vector<int32_t> sorted(slen);
-        std::sort(sorted.begin(), sorted.end());
-        const int32_t q95 = sorted.empty() ? 0 : sorted[(size_t)(0.95 * (double)(sorted.size() - 1))];
-        f->slice_b = q95 <= 4 ? 4 : (q95 <= 8 ? 8 : 16);
-        if (const char* e = std::getenv("EIGSOL_TRSV_SLICE_B")) {
-            const int b = std::atoi(e);
-            if (b == 4 || b == 8 || b == 16) f->slice_b = b;
-        }
-    }
-    const int32_t Bs = f->slice_b;
-    // the kernel prefetches "slice 0" for a wave past the last slice: slice 0 always exists (an
-    // empty one when the head holds every level)
-    std::vector<int2> smeta(std::max(1, f->nslices), make_int2(0, Bs));
-    std::vector<int32_t> trow((size_t)std::max(1, f->nslices) * 64, -1);
-    std::vector<S> tpiv((size_t)std::max(1, f->nslices) * 64, make_sigma<S>(1.0, 0.0));
-    int64_t tent = 0;
-    for (int32_t sl = 0; sl < f->nslices; ++sl) tent += 64 * (int64_t)std::max(slen[sl], Bs);
-    tent += 64 * (int64_t)Bs;   // the prefetch of "slice ns" reads slice 0's range: keep it in bounds
-    if (tent * (int64_t)sizeof(S) >= (int64_t)1 << 32) {
-        shift_free(f);
-        return fail(EIGSOL_E_UNSUPPORTED, "triangular solve: factor streams exceed 4 GiB");
-    }
-    std::vector<int32_t> tcol((size_t)tent, (int32_t)n);   // padding: the zero slot z[n]
-    std::vector<S> tval((size_t)tent, s_zero<S>());
-    {
-        int64_t off = 0;
-        for (int32_t sl = 0; sl < f->nslices; ++sl) {
-            const int32_t Kp = std::max(slen[sl], Bs);
-            smeta[sl] = make_int2((int32_t)off, Kp);
-            for (int32_t u = 0; u < scount[sl]; ++u) {
-                const int32_t i = order[sfirst[sl] + u];
-                trow[(size_t)sl * 64 + u] = i;
-                tpiv[(size_t)sl * 64 + u] = pv[i];
-                for (int32_t e = orp[i]; e < orp[i + 1]; ++e) {
-                    tcol[(size_t)(off + 64 * (e - orp[i]) + u)] = oci[e];
-                    tval[(size_t)(off + 64 * (e - orp[i]) + u)] = ov[e];
-                }
-            }
-            off += 64 * (int64_t)Kp;
-        }
-    }
-    std::vector<int32_t>().swap(oci);
-    std::vector<S>().swap(ov);
-    auto up_ = [&](void** dst, const void* src, size_t bytes) -> int { return dev_upload(st, dst, src, bytes); };
-    if (rc == EIGSOL_OK) rc = tri_launch_setup<S>(f);
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->order, order.data(), (size_t)f->hpos * 4);
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->hcol, hcol.data(), hcol.size() * 4);
-    if (rc == EIGSOL_OK) rc = up_(&f->hval, hval.data(), hval.size() * sizeof(S));
-    if (rc == EIGSOL_OK) rc = up_(&f->hpiv, hpiv.data(), hpiv.size() * sizeof(S));
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->passes, passes.data(), passes.size() * sizeof(int2));
-    if (rc == EIGSOL_OK) rc = up_(&f->wval, wval.data(), wval.size() * sizeof(S));
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->wcol, wcol.data(), wcol.size() * 4);
-    if (rc == EIGSOL_OK) rc = up_(&f->wrp, wrp.data(), wrp.size() * sizeof(S));
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->wdst, wdst.data(), wdst.size() * 4);
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->smeta, smeta.data(), smeta.size() * sizeof(int2));
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->trow, trow.data(), trow.size() * 4);
-    if (rc == EIGSOL_OK) rc = up_(&f->tpiv, tpiv.data(), tpiv.size() * sizeof(S));
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->tcol, tcol.data(), tcol.size() * 4);
-    if (rc == EIGSOL_OK) rc = up_(&f->tval, tval.data(), tval.size() * sizeof(S));
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->porder, porder.data(), porder.size() * 4);
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->pptr, pptr.data(), pptr.size() * 4);
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->pcol, pcol.data(), pcol.size() * 4);
-    if (rc == EIGSOL_OK) rc = up_(&f->pval, pval.data(), pval.size() * sizeof(S));
-    if (rc == EIGSOL_OK) rc = up_(&f->ppiv, ppiv.data(), ppiv.size() * sizeof(S));
-    if (rc == EIGSOL_OK) rc = tri_state_alloc<S>(f);
-    if (rc != EIGSOL_OK) { shift_free(f); return rc; }
-    f->kind = 0;
-    tri_dump<S>(f);
-    *out = f;
-    return EIGSOL_OK;
-}
-
-// EIGSOL_TRSV_DUMP=prefix (debugging): the built factor's position-indexed arrays, downloaded and
-// written to prefix_<name>.bin (host and device builds compare byte for byte)
-template <class S>
-static void tri_dump(const ShiftFactor* f) {
-    const char* pre = std::getenv("EIGSOL_TRSV_DUMP");
-    if (!pre || f->kind != 0) return;
-    hipStreamSynchronize(f->ctx->stream);
-    auto put = [&](const char* name, const void* d, size_t bytes) {
-        std::vector<unsigned char> h(bytes);
-        if (bytes && hipMemcpy(h.data(), d, bytes, hipMemcpyDeviceToHost) != hipSuccess) return;
-        const std::string path = std::string(pre) + "_" + name + ".bin";
-        if (FILE* fp = std::fopen(path.c_str(), "wb")) {
-            std::fwrite(h.data(), 1, bytes, fp);
-            std::fclose(fp);
-        }
-    };
-    const int32_t meta[12] = {f->nlevels, f->npos, f->hpos, f->hlevels, f->nwpass, f->chunk0, f->nchunks, f->chunk_two,
-                              f->tail_chunks, f->grid, f->multi, (int32_t)f->nnz_off};
-    if (FILE* fp = std::fopen((std::string(pre) + "_meta.bin").c_str(), "wb")) {
-        std::fwrite(meta, sizeof(meta), 1, fp);
-        std::fclose(fp);
-    }
-    put("porder", f->porder, (size_t)f->npos * 4);
-    put("pptr", f->pptr, ((size_t)f->npos + 1) * 4);
-    put("pcol", f->pcol, (size_t)f->nnz_off * 4);
-    put("pval", f->pval, (size_t)f->nnz_off * sizeof(S));
-    put("ppiv", f->ppiv, (size_t)f->npos * sizeof(S));
-    put("order", f->order, (size_t)f->hpos * 4);
-    put("wval", f->wval, (size_t)f->nwpass * 256 * sizeof(S));
-    put("wcol", f->wcol, (size_t)f->nwpass * 256 * 4);
-    put("wrp", f->wrp, (size_t)f->nwpass * 16 * sizeof(S));
-    put("wdst", f->wdst, (size_t)f->nwpass * 16 * 4);
-}
-
-hipError_t tri_sort_rows_by_level(hipStream_t st, const int32_t* lev, int32_t* lev_out, int32_t* rows_out, int64_t n,
-                                  int bits);
-hipError_t tri_exclusive_scan(hipStream_t st, const int32_t* in, int32_t* out, int64_t n);
-
-// Triangular CSR already on the device -> the level-ordered factor of A - sigma I, built on the device
-// (round 5; the host build of config 5's 1M-row factor took 0.37 s, most of it moving 320 MB of
-// matrix down and the layout back up).  The result is the host build's layout bit for bit: the
-// same levels, positions sorted by level with ascending rows inside a level (stable radix sort),
-// the same padding, the same position-indexed chunk CSR and the same one-wave head.  Only the small
-// per-level tables (counts, longest rows) travel to the host, which takes the same head / tail
-// decisions as factor_tri_host.  declined = true (nothing built) for a matrix that is not
-// triangular or a layout this build does not produce (slice tail, one-workgroup head): the caller
-// then takes the host path.
-template <class S>
-static int factor_tri_device(eigsol_csr* A, double sre, double sim, ShiftFactor** out, bool& declined) {
-    declined = false;
-    eigsol_ctx* ctx = A->ctx;
-    hipStream_t st = ctx->stream;
-    const int64_t n = A->nrows, nnz = A->nnz;
-    const S* val = static_cast<const S*>(A->val);
-    std::vector<void*> scratch;
-    auto dalloc = [&](void** p, size_t bytes) -> int {
-        EIGSOL_HIP(hipMalloc(p, std::max<size_t>(bytes, 16)));
-        scratch.push_back(*p);
-        return EIGSOL_OK;
-    };
-    int32_t* hostw = nullptr;   // pinned: flags[0..2], maxlev, err, nnz_off
-    ShiftFactor* f = nullptr;
-    auto finish = [&](int rc) {
-        hipStreamSynchronize(st);
-        for (void* p : scratch) hipFree(p);
-        if (hostw) hipHostFree(hostw);
-        if (rc != EIGSOL_OK || declined) {
-            if (f) shift_free(f);
-            return rc;
-        }
-        *out = f;
-        return rc;
-    };
-    constexpr int64_t W = dev::kWaveRows;
-    S* pv = nullptr;
-    int32_t *offlen = nullptr, *lev = nullptr, *lcnt = nullptr, *lmax = nullptr, *words = nullptr;
-    int rc = EIGSOL_OK;
-    if ((rc = dalloc((void**)&pv, n * sizeof(S))) || (rc = dalloc((void**)&offlen, n * 4)) ||
-        (rc = dalloc((void**)&lev, n * 4)) || (rc = dalloc((void**)&lcnt, (n + 1) * 4)) ||
-        (rc = dalloc((void**)&lmax, (n + 1) * 4)) || (rc = dalloc((void**)&words, 64)))
-        return finish(rc);
-    if (hipHostMalloc(&hostw, 64, hipHostMallocDefault) != hipSuccess) return finish(fail(EIGSOL_E_HIP, "hipHostMalloc"));
-    // words: [0..2] flags, [3] deepest level, [4] err, [5] ticket
-    hipMemsetAsync(words, 0, 64, st);
-    hipMemsetAsync(lev, 0xFF, n * 4, st);
-    hipMemsetAsync(lcnt, 0, (n + 1) * 4, st);
-    hipMemsetAsync(lmax, 0, (n + 1) * 4, st);
-    const unsigned gb = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL((dev::tri_rows_kernel<S>), dim3(gb), dim3(256), 0, st, A->rowptr, A->col, val, n,
-                       make_sigma<S>(sre, sim), pv, offlen, words);
-    EIGSOL_HIP(hipMemcpyAsync(hostw, words, 64, hipMemcpyDeviceToHost, st));
-    if (hipStreamSynchronize(st) != hipSuccess) return finish(fail(EIGSOL_E_HIP, "triangular analysis: row scan"));
-    const bool up = !hostw[0], lo = !hostw[1];
-    if (!up && !lo) {
-        declined = true;
-        return finish(EIGSOL_OK);
-    }
-    if (hostw[2]) return finish(fail(EIGSOL_E_SOLVER, "solve_shifted: SparseLU factorization failed"));
-    hipLaunchKernelGGL(dev::tri_level_kernel, dim3(std::max(1, 4 * ctx->num_cus)), dim3(256), 0, st, A->rowptr, A->col,
-                       offlen, n, up ? 1 : 0, lev, reinterpret_cast<uint32_t*>(words + 5), lcnt, lmax, words + 3,
-                       words + 4);
-    EIGSOL_HIP(hipMemcpyAsync(hostw, words, 64, hipMemcpyDeviceToHost, st));
-    if (hipStreamSynchronize(st) != hipSuccess) return finish(fail(EIGSOL_E_HIP, "triangular analysis: levels"));
-    if (hostw[4]) {   // a dependency wait ran out of time: build on the host instead
-        declined = true;
-        return finish(EIGSOL_OK);
-    }
-    const int32_t nlevels = hostw[3] + 1;
-    std::vector<int32_t> hcnt(nlevels), hmax(nlevels);
-    EIGSOL_HIP(hipMemcpyAsync(hcnt.data(), lcnt, nlevels * 4, hipMemcpyDeviceToHost, st));
-    EIGSOL_HIP(hipMemcpyAsync(hmax.data(), lmax, nlevels * 4, hipMemcpyDeviceToHost, st));
-    EIGSOL_HIP(hipStreamSynchronize(st));
-    std::vector<int64_t> lstart(nlevels + 1, 0), lcount(hcnt.begin(), hcnt.end());
-    for (int32_t l = 0; l < nlevels; ++l) lstart[l + 1] = lstart[l] + ((lcount[l] + W - 1) / W) * W;
-    f = new ShiftFactor();
-    f->ctx = ctx;
-    ctx_retain(ctx);
-    f->dtype = A->dtype;
-    f->n = n;
-    f->sig_re = sre;
-    f->sig_im = sim;
-    f->nnz_total = nnz;
-    f->upper = up ? 1 : 0;
-    f->nlevels = nlevels;
-    f->npos = (int32_t)lstart[nlevels];
-    if (const char* e = std::getenv("EIGSOL_TRSV_HEAD")) f->wave_head = std::strcmp(e, "block") ? 1 : 0;
-    f->hlevels = head_levels<S>(lstart, lcount, hmax, f->nlevels, f->wave_head != 0);
-    if (const char* e = std::getenv("EIGSOL_TRSV_POLL_FAST"))
-        f->poll_fast = (f->poll_fast & ~0xffff) | std::min(0xffff, std::max(0, std::atoi(e)));
-    if (const char* e = std::getenv("EIGSOL_TRSV_POLL_SLOW"))
-        f->poll_fast = (f->poll_fast & 0xffff) | (std::min(7, std::max(0, std::atoi(e))) << 16);
-    if (const char* e = std::getenv("EIGSOL_TRSV_POLL_MODE")) f->poll_mode = std::atoi(e);
-    f->hpos = (int32_t)lstart[f->hlevels];
-    {   // tail variant: the rule of factor_tri_host
-        int64_t trows = 0, wide = 0;
-        for (int32_t l = f->hlevels; l < f->nlevels; ++l) {
-            trows += lcount[l];
-            if (lcount[l] >= 65536) wide += lcount[l];
-        }
-        f->tail_chunks = (trows > 0 && 2 * wide < trows) ? 1 : 0;
-        if (const char* e = std::getenv("EIGSOL_TRSV_TAIL")) f->tail_chunks = std::strcmp(e, "slice") ? 1 : 0;
-    }
-    if (!f->tail_chunks || (f->hpos > 0 && !f->wave_head)) {
-        declined = true;
-        return finish(EIGSOL_OK);
-    }
-    // positions: rows sorted by level, at each level's padded start
-    int bits = 1;
-    while (bits < 31 && (int64_t(1) << bits) <= (int64_t)(nlevels - 1)) ++bits;
-    int32_t *lev_s = nullptr, *rows_s = nullptr, *ustart = nullptr, *pstart = nullptr, *plen = nullptr;
-    if ((rc = dalloc((void**)&lev_s, n * 4)) || (rc = dalloc((void**)&rows_s, n * 4)) ||
-        (rc = dalloc((void**)&ustart, (size_t)nlevels * 4)) || (rc = dalloc((void**)&pstart, (size_t)nlevels * 4)) ||
-        (rc = dalloc((void**)&plen, ((size_t)f->npos + 1) * 4)))
-        return finish(rc);
-    if (tri_sort_rows_by_level(st, lev, lev_s, rows_s, n, bits) != hipSuccess)
-        return finish(fail(EIGSOL_E_HIP, "triangular analysis: level sort"));
-    std::vector<int32_t> hu(nlevels), hp(nlevels);
-    {
-        int64_t u = 0;
-        for (int32_t l = 0; l < nlevels; ++l) {
-            hu[l] = (int32_t)u;
-            hp[l] = (int32_t)lstart[l];
-            u += lcount[l];
-        }
-    }
-    EIGSOL_HIP(hipMemcpyAsync(ustart, hu.data(), (size_t)nlevels * 4, hipMemcpyHostToDevice, st));
-    EIGSOL_HIP(hipMemcpyAsync(pstart, hp.data(), (size_t)nlevels * 4, hipMemcpyHostToDevice, st));
-    const int64_t npos = f->npos;
-    EIGSOL_TRY(dev_upload(st, (void**)&f->porder, nullptr, (size_t)npos * 4));
-    EIGSOL_HIP(hipMemsetAsync(f->porder, 0xFF, (size_t)npos * 4, st));
-    hipLaunchKernelGGL(dev::tri_order_kernel, dim3(gb), dim3(256), 0, st, lev_s, rows_s, n, ustart, pstart, f->porder);
-    EIGSOL_TRY(dev_upload(st, (void**)&f->order, nullptr, (size_t)f->hpos * 4));
-    if (f->hpos > 0)
-        EIGSOL_HIP(hipMemcpyAsync(f->order, f->porder, (size_t)f->hpos * 4, hipMemcpyDeviceToDevice, st));
-    // position-indexed chunk CSR: pivots, row pointers (scan of the off-diagonal counts), entries
-    const S one = make_sigma<S>(1.0, 0.0);
-    EIGSOL_TRY(dev_upload(st, &f->ppiv, nullptr, (size_t)npos * sizeof(S)));
-    EIGSOL_TRY(dev_upload(st, (void**)&f->pptr, nullptr, ((size_t)npos + 1) * 4));
-    hipLaunchKernelGGL((dev::tri_poslen_kernel<S>), dim3((unsigned)((npos + 256) / 256)), dim3(256), 0, st, f->porder,
-                       npos, offlen, pv, one, plen, static_cast<S*>(f->ppiv));
-    if (tri_exclusive_scan(st, plen, f->pptr, npos) != hipSuccess)
-        return finish(fail(EIGSOL_E_HIP, "triangular analysis: row pointer scan"));
-    EIGSOL_HIP(hipMemcpyAsync(hostw + 5, f->pptr + npos, 4, hipMemcpyDeviceToHost, st));
-    EIGSOL_HIP(hipStreamSynchronize(st));
-    f->nnz_off = hostw[5];
-    EIGSOL_TRY(dev_upload(st, (void**)&f->pcol, nullptr, (size_t)f->nnz_off * 4));
-    EIGSOL_TRY(dev_upload(st, &f->pval, nullptr, (size_t)f->nnz_off * sizeof(S)));
-    hipLaunchKernelGGL((dev::tri_gather_kernel<S>), dim3((unsigned)((npos * dev::kRowLanes + 255) / 256)), dim3(256), 0,
-                       st, f->porder, npos, f->pptr, A->rowptr, A->col, val, offlen, f->pcol, static_cast<S*>(f->pval));
-    f->chunk0 = f->hpos / dev::kWaveRows;
-    f->nchunks = f->npos / dev::kWaveRows;
-    {   // rows past 16 entries in the tail: the second entry of every lane is polled with the first
-        int32_t longest = 0;
-        for (int32_t l = f->hlevels; l < f->nlevels; ++l) longest = std::max(longest, hmax[l]);
-        f->chunk_two = longest > dev::kRowLanes ? 1 : 0;
-        if (const char* e = std::getenv("EIGSOL_TRSV_TWO")) f->chunk_two = std::atoi(e) != 0;
-    }
-    // one-wave head: passes of <= 16 rows inside a level, padded to the ring depth
-    std::vector<int2> ptab;
-    for (int32_t l = 0; l < f->hlevels; ++l) {
-        const int32_t p0 = (int32_t)lstart[l], p1 = (int32_t)(lstart[l] + lcount[l]);
-        for (int32_t p = p0; p < p1; p += dev::kWHeadRows) ptab.push_back(make_int2(p, std::min(dev::kWHeadRows, p1 - p)));
-    }
-    const int32_t nreal = (int32_t)ptab.size();
-    int32_t nw = nreal;
-    while (nw % dev::kWHeadDepth) ++nw;
-    f->nwpass = f->hpos > 0 ? nw : 0;
-    const size_t wslots = (size_t)f->nwpass * 256, wrows = (size_t)f->nwpass * dev::kWHeadRows;
-    EIGSOL_TRY(dev_upload(st, &f->wval, nullptr, wslots * sizeof(S)));
-    EIGSOL_TRY(dev_upload(st, (void**)&f->wcol, nullptr, wslots * 4));
-    EIGSOL_TRY(dev_upload(st, &f->wrp, nullptr, wrows * sizeof(S)));
-    EIGSOL_TRY(dev_upload(st, (void**)&f->wdst, nullptr, wrows * 4));
-    if (f->nwpass > 0) {
-        int32_t* rowpos = nullptr;
-        int2* dtab = nullptr;
-        if ((rc = dalloc((void**)&rowpos, n * 4)) || (rc = dalloc((void**)&dtab, (size_t)nreal * sizeof(int2))))
-            return finish(rc);
-        EIGSOL_HIP(hipMemcpyAsync(dtab, ptab.data(), (size_t)nreal * sizeof(int2), hipMemcpyHostToDevice, st));
-        EIGSOL_HIP(hipMemsetAsync(rowpos, 0xFF, n * 4, st));
-        EIGSOL_HIP(hipMemsetAsync(f->wval, 0, wslots * sizeof(S), st));
-        EIGSOL_HIP(hipMemsetAsync(f->wdst, 0xFF, wrows * 4, st));
-        hipLaunchKernelGGL((dev::fill_kernel<int32_t>), dim3(256), dim3(256), 0, st, f->wcol, (int64_t)wslots, f->hpos);
-        hipLaunchKernelGGL((dev::fill_kernel<S>), dim3(64), dim3(256), 0, st, static_cast<S*>(f->wrp), (int64_t)wrows, one);
-        hipLaunchKernelGGL(dev::tri_rowpos_kernel, dim3((unsigned)((f->hpos + 255) / 256)), dim3(256), 0, st, f->porder,
-                           f->hpos, rowpos);
-        hipLaunchKernelGGL((dev::tri_whead_kernel<S>), dim3((unsigned)((nreal * dev::kWHeadRows + 255) / 256)), dim3(256),
-                           0, st, dtab, nreal, f->porder, A->rowptr, A->col, val, pv, rowpos, static_cast<S*>(f->wval),
-                           f->wcol, static_cast<S*>(f->wrp), f->wdst);
-    }
-    // the one-workgroup head's tables stay empty (npass = 0: that head is not built here)
-    EIGSOL_TRY(dev_upload(st, (void**)&f->hcol, nullptr, 0));
-    EIGSOL_TRY(dev_upload(st, &f->hval, nullptr, 0));
-    EIGSOL_TRY(dev_upload(st, &f->hpiv, nullptr, 0));
-    EIGSOL_TRY(dev_upload(st, (void**)&f->passes, nullptr, 0));
-    // slice tail: none (nslices = 0), but the empty slice 0 the slice kernels may prefetch exists
-    {
-        f->slice_b = 4;
-        if (const char* e = std::getenv("EIGSOL_TRSV_SLICE_B")) {
-            const int b = std::atoi(e);
-            if (b == 4 || b == 8 || b == 16) f->slice_b = b;
-        }
-        const int32_t Bs = f->slice_b;
-        f->nslices = 0;
-        const std::vector<int2> smeta(1, make_int2(0, Bs));
-        const std::vector<int32_t> trow(64, -1), tcol((size_t)64 * Bs, (int32_t)n);
-        const std::vector<S> tpiv(64, one), tval((size_t)64 * Bs, s_zero<S>());
-        EIGSOL_TRY(dev_upload(st, (void**)&f->smeta, smeta.data(), smeta.size() * sizeof(int2)));
-        EIGSOL_TRY(dev_upload(st, (void**)&f->trow, trow.data(), trow.size() * 4));
-        EIGSOL_TRY(dev_upload(st, &f->tpiv, tpiv.data(), tpiv.size() * sizeof(S)));
-        EIGSOL_TRY(dev_upload(st, (void**)&f->tcol, tcol.data(), tcol.size() * 4));
-        EIGSOL_TRY(dev_upload(st, &f->tval, tval.data(), tval.size() * sizeof(S)));
-        EIGSOL_HIP(hipStreamSynchronize(st));   // the small host vectors above go out of scope
-    }
-    if (hipGetLastError() != hipSuccess) return finish(fail(EIGSOL_E_HIP, "triangular analysis: launch"));
-    if ((rc = tri_launch_setup<S>(f)) != EIGSOL_OK) return finish(rc);
-    if ((rc = tri_state_alloc<S>(f)) != EIGSOL_OK) return finish(rc);
-    f->kind = 0;
-    tri_dump<S>(f);
-    return finish(EIGSOL_OK);
-}
-
-// triangular factor from host CSR arrays (the ILU(0) factors of the GMRES path, gmres.hip)
-int shift_factor_tri(eigsol_ctx* ctx, int dtype, int64_t n, std::vector<int32_t>& rp, std::vector<int32_t>& ci,
-                     const void* vals, bool up, ShiftFactor** out) {
-    // the GMRES path's L / U (host arrays): uploaded once and analysed and laid out on the device
-    // like a triangular A (round 5: the 1M general-sparse factor's two host layouts took ~0.8 s);
-    // EIGSOL_TRSV_HOST=1 or a declined device analysis keeps the host build (the same bytes)
-    auto run = [&](auto tag) {
-        using S = decltype(tag);
-        const char* host_env = std::getenv("EIGSOL_TRSV_HOST");
-        if (n > 0 && !(host_env && std::atoi(host_env))) {
-            // a bare device CSR (row pointers, columns, values): all the device analysis reads
-            eigsol_csr A;
-            A.ctx = ctx;
-            A.dtype = dtype;
-            A.nrows = A.ncols = n;
-            A.nnz = rp[n];
-            hipStream_t st = ctx->stream;
-            int rc = EIGSOL_OK;
-            if (hipMalloc(&A.rowptr, (n + 1) * 4) != hipSuccess || hipMalloc(&A.col, std::max<int64_t>(1, A.nnz) * 4) != hipSuccess ||
-                hipMalloc(&A.val, std::max<int64_t>(1, A.nnz) * sizeof(S)) != hipSuccess)
-                rc = fail(EIGSOL_E_HIP, "solve_shifted: triangular factor upload");
-            if (rc == EIGSOL_OK) {
-                hipMemcpyAsync(A.rowptr, rp.data(), (n + 1) * 4, hipMemcpyHostToDevice, st);
-                hipMemcpyAsync(A.col, ci.data(), A.nnz * 4, hipMemcpyHostToDevice, st);
-                hipMemcpyAsync(A.val, vals, A.nnz * sizeof(S), hipMemcpyHostToDevice, st);
-            }
-            bool declined = false;
-            if (rc == EIGSOL_OK) rc = factor_tri_device<S>(&A, 0.0, 0.0, out, declined);
-            hipStreamSynchronize(st);
-            for (void* p : {(void*)A.rowptr, (void*)A.col, A.val})
-                if (p) hipFree(p);
-            A.rowptr = nullptr;
-            A.col = nullptr;
-            A.val = nullptr;
-            if (!declined || rc != EIGSOL_OK) return rc;
-        }
-        std::vector<S> v(static_cast<const S*>(vals), static_cast<const S*>(vals) + rp[n]);
-        return factor_tri_host<S>(ctx, dtype, n, rp, ci, v, up, 0.0, 0.0, out);
-    };
-    switch (dtype) {
-        case EIGSOL_C128: return run(cplx{});
-        case EIGSOL_F32: return run(0.0f);
-        case EIGSOL_C64: return run(cplxf{});
-        default: return run(0.0);
-    }
-}
-
-// A triangular factor given as device CSR arrays (the GMRES path's L / U, split on the device):
-// analysed and laid out on the device; a declined analysis or EIGSOL_TRSV_HOST=1 takes the host
-// build on a downloaded copy (the same bytes).  The arrays stay the caller's.
-int shift_factor_tri_dev(eigsol_ctx* ctx, int dtype, int64_t n, int32_t* rp, int32_t* ci, void* vals, int64_t nnz,
-                         bool up, ShiftFactor** out) {
-    auto run = [&](auto tag) -> int {
-        using S = decltype(tag);
-        hipStream_t st = ctx->stream;
-        const char* host_env = std::getenv("EIGSOL_TRSV_HOST");
-        if (n > 0 && !(host_env && std::atoi(host_env))) {
-            eigsol_csr A;
-            A.ctx = ctx;
-            A.dtype = dtype;
-            A.nrows = A.ncols = n;
-            A.nnz = nnz;
-            A.rowptr = rp;
-            A.col = ci;
-            A.val = vals;
-            bool declined = false;
-            const int rc = factor_tri_device<S>(&A, 0.0, 0.0, out, declined);
-            A.rowptr = nullptr;
-            A.col = nullptr;
-            A.val = nullptr;
-            if (!declined || rc != EIGSOL_OK) return rc;
-        }
-        std::vector<int32_t> hrp(n + 1), hci(nnz);
-        std::vector<S> hv(nnz);
-        EIGSOL_HIP(hipMemcpyAsync(hrp.data(), rp, (n + 1) * 4, hipMemcpyDeviceToHost, st));
-        EIGSOL_HIP(hipMemcpyAsync(hci.data(), ci, nnz * 4, hipMemcpyDeviceToHost, st));
-        EIGSOL_HIP(hipMemcpyAsync(hv.data(), vals, nnz * sizeof(S), hipMemcpyDeviceToHost, st));
-        EIGSOL_HIP(hipStreamSynchronize(st));
-        return factor_tri_host<S>(ctx, dtype, n, hrp, hci, hv, up, 0.0, 0.0, out);
-    };
-    switch (dtype) {
-        case EIGSOL_C128: return run(cplx{});
-        case EIGSOL_F32: return run(0.0f);
-        case EIGSOL_C64: return run(cplxf{});
-        default: return run(0.0);
-    }
+int tri_launch_setup(ShiftFactor* f) {
+    return by_dtype(f->dtype, [&](auto tag) { return tri_launch_setup_t<decltype(tag)>(f); });
 }
 
 int shift_factor_csr(eigsol_csr* A, const void* sigma, ShiftFactor** out) {
     if (A->dist) return fail(EIGSOL_E_UNSUPPORTED, "shifted inverse iteration: row-sharded matrices are not supported");
     double s[2] = {0.0, 0.0};
-    load_scalar(sigma, A->dtype, s[0], s[1]);
+    load_scalar(sigma, A->dtype, s[0], s[1]);   // a real dtype leaves s[1] = 0
     EIGSOL_HIP(hipSetDevice(A->ctx->device));
-    switch (A->dtype) {
-        case EIGSOL_C128: return factor_csr_t<cplx>(A, s[0], s[1], out);
-        case EIGSOL_F32: return factor_csr_t<float>(A, s[0], 0.0, out);
-        case EIGSOL_C64: return factor_csr_t<cplxf>(A, s[0], s[1], out);
-        default: return factor_csr_t<double>(A, s[0], 0.0, out);
-    }
+    return by_dtype(A->dtype, [&](auto tag) { return factor_csr_t<decltype(tag)>(A, s[0], s[1], out); });
 }
 
 int shift_grid(const ShiftFactor* f) { return (f->kind == 0 || f->dense_multi) ? f->grid : 1; }
@@ -3860,16 +2792,6 @@ static int shift_launch_t(ShiftFactor* f, bool iter, const void* b, void* y, voi
     }
     EIGSOL_HIP(hipGetLastError());
     return EIGSOL_OK;
-}
-
-template <class F>
-static int by_dtype(int dtype, F&& fn) {
-    switch (dtype) {
-        case EIGSOL_C128: return fn(cplx{});
-        case EIGSOL_F32: return fn(0.0f);
-        case EIGSOL_C64: return fn(cplxf{});
-        default: return fn(0.0);
-    }
 }
 
 int shift_iter_launch(ShiftFactor* f, void* buf0, void* buf1, PowerCtl* ctl, const void* rank_part,

@@ -31,19 +31,13 @@
 #include <vector>
 
 #include "internal.hpp"
+#include "shifted.hpp"
 #include "wide.hpp"
 
 namespace eigsol {
 
 int csr_upload(eigsol_ctx* ctx, int dtype, int64_t nrows, int64_t ncols, int64_t nnz, const int32_t* rowptr,
                const int32_t* colidx, const void* values, eigsol_csr** out, int64_t xoff);
-struct ShiftFactor;
-int shift_factor_csr(eigsol_csr* A, const void* sigma, ShiftFactor** out);
-int shift_factor_dense(eigsol_dense* A, const void* sigma, ShiftFactor** out);
-void shift_factor_free(ShiftFactor* f);
-int shift_solve_launch(ShiftFactor* f, const void* b_dev, void* y_dev);
-int shift_error(ShiftFactor* f);
-void shift_info(const ShiftFactor* f, double* bytes, int32_t* variant, int32_t* tiles);
 
 namespace wdev {
 

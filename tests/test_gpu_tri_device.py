@@ -1,6 +1,6 @@
 """GPU: the triangular factor of shiftedInversePowerMethod / solve_shifted
 (shifted_inverse_power_solver.hpp:21-79, solve_shifted.hpp:48-118) analysed and laid out on the device
-(round 5, shifted.hip factor_tri_device) against the host build (EIGSOL_TRSV_HOST=1).
+(round 5, tri_factor.hip factor_tri_device) against the host build (EIGSOL_TRSV_HOST=1).
 
 The device build produces the host build's layout bit for bit (same dependency levels, positions
 sorted by level with ascending rows inside a level, same padding, chunk CSR and one-wave head), so
@@ -8,7 +8,10 @@ every solve must agree BITWISE: solve_shifted's solution, the shifted inverse it
 trace, iteration count and eigenvector, and kernel_info.  Cases: config-5-class complex upper
 triangular (planted eigenvalue), real upper and lower, single precision, rows without a stored
 diagonal (pivot 0 - sigma), a diagonal matrix, rows longer than 16 entries (two entries per lane),
-an empty head (wide first level), and the zero-pivot error."""
+an empty head (wide first level), and the zero-pivot error.
+
+The slice tail and the one-workgroup head are laid out by the host build only (the device analysis
+declines): there the two routes into the host build, forced and declined, must agree bitwise."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -114,10 +117,8 @@ def test_missing_diagonal_diag_only_and_long_rows(ctx, monkeypatch):
     _same(ctx, D, 1.2501 + 0j, monkeypatch, K=1)
 
 
-def test_empty_head_wide_first_level(ctx, monkeypatch):
-    """A first level wider than the head allows (every row of the upper half independent): the
-    head is empty and the whole solve is the chunk tail."""
-    n = 40_000
+def _wide_first_level(n):
+    """Two levels of n / 2 rows: every row of the upper half reads six rows of the lower half."""
     rng = np.random.default_rng(4)
     rows, cols, vals = [np.arange(n)], [np.arange(n)], [1.0 + rng.random(n)]
     top = np.arange(n // 2)
@@ -128,7 +129,56 @@ def test_empty_head_wide_first_level(ctx, monkeypatch):
     M = sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(n, n))
     M.sum_duplicates()
     M.sort_indices()
-    _same(ctx, M, 1.5, monkeypatch, K=1)
+    return M
+
+
+def test_empty_head_wide_first_level(ctx, monkeypatch):
+    """A first level wider than the head allows (every row of the upper half independent): the
+    head is empty and the whole solve is the chunk tail."""
+    _same(ctx, _wide_first_level(40_000), 1.5, monkeypatch, K=1)
+
+
+def _solve(ctx, M, sigma, b, host, monkeypatch):
+    if host:
+        monkeypatch.setenv("EIGSOL_TRSV_HOST", "1")
+    else:
+        monkeypatch.delenv("EIGSOL_TRSV_HOST", raising=False)
+    A = E.CsrMatrix.from_scipy(ctx, M)
+    y = E.solve_shifted(A, sigma, b)
+    A.close()
+    return y
+
+
+def test_slice_tail_default_on_wide_levels(ctx, monkeypatch):
+    """Two levels of 70 000 rows (each >= 65 536): the default rule picks the slice tail, which only
+    the host build lays out, so the device analysis declines.  Both routes into the host build give
+    the same bits, and the solve meets the residual bound of test_solve_shifted_triangular_large."""
+    n = 140_000
+    M = _wide_first_level(n)
+    b = S.start_vector(n, np.float64, seed=6)
+    yd = _solve(ctx, M, 1.5, b, False, monkeypatch)
+    yh = _solve(ctx, M, 1.5, b, True, monkeypatch)
+    assert np.array_equal(yh, yd)
+    assert np.linalg.norm(M @ yd - 1.5 * yd - b) <= 1e-10 * np.linalg.norm(b)
+
+
+def test_block_head_forced(ctx, monkeypatch):
+    """EIGSOL_TRSV_HEAD=block: the one-workgroup head, which only the host build lays out (the
+    device analysis declines).  Both routes into the host build agree bitwise."""
+    n = 5000
+    rp, ci, v, _ = S.triu_complex(n, 16, seed=3)
+    M = _csr(rp, ci, v, n)
+    sigma = TARGET + 2e-3
+    monkeypatch.setenv("EIGSOL_TRSV_HEAD", "block")
+    x0 = S.start_vector(n, np.complex128, seed=5)
+    b = S.start_vector(n, np.complex128, seed=6)
+    yh, rh, _, ih = _run(ctx, M, sigma, x0, b, True, monkeypatch)
+    yd, rd, _, idv = _run(ctx, M, sigma, x0, b, False, monkeypatch)
+    assert ih == idv, (ih, idv)
+    assert np.array_equal(yh, yd)
+    assert np.linalg.norm(M @ yd - sigma * yd - b) <= 1e-10 * np.linalg.norm(b)
+    for r in (rh, rd):
+        assert r.converged and abs(r.eigenvalue - TARGET) <= 1e-10
 
 
 def test_zero_pivot_reported(ctx, monkeypatch):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Build one triangular factor on the device and on the host (EIGSOL_TRSV_DUMP) and report the
-first differences of their layouts (debugging aid for factor_tri_device)."""
+first differences of their layouts (debugging aid for tri_factor.hip's two builds)."""
 import os
 import sys
 
@@ -25,19 +25,25 @@ for mode in ("host", "dev"):
         os.environ.pop("EIGSOL_TRSV_HOST", None)
     s = E.ShiftedSession(A, sigma)
     s.close()
-names = ["meta", "porder", "pptr", "pcol", "pval", "ppiv", "order", "wval", "wcol", "wrp", "wdst"]
+META = ["nlevels", "npos", "hpos", "hlevels", "nwpass", "chunk0", "nchunks", "chunk_two", "tail_chunks", "grid",
+        "multi", "nnz_off", "npass", "nslices", "slice_b", "wave_head", "poll_fast", "poll_mode", "grid_multi",
+        "hconc", "red_grid"]
+names = ["meta", "porder", "pptr", "pcol", "pval", "ppiv", "order", "wval", "wcol", "wrp", "wdst",
+         "smeta", "trow", "tpiv", "tcol", "tval", "hcol", "hval", "hpiv", "passes"]
+INT32 = ("porder", "pptr", "pcol", "order", "wcol", "wdst", "smeta", "trow", "tcol", "hcol", "passes")
 for nm in names:
     a = np.fromfile(os.path.join(out, f"host_{nm}.bin"), np.uint8)
     b = np.fromfile(os.path.join(out, f"dev_{nm}.bin"), np.uint8)
     if nm == "meta":
-        print("meta host", a.view(np.int32).tolist(), "dev", b.view(np.int32).tolist())
+        for mode, m in (("host", a), ("dev", b)):
+            print("meta", mode, dict(zip(META, m.view(np.int32).tolist())))
         continue
     if len(a) != len(b):
         print(nm, "length", len(a), len(b))
         continue
     d = np.nonzero(a != b)[0]
     print(nm, "bytes", len(a), "differ", len(d), "first", d[:8].tolist())
-    if len(d) and nm in ("porder", "pptr", "pcol", "order", "wcol", "wdst"):
+    if len(d) and nm in INT32:
         i = d[0] // 4
         print("   host", a.view(np.int32)[max(0, i - 4):i + 8].tolist())
         print("   dev ", b.view(np.int32)[max(0, i - 4):i + 8].tolist())
