@@ -7,8 +7,10 @@
 //   to_hessenberg<S> / _dense      src/qr_method/to_hessenberg.hpp:23-119
 //   qr_decompose<S> / _dense       src/qr_method/qr_decompose.hpp:25-132
 //   qr_eigenvalues<S> / _dense     src/qr_method/qr_eigenvalues.hpp:40-147
-//   subspaceIteration<S>           new: nev dominant eigenpairs of a sparse matrix (eigsol_subspace_csr)
-//   krylovSchur<S>                 new: nev eigenpairs, dominant or nearest a shift (eigsol_krylov_csr)
+//   subspaceIteration<S> / _dense  new: nev dominant eigenpairs of a sparse matrix (eigsol_subspace_csr)
+//                                  or of a DenseMatrix<S> (eigsol_subspace_dense)
+//   krylovSchur<S> / _dense        new: nev eigenpairs, dominant or nearest a shift (eigsol_krylov_csr /
+//                                  eigsol_krylov_dense)
 //
 // Scalars: double and std::complex<double> natively; float and std::complex<float> natively for the
 // power method and the triangular-CSR shifted inverse, promoted to fp64 for the other solvers
@@ -240,15 +242,14 @@ EigenResult<S> shiftedInversePowerMethod(const Matrix& M, const ShiftedSolverOpt
 // The opts.nev eigenpairs of largest modulus of a sparse matrix (eigsol_subspace_csr: orthogonal
 // iteration with Rayleigh-Ritz on opts.block vectors).  S = double and std::complex<double>; the
 // default start block is drawn with random_vector<S> (column by column), so set_random_seed governs it.
+// subspaceIteration_dense takes a DenseMatrix<S> instead (eigsol_subspace_dense: the product runs on
+// the fp64 matrix cores); the matrix is on the device for the duration of the call.
 namespace detail {
-template <typename S>
-SubspaceResult<S> subspace_run(const Matrix& M, const SubspaceOptions& opts, const DenseMatrix<S>* X0) {
-    const char* who = "subspaceIteration";
-    if (M.scalar_type() != typeid(S)) throw std::runtime_error(std::string(who) + ": scalar type mismatch");
-    const std::int64_t n = M.rows();
-    if (n != M.cols()) throw std::runtime_error(std::string(who) + ": matrix must be square");
-    if (n == 0) throw std::runtime_error(std::string(who) + ": matrix has zero size");
-    if (M.isDense()) throw std::runtime_error(std::string(who) + ": only sparse matrices are supported");
+// Defaults, start block and result of one run on an n x n matrix; entry(o, X0, eigenvalues,
+// eigenvectors, residuals, iterations, converged) is the C entry bound to its matrix handle.
+template <typename S, typename Entry>
+SubspaceResult<S> subspace_device(std::int64_t n, const SubspaceOptions& opts, const DenseMatrix<S>* X0,
+                                  const char* who, Entry&& entry) {
     SubspaceResult<S> res;
     if constexpr (!DeviceScalar<S>) {
         throw std::runtime_error(std::string(who) + ": scalar type not supported by the device path "
@@ -276,10 +277,9 @@ SubspaceResult<S> subspace_run(const Matrix& M, const SubspaceOptions& opts, con
         res.residuals.assign(std::max<std::size_t>(k, 1), 0.0);
         res.eigenvectors = DenseMatrix<std::complex<double>>(n, static_cast<std::int64_t>(k));
         std::int32_t it = 0, conv = 0;
-        const int st = eigsol_subspace_csr(M.device<S>().csr(), &o, X0->data(),
-                                           reinterpret_cast<double*>(res.eigenvalues.data()),
-                                           k ? reinterpret_cast<double*>(res.eigenvectors.data()) : nullptr,
-                                           res.residuals.data(), &it, &conv);
+        const int st = entry(&o, X0->data(), reinterpret_cast<double*>(res.eigenvalues.data()),
+                             k ? reinterpret_cast<double*>(res.eigenvectors.data()) : nullptr, res.residuals.data(),
+                             &it, &conv);
         check(st, who);
         res.eigenvalues.resize(k);
         res.residuals.resize(k);
@@ -287,6 +287,37 @@ SubspaceResult<S> subspace_run(const Matrix& M, const SubspaceOptions& opts, con
         res.converged = conv != 0;
     }
     return res;
+}
+
+template <typename S>
+SubspaceResult<S> subspace_run(const Matrix& M, const SubspaceOptions& opts, const DenseMatrix<S>* X0) {
+    const char* who = "subspaceIteration";
+    if (M.scalar_type() != typeid(S)) throw std::runtime_error(std::string(who) + ": scalar type mismatch");
+    const std::int64_t n = M.rows();
+    if (n != M.cols()) throw std::runtime_error(std::string(who) + ": matrix must be square");
+    if (n == 0) throw std::runtime_error(std::string(who) + ": matrix has zero size");
+    if (M.isDense()) throw std::runtime_error(std::string(who) + ": only sparse matrices are supported");
+    return subspace_device<S>(n, opts, X0, who, [&](auto... a) {
+        if constexpr (DeviceScalar<S>) return eigsol_subspace_csr(M.device<S>().csr(), a...);
+        else return static_cast<int>(EIGSOL_E_UNSUPPORTED);
+    });
+}
+
+template <typename S>
+SubspaceResult<S> subspace_run_dense(const DenseMatrix<S>& A, const SubspaceOptions& opts, const DenseMatrix<S>* X0) {
+    const char* who = "subspaceIteration_dense";
+    const std::int64_t n = A.rows();
+    if (n != A.cols()) throw std::runtime_error(std::string(who) + ": matrix must be square");
+    if (n == 0) throw std::runtime_error(std::string(who) + ": matrix has zero size");
+    return subspace_device<S>(n, opts, X0, who, [&](auto... a) {
+        if constexpr (DeviceScalar<S>) {
+            // on the device for this call: the handle is freed on every return, a throw included
+            const std::shared_ptr<DeviceMatrix> d = DeviceMatrix::dense(dtype_of<S>(), n, n, A.data());
+            return eigsol_subspace_dense(d->dense(), a...);
+        } else {
+            return static_cast<int>(EIGSOL_E_UNSUPPORTED);
+        }
+    });
 }
 }  // namespace detail
 
@@ -298,20 +329,29 @@ template <ScalarConcept S>
 SubspaceResult<S> subspaceIteration(const Matrix& M, const SubspaceOptions& opts, const DenseMatrix<S>& X0) {
     return detail::subspace_run<S>(M, opts, &X0);
 }
+template <ScalarConcept S>
+SubspaceResult<S> subspaceIteration_dense(const DenseMatrix<S>& A, const SubspaceOptions& opts = SubspaceOptions{}) {
+    return detail::subspace_run_dense<S>(A, opts, nullptr);
+}
+template <ScalarConcept S>
+SubspaceResult<S> subspaceIteration_dense(const DenseMatrix<S>& A, const SubspaceOptions& opts,
+                                          const DenseMatrix<S>& X0) {
+    return detail::subspace_run_dense<S>(A, opts, &X0);
+}
 
 // ----------------------------------------------------------------------------------- Krylov-Schur
 // opts.nev eigenpairs of a sparse matrix by thick-restart Arnoldi (eigsol_krylov_csr): of largest
 // modulus, or nearest opts.shift with opts.shiftInvert.  S = double and std::complex<double>; the
 // default start vector is drawn with random_vector<S>, so set_random_seed governs it.
+// krylovSchur_dense takes a DenseMatrix<S> instead (eigsol_krylov_dense); with shiftInvert and a shift
+// next to an eigenvalue qr_eigenvalues_dense returned, it gives that eigenvalue's eigenvector.  The
+// matrix is on the device for the duration of the call.
 namespace detail {
-template <typename S>
-KrylovResult<S> krylov_run(const Matrix& M, const KrylovOptions<S>& opts, const Vector<S>* v0) {
-    const char* who = "krylovSchur";
-    if (M.scalar_type() != typeid(S)) throw std::runtime_error(std::string(who) + ": scalar type mismatch");
-    const std::int64_t n = M.rows();
-    if (n != M.cols()) throw std::runtime_error(std::string(who) + ": matrix must be square");
-    if (n == 0) throw std::runtime_error(std::string(who) + ": matrix has zero size");
-    if (M.isDense()) throw std::runtime_error(std::string(who) + ": only sparse matrices are supported");
+// Defaults, start vector and result of one run on an n x n matrix; entry(o, sigma, v0, eigenvalues,
+// eigenvectors, residuals, restarts, applications, converged) is the C entry bound to its handle.
+template <typename S, typename Entry>
+KrylovResult<S> krylov_device(std::int64_t n, const KrylovOptions<S>& opts, const Vector<S>* v0, const char* who,
+                              Entry&& entry) {
     KrylovResult<S> res;
     if constexpr (!DeviceScalar<S>) {
         throw std::runtime_error(std::string(who) + ": scalar type not supported by the device path "
@@ -339,10 +379,9 @@ KrylovResult<S> krylov_run(const Matrix& M, const KrylovOptions<S>& opts, const 
         res.eigenvectors = DenseMatrix<std::complex<double>>(n, static_cast<std::int64_t>(k));
         std::int32_t rs = 0, ap = 0, conv = 0;
         const S shift = opts.shift;
-        const int st = eigsol_krylov_csr(M.device<S>().csr(), &o, &shift, v0->data(),
-                                         reinterpret_cast<double*>(res.eigenvalues.data()),
-                                         k ? reinterpret_cast<double*>(res.eigenvectors.data()) : nullptr,
-                                         res.residuals.data(), &rs, &ap, &conv);
+        const int st = entry(&o, &shift, v0->data(), reinterpret_cast<double*>(res.eigenvalues.data()),
+                             k ? reinterpret_cast<double*>(res.eigenvectors.data()) : nullptr, res.residuals.data(),
+                             &rs, &ap, &conv);
         check(st, who);
         res.eigenvalues.resize(k);
         res.residuals.resize(k);
@@ -351,6 +390,37 @@ KrylovResult<S> krylov_run(const Matrix& M, const KrylovOptions<S>& opts, const 
         res.converged = conv != 0;
     }
     return res;
+}
+
+template <typename S>
+KrylovResult<S> krylov_run(const Matrix& M, const KrylovOptions<S>& opts, const Vector<S>* v0) {
+    const char* who = "krylovSchur";
+    if (M.scalar_type() != typeid(S)) throw std::runtime_error(std::string(who) + ": scalar type mismatch");
+    const std::int64_t n = M.rows();
+    if (n != M.cols()) throw std::runtime_error(std::string(who) + ": matrix must be square");
+    if (n == 0) throw std::runtime_error(std::string(who) + ": matrix has zero size");
+    if (M.isDense()) throw std::runtime_error(std::string(who) + ": only sparse matrices are supported");
+    return krylov_device<S>(n, opts, v0, who, [&](auto... a) {
+        if constexpr (DeviceScalar<S>) return eigsol_krylov_csr(M.device<S>().csr(), a...);
+        else return static_cast<int>(EIGSOL_E_UNSUPPORTED);
+    });
+}
+
+template <typename S>
+KrylovResult<S> krylov_run_dense(const DenseMatrix<S>& A, const KrylovOptions<S>& opts, const Vector<S>* v0) {
+    const char* who = "krylovSchur_dense";
+    const std::int64_t n = A.rows();
+    if (n != A.cols()) throw std::runtime_error(std::string(who) + ": matrix must be square");
+    if (n == 0) throw std::runtime_error(std::string(who) + ": matrix has zero size");
+    return krylov_device<S>(n, opts, v0, who, [&](auto... a) {
+        if constexpr (DeviceScalar<S>) {
+            // on the device for this call: the handle is freed on every return, a throw included
+            const std::shared_ptr<DeviceMatrix> d = DeviceMatrix::dense(dtype_of<S>(), n, n, A.data());
+            return eigsol_krylov_dense(d->dense(), a...);
+        } else {
+            return static_cast<int>(EIGSOL_E_UNSUPPORTED);
+        }
+    });
 }
 }  // namespace detail
 
@@ -361,6 +431,14 @@ KrylovResult<S> krylovSchur(const Matrix& M, const KrylovOptions<S>& opts = Kryl
 template <ScalarConcept S>
 KrylovResult<S> krylovSchur(const Matrix& M, const KrylovOptions<S>& opts, const Vector<S>& v0) {
     return detail::krylov_run<S>(M, opts, &v0);
+}
+template <ScalarConcept S>
+KrylovResult<S> krylovSchur_dense(const DenseMatrix<S>& A, const KrylovOptions<S>& opts = KrylovOptions<S>{}) {
+    return detail::krylov_run_dense<S>(A, opts, nullptr);
+}
+template <ScalarConcept S>
+KrylovResult<S> krylovSchur_dense(const DenseMatrix<S>& A, const KrylovOptions<S>& opts, const Vector<S>& v0) {
+    return detail::krylov_run_dense<S>(A, opts, &v0);
 }
 
 // --------------------------------------------------------------------------------- solve_shifted

@@ -194,9 +194,10 @@ int eigsol_power_kernel_name(eigsol_power* s, char* buf, size_t capacity);
  *               conditioned (Skeel condition number above 1e6), or by EIGSOL_DENSE_TRSV=1 */
 
 /* ---------------------------------------------------------------- block subspace iteration
- * The k = nev eigenpairs of largest modulus of a sparse matrix by orthogonal iteration with
- * Rayleigh-Ritz on a block of m = block >= k vectors (csrc/subspace.hip; the reference has no
- * counterpart).  Block vectors on the device are row-major interleaved: n x m with the vector
+ * The k = nev eigenpairs of largest modulus of a sparse or a dense matrix by orthogonal iteration
+ * with Rayleigh-Ritz on a block of m = block >= k vectors (csrc/subspace.hip; the reference has no
+ * counterpart).  The two entries differ in the product Z = A Q alone: eigsol_csr_spmm for a CSR
+ * matrix, eigsol_dense_gemm for a dense one.  Block vectors on the device are row-major interleaved: n x m with the vector
  * index fastest, X[i * m + j].
  *   Q = cholqr2(X0); repeat: Z = A Q; B = Q^H Z; (theta, Y) = eig(B), sorted by |theta| descending
  *   (moduli equal to 1e-12 relative: the larger imaginary part first); stop when every wanted theta
@@ -212,10 +213,10 @@ int eigsol_power_kernel_name(eigsol_power* s, char* buf, size_t capacity);
  * through eigenvalues of equal modulus (a conjugate pair split by k = m, say) may never settle
  * and end with converged = 0.
  * Status: EIGSOL_E_INVALID (null pointers; nev < 1; block < nev; block > 32; block > n;
- * max_iterations < 1; m outside 1..32 for spmm), EIGSOL_E_NOT_SQUARE, EIGSOL_E_ZERO_SIZE,
- * EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD matrices and row-sharded matrices, spmm too); all of
- * these are decided before any device call.
- * Out of scope: dense matrices, single precision, double-double, row-sharded matrices and a
+ * max_iterations < 1; m outside 1..32 for spmm / gemm), EIGSOL_E_NOT_SQUARE, EIGSOL_E_ZERO_SIZE,
+ * EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD matrices and row-sharded matrices, spmm / gemm too);
+ * all of these are decided before any device call.
+ * Out of scope: single precision, double-double, row-sharded matrices and a
  * session / step form. */
 typedef struct eigsol_subspace_options {
     int32_t max_iterations;      /* 1000 */
@@ -236,15 +237,40 @@ int eigsol_subspace_csr(eigsol_csr* A, const eigsol_subspace_options* opts, cons
                         double* eigenvalues, double* eigenvectors, double* residuals,
                         int32_t* iterations, int32_t* converged);
 
+/* Y = A X for a dense matrix on device buffers, row-major interleaved blocks as for eigsol_csr_spmm
+ * (X: ncols x m, X[i * m + j]; Y: nrows x m), 1 <= m <= 32, EIGSOL_F64 / EIGSOL_C128, any nrows,
+ * ncols >= 0 (rectangular too), stream-ordered (csrc/dense_block.hip).  The products run on the
+ * fp64 matrix cores (v_mfma_f64_16x16x4_f64; four real instructions per complex product) with m
+ * padded to 16 or 32 block columns; the padding and the remainders of A are masked on load.  A is
+ * read once per product.  Column chunks write partials to a workspace kept on the matrix (nchunk x
+ * nrows x m scalars, allocated on first use); a second kernel adds them in ascending chunk order:
+ * no floating-point atomics, two runs give identical bits.  The sums' order differs from
+ * eigsol_dense_gemv's, so m = 1 agrees with it to rounding, not bitwise.
+ * Status, decided before any device call: EIGSOL_E_INVALID (null pointer with a non-empty operand;
+ * m outside 1..32), EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD).  nrows == 0 returns EIGSOL_OK;
+ * ncols == 0 with nrows > 0 writes zeros to Y. */
+int eigsol_dense_gemm(eigsol_dense* A, int32_t m, const void* X_dev, void* Y_dev);
+
+/* eigsol_subspace_csr on a dense matrix: the same algorithm, arguments, output order, stopping test,
+ * rank-loss rule, counters and status codes (no row-sharded case); Z = A Q through
+ * eigsol_dense_gemm. */
+int eigsol_subspace_dense(eigsol_dense* A, const eigsol_subspace_options* opts, const void* X0,
+                          double* eigenvalues, double* eigenvectors, double* residuals,
+                          int32_t* iterations, int32_t* converged);
+
 /* ---------------------------------------------------------------- Krylov-Schur (thick-restart Arnoldi)
- * k = nev eigenpairs of a sparse matrix from a Krylov basis of m = ncv vectors (csrc/krylov.hip; the
+ * k = nev eigenpairs of a sparse or a dense matrix from a Krylov basis of m = ncv vectors (csrc/krylov.hip; the
  * reference has no counterpart), in two modes:
  *   EIGSOL_KRYLOV_LM            Op = A: the eigenvalues of largest modulus (the product runs on the
- *                               single-vector layout the eigsol_csr selected at upload);
+ *                               single-vector layout the eigsol_csr selected at upload, or
+ *                               through eigsol_dense_gemv);
  *   EIGSOL_KRYLOV_SHIFT_INVERT  Op = (A - sigma I)^-1: the eigenvalues nearest sigma.  A - sigma I is
  *                               factored once (the factors of the shifted inverse iteration below) and
  *                               solved once per step; a factor failure (a singular A - sigma I, say)
- *                               returns with that path's own status and message.
+ *                               returns with that path's own status and message.  For a dense
+ *                               matrix the factor is the partial-pivot LU of the dense shifted
+ *                               solves, which reports no zero pivot: a singular A - sigma I is not
+ *                               detected there, and the loop is bounded by max_restarts.
  * V is n x (m + 1) on the device, column-major, in the matrix dtype; S is the (m + 1) x m Rayleigh
  * matrix, B = S[:m, :m], b^T = S[m, :m].
  *   v_0 = v0 / ||v0||, p = 0; cycle 1 .. max_restarts:
@@ -274,7 +300,7 @@ int eigsol_subspace_csr(eigsol_csr* A, const eigsol_subspace_options* opts, cons
  * Status, all decided before any device call: EIGSOL_E_INVALID (null pointers; nev < 1;
  * ncv < nev + 2; ncv > 64; ncv > n; max_restarts < 1; unknown mode), EIGSOL_E_NOT_SQUARE,
  * EIGSOL_E_ZERO_SIZE, EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD matrices, row-sharded matrices).
- * Out of scope: dense matrices, single precision, double-double, row-sharded matrices, a session /
+ * Out of scope: single precision, double-double, row-sharded matrices, a session /
  * step form, generalised problems and selections other than these two. */
 #define EIGSOL_KRYLOV_LM 0
 #define EIGSOL_KRYLOV_SHIFT_INVERT 1
@@ -293,6 +319,12 @@ typedef struct eigsol_krylov_options {
 int eigsol_krylov_csr(eigsol_csr* A, const eigsol_krylov_options* opts, const void* sigma, const void* v0,
                       double* eigenvalues, double* eigenvectors, double* residuals, int32_t* restarts,
                       int32_t* applications, int32_t* converged);
+/* eigsol_krylov_csr on a dense matrix: the same algorithm, arguments, output order, breakdown rule,
+ * counters and status codes (no row-sharded case).  With shift-invert this returns the
+ * eigenvectors that belong to an eigenvalue eigsol_qr_eigenvalues_dense found (sigma next to it). */
+int eigsol_krylov_dense(eigsol_dense* A, const eigsol_krylov_options* opts, const void* sigma, const void* v0,
+                        double* eigenvalues, double* eigenvectors, double* residuals, int32_t* restarts,
+                        int32_t* applications, int32_t* converged);
 
 /* The solver's two kernel groups on device buffers (dtype EIGSOL_F64 / EIGSOL_C128), enqueued on the
  * context's stream.

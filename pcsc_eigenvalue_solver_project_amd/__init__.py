@@ -21,7 +21,7 @@ from ._capi import (EIGSOL_C64, EIGSOL_C128, EIGSOL_CDD, EIGSOL_DD, EIGSOL_E_INV
 __all__ = [
     "EigSolError", "SolverOptions", "EigenResult", "Context", "CsrMatrix", "DenseMatrix",
     "PowerSession", "power_method", "device_count", "lib", "last_error",
-    "SubspaceOptions", "SubspaceResult", "subspace_iteration", "spmm",
+    "SubspaceOptions", "SubspaceResult", "subspace_iteration", "spmm", "dense_mm",
     "KrylovOptions", "KrylovResult", "krylov_schur", "krylov_orth", "krylov_rotate",
 ]
 
@@ -302,6 +302,10 @@ class DenseMatrix:
     def gemv(self, x_dev: int, y_dev: int) -> None:
         call("eigsol_dense_gemv", self.handle, C.c_void_p(x_dev), C.c_void_p(y_dev))
 
+    def gemm(self, x_dev: int, y_dev: int, m: int) -> None:
+        """Y = A X on row-major interleaved device blocks (X: ncols x m, Y: nrows x m)."""
+        call("eigsol_dense_gemm", self.handle, int(m), C.c_void_p(x_dev), C.c_void_p(y_dev))
+
     def close(self) -> None:
         if getattr(self, "handle", None):
             lib().eigsol_dense_destroy(self.handle)
@@ -446,6 +450,22 @@ def spmm(matrix: CsrMatrix, X) -> np.ndarray:
     if X.ndim != 2 or X.shape[0] != ncols:
         raise EigSolError(EIGSOL_E_SIZE_MISMATCH, f"X has shape {X.shape}, the matrix has {ncols} columns")
     m = X.shape[1]
+    return _block_product(matrix, X, matrix.spmm)
+
+
+def dense_mm(matrix: DenseMatrix, X) -> np.ndarray:
+    """``A @ X`` for a host block X (ncols x m, 1 <= m <= 32) through ``eigsol_dense_gemm`` (the fp64
+    matrix cores; double and complex double matrices)."""
+    X = np.asarray(X)
+    if X.ndim != 2 or X.shape[0] != matrix.shape[1]:
+        raise EigSolError(EIGSOL_E_SIZE_MISMATCH, f"X has shape {X.shape}, the matrix has {matrix.shape[1]} columns")
+    if is_wide(matrix.dtype):
+        raise EigSolError(EIGSOL_E_UNSUPPORTED, "dense_mm: long double matrices are not supported")
+    return _block_product(matrix, X, matrix.gemm)
+
+
+def _block_product(matrix, X, product) -> np.ndarray:
+    nrows, m = matrix.shape[0], X.shape[1]
     Xr = np.ascontiguousarray(X, dtype=matrix.dtype)      # row-major = interleaved
     Y = np.empty((nrows, m), dtype=matrix.dtype)
     ctx = matrix.ctx
@@ -453,7 +473,7 @@ def spmm(matrix: CsrMatrix, X) -> np.ndarray:
     try:
         if Xr.nbytes:
             ctx.h2d(dx, Xr)
-        matrix.spmm(dx, dy, m)
+        product(dx, dy, m)
         if Y.nbytes:
             ctx.d2h(Y, dy)
     finally:
@@ -482,8 +502,8 @@ class SubspaceResult:
 
 def subspace_iteration(matrix, nev: int, opts: SubspaceOptions = SubspaceOptions(), block: Optional[int] = None,
                        X0=None, seed: int = 0) -> SubspaceResult:
-    """The ``nev`` eigenpairs of largest modulus of a device-resident CSR matrix by block subspace
-    iteration with Rayleigh-Ritz (``eigsol_subspace_csr``).  ``block`` (default min(n, 32, 2 nev))
+    """The ``nev`` eigenpairs of largest modulus of a device-resident CSR or dense matrix by block
+    subspace iteration with Rayleigh-Ritz (``eigsol_subspace_csr`` / ``eigsol_subspace_dense``).  ``block`` (default min(n, 32, 2 nev))
     vectors are iterated; ``X0`` (n x block) defaults to uniform(-1, 1) entries from
     ``numpy.random.default_rng(seed)``.  A cut between nev and nev + 1 through eigenvalues of equal
     modulus (a conjugate pair split by nev = block) may end with ``converged`` false."""
@@ -508,7 +528,8 @@ def subspace_iteration(matrix, nev: int, opts: SubspaceOptions = SubspaceOptions
     it, conv = C.c_int32(0), C.c_int32(0)
     o = SubspaceOptionsC(int(opts.max_iterations), float(opts.tolerance), float(opts.residual_tolerance), nev, m)
     pd = C.POINTER(C.c_double)
-    call("eigsol_subspace_csr", matrix.handle, C.byref(o), _ptr(Xf), ev.ctypes.data_as(pd),
+    fn = "eigsol_subspace_dense" if isinstance(matrix, DenseMatrix) else "eigsol_subspace_csr"
+    call(fn, matrix.handle, C.byref(o), _ptr(Xf), ev.ctypes.data_as(pd),
          vec.ctypes.data_as(pd) if vec.size else None, res.ctypes.data_as(pd), C.byref(it), C.byref(conv))
     return SubspaceResult(ev[:k], vec, res[:k], int(it.value), bool(conv.value))
 
@@ -538,8 +559,8 @@ def default_ncv(n: int, nev: int) -> int:
 
 def krylov_schur(matrix, nev: int, opts: KrylovOptions = KrylovOptions(), sigma=None, ncv: Optional[int] = None,
                  v0=None, seed: int = 0) -> KrylovResult:
-    """``nev`` eigenpairs of a device-resident CSR matrix by the Krylov-Schur method
-    (``eigsol_krylov_csr``): those of largest modulus (``sigma is None``), or those nearest ``sigma``
+    """``nev`` eigenpairs of a device-resident CSR or dense matrix by the Krylov-Schur method
+    (``eigsol_krylov_csr`` / ``eigsol_krylov_dense``): those of largest modulus (``sigma is None``), or those nearest ``sigma``
     through one factorisation of A - sigma I.  ``ncv`` basis vectors (default
     min(n, 64, max(2 nev + 1, 20))); ``v0`` defaults to uniform(-1, 1) entries from
     ``numpy.random.default_rng(seed)`` (complex for complex matrices)."""
@@ -563,7 +584,8 @@ def krylov_schur(matrix, nev: int, opts: KrylovOptions = KrylovOptions(), sigma=
                        EIGSOL_KRYLOV_LM if sigma is None else EIGSOL_KRYLOV_SHIFT_INVERT)
     sg = None if sigma is None else _sigma(sigma, matrix.dtype)
     pd = C.POINTER(C.c_double)
-    call("eigsol_krylov_csr", matrix.handle, C.byref(o), None if sg is None else _ptr(sg), _ptr(v0),
+    fn = "eigsol_krylov_dense" if isinstance(matrix, DenseMatrix) else "eigsol_krylov_csr"
+    call(fn, matrix.handle, C.byref(o), None if sg is None else _ptr(sg), _ptr(v0),
          ev.ctypes.data_as(pd), vec.ctypes.data_as(pd) if vec.size else None, res.ctypes.data_as(pd), C.byref(rs),
          C.byref(ap), C.byref(conv))
     return KrylovResult(ev[:k], vec, res[:k], int(rs.value), int(ap.value), bool(conv.value))

@@ -109,6 +109,9 @@ SIGNATURES = {
     "eigsol_dense_create": [_vp, C.c_int, _i64, _i64, _vp, _ppv],
     "eigsol_dense_destroy": [_vp],
     "eigsol_dense_gemv": [_vp, _vp, _vp],
+    "eigsol_dense_gemm": [_vp, _i32, _vp, _vp],
+    "eigsol_subspace_dense": [_vp, C.POINTER(SubspaceOptionsC), _vp, _pd, _pd, _pd, _pi32, _pi32],
+    "eigsol_krylov_dense": [_vp, C.POINTER(KrylovOptionsC), _vp, _vp, _pd, _pd, _pd, _pi32, _pi32, _pi32],
     "eigsol_power_csr": [_vp, C.POINTER(SolverOptionsC), _vp, _vp, _vp, _pi32, _pi32],
     "eigsol_power_dense": [_vp, C.POINTER(SolverOptionsC), _vp, _vp, _vp, _pi32, _pi32],
     "eigsol_power_create_csr": [_vp, _i32, _ppv],

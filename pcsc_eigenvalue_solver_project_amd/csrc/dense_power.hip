@@ -249,6 +249,7 @@ void dense_release(eigsol_dense* A) {
     (void)hipStreamSynchronize(A->ctx->stream);
     if (A->ypart) (void)hipFree(A->ypart);
     if (A->tile_cnt) (void)hipFree(A->tile_cnt);
+    if (A->gpart) (void)hipFree(A->gpart);
     if (A->a) (void)hipFree(A->a);
     if (A->shadow) dense_release(A->shadow);
     eigsol_ctx* c = A->ctx;

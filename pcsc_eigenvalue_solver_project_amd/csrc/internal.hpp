@@ -311,5 +311,8 @@ struct eigsol_dense {
     void* ypart = nullptr;
     uint32_t* tile_cnt = nullptr;
     int ntr = 0, nchunk = 1, cw = 1;
+    // block-product workspace (dense_block.hip, allocated on first use): per-chunk partials of Y
+    void* gpart = nullptr;
+    size_t gpart_bytes = 0;
     eigsol_dense* shadow = nullptr;   // extended precision: the matrix rounded to fp64 (see eigsol_csr)
 };

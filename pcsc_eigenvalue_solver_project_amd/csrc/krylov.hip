@@ -1,5 +1,6 @@
-// Krylov-Schur (thick-restart Arnoldi): k eigenpairs of a sparse matrix, of largest modulus or
-// nearest a shift, from a Krylov basis of m <= 64 vectors (algorithm: include/eigsol_hip.h).
+// Krylov-Schur (thick-restart Arnoldi): k eigenpairs of a sparse or a dense matrix, of largest
+// modulus or nearest a shift, from a Krylov basis of m <= 64 vectors (algorithm:
+// include/eigsol_hip.h).  The driver reaches the matrix through LinearOp (linear_op.hpp).
 //
 // The basis V is n x (m + 1), column-major, so that a basis vector is a contiguous operand of the
 // single-vector SpMV layouts and of the shifted solves.  Per Arnoldi step the host enqueues the
@@ -20,13 +21,14 @@
 // No floating-point atomics: every reduction is ordered workgroup partials plus a fixed-order final
 // sum, so two runs give identical bits.
 //
-// Out of scope: dense matrices, single precision, double-double, row-sharded matrices, a session /
+// Out of scope: single precision, double-double, row-sharded matrices, a session /
 // step form, generalised problems and selections other than largest modulus / nearest sigma.
 #include <algorithm>
 #include <cmath>
 #include <complex>
 
 #include "kernels_common.hpp"
+#include "linear_op.hpp"
 #include "shifted.hpp"
 #include "small_eig.hpp"
 
@@ -455,14 +457,14 @@ bool orth_basis(int m, int ncand, int p, std::vector<T>& C, std::vector<T>& Q) {
 }
 
 template <class S>
-int krylov_run(eigsol_csr* A, const eigsol_krylov_options* o, const void* sigma, const void* v0v, double* eigenvalues,
+int krylov_run(const LinearOp& A, const eigsol_krylov_options* o, const void* sigma, const void* v0v, double* eigenvalues,
                double* eigenvectors, double* residuals, int32_t* restarts, int32_t* applications, int32_t* converged) {
     using HS = typename host_of<S>::type;
     constexpr bool real = std::is_same_v<S, double>;
-    const int64_t n = A->nrows;
+    const int64_t n = A.nrows();
     const int m = o->ncv, k = o->nev;
     const bool invert = o->mode == EIGSOL_KRYLOV_SHIFT_INVERT;
-    const eigsol_ctx* ctx = A->ctx;
+    const eigsol_ctx* ctx = A.ctx();
     hipStream_t st = ctx->stream;
 
     // v_0 = v0 / ||v0|| on the host
@@ -490,9 +492,9 @@ int krylov_run(eigsol_csr* A, const eigsol_krylov_options* o, const void* sigma,
     cd sig(0.0, 0.0);
     if (invert) {
         double sr = 0.0, si = 0.0;
-        load_scalar(sigma, A->dtype, sr, si);
+        load_scalar(sigma, A.dtype(), sr, si);
         sig = cd(sr, si);
-        EIGSOL_TRY(shift_factor_csr(A, sigma, &fac.f));
+        EIGSOL_TRY(A.factor(sigma, &fac.f));
     }
 
     // columns start on 16-byte boundaries for every n
@@ -524,7 +526,7 @@ int krylov_run(eigsol_csr* A, const eigsol_krylov_options* o, const void* sigma,
             S* vj = V + (size_t)j * ldv;
             S* wj = V + (size_t)(j + 1) * ldv;
             if (invert) EIGSOL_TRY(shift_solve_launch(fac.f, vj, wj));
-            else EIGSOL_TRY(eigsol_csr_spmv(A, vj, wj));
+            else EIGSOL_TRY(A.apply(vj, wj));
             EIGSOL_TRY(orth_step<S>(ws, V, ldv, j + 1, wj, n, SD + (size_t)j * ms, (double)m, st));
         }
         // the cycle's one host wait: S, the breakdown word and the factor's error word
@@ -653,13 +655,13 @@ int krylov_run(eigsol_csr* A, const eigsol_krylov_options* o, const void* sigma,
             double *xi = xr + n, *yr = xr + 2 * n, *yi = xr + 3 * n;
             hipLaunchKernelGGL(ks::ks_split_kernel, grid, blk, 0, st, x, n, xr, xi);
             EIGSOL_HIP(hipGetLastError());
-            EIGSOL_TRY(eigsol_csr_spmv(A, xr, yr));
-            EIGSOL_TRY(eigsol_csr_spmv(A, xi, yi));
+            EIGSOL_TRY(A.apply(xr, yr));
+            EIGSOL_TRY(A.apply(xi, yi));
             hipLaunchKernelGGL(ks::ks_resid_kernel, grid, blk, 0, st, (const cplx*)nullptr, (const double*)yr,
                                (const double*)yi, x, n, lam[c].real(), lam[c].imag(), np_);
         } else {
             cplx* y = ybuf.as<cplx>();
-            EIGSOL_TRY(eigsol_csr_spmv(A, x, y));
+            EIGSOL_TRY(A.apply(x, y));
             hipLaunchKernelGGL(ks::ks_resid_kernel, grid, blk, 0, st, (const cplx*)y, (const double*)nullptr,
                                (const double*)nullptr, x, n, lam[c].real(), lam[c].imag(), np_);
         }
@@ -716,6 +718,26 @@ int rotate_entry(eigsol_ctx* ctx, int64_t n, int m, int p, S* V, int64_t ldv, co
     return EIGSOL_OK;
 }
 
+// the checks every matrix kind shares, then the run
+int krylov_entry(const LinearOp& A, int64_t ncols, const eigsol_krylov_options* opts, const void* sigma,
+                 const void* v0, double* eigenvalues, double* eigenvectors, double* residuals, int32_t* restarts,
+                 int32_t* applications, int32_t* converged) {
+    if (A.dtype() != EIGSOL_F64 && A.dtype() != EIGSOL_C128)
+        return fail(EIGSOL_E_UNSUPPORTED, "krylov_schur: only double and complex double matrices are supported");
+    if (A.nrows() != ncols) return fail(EIGSOL_E_NOT_SQUARE, "krylov_schur: matrix must be square");
+    if (A.nrows() == 0) return fail(EIGSOL_E_ZERO_SIZE, "krylov_schur: matrix has zero size");
+    if (opts->nev < 1) return fail(EIGSOL_E_INVALID, "krylov_schur: nev must be at least 1");
+    if (opts->ncv > dev::ks::kMaxBasis) return fail(EIGSOL_E_INVALID, "krylov_schur: ncv must be at most 64");
+    if (opts->ncv < opts->nev + 2) return fail(EIGSOL_E_INVALID, "krylov_schur: ncv must be at least nev + 2");
+    if (opts->ncv > A.nrows()) return fail(EIGSOL_E_INVALID, "krylov_schur: ncv exceeds the matrix order");
+    if (opts->max_restarts < 1) return fail(EIGSOL_E_INVALID, "krylov_schur: max_restarts must be at least 1");
+    if (A.dtype() == EIGSOL_C128)
+        return krylov_run<cplx>(A, opts, sigma, v0, eigenvalues, eigenvectors, residuals, restarts, applications,
+                                converged);
+    return krylov_run<double>(A, opts, sigma, v0, eigenvalues, eigenvectors, residuals, restarts, applications,
+                              converged);
+}
+
 }  // namespace
 }  // namespace eigsol
 
@@ -732,20 +754,20 @@ int eigsol_krylov_csr(eigsol_csr* A, const eigsol_krylov_options* opts, const vo
     if (opts->mode == EIGSOL_KRYLOV_SHIFT_INVERT && !sigma)
         return fail(EIGSOL_E_INVALID, "eigsol_krylov_csr: null sigma in shift-invert mode");
     if (A->dist) return fail(EIGSOL_E_UNSUPPORTED, "krylov_schur: row-sharded matrix");
-    if (A->dtype != EIGSOL_F64 && A->dtype != EIGSOL_C128)
-        return fail(EIGSOL_E_UNSUPPORTED, "krylov_schur: only double and complex double matrices are supported");
-    if (A->nrows != A->ncols) return fail(EIGSOL_E_NOT_SQUARE, "krylov_schur: matrix must be square");
-    if (A->nrows == 0) return fail(EIGSOL_E_ZERO_SIZE, "krylov_schur: matrix has zero size");
-    if (opts->nev < 1) return fail(EIGSOL_E_INVALID, "krylov_schur: nev must be at least 1");
-    if (opts->ncv > dev::ks::kMaxBasis) return fail(EIGSOL_E_INVALID, "krylov_schur: ncv must be at most 64");
-    if (opts->ncv < opts->nev + 2) return fail(EIGSOL_E_INVALID, "krylov_schur: ncv must be at least nev + 2");
-    if (opts->ncv > A->nrows) return fail(EIGSOL_E_INVALID, "krylov_schur: ncv exceeds the matrix order");
-    if (opts->max_restarts < 1) return fail(EIGSOL_E_INVALID, "krylov_schur: max_restarts must be at least 1");
-    if (A->dtype == EIGSOL_C128)
-        return krylov_run<cplx>(A, opts, sigma, v0, eigenvalues, eigenvectors, residuals, restarts, applications,
-                                converged);
-    return krylov_run<double>(A, opts, sigma, v0, eigenvalues, eigenvectors, residuals, restarts, applications,
-                              converged);
+    return krylov_entry(LinearOp(A), A->ncols, opts, sigma, v0, eigenvalues, eigenvectors, residuals, restarts,
+                        applications, converged);
+}
+
+int eigsol_krylov_dense(eigsol_dense* A, const eigsol_krylov_options* opts, const void* sigma, const void* v0,
+                        double* eigenvalues, double* eigenvectors, double* residuals, int32_t* restarts,
+                        int32_t* applications, int32_t* converged) {
+    if (!A || !opts || !v0 || !eigenvalues) return fail(EIGSOL_E_INVALID, "eigsol_krylov_dense: null pointer");
+    if (opts->mode != EIGSOL_KRYLOV_LM && opts->mode != EIGSOL_KRYLOV_SHIFT_INVERT)
+        return fail(EIGSOL_E_INVALID, "krylov_schur: unknown mode");
+    if (opts->mode == EIGSOL_KRYLOV_SHIFT_INVERT && !sigma)
+        return fail(EIGSOL_E_INVALID, "eigsol_krylov_dense: null sigma in shift-invert mode");
+    return krylov_entry(LinearOp(A), A->ncols, opts, sigma, v0, eigenvalues, eigenvectors, residuals, restarts,
+                        applications, converged);
 }
 
 int eigsol_krylov_orth(eigsol_ctx* ctx, int dtype, int64_t n, int32_t j, const void* V_dev, int64_t ldv, void* w_dev,

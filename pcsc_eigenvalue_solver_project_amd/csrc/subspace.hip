@@ -1,5 +1,6 @@
 // Block subspace iteration (orthogonal iteration with Rayleigh-Ritz): the k dominant eigenpairs
-// of a sparse matrix, plus the block product Y = A X it is built on.
+// of a sparse or a dense matrix, plus the sparse block product Y = A X it is built on (the dense
+// one: dense_block.hip).  The driver reaches the matrix through LinearOp (linear_op.hpp).
 //
 // Block vectors are n x m, row-major interleaved: X[i * m + j], the vector index fastest, so the m
 // scalars one matrix entry needs are one contiguous segment.
@@ -18,13 +19,14 @@
 //                         update Q <- Z R^-1, the Ritz vectors X = Q Y and the residual block
 //                         Z Y - X Theta.
 //
-// Out of scope: dense matrices, single precision, double-double, row-sharded matrices and a
+// Out of scope: single precision, double-double, row-sharded matrices and a
 // session / step form (one call runs the whole iteration).
 #include <algorithm>
 #include <cmath>
 #include <complex>
 
 #include "kernels_common.hpp"
+#include "linear_op.hpp"
 #include "small_eig.hpp"
 
 namespace eigsol {
@@ -322,6 +324,13 @@ int launch_spmm(const eigsol_csr* A, int m, const S* X, S* Y, hipStream_t st) {
     });
 }
 
+// Z = A Q: the CSR kernel above, or the MFMA block product of the dense matrix
+template <class S>
+int launch_product(const LinearOp& A, int m, const S* X, S* Y, hipStream_t st) {
+    if (A.csr) return launch_spmm<S>(A.csr, m, X, Y, st);
+    return dense_gemm_launch(A.dense, m, X, Y);
+}
+
 inline int gram_grid(int64_t n, int m, int num_cus) {
     const int mp = pad_width(m);
     const int t = std::min(mp, 4), slots = dev::kThreads / ((mp / t) * (mp / t));
@@ -371,11 +380,11 @@ using smalleig::ritz_order;
 using smalleig::small_eig;
 
 template <class S>
-int subspace_run(eigsol_csr* A, const eigsol_subspace_options* o, const void* X0v, double* eigenvalues,
+int subspace_run(const LinearOp& A, const eigsol_subspace_options* o, const void* X0v, double* eigenvalues,
                  double* eigenvectors, double* residuals, int32_t* iterations, int32_t* converged) {
-    const int64_t n = A->nrows;
+    const int64_t n = A.nrows();
     const int m = o->block, k = o->nev;
-    const eigsol_ctx* ctx = A->ctx;
+    const eigsol_ctx* ctx = A.ctx();
     hipStream_t st = ctx->stream;
     EIGSOL_HIP(hipSetDevice(ctx->device));
     const size_t nm = (size_t)n * m;
@@ -461,7 +470,7 @@ int subspace_run(eigsol_csr* A, const eigsol_subspace_options* o, const void* X0
     const std::vector<double> ones(k, 1.0);
 
     for (it = 1; it <= o->max_iterations; ++it) {
-        EIGSOL_TRY(launch_spmm<S>(A, m, Q, Z, st));
+        EIGSOL_TRY(launch_product<S>(A, m, Q, Z, st));
         EIGSOL_TRY(launch_gram<S>(ctx, Q, Z, n, m, part.as<S>(), GB, st));
         // the iteration's one host wait: B and the error words of the factorisations before it
         EIGSOL_HIP(hipMemcpyAsync(hB.data(), GB + (size_t)m * m, hB.size() * sizeof(S), hipMemcpyDeviceToHost, st));
@@ -546,6 +555,24 @@ int subspace_run(eigsol_csr* A, const eigsol_subspace_options* o, const void* X0
     return EIGSOL_OK;
 }
 
+// the checks every matrix kind shares, then the run
+int subspace_entry(const LinearOp& A, int64_t ncols, const eigsol_subspace_options* opts, const void* X0,
+                   double* eigenvalues, double* eigenvectors, double* residuals, int32_t* iterations,
+                   int32_t* converged) {
+    if (A.dtype() != EIGSOL_F64 && A.dtype() != EIGSOL_C128)
+        return fail(EIGSOL_E_UNSUPPORTED, "subspace_iteration: only double and complex double matrices are supported");
+    if (A.nrows() != ncols) return fail(EIGSOL_E_NOT_SQUARE, "subspace_iteration: matrix must be square");
+    if (A.nrows() == 0) return fail(EIGSOL_E_ZERO_SIZE, "subspace_iteration: matrix has zero size");
+    if (opts->nev < 1) return fail(EIGSOL_E_INVALID, "subspace_iteration: nev must be at least 1");
+    if (opts->block < opts->nev) return fail(EIGSOL_E_INVALID, "subspace_iteration: block must be at least nev");
+    if (opts->block > dev::kMaxBlock) return fail(EIGSOL_E_INVALID, "subspace_iteration: block must be at most 32");
+    if (opts->block > A.nrows()) return fail(EIGSOL_E_INVALID, "subspace_iteration: block exceeds the matrix order");
+    if (opts->max_iterations < 1) return fail(EIGSOL_E_INVALID, "subspace_iteration: max_iterations must be at least 1");
+    if (A.dtype() == EIGSOL_C128)
+        return subspace_run<cplx>(A, opts, X0, eigenvalues, eigenvectors, residuals, iterations, converged);
+    return subspace_run<double>(A, opts, X0, eigenvalues, eigenvectors, residuals, iterations, converged);
+}
+
 }  // namespace
 }  // namespace eigsol
 
@@ -574,18 +601,17 @@ int eigsol_subspace_csr(eigsol_csr* A, const eigsol_subspace_options* opts, cons
     if (!A || !opts || !X0 || !eigenvalues)
         return fail(EIGSOL_E_INVALID, "eigsol_subspace_csr: null pointer");
     if (A->dist) return fail(EIGSOL_E_UNSUPPORTED, "subspace_iteration: row-sharded matrix");
-    if (A->dtype != EIGSOL_F64 && A->dtype != EIGSOL_C128)
-        return fail(EIGSOL_E_UNSUPPORTED, "subspace_iteration: only double and complex double matrices are supported");
-    if (A->nrows != A->ncols) return fail(EIGSOL_E_NOT_SQUARE, "subspace_iteration: matrix must be square");
-    if (A->nrows == 0) return fail(EIGSOL_E_ZERO_SIZE, "subspace_iteration: matrix has zero size");
-    if (opts->nev < 1) return fail(EIGSOL_E_INVALID, "subspace_iteration: nev must be at least 1");
-    if (opts->block < opts->nev) return fail(EIGSOL_E_INVALID, "subspace_iteration: block must be at least nev");
-    if (opts->block > dev::kMaxBlock) return fail(EIGSOL_E_INVALID, "subspace_iteration: block must be at most 32");
-    if (opts->block > A->nrows) return fail(EIGSOL_E_INVALID, "subspace_iteration: block exceeds the matrix order");
-    if (opts->max_iterations < 1) return fail(EIGSOL_E_INVALID, "subspace_iteration: max_iterations must be at least 1");
-    if (A->dtype == EIGSOL_C128)
-        return subspace_run<cplx>(A, opts, X0, eigenvalues, eigenvectors, residuals, iterations, converged);
-    return subspace_run<double>(A, opts, X0, eigenvalues, eigenvectors, residuals, iterations, converged);
+    return subspace_entry(LinearOp(A), A->ncols, opts, X0, eigenvalues, eigenvectors, residuals, iterations,
+                          converged);
+}
+
+int eigsol_subspace_dense(eigsol_dense* A, const eigsol_subspace_options* opts, const void* X0,
+                          double* eigenvalues, double* eigenvectors, double* residuals,
+                          int32_t* iterations, int32_t* converged) {
+    if (!A || !opts || !X0 || !eigenvalues)
+        return fail(EIGSOL_E_INVALID, "eigsol_subspace_dense: null pointer");
+    return subspace_entry(LinearOp(A), A->ncols, opts, X0, eigenvalues, eigenvectors, residuals, iterations,
+                          converged);
 }
 
 }  // extern "C"
