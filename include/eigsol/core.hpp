@@ -563,6 +563,22 @@ struct KrylovResult {
     bool converged = false;
 };
 
+// Symmetric / Hermitian eigensolver (eigh, eigvalsh, solvers.hpp; no counterpart in the reference):
+// all eigenpairs, those with ascending index il <= i <= iu (0-based), or those with vl < lambda <= vu.
+struct EighOptions {
+    enum class Select { All, Index, Value };
+    Select select = Select::All;
+    std::int64_t il = 0, iu = 0;
+    double vl = 0, vu = 0;
+};
+
+template <typename S>
+struct EighResult {
+    std::vector<double> eigenvalues;   // ascending
+    DenseMatrix<S> eigenvectors;       // n x m, unit columns, largest-modulus component real positive
+    std::int64_t notConverged = 0;     // eigenvectors that failed the inverse iteration's growth test
+};
+
 template <typename S>
 struct QRResult {
     Vector<S> eigenvalues;

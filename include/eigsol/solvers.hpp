@@ -441,6 +441,58 @@ KrylovResult<S> krylovSchur_dense(const DenseMatrix<S>& A, const KrylovOptions<S
     return detail::krylov_run_dense<S>(A, opts, &v0);
 }
 
+// ------------------------------------------------------------------------------------------ eigh
+// Eigenvalues (ascending) and an orthonormal set of eigenvectors of the real symmetric / complex
+// Hermitian matrix whose lower triangle is A's (eigsol_eigh_dense: blocked Hessenberg reduction,
+// bisection, inverse iteration, back-transformation; the strict upper triangle is not read).
+// S = double and std::complex<double>.  eigvalsh returns the eigenvalues alone (no vectors are formed).
+namespace detail {
+template <typename S>
+EighResult<S> eigh_run(const DenseMatrix<S>& A, const EighOptions& opts, bool vectors, const char* who) {
+    EighResult<S> res;
+    const std::int64_t n = A.rows();
+    if (n != A.cols()) throw std::runtime_error(std::string(who) + ": matrix must be square");
+    if (n == 0) throw std::runtime_error(std::string(who) + ": matrix has zero size");
+    if constexpr (!DeviceScalar<S>) {
+        throw std::runtime_error(std::string(who) + ": scalar type not supported by the device path "
+                                                    "(double, std::complex<double>)");
+    } else {
+        eigsol_eigh_options o;
+        o.select = opts.select == EighOptions::Select::Index   ? EIGSOL_EIGH_INDEX
+                   : opts.select == EighOptions::Select::Value ? EIGSOL_EIGH_VALUE
+                                                               : EIGSOL_EIGH_ALL;
+        o.il = opts.il;
+        o.iu = opts.iu;
+        o.vl = opts.vl;
+        o.vu = opts.vu;
+        res.eigenvalues.assign(static_cast<std::size_t>(n), 0.0);
+        DenseMatrix<S> Z;
+        if (vectors) Z = DenseMatrix<S>(n, n);
+        std::int64_t m = 0, nc = 0;
+        check(eigsol_eigh_dense(ctx(), dtype_of<S>(), n, A.data(), &o, res.eigenvalues.data(),
+                                vectors ? static_cast<void*>(Z.data()) : nullptr, &m, &nc),
+              who);
+        res.eigenvalues.resize(static_cast<std::size_t>(m));
+        res.notConverged = nc;
+        if (vectors) {
+            res.eigenvectors = DenseMatrix<S>(n, m);
+            for (std::int64_t j = 0; j < m; ++j)
+                for (std::int64_t i = 0; i < n; ++i) res.eigenvectors(i, j) = Z(i, j);
+        }
+    }
+    return res;
+}
+}  // namespace detail
+
+template <ScalarConcept S>
+EighResult<S> eigh(const DenseMatrix<S>& A, const EighOptions& opts = {}) {
+    return detail::eigh_run<S>(A, opts, true, "eigh");
+}
+template <ScalarConcept S>
+std::vector<double> eigvalsh(const DenseMatrix<S>& A, const EighOptions& opts = {}) {
+    return detail::eigh_run<S>(A, opts, false, "eigvalsh").eigenvalues;
+}
+
 // --------------------------------------------------------------------------------- solve_shifted
 template <ScalarConcept S>
 Vector<S> solve_shifted(const Matrix& A, const S shift, const Vector<S>& b) {

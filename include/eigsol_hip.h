@@ -429,6 +429,66 @@ int eigsol_qr_refine_info(eigsol_ctx* ctx, int64_t* unrefined, int32_t* max_newt
 int eigsol_hyman_refine(eigsol_ctx* ctx, int dtype, int64_t n, const void* H_colmajor, int64_t count,
                         const double* starts, double* refined, int32_t* steps);
 
+/* ---------------------------------------------------------------- symmetric / Hermitian (dense)
+ * All, or a selected range, of the eigenvalues of a real symmetric (EIGSOL_F64) or complex Hermitian
+ * (EIGSOL_C128) matrix, and an orthonormal set of eigenvectors.  The reference has no such solver.
+ * Algorithm: the lower triangle is mirrored on the device; the blocked Householder Hessenberg
+ * reduction (the general one of eigsol_hessenberg_dense, not a symmetric tridiagonalisation) leaves
+ * a tridiagonal H; T = D^H H D is real with non-negative off-diagonals for a unitary diagonal D of
+ * accumulated sub-diagonal phases; T splits into blocks where |e_i| <= eps sqrt(|d_i d_{i+1}|) or
+ * e_i^2 <= DBL_MIN (LAPACK dstebz's rule); every eigenvalue of every block is found, and the
+ * selection taken from the sorted values, by bisection on the Sturm count (one lane each, to 2 eps max(|lo|, |hi|));
+ * eigenvectors of T by inverse iteration with Gram-Schmidt inside clusters (LAPACK dstein's scheme:
+ * eigenvalues of a block closer than 1e-3 ||T_block||_1 to their neighbour share a cluster, which
+ * one workgroup works through in ascending order; at most 5 iterations each, deterministic start
+ * vectors); Z = Q (D Z_T) with the reduction's stored
+ * panels on the fp64 matrix cores.  No Francis sweeps run.  No floating-point atomics: two calls on
+ * the same input return the same bits.
+ * Read: A_colmajor (host, n x n, column-major): ONLY the lower triangle, diagonal included (for C128
+ * the diagonal's imaginary parts are ignored); the strict upper triangle may hold anything.
+ * opts (NULL: all): EIGSOL_EIGH_INDEX takes the il-th .. iu-th smallest (0-based, inclusive),
+ * EIGSOL_EIGH_VALUE those with vl < lambda <= vu.  A selection returns bitwise the values the full
+ * call returns at those places.
+ * Out: *m_out eigenvalues in w, ascending (capacity n); Z (NULL: eigenvalues only), n x *m_out scalars
+ * of the dtype, column-major with leading dimension n (capacity n x n): column j belongs to w[j], has
+ * unit 2-norm, and its largest-modulus component (the first on ties) is real and positive.
+ * not_converged (optional): how many eigenvectors failed dstein's growth test within 5 iterations
+ * (their last iterate is returned; 0 on a values-only call).
+ * Status, decided before any device call: EIGSOL_E_INVALID (n < 0; with n > 0 a null ctx, A, w or
+ * m_out; unknown select; il > iu or an index outside 0 .. n-1; vl >= vu or a NaN bound; unknown
+ * dtype), EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD; n above the order the blocked reduction
+ * accepts: 16384 real, 8192 complex).  n == 0: EIGSOL_OK with *m_out = 0.  A non-finite entry in the
+ * lower triangle fails with EIGSOL_E_SOLVER.
+ * Out of scope: single precision and double-double, row-sharded matrices, a symmetric (sytrd) or
+ * two-stage reduction, divide and conquer / MRRR, generalised problems, and high relative accuracy
+ * of tiny eigenvalues of graded matrices (the Householder reduction loses it; entries are not
+ * rescaled, so e_i^2 must neither overflow nor underflow).
+ * eigsol_eigh_stage_times: the context's last eigsol_eigh_dense call by stream events, 4 doubles in
+ * ms: reduction (mirror, Hessenberg, extraction), bisection, inverse iteration, back-transformation
+ * (with the copy of Z to the host); stages that did not run are 0. */
+#define EIGSOL_EIGH_ALL 0
+#define EIGSOL_EIGH_INDEX 1   /* il <= i <= iu, 0-based, ascending order */
+#define EIGSOL_EIGH_VALUE 2   /* vl < lambda <= vu */
+typedef struct eigsol_eigh_options {
+    int32_t select;
+    int64_t il, iu;
+    double  vl, vu;
+} eigsol_eigh_options;
+int eigsol_eigh_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor,
+                      const eigsol_eigh_options* opts, double* w, void* Z, int64_t* m_out,
+                      int64_t* not_converged);
+int eigsol_eigh_stage_times(eigsol_ctx* ctx, double* ms4);
+/* Host only (no device): the plan eigsol_eigh_dense makes for the tridiagonal T = (d: n, e: n - 1)
+ * and m of its eigenvalues w (ascending).  block_of[i] (n): the split block of row i, blocks numbered
+ * from 0 upwards; cluster_of[j] (m): the cluster of w[j], clusters numbered in the order their first
+ * eigenvalue appears in w.  An eigenvalue is given to the block whose Sturm count claims it (equal
+ * eigenvalues of several blocks: the lowest block that has one left); within a block it starts a new
+ * cluster when it lies more than 1e-3 ||T_block||_1 above the block's previous one.  Fails with
+ * EIGSOL_E_INVALID on null pointers, n < 0, m < 0, m > n, a descending w, or a w[j] that no block
+ * claims. */
+int eigsol_tridiag_plan(int64_t n, const double* d, const double* e, int64_t m, const double* w,
+                        int64_t* block_of, int64_t* cluster_of, int64_t* nblocks, int64_t* nclusters);
+
 /* ---------------------------------------------------------------- row-sharded power iteration
  * One process per GPU; RCCL over xGMI (the reference has no distribution: SURVEY.md §2.1).
  * Rank r owns global rows [row_begins[r], row_begins[r+1]).  Bootstrap: rank 0 calls

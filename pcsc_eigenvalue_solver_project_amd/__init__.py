@@ -17,12 +17,14 @@ import numpy as np
 from ._capi import (EIGSOL_C64, EIGSOL_C128, EIGSOL_CDD, EIGSOL_DD, EIGSOL_E_INVALID, EIGSOL_E_SIZE_MISMATCH, EIGSOL_E_UNSUPPORTED, EIGSOL_F32,
                     EIGSOL_F64, EIGSOL_KRYLOV_LM, EIGSOL_KRYLOV_SHIFT_INVERT, EigSolError, KrylovOptionsC, SolverOptionsC,
                     SubspaceOptionsC, call, check, last_error, lib)
+from ._capi import EIGSOL_EIGH_INDEX, EIGSOL_EIGH_VALUE, EighOptionsC
 
 __all__ = [
     "EigSolError", "SolverOptions", "EigenResult", "Context", "CsrMatrix", "DenseMatrix",
     "PowerSession", "power_method", "device_count", "lib", "last_error",
     "SubspaceOptions", "SubspaceResult", "subspace_iteration", "spmm", "dense_mm",
     "KrylovOptions", "KrylovResult", "krylov_schur", "krylov_orth", "krylov_rotate",
+    "EighResult", "eigh", "eigvalsh", "eigh_stage_times", "tridiag_plan",
 ]
 
 
@@ -798,6 +800,78 @@ def qr_eigenvalues(ctx: Context, A, opts: SolverOptions = SolverOptions(), varia
     elif v == 0 and A.dtype == np.complex128:
         full = eig.copy()
     return QRResult(eig, int(it.value), bool(conv.value), full)
+
+
+@dataclass
+class EighResult:
+    """Result of :func:`eigh`: ``eigenvalues`` ascending (m), ``eigenvectors`` n x m with unit columns
+    (column j belongs to eigenvalue j; its largest-modulus component is real and positive),
+    ``not_converged`` the number of vectors that failed the inverse iteration's growth test."""
+
+    eigenvalues: np.ndarray
+    eigenvectors: np.ndarray
+    not_converged: int
+
+
+def _eigh_call(ctx: Context, A, select, vectors: bool, who: str):
+    A = _square_dense(A, who)
+    code = _dtype_code(A.dtype)
+    n = A.shape[0]
+    o = None
+    if select is not None:
+        if len(select) != 3 or select[0] not in ("i", "v"):
+            raise EigSolError(EIGSOL_E_INVALID, f'{who}: select is None, ("i", il, iu) or ("v", vl, vu)')
+        o = (EighOptionsC(EIGSOL_EIGH_INDEX, int(select[1]), int(select[2]), 0.0, 0.0) if select[0] == "i"
+             else EighOptionsC(EIGSOL_EIGH_VALUE, 0, 0, float(select[1]), float(select[2])))
+    Af = np.asfortranarray(A)
+    w = np.zeros(max(n, 1))
+    Z = np.zeros((n, max(n, 1)), dtype=A.dtype, order="F") if vectors else None
+    m, nc = C.c_int64(0), C.c_int64(0)
+    call("eigsol_eigh_dense", ctx.handle, code, n, _ptr(Af), None if o is None else C.byref(o), _ptr(w),
+         None if Z is None else _ptr(Z), C.byref(m), C.byref(nc))
+    k = int(m.value)
+    return w[:k].copy(), (None if Z is None else np.asfortranarray(Z[:, :k])), int(nc.value)
+
+
+def eigvalsh(ctx: Context, A, select=None) -> np.ndarray:
+    """Eigenvalues (ascending) of the real symmetric / complex Hermitian matrix whose lower triangle
+    is that of ``A`` (float64 / complex128; the strict upper triangle is not read), on the device
+    (``eigsol_eigh_dense``): Hessenberg reduction, then bisection.  ``select``: ``None`` (all),
+    ``("i", il, iu)`` (0-based, inclusive) or ``("v", vl, vu)`` (vl < lambda <= vu)."""
+    return _eigh_call(ctx, A, select, False, "eigvalsh")[0]
+
+
+def eigh(ctx: Context, A, select=None) -> EighResult:
+    """:func:`eigvalsh` with an orthonormal set of eigenvectors (inverse iteration on the tridiagonal
+    matrix, back-transformed through the reduction's stored reflectors)."""
+    w, Z, nc = _eigh_call(ctx, A, select, True, "eigh")
+    return EighResult(w, Z, nc)
+
+
+def eigh_stage_times(ctx: Context) -> dict:
+    """The context's last :func:`eigh` / :func:`eigvalsh` call by stream events, in seconds."""
+    ms = (C.c_double * 4)()
+    call("eigsol_eigh_stage_times", ctx.handle, ms)
+    return {k: ms[i] * 1e-3 for i, k in enumerate(("reduction", "bisection", "inverse_iteration", "back_transform"))}
+
+
+def tridiag_plan(d, e, w):
+    """Host only (``eigsol_tridiag_plan``): the split blocks of the tridiagonal (d, e) and the clusters
+    of its ascending eigenvalues ``w`` that :func:`eigh` uses.  Returns (block_of, cluster_of, nblocks,
+    nclusters)."""
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    e = np.ascontiguousarray(e, dtype=np.float64)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    n, m = d.size, w.size
+    if e.size != max(n - 1, 0):
+        raise EigSolError(EIGSOL_E_SIZE_MISMATCH, "tridiag_plan: e must hold n - 1 entries")
+    eb = np.zeros(max(n, 1))
+    eb[:e.size] = e
+    bo, co = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(m, 1), dtype=np.int64)
+    nb, ncl = C.c_int64(0), C.c_int64(0)
+    call("eigsol_tridiag_plan", n, _ptr(d) if n else _ptr(eb), _ptr(eb), m, _ptr(w) if m else _ptr(co), _ptr(bo),
+         _ptr(co), C.byref(nb), C.byref(ncl))
+    return bo[:n], co[:m], int(nb.value), int(ncl.value)
 
 
 def hyman_refine(ctx: Context, H, starts):

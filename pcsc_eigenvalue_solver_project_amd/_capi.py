@@ -70,6 +70,15 @@ class KrylovOptionsC(C.Structure):
                 ("mode", C.c_int32)]
 
 
+EIGSOL_EIGH_ALL = 0
+EIGSOL_EIGH_INDEX = 1
+EIGSOL_EIGH_VALUE = 2
+
+
+class EighOptionsC(C.Structure):
+    _fields_ = [("select", C.c_int32), ("il", C.c_int64), ("iu", C.c_int64), ("vl", C.c_double), ("vu", C.c_double)]
+
+
 _vp = C.c_void_p
 _i32 = C.c_int32
 _i64 = C.c_int64
@@ -147,6 +156,9 @@ SIGNATURES = {
                                     _vp, _pi32, _pi32],
     "eigsol_qr_refine_info": [_vp, _pi64, _pi32],
     "eigsol_hyman_refine": [_vp, C.c_int, _i64, _vp, _i64, _vp, _vp, _vp],
+    "eigsol_eigh_dense": [_vp, C.c_int, _i64, _vp, C.POINTER(EighOptionsC), _vp, _vp, _pi64, _pi64],
+    "eigsol_eigh_stage_times": [_vp, _pd],
+    "eigsol_tridiag_plan": [_i64, _vp, _vp, _i64, _vp, _vp, _vp, _pi64, _pi64],
     "eigsol_hbm_probe": [_vp, C.c_size_t, C.c_int, _pd, _pd, _pd, _pint],
     "eigsol_hbm_probe_mix": [_vp, C.c_size_t, C.c_int, _pd, _pint],
     "eigsol_ctx_info": [_vp, _pint, _pint, _pint, _pint],

@@ -1532,8 +1532,11 @@ void gemm(hipStream_t st, int m, int nn, int kk, double alpha, const S* A, int64
 }
 
 // In place on the device matrix A (n x n, column-major, ld = n).
+// Vout / Tout (optional, device): panel p's reflectors V (n x nbp, leading dimension n, as the panel
+// leaves it) at Vout + p n NB and its T (NB x NB) at Tout + p NB NB, copied on the stream after the
+// panel (the symmetric eigensolver's back-transformation, hess_backtransform below).
 template <class S>
-int hessenberg_blocked(hipStream_t st, S* A, int64_t n64) {
+int hessenberg_blocked(hipStream_t st, S* A, int64_t n64, S* Vout = nullptr, S* Tout = nullptr) {
     constexpr bool kC = !is_real_v<S>;
     using Cfg = dev::HessCfg<S>;
     const int n = (int)n64;
@@ -1655,6 +1658,12 @@ int hessenberg_blocked(hipStream_t st, S* A, int64_t n64) {
                                V + (int64_t)i * n, yp, skip);
             hipLaunchKernelGGL(dev::hess_y<S>, dim3((n + 255) / 256), dim3(256), 0, st, n, i, nch, yp, tv, Y, T, skip);
         }
+        if (Vout)
+            EIGSOL_HIP(hipMemcpyAsync(Vout + (int64_t)(k / NB) * n * NB, V, (size_t)n * nbp * sizeof(S),
+                                      hipMemcpyDeviceToDevice, st));
+        if (Tout)
+            EIGSOL_HIP(hipMemcpyAsync(Tout + (int64_t)(k / NB) * NB * NB, T, (size_t)NB * NB * sizeof(S),
+                                      hipMemcpyDeviceToDevice, st));
         const int c1 = k + nbp;           // first trailing column
         const int mt = n - c1;
         if (mt > 0) {
@@ -1700,6 +1709,36 @@ int hessenberg_blocked(hipStream_t st, S* A, int64_t n64) {
                     (void*)part, (void*)tpart, (void*)x0s, (void*)xu, (void*)bar, (void*)err, (void*)SK})
         if (p) (void)hipFree(p);
     if (errh) return fail(EIGSOL_E_HIP, "blocked Hessenberg: grid barrier timed out (internal error)");
+    return EIGSOL_OK;
+}
+
+// Z <- Q Z for the Q of hessenberg_blocked (A = Q H Q^H, Q = Q_0 Q_1 ... the panels' I - V T V^H), from
+// the panels it stored in Vall / Tall: last panel first, Z(k+1:, :) -= V (T (V^H Z(k+1:, :))) (V is
+// zero above row k + 1).  Z: n x m, leading dimension ldz.  The last panel may be partial (n - 2
+// reflectors in all).
+template <class S>
+int hess_backtransform(hipStream_t st, int64_t n64, int64_t m64, const S* Vall, const S* Tall, S* Z, int64_t ldz) {
+    constexpr int NB = dev::HessCfg<S>::NB;
+    const int n = (int)n64, m = (int)m64;
+    if (n < 3 || m < 1) return EIGSOL_OK;
+    S *W1 = nullptr, *W2 = nullptr, *SK = nullptr;
+    const int64_t sk_elems = (int64_t)16 * NB * m;
+    EIGSOL_HIP(hipMalloc(&W1, (size_t)NB * m * sizeof(S)));
+    EIGSOL_HIP(hipMalloc(&W2, (size_t)NB * m * sizeof(S)));
+    EIGSOL_HIP(hipMalloc(&SK, sk_elems * sizeof(S)));
+    const int last = n - 3;
+    for (int k = last / NB * NB; k >= 0; k -= NB) {
+        const int nbp = std::min(NB, last - k + 1);
+        const int rows = n - (k + 1);
+        const S* V = Vall + (int64_t)(k / NB) * n * NB + (k + 1);
+        const S* T = Tall + (int64_t)(k / NB) * NB * NB;
+        gemm<S, true, false>(st, nbp, m, rows, 1.0, V, n, Z + (k + 1), ldz, 0.0, W1, NB, SK, sk_elems);
+        gemm<S, false, false>(st, nbp, m, nbp, 1.0, T, NB, W1, NB, 0.0, W2, NB);
+        gemm<S, false, false>(st, rows, m, nbp, -1.0, V, n, W2, NB, 1.0, Z + (k + 1), ldz);
+    }
+    EIGSOL_HIP(hipGetLastError());
+    EIGSOL_HIP(hipStreamSynchronize(st));
+    for (void* p : {(void*)W1, (void*)W2, (void*)SK}) (void)hipFree(p);
     return EIGSOL_OK;
 }
 
@@ -1797,6 +1836,22 @@ int qr_blocked(hipStream_t st, S* R, int m, int n, S* Q) {
 
 int hessenberg_blocked_f64(hipStream_t st, double* A, int64_t n) { return hessenberg_blocked<double>(st, A, n); }
 int hessenberg_blocked_c128(hipStream_t st, cplx* A, int64_t n) { return hessenberg_blocked<cplx>(st, A, n); }
+int hessenberg_blocked_vt_f64(hipStream_t st, double* A, int64_t n, double* V, double* T) {
+    return hessenberg_blocked<double>(st, A, n, V, T);
+}
+int hessenberg_blocked_vt_c128(hipStream_t st, cplx* A, int64_t n, cplx* V, cplx* T) {
+    return hessenberg_blocked<cplx>(st, A, n, V, T);
+}
+int hess_backtransform_f64(hipStream_t st, int64_t n, int64_t m, const double* V, const double* T, double* Z, int64_t ldz) {
+    return hess_backtransform<double>(st, n, m, V, T, Z, ldz);
+}
+int hess_backtransform_c128(hipStream_t st, int64_t n, int64_t m, const cplx* V, const cplx* T, cplx* Z, int64_t ldz) {
+    return hess_backtransform<cplx>(st, n, m, V, T, Z, ldz);
+}
+int hess_panel_width_f64() { return dev::HessCfg<double>::NB; }
+int hess_panel_width_c128() { return dev::HessCfg<cplx>::NB; }
+int hess_max_order_f64() { return dev::HessCfg<double>::kMaxLdsN; }
+int hess_max_order_c128() { return dev::HessCfg<cplx>::kMaxLdsN; }
 int qr_blocked_f64(hipStream_t st, double* R, int64_t m, int64_t n, double* Q) { return qr_blocked<double>(st, R, (int)m, (int)n, Q); }
 int qr_blocked_c128(hipStream_t st, cplx* R, int64_t m, int64_t n, cplx* Q) { return qr_blocked<cplx>(st, R, (int)m, (int)n, Q); }
 int hessenberg_blocked_f32(hipStream_t st, float* A, int64_t n) { return hessenberg_blocked<float>(st, A, n); }

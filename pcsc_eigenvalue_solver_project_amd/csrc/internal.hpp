@@ -87,6 +87,20 @@ template <> struct dtype_of<cplxf> { static constexpr int value = EIGSOL_C64; };
 template <class S> inline constexpr bool is_real_v = std::is_same_v<S, double> || std::is_same_v<S, float>;
 template <class S> inline constexpr bool is_cplx_v = !is_real_v<S>;
 
+// hessenberg.hip, for the symmetric eigensolver (eigh.hip): the blocked reduction with every panel's
+// reflectors V (n x NB per panel, leading dimension n) and T (NB x NB per panel) kept, and Z <- Q Z
+// from them (Z: n x m, leading dimension ldz).  NB and the largest order are the reduction's own.
+int hessenberg_blocked_vt_f64(hipStream_t st, double* A, int64_t n, double* V, double* T);
+int hessenberg_blocked_vt_c128(hipStream_t st, cplx* A, int64_t n, cplx* V, cplx* T);
+int hess_backtransform_f64(hipStream_t st, int64_t n, int64_t m, const double* V, const double* T, double* Z,
+                           int64_t ldz);
+int hess_backtransform_c128(hipStream_t st, int64_t n, int64_t m, const cplx* V, const cplx* T, cplx* Z,
+                            int64_t ldz);
+int hess_panel_width_f64();
+int hess_panel_width_c128();
+int hess_max_order_f64();
+int hess_max_order_c128();
+
 inline bool dtype_complex(int dtype) { return dtype == EIGSOL_C128 || dtype == EIGSOL_C64 || dtype == EIGSOL_CDD; }
 inline bool dtype_single(int dtype) { return dtype == EIGSOL_F32 || dtype == EIGSOL_C64; }
 // the fp64 / fp32 kernel families (every layout, factor and QR kernel); EIGSOL_DD / EIGSOL_CDD
@@ -236,6 +250,9 @@ struct eigsol_ctx {
     // the last long double Francis call's refinement (eigsol_qr_refine_info)
     int64_t wide_unrefined = 0;
     int32_t wide_newton_max = 0;
+    // the last eigsol_eigh_dense call's stages in ms, by stream events (eigsol_eigh_stage_times):
+    // reduction, bisection, inverse iteration, back-transformation
+    double eigh_ms[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 struct eigsol_csr {
