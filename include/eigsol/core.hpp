@@ -575,7 +575,7 @@ struct EighOptions {
 template <typename S>
 struct EighResult {
     std::vector<double> eigenvalues;   // ascending
-    DenseMatrix<S> eigenvectors;       // n x m, unit columns, largest-modulus component real positive
+    DenseMatrix<S> eigenvectors;       // n x m, unit columns (with B: B-orthonormal), largest-modulus component real positive
     std::int64_t notConverged = 0;     // eigenvectors that failed the inverse iteration's growth test
 };
 

@@ -446,12 +446,18 @@ KrylovResult<S> krylovSchur_dense(const DenseMatrix<S>& A, const KrylovOptions<S
 // Hermitian matrix whose lower triangle is A's (eigsol_eigh_dense: blocked Hessenberg reduction,
 // bisection, inverse iteration, back-transformation; the strict upper triangle is not read).
 // S = double and std::complex<double>.  eigvalsh returns the eigenvalues alone (no vectors are formed).
+// With a second matrix B (Hermitian positive definite, its lower triangle read): A x = lambda B x
+// (eigsol_geigh_dense: Cholesky B = L L^H, C = L^-1 A L^-H, the solver above, X = L^-H Y); the
+// eigenvectors are then B-orthonormal (X^H B X = I).  A B that is not positive definite throws the
+// library's message, which names the first column whose pivot is not > 0.  cholesky(B) returns L alone.
 namespace detail {
 template <typename S>
-EighResult<S> eigh_run(const DenseMatrix<S>& A, const EighOptions& opts, bool vectors, const char* who) {
+EighResult<S> eigh_run(const DenseMatrix<S>& A, const EighOptions& opts, bool vectors, const char* who,
+                       const DenseMatrix<S>* B = nullptr) {
     EighResult<S> res;
     const std::int64_t n = A.rows();
     if (n != A.cols()) throw std::runtime_error(std::string(who) + ": matrix must be square");
+    if (B && (B->rows() != n || B->cols() != n)) throw std::runtime_error(std::string(who) + ": B must be square and of A's order");
     if (n == 0) throw std::runtime_error(std::string(who) + ": matrix has zero size");
     if constexpr (!DeviceScalar<S>) {
         throw std::runtime_error(std::string(who) + ": scalar type not supported by the device path "
@@ -469,9 +475,13 @@ EighResult<S> eigh_run(const DenseMatrix<S>& A, const EighOptions& opts, bool ve
         DenseMatrix<S> Z;
         if (vectors) Z = DenseMatrix<S>(n, n);
         std::int64_t m = 0, nc = 0;
-        check(eigsol_eigh_dense(ctx(), dtype_of<S>(), n, A.data(), &o, res.eigenvalues.data(),
-                                vectors ? static_cast<void*>(Z.data()) : nullptr, &m, &nc),
-              who);
+        void* zp = vectors ? static_cast<void*>(Z.data()) : nullptr;
+        if (B)
+            check(eigsol_geigh_dense(ctx(), dtype_of<S>(), n, A.data(), B->data(), &o, res.eigenvalues.data(), zp, &m, &nc,
+                                     nullptr),
+                  who);
+        else
+            check(eigsol_eigh_dense(ctx(), dtype_of<S>(), n, A.data(), &o, res.eigenvalues.data(), zp, &m, &nc), who);
         res.eigenvalues.resize(static_cast<std::size_t>(m));
         res.notConverged = nc;
         if (vectors) {
@@ -491,6 +501,28 @@ EighResult<S> eigh(const DenseMatrix<S>& A, const EighOptions& opts = {}) {
 template <ScalarConcept S>
 std::vector<double> eigvalsh(const DenseMatrix<S>& A, const EighOptions& opts = {}) {
     return detail::eigh_run<S>(A, opts, false, "eigvalsh").eigenvalues;
+}
+template <ScalarConcept S>
+EighResult<S> eigh(const DenseMatrix<S>& A, const DenseMatrix<S>& B, const EighOptions& opts = {}) {
+    return detail::eigh_run<S>(A, opts, true, "eigh", &B);
+}
+template <ScalarConcept S>
+std::vector<double> eigvalsh(const DenseMatrix<S>& A, const DenseMatrix<S>& B, const EighOptions& opts = {}) {
+    return detail::eigh_run<S>(A, opts, false, "eigvalsh", &B).eigenvalues;
+}
+// L of B = L L^H (eigsol_cholesky_dense): zero strict upper triangle, real positive diagonal.
+template <ScalarConcept S>
+DenseMatrix<S> cholesky(const DenseMatrix<S>& B) {
+    const std::int64_t n = B.rows();
+    if (n != B.cols()) throw std::runtime_error("cholesky: matrix must be square");
+    if (n == 0) throw std::runtime_error("cholesky: matrix has zero size");
+    if constexpr (!DeviceScalar<S>) {
+        throw std::runtime_error("cholesky: scalar type not supported by the device path (double, std::complex<double>)");
+    } else {
+        DenseMatrix<S> L(n, n);
+        detail::check(eigsol_cholesky_dense(detail::ctx(), detail::dtype_of<S>(), n, B.data(), L.data(), nullptr), "cholesky");
+        return L;
+    }
 }
 
 // --------------------------------------------------------------------------------- solve_shifted

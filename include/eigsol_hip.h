@@ -460,9 +460,12 @@ int eigsol_hyman_refine(eigsol_ctx* ctx, int dtype, int64_t n, const void* H_col
  * accepts: 16384 real, 8192 complex).  n == 0: EIGSOL_OK with *m_out = 0.  A non-finite entry in the
  * lower triangle fails with EIGSOL_E_SOLVER.
  * Out of scope: single precision and double-double, row-sharded matrices, a symmetric (sytrd) or
- * two-stage reduction, divide and conquer / MRRR, generalised problems, and high relative accuracy
+ * two-stage reduction, divide and conquer / MRRR, and high relative accuracy
  * of tiny eigenvalues of graded matrices (the Householder reduction loses it; entries are not
- * rescaled, so e_i^2 must neither overflow nor underflow).
+ * rescaled, so e_i^2 must neither overflow nor underflow).  The generalised problem A x = lambda B x
+ * is eigsol_geigh_dense (below); out of scope there: types 2 and 3 (A B x = lambda x,
+ * B A x = lambda x), a semidefinite or indefinite B, single and double-double precision, a two-sided
+ * reduction to standard form (LAPACK sygst), and sparse generalised problems in krylov_schur.
  * eigsol_eigh_stage_times: the context's last eigsol_eigh_dense call by stream events, 4 doubles in
  * ms: reduction (mirror, Hessenberg, extraction), bisection, inverse iteration, back-transformation
  * (with the copy of Z to the host); stages that did not run are 0. */
@@ -478,6 +481,39 @@ int eigsol_eigh_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colma
                       const eigsol_eigh_options* opts, double* w, void* Z, int64_t* m_out,
                       int64_t* not_converged);
 int eigsol_eigh_stage_times(eigsol_ctx* ctx, double* ms4);
+
+/* ---------------------------------------------------------------- Cholesky and A x = lambda B x (dense)
+ * eigsol_cholesky_dense: B = L L^H of a real symmetric / complex Hermitian positive definite B
+ * (EIGSOL_F64 / EIGSOL_C128; host, n x n, column-major; ONLY the lower triangle is read, and for
+ * C128 the diagonal's imaginary parts are ignored).  Blocked and right-looking with block width 64
+ * (real) or 32 (complex); the trailing update runs on the fp64 matrix cores.  L_colmajor (host, n x n)
+ * receives L with an exactly zero strict upper triangle and a real positive diagonal.
+ * eigsol_geigh_dense: type 1 only, A x = lambda B x with A Hermitian and B Hermitian positive
+ * definite (the lower triangles of both are read, as above).  B = L L^H; C = L^-1 A L^-H by two blocked
+ * triangular solves with n right-hand sides and a conjugate transpose between (2 n^3 flops against
+ * sygst's n^3); eigsol_eigh_dense's solver on C without leaving the device; X = L^-H Y by a blocked
+ * upper-triangular solve.  opts, w, Z, m_out and not_converged are eigsol_eigh_dense's, but the columns
+ * of Z are B-orthonormal (Z^H B Z = I, LAPACK's convention) instead of unit 2-norm; the phase
+ * convention is the same.  A selection returns bitwise the values of the full call; two calls on the
+ * same input return the same bits; a values-only call (Z NULL) skips the eigenvector stages.
+ * info (optional, both entries): -1 on success; else the 0-based index of the first column whose
+ * pivot is not > 0 (NaN included), the call returns EIGSOL_E_SOLVER and the message names the index
+ * and says "not positive definite".  A non-finite entry in either lower triangle fails with
+ * EIGSOL_E_SOLVER.
+ * Status, decided before any device call: as eigsol_eigh_dense (EIGSOL_E_INVALID: n < 0; with n > 0
+ * a null ctx, A, B, w or m_out - for the Cholesky entry B or L; a bad selection; an unknown dtype;
+ * EIGSOL_E_UNSUPPORTED: F32 / C64 / DD / CDD; n above eigsol_eigh_dense's limit).  n == 0: EIGSOL_OK
+ * with *m_out = 0 and *info = -1.
+ * eigsol_geigh_stage_times: the context's last eigsol_geigh_dense call by stream events, 7 doubles in
+ * ms: cholesky (with the mirroring), standardise, reduction, bisection, inverse_iteration,
+ * back_transform (the stored-panel step and the copy of Z), triangular_back_solve; stages that did
+ * not run are 0. */
+int eigsol_cholesky_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* B_colmajor,
+                          void* L_colmajor, int64_t* info);
+int eigsol_geigh_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor, const void* B_colmajor,
+                       const eigsol_eigh_options* opts, double* w, void* Z, int64_t* m_out,
+                       int64_t* not_converged, int64_t* info);
+int eigsol_geigh_stage_times(eigsol_ctx* ctx, double* ms7);
 /* Host only (no device): the plan eigsol_eigh_dense makes for the tridiagonal T = (d: n, e: n - 1)
  * and m of its eigenvalues w (ascending).  block_of[i] (n): the split block of row i, blocks numbered
  * from 0 upwards; cluster_of[j] (m): the cluster of w[j], clusters numbered in the order their first

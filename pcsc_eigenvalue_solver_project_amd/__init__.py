@@ -25,6 +25,7 @@ __all__ = [
     "SubspaceOptions", "SubspaceResult", "subspace_iteration", "spmm", "dense_mm",
     "KrylovOptions", "KrylovResult", "krylov_schur", "krylov_orth", "krylov_rotate",
     "EighResult", "eigh", "eigvalsh", "eigh_stage_times", "tridiag_plan",
+    "cholesky", "geigh_stage_times",
 ]
 
 
@@ -806,17 +807,24 @@ def qr_eigenvalues(ctx: Context, A, opts: SolverOptions = SolverOptions(), varia
 class EighResult:
     """Result of :func:`eigh`: ``eigenvalues`` ascending (m), ``eigenvectors`` n x m with unit columns
     (column j belongs to eigenvalue j; its largest-modulus component is real and positive),
-    ``not_converged`` the number of vectors that failed the inverse iteration's growth test."""
+    ``not_converged`` the number of vectors that failed the inverse iteration's growth test.
+    With ``B`` (A x = lambda B x) the columns are B-orthonormal (X^H B X = I) instead of unit 2-norm."""
 
     eigenvalues: np.ndarray
     eigenvectors: np.ndarray
     not_converged: int
 
 
-def _eigh_call(ctx: Context, A, select, vectors: bool, who: str):
+def _eigh_call(ctx: Context, A, select, vectors: bool, who: str, B=None):
     A = _square_dense(A, who)
     code = _dtype_code(A.dtype)
     n = A.shape[0]
+    if B is not None:
+        B = np.asarray(B)
+        if B.shape != A.shape:
+            raise EigSolError(EIGSOL_E_SIZE_MISMATCH, f"{who}: B must be square and of A's order")
+        if B.dtype != A.dtype:
+            raise EigSolError(3, f"{who}: scalar type mismatch: A is {A.dtype}, B is {B.dtype}")
     o = None
     if select is not None:
         if len(select) != 3 or select[0] not in ("i", "v"):
@@ -827,25 +835,55 @@ def _eigh_call(ctx: Context, A, select, vectors: bool, who: str):
     w = np.zeros(max(n, 1))
     Z = np.zeros((n, max(n, 1)), dtype=A.dtype, order="F") if vectors else None
     m, nc = C.c_int64(0), C.c_int64(0)
-    call("eigsol_eigh_dense", ctx.handle, code, n, _ptr(Af), None if o is None else C.byref(o), _ptr(w),
-         None if Z is None else _ptr(Z), C.byref(m), C.byref(nc))
+    if B is None:
+        call("eigsol_eigh_dense", ctx.handle, code, n, _ptr(Af), None if o is None else C.byref(o), _ptr(w),
+             None if Z is None else _ptr(Z), C.byref(m), C.byref(nc))
+    else:
+        Bf = np.asfortranarray(B)
+        call("eigsol_geigh_dense", ctx.handle, code, n, _ptr(Af), _ptr(Bf), None if o is None else C.byref(o), _ptr(w),
+             None if Z is None else _ptr(Z), C.byref(m), C.byref(nc), None)
     k = int(m.value)
     return w[:k].copy(), (None if Z is None else np.asfortranarray(Z[:, :k])), int(nc.value)
 
 
-def eigvalsh(ctx: Context, A, select=None) -> np.ndarray:
+def eigvalsh(ctx: Context, A, select=None, B=None) -> np.ndarray:
     """Eigenvalues (ascending) of the real symmetric / complex Hermitian matrix whose lower triangle
     is that of ``A`` (float64 / complex128; the strict upper triangle is not read), on the device
     (``eigsol_eigh_dense``): Hessenberg reduction, then bisection.  ``select``: ``None`` (all),
-    ``("i", il, iu)`` (0-based, inclusive) or ``("v", vl, vu)`` (vl < lambda <= vu)."""
-    return _eigh_call(ctx, A, select, False, "eigvalsh")[0]
+    ``("i", il, iu)`` (0-based, inclusive) or ``("v", vl, vu)`` (vl < lambda <= vu).
+    With ``B`` (Hermitian positive definite, same shape and dtype; its lower triangle is read): the
+    eigenvalues of A x = lambda B x (``eigsol_geigh_dense``: Cholesky, reduction to standard form)."""
+    return _eigh_call(ctx, A, select, False, "eigvalsh", B)[0]
 
 
-def eigh(ctx: Context, A, select=None) -> EighResult:
+def eigh(ctx: Context, A, select=None, B=None) -> EighResult:
     """:func:`eigvalsh` with an orthonormal set of eigenvectors (inverse iteration on the tridiagonal
-    matrix, back-transformed through the reduction's stored reflectors)."""
-    w, Z, nc = _eigh_call(ctx, A, select, True, "eigh")
+    matrix, back-transformed through the reduction's stored reflectors).  With ``B`` the eigenvectors
+    of A x = lambda B x, B-orthonormal; a ``B`` that is not positive definite raises with the first
+    failing column's index in the message."""
+    w, Z, nc = _eigh_call(ctx, A, select, True, "eigh", B)
     return EighResult(w, Z, nc)
+
+
+def cholesky(ctx: Context, B) -> np.ndarray:
+    """L of B = L L^H (``eigsol_cholesky_dense``; float64 / complex128; only the lower triangle of ``B``
+    is read): zero strict upper triangle, real positive diagonal.  Raises ``EigSolError`` naming the
+    first column whose pivot is not > 0 when ``B`` is not positive definite."""
+    B = _square_dense(B, "cholesky")
+    code = _dtype_code(B.dtype)
+    n = B.shape[0]
+    Bf = np.asfortranarray(B)
+    L = np.zeros((n, n), dtype=B.dtype, order="F")
+    call("eigsol_cholesky_dense", ctx.handle, code, n, _ptr(Bf), _ptr(L), None)
+    return L
+
+
+def geigh_stage_times(ctx: Context) -> dict:
+    """The context's last :func:`eigh` / :func:`eigvalsh` call with ``B`` by stream events, in seconds."""
+    ms = (C.c_double * 7)()
+    call("eigsol_geigh_stage_times", ctx.handle, ms)
+    return {k: ms[i] * 1e-3 for i, k in enumerate(("cholesky", "standardise", "reduction", "bisection",
+                                                   "inverse_iteration", "back_transform", "triangular_back_solve"))}
 
 
 def eigh_stage_times(ctx: Context) -> dict:

@@ -158,6 +158,9 @@ SIGNATURES = {
     "eigsol_hyman_refine": [_vp, C.c_int, _i64, _vp, _i64, _vp, _vp, _vp],
     "eigsol_eigh_dense": [_vp, C.c_int, _i64, _vp, C.POINTER(EighOptionsC), _vp, _vp, _pi64, _pi64],
     "eigsol_eigh_stage_times": [_vp, _pd],
+    "eigsol_cholesky_dense": [_vp, C.c_int, _i64, _vp, _vp, _pi64],
+    "eigsol_geigh_dense": [_vp, C.c_int, _i64, _vp, _vp, C.POINTER(EighOptionsC), _vp, _vp, _pi64, _pi64, _pi64],
+    "eigsol_geigh_stage_times": [_vp, _pd],
     "eigsol_tridiag_plan": [_i64, _vp, _vp, _i64, _vp, _vp, _vp, _pi64, _pi64],
     "eigsol_hbm_probe": [_vp, C.c_size_t, C.c_int, _pd, _pd, _pd, _pint],
     "eigsol_hbm_probe_mix": [_vp, C.c_size_t, C.c_int, _pd, _pint],

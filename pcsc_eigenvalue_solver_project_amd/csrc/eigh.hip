@@ -27,6 +27,7 @@
 #include <cmath>
 #include <vector>
 
+#include "cholesky.hpp"
 #include "kernels_common.hpp"
 
 namespace eigsol {
@@ -612,14 +613,6 @@ int tridiag_plan_impl(int64_t n, const double* d, const double* e, int64_t m, co
     return EIGSOL_OK;
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    template <class T> T* as() { return static_cast<T*>(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 64)); }
-};
 struct Events {
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     ~Events() {
@@ -658,26 +651,27 @@ struct EigItem {
     int64_t block, k;
 };
 
+// The solver on a matrix already on the device (dA: n x n, its lower triangle read; freed once reduced).
+// w_out (host) receives the m selected eigenvalues; with `vectors` dZ receives Z (n x m, on the device),
+// which is also copied to Z_host where that is given.  fix_phase: apply the phase convention to Z.
 template <class S>
-int eigh_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int select, int64_t il, int64_t iu, double vl, double vu,
-              double* w_out, void* Z_out, int64_t* m_out, int64_t* not_converged) {
+int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, int64_t iu, double vl, double vu,
+              double* w_out, bool vectors, bool fix_phase, void* Z_host, DevBuf& dZ, int64_t* m_out,
+              int64_t* not_converged) {
     using Ops = EighOps<S>;
     hipStream_t st = ctx->stream;
     const int NB = Ops::nb();
     const int64_t npan = n >= 3 ? (n - 2 + NB - 1) / NB : 0;
     Events E;
     for (auto& x : E.ev) EIGSOL_HIP(hipEventCreate(&x));
-    DevBuf dA, dV, dT, dd, de, dph;
-    EIGSOL_HIP(dA.alloc((size_t)n * n * sizeof(S)));
+    DevBuf dV, dT, dd, de, dph;
     EIGSOL_HIP(dd.alloc((size_t)n * sizeof(double)));
     EIGSOL_HIP(de.alloc((size_t)n * sizeof(double)));
     EIGSOL_HIP(dph.alloc((size_t)n * sizeof(S)));
-    const bool vectors = Z_out != nullptr;
     if (vectors && npan) {
         EIGSOL_HIP(dV.alloc((size_t)npan * n * NB * sizeof(S)));
         EIGSOL_HIP(dT.alloc((size_t)npan * NB * NB * sizeof(S)));
     }
-    EIGSOL_HIP(hipMemcpyAsync(dA.p, A_host, (size_t)n * n * sizeof(S), hipMemcpyHostToDevice, st));
     EIGSOL_HIP(hipEventRecord(E.ev[0], st));
     const unsigned gnn = (unsigned)(((int64_t)n * n + 255) / 256);
     hipLaunchKernelGGL(dev::eigh_symmetrise<S>, dim3(gnn), dim3(256), 0, st, dA.as<S>(), (int)n);
@@ -807,7 +801,7 @@ int eigh_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int select, int64_
     }
     constexpr int kClusterThreads = 1024;
     const int slots1 = (int)std::min<int64_t>(nsingle, 2048), slots2 = (int)std::min<int64_t>(ncl - nsingle, 512);
-    DevBuf dw, dcl, dit, dik, dZT, dwork, dfail, dD, dZ;
+    DevBuf dw, dcl, dit, dik, dZT, dwork, dfail, dD;
     EIGSOL_HIP(dw.alloc((size_t)m * sizeof(double)));
     EIGSOL_HIP(dcl.alloc((size_t)ncl * sizeof(dev::SteinCluster)));
     EIGSOL_HIP(dit.alloc((size_t)m * sizeof(int)));
@@ -845,9 +839,9 @@ int eigh_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int select, int64_
     const unsigned gnm = (unsigned)(((int64_t)n * m + 255) / 256);
     hipLaunchKernelGGL(dev::eigh_apply_phase<S>, dim3(gnm), dim3(256), 0, st, (int)n, m, dD.as<S>(), dZT.as<double>(), dZ.as<S>());
     if (npan) EIGSOL_TRY(Ops::back(st, n, m, dV.as<S>(), dT.as<S>(), dZ.as<S>()));
-    hipLaunchKernelGGL(dev::eigh_fix_phase<S>, dim3((unsigned)m), dim3(256), 0, st, (int)n, dZ.as<S>(), n);
+    if (fix_phase) hipLaunchKernelGGL(dev::eigh_fix_phase<S>, dim3((unsigned)m), dim3(256), 0, st, (int)n, dZ.as<S>(), n);
     EIGSOL_HIP(hipGetLastError());
-    EIGSOL_HIP(hipMemcpyAsync(Z_out, dZ.p, (size_t)n * m * sizeof(S), hipMemcpyDeviceToHost, st));
+    if (Z_host) EIGSOL_HIP(hipMemcpyAsync(Z_host, dZ.p, (size_t)n * m * sizeof(S), hipMemcpyDeviceToHost, st));
     EIGSOL_HIP(hipEventRecord(E.ev[4], st));
     EIGSOL_HIP(hipStreamSynchronize(st));
     if (not_converged) *not_converged = nfail;
@@ -856,7 +850,54 @@ int eigh_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int select, int64_
     return EIGSOL_OK;
 }
 
+template <class S>
+int eigh_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int select, int64_t il, int64_t iu, double vl, double vu,
+              double* w_out, void* Z_out, int64_t* m_out, int64_t* not_converged) {
+    DevBuf dA, dZ;
+    EIGSOL_HIP(dA.alloc((size_t)n * n * sizeof(S)));
+    EIGSOL_HIP(hipMemcpyAsync(dA.p, A_host, (size_t)n * n * sizeof(S), hipMemcpyHostToDevice, ctx->stream));
+    return eigh_core<S>(ctx, n, dA, select, il, iu, vl, vu, w_out, Z_out != nullptr, true, Z_out, dZ, m_out, not_converged);
+}
+
 }  // namespace
+
+int eigh_device(eigsol_ctx* ctx, int dtype, int64_t n, DevBuf& dA, int select, int64_t il, int64_t iu, double vl,
+                double vu, double* w_out, bool vectors, DevBuf& dZ, int64_t* m_out, int64_t* not_converged) {
+    return dtype == EIGSOL_C128
+               ? eigh_core<cplx>(ctx, n, dA, select, il, iu, vl, vu, w_out, vectors, false, nullptr, dZ, m_out, not_converged)
+               : eigh_core<double>(ctx, n, dA, select, il, iu, vl, vu, w_out, vectors, false, nullptr, dZ, m_out, not_converged);
+}
+
+int eigh_fix_phase_device(hipStream_t st, int dtype, int64_t n, int64_t m, void* Z) {
+    if (m <= 0) return EIGSOL_OK;
+    if (dtype == EIGSOL_C128)
+        hipLaunchKernelGGL(dev::eigh_fix_phase<cplx>, dim3((unsigned)m), dim3(256), 0, st, (int)n, static_cast<cplx*>(Z), n);
+    else
+        hipLaunchKernelGGL(dev::eigh_fix_phase<double>, dim3((unsigned)m), dim3(256), 0, st, (int)n, static_cast<double*>(Z), n);
+    EIGSOL_HIP(hipGetLastError());
+    return EIGSOL_OK;
+}
+
+int eigh_parse_selection(const char* who, int64_t n, const eigsol_eigh_options* opts, int* select, int64_t* il,
+                         int64_t* iu, double* vl, double* vu) {
+    *select = opts ? opts->select : EIGSOL_EIGH_ALL;
+    *il = 0;
+    *iu = n - 1;
+    *vl = *vu = 0.0;
+    if (*select == EIGSOL_EIGH_INDEX) {
+        *il = opts->il;
+        *iu = opts->iu;
+        if (*il > *iu || *il < 0 || *iu >= n) return fail(EIGSOL_E_INVALID, std::string(who) + ": index range outside 0 <= il <= iu < n");
+    } else if (*select == EIGSOL_EIGH_VALUE) {
+        *vl = opts->vl;
+        *vu = opts->vu;
+        if (std::isnan(*vl) || std::isnan(*vu) || !(*vl < *vu)) return fail(EIGSOL_E_INVALID, std::string(who) + ": value range needs vl < vu");
+    } else if (*select != EIGSOL_EIGH_ALL) {
+        return fail(EIGSOL_E_INVALID, std::string(who) + ": unknown selection");
+    }
+    return EIGSOL_OK;
+}
+
 }  // namespace eigsol
 
 using namespace eigsol;
@@ -887,20 +928,10 @@ int eigsol_eigh_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colma
         return EIGSOL_OK;
     }
     if (!ctx || !A_colmajor || !w || !m_out) return fail(EIGSOL_E_INVALID, "eigsol_eigh_dense: null pointer");
-    const int select = opts ? opts->select : EIGSOL_EIGH_ALL;
-    int64_t il = 0, iu = n - 1;
-    double vl = 0.0, vu = 0.0;
-    if (select == EIGSOL_EIGH_INDEX) {
-        il = opts->il;
-        iu = opts->iu;
-        if (il > iu || il < 0 || iu >= n) return fail(EIGSOL_E_INVALID, "eigsol_eigh_dense: index range outside 0 <= il <= iu < n");
-    } else if (select == EIGSOL_EIGH_VALUE) {
-        vl = opts->vl;
-        vu = opts->vu;
-        if (std::isnan(vl) || std::isnan(vu) || !(vl < vu)) return fail(EIGSOL_E_INVALID, "eigsol_eigh_dense: value range needs vl < vu");
-    } else if (select != EIGSOL_EIGH_ALL) {
-        return fail(EIGSOL_E_INVALID, "eigsol_eigh_dense: unknown selection");
-    }
+    int select;
+    int64_t il, iu;
+    double vl, vu;
+    EIGSOL_TRY(eigh_parse_selection("eigsol_eigh_dense", n, opts, &select, &il, &iu, &vl, &vu));
     if (dtype_wide(dtype) || dtype_single(dtype))
         return fail(EIGSOL_E_UNSUPPORTED, "eigsol_eigh_dense: double and complex double matrices only");
     if (!dtype_valid(dtype)) return fail(EIGSOL_E_INVALID, "eigsol_eigh_dense: unknown dtype");

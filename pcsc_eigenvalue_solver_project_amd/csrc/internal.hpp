@@ -253,6 +253,9 @@ struct eigsol_ctx {
     // the last eigsol_eigh_dense call's stages in ms, by stream events (eigsol_eigh_stage_times):
     // reduction, bisection, inverse iteration, back-transformation
     double eigh_ms[4] = {0.0, 0.0, 0.0, 0.0};
+    // the last eigsol_geigh_dense call's stages in ms (eigsol_geigh_stage_times): cholesky, standardise,
+    // the four above, triangular back solve
+    double geigh_ms[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 };
 
 struct eigsol_csr {

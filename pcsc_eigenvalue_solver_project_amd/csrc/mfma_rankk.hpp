@@ -3,6 +3,7 @@
 //
 //   C(m x nn) += alpha * L(m x K) * R^T          R stored nn x K      (kRT = false)
 //   C(m x nn) += alpha * L(m x K) * Rt           Rt stored K x nn     (kRT = true)
+//   kConj (default off): R is conjugated as it is read, so kRT = false forms L R^H (cholesky.hip)
 //
 // all column-major; S = double, cplx, float or cplxf (interleaved re, im; alpha real).  K <= KMAX, any K
 // (the k-steps past K are masked).  Every operand fragment is loaded straight from global memory
@@ -63,7 +64,7 @@ template <> struct MfmaOf<cplxf> : MfmaOf<float> {};
 
 // One 64 x 64 tile (tile row bx, tile column by) of the update, by a 256-thread workgroup; shared by
 // rankk_mfma (one launch per update) and batched callers (multifrontal.hip: many fronts per launch).
-template <class S, bool kRT>
+template <class S, bool kRT, bool kConj = false>
 __device__ __forceinline__ void rankk_tile(int bx, int by, int m, int nn, int K, double alpha, const S* L, int64_t ldl,
                                            const S* R, int64_t ldr, S* C, int64_t ldc) {
     constexpr bool kC = std::is_same_v<S, cplx> || std::is_same_v<S, cplxf>;
@@ -114,7 +115,8 @@ __device__ __forceinline__ void rankk_tile(int bx, int by, int m, int nn, int K,
                 const Real rr = kv ? re_of(ra[tj][q]) : Real(0), lr = kv ? re_of(lb[ti][q]) : Real(0);
                 are[ti][tj] = M::step(rr, lr, are[ti][tj]);
                 if constexpr (kC) {
-                    const Real ri = kv ? im_of(ra[tj][q]) : Real(0), li_ = kv ? im_of(lb[ti][q]) : Real(0);
+                    const Real ri = kv ? (kConj ? -im_of(ra[tj][q]) : im_of(ra[tj][q])) : Real(0),
+                               li_ = kv ? im_of(lb[ti][q]) : Real(0);
                     are[ti][tj] = M::step(-ri, li_, are[ti][tj]);
                     aim[ti][tj] = M::step(rr, li_, aim[ti][tj]);
                     aim[ti][tj] = M::step(ri, lr, aim[ti][tj]);
