@@ -174,6 +174,10 @@ int eigsol_power_kernel_info(eigsol_power* s, double* bytes_per_iteration, int32
  * "void eigsol::dev::csr_slice_kernel<double, true, 12, false, false>(...)"), the string rocprofv3
  * reports; empty for other sessions. */
 int eigsol_power_kernel_name(eigsol_power* s, char* buf, size_t capacity);
+/* Reference iterations one pass over the matrix runs: 2 for a CSR session on the pair path
+ * (csr_pair_kernel; EIGSOL_POWER_PAIR=0 forces single launches), else 1.  eigsol_power_step keeps
+ * counting reference iterations either way. */
+int eigsol_power_iterations_per_pass(eigsol_power* s, int32_t* n);
 /* variant: 0 = CSR, x gathered from HBM; 1 = CSR, x window staged in LDS; 2 = dense GEMV;
  *          3 = shifted inverse, sync-free triangular solve (tiles = dependency levels);
  *          4 = shifted inverse, dense LU substitution;

@@ -404,9 +404,12 @@ class PowerSession:
                  20: "dense LU substitution by triangles (dense_trsv_kernel: 64-row block rows, 64-step "
                      "triangles, epoch flags; chosen for a factor whose diagonal blocks are too ill "
                      "conditioned for products with their inverses, or by EIGSOL_DENSE_TRSV=1)"}
+        ipp = C.c_int32(1)
+        call("eigsol_power_iterations_per_pass", self.handle, C.byref(ipp))
         return {"bytes_per_iteration": b.value, "grid": g.value, "tiles": t.value,
                 "variant": v.value, "kernel": names.get(v.value, "?"),
-                "iterations_per_launch": v.value - 10 if 12 <= v.value <= 14 else 1}
+                "iterations_per_launch": v.value - 10 if 12 <= v.value <= 14 else 1,
+                "iterations_per_pass": ipp.value}
 
     def kernel_name(self) -> str:
         """Demangled name of the per-iteration kernel (CSR power sessions), as rocprofv3 reports it."""

@@ -102,6 +102,12 @@ struct CsrArgs {
     int32_t bcbits;          // log2 of the columns per block
     int32_t cbeg, cend;      // chunks of this launch (an iteration split in two row parts)
     int32_t cont;            // second part: read the first part's decision, add to its partial
+    // pair path (csr_pair_kernel; pair_prologue in kernels_common.hpp)
+    int32_t pair_mode;       // the session runs on the pair carry (single launches use pair_prologue too)
+    int32_t pair_ntiles;
+    const int4* pair_meta;   // per tile {first halo slice, end halo slice, first row read, end row read}
+    part4* pair_part;        // partials of a pair launch's second product
+    part4* pair_blk;
 };
 
 // Registers holding one tile's stream for one lane: P slots of (values, columns) plus the lane's
@@ -728,10 +734,14 @@ __device__ __forceinline__ uint32_t slice_entry(uint32_t off, int k, int lane) {
 
 // Every load of one slice's first KB entries, its window and the row lengths.  Loads are clamped
 // (to entry K-1, window entry wl-1): same cache lines, no extra bytes, no exec-masked loads.
-template <class S, int KB, bool kG, bool kDist = false>
+// kClamp (halo slices of a pair tile): only lanes [lane_lo, lane_hi] hold rows that are read, so
+// the value and offset loads of the other lanes repeat the nearest such lane's addresses.
+template <class S, int KB, bool kG, bool kDist = false, bool kClamp = false>
 __device__ __forceinline__ void slice_issue(const CsrArgs<S>& a, const S* xin, int slice, int4 m,
-                                            SliceRegs<S, KB, kG>& R, const S* gin = nullptr) {
-    const int lane = threadIdx.x & 63;
+                                            SliceRegs<S, KB, kG>& R, const S* gin = nullptr, int lane_lo = 0,
+                                            int lane_hi = 63) {
+    const int wlane = threadIdx.x & 63;   // the window loads always spread over all lanes
+    const int lane = kClamp ? min(max(wlane, lane_lo), lane_hi) : wlane;
     // K = 0 (all rows empty) clamps to entry 0 of the slice: the streams carry one slice of
     // padding past their end, so even an empty last slice loads in bounds
     const int K = max(m.z & 0xff, 1);
@@ -769,11 +779,11 @@ __device__ __forceinline__ void slice_issue(const CsrArgs<S>& a, const S* xin, i
 #pragma unroll
             for (int j = 0; j < SliceRegs<S, KB, kG>::NW; ++j) {
                 if constexpr (is_real_v<S>) {
-                    const int e = m.y + 2 * min(lane + 64 * j, (wl >> 1) - 1);
+                    const int e = m.y + 2 * min(wlane + 64 * j, (wl >> 1) - 1);
                     R.w[j].x = ld_x_peer(a, xin, gin, e);
                     R.w[j].y = ld_x_peer(a, xin, gin, e + 1);
                 } else {
-                    R.w[j] = ld_x_peer(a, xin, gin, m.y + min(lane + 64 * j, wl - 1));
+                    R.w[j] = ld_x_peer(a, xin, gin, m.y + min(wlane + 64 * j, wl - 1));
                 }
             }
         } else
@@ -781,9 +791,9 @@ __device__ __forceinline__ void slice_issue(const CsrArgs<S>& a, const S* xin, i
         for (int j = 0; j < SliceRegs<S, KB, kG>::NW; ++j)
             if constexpr (is_real_v<S>)
                 R.w[j] = ldg(reinterpret_cast<const pair_t<S>*>(xin),
-                             (uint32_t)((m.y >> 1) + min(lane + 64 * j, (wl >> 1) - 1)));
+                             (uint32_t)((m.y >> 1) + min(wlane + 64 * j, (wl >> 1) - 1)));
             else
-                R.w[j] = ldg(xin, (uint32_t)(m.y + min(lane + 64 * j, wl - 1)));
+                R.w[j] = ldg(xin, (uint32_t)(m.y + min(wlane + 64 * j, wl - 1)));
     } else if constexpr (kG) {
 #pragma unroll
         for (int u = 0; u < KB; ++u)
@@ -798,11 +808,15 @@ __device__ __forceinline__ S shfl_s(S v, int src) {
     else return S{__shfl(v.re, src, 64), __shfl(v.im, src, 64)};
 }
 
-template <class S, bool kPower, int KB, bool kG, bool kDist = false>
+// kPair (csr_pair_kernel, first product of a tile): 1: an own slice, whose rows also go, scaled
+// by s, to the tile's LDS array lw (entry 0 = row span_lo); 2: a halo slice, whose rows
+// [need_lo, need_hi) go to the LDS array only.
+template <class S, bool kPower, int KB, bool kG, bool kDist = false, int kPair = 0>
 __device__ __forceinline__ void slice_compute(const CsrArgs<S>& a, const S* xin, S* yout, double nrm,
                                               const SliceRegs<S, KB, kG>& R, int4 mc, int sl, S* xw,
                                               double& n2, double& rr, double& ri, const S* gin = nullptr,
-                                              int parity = 0) {
+                                              int parity = 0, S* lw = nullptr, int span_lo = 0, double s = 1.0,
+                                              int need_lo = 0, int need_hi = 0) {
     const int lane = threadIdx.x & 63;
     const int K = mc.z & 0xff;
     const S* sval = a.sval;
@@ -886,8 +900,11 @@ __device__ __forceinline__ void slice_compute(const CsrArgs<S>& a, const S* xin,
         if constexpr (kPower) xi = scale_in(xin[rowc + a.xoff], nrm);
     }
     if (valid) {
-        yout[row] = sacc;   // a non-temporal store measured slower: the next launch reads y as x
-        if constexpr (kPower) {
+        if constexpr (kPair != 2) yout[row] = sacc;   // a non-temporal store measured slower: the next launch reads y as x
+        if constexpr (kPair == 1) lw[row - span_lo] = s * sacc;   // s = 2^-e: exact
+        if constexpr (kPair == 2)
+            if (row >= need_lo && row < need_hi) lw[row - span_lo] = s * sacc;
+        if constexpr (kPower && kPair != 2) {
             n2 += sq_abs(sacc);
             acc_dot(rr, ri, xi, sacc);
         }
@@ -951,7 +968,10 @@ __global__ __launch_bounds__(kThreads) void csr_slice_kernel(CsrArgs<S> a, int p
     double nrm = 0.0;
     const S* gin = nullptr;   // peer exchange: ghost entries of the input (inbox, previous parity)
     if constexpr (kPower) {
-        power_prologue<S>(a.ctl, a.rank_part, a.nranks, parity, a.trace, &pro, kDist ? &a.peer : nullptr);
+        if (!kDist && !kG && a.pair_mode)   // a single launch of a session on the pair carry
+            pair_prologue<S>(a.ctl, a.rank_part, a.pair_part, parity, a.trace, &pro, false);
+        else
+            power_prologue<S>(a.ctl, a.rank_part, a.nranks, parity, a.trace, &pro, kDist ? &a.peer : nullptr);
         if (!__builtin_amdgcn_readfirstlane(pro.go)) return;   // block-uniform exit
         nrm = pro.nrm;
         xin = parity ? a.buf0 : a.buf1;
@@ -1039,6 +1059,165 @@ __global__ __launch_bounds__(kThreads) void csr_slice_kernel(CsrArgs<S> a, int p
             }
         }
     }
+}
+
+// ============================================================================ pair kernel
+// Two power iterations per pass over a matrix whose slices are all window slices (pair_prologue
+// in kernels_common.hpp has the algebra and the control plane).  A workgroup takes tiles of
+// kPairT consecutive slices, XCD-contiguous like the slice ranges above.  First product: the
+// tile's own slices and the halo slices their windows reach are multiplied exactly as
+// slice_compute does for a single launch (w1 is bitwise a single launch's y); own rows go to
+// global memory, and own and halo rows, scaled by s, to a block-level LDS array.  After one block
+// barrier the own slices, whose values and offsets are still in the owning wave's registers, are
+// multiplied again with s w1 read from the LDS array in place of the x window.  The LDS array is
+// double buffered, so one barrier per tile is enough: a wave can only write buffer b again after
+// the barrier of the tile in between, which every wave reaches after its reads of b.
+// Halo slices load only the lanes whose rows are read (slice_issue, kClamp).
+#ifndef EIGSOL_PAIR_T
+#define EIGSOL_PAIR_T 16
+#endif
+// own slices per tile (EIGSOL_PAIR_T, compile time, for A/B builds).  band10m f64, us per iteration,
+// two workgroups per CU: 4: 175, 8: 142, 16: 120-125, 20: 123 (248 VGPRs); the halo slices of a
+// band of half-width 64 are read whole, so the tile size sets the extra matrix traffic (2 / T)
+constexpr int kPairT = EIGSOL_PAIR_T;
+constexpr int kPairHalo = 4;              // halo slices a tile may have (both sides together)
+constexpr int kPairSpan = (kPairT + kPairHalo) * kSliceRows;
+constexpr int kPairBlocksPerCU = 2;        // T = 16: 1 / 2 / 3 per CU 148 / 120 / 130 us
+// the next tile's loads go out while this tile computes (two register sets of kPairT / kWaves
+// slices per wave); larger tiles hold too many registers for that and rely on the other resident blocks
+constexpr bool kPairPipe = kPairT <= 8;
+static_assert(kPairT % kWaves == 0 && kPairHalo <= kWaves, "pair tile: whole rounds of waves, one halo slice per wave");
+
+// Second product of one own slice from its registers: x = s w1 from the tile's LDS array.
+template <class S, int KB>
+__device__ __forceinline__ void slice_compute2(const CsrArgs<S>& a, S* yout, const SliceRegs<S, KB, false>& R,
+                                               int4 mc, int sl, const S* lw, int span_lo, double& n2,
+                                               double& rr, double& ri) {
+    const int lane = threadIdx.x & 63;
+    const int K = mc.z & 0xff;
+    const S* sval = a.sval;
+    const uint32_t* scol8 = a.scol8;
+    if (a.nseg > 1) {
+        const int seg = (mc.z >> kSliceSegShift) & (kMaxSliceSeg - 1);
+        sval += a.seg_val[seg];
+        scol8 += a.seg_c8[seg];
+    }
+    const int row = sl * kSliceRows + lane;
+    const bool valid = row < a.nrows;
+    const int rowc = valid ? row : a.nrows - 1;
+    const S* xw = lw + (mc.y - span_lo);   // the slice's window lies inside the tile's span
+    S sacc = s_zero<S>();
+#pragma unroll
+    for (int u = 0; u < KB; ++u) {
+        const S pr = mul(slice_val(R, u), xw[(R.c[u >> 2] >> (8 * (u & 3))) & 0xffu]);
+        if (u < R.len) sacc = add(sacc, pr);
+    }
+    for (int k0 = KB & ~3; k0 < K; k0 += 4) {
+        const uint32_t cw = ldg(scol8, (uint32_t)mc.w + 64u * (uint32_t)(k0 >> 2) + (uint32_t)lane);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const S pr = mul(ldg(sval, slice_entry<S>((uint32_t)mc.x, min(k0 + u, K - 1), lane)),
+                             xw[(cw >> (8 * u)) & 0xffu]);
+            if (k0 + u >= KB && k0 + u < R.len) sacc = add(sacc, pr);
+        }
+    }
+    if (valid) {
+        const S xi = lw[rowc - span_lo];
+        yout[row] = sacc;
+        n2 += sq_abs(sacc);
+        acc_dot(rr, ri, xi, sacc);
+    }
+}
+
+template <class S, int KB>
+__global__ __launch_bounds__(kThreads) void csr_pair_kernel(CsrArgs<S> a, int parity, const S* xin, S* out1,
+                                                            S* out2) {
+    static_assert(is_real_v<S>, "pair kernel: real scalars");
+    constexpr int Q = kPairT / kWaves;   // own slices a wave holds across the barrier
+    using Regs = SliceRegs<S, KB, false>;
+    __shared__ __align__(16) S xw_all[kWaves][kSliceWin];
+    __shared__ __align__(16) S w1s[2][kPairSpan];
+    __shared__ double sm[3 * kWaves];
+    __shared__ Prologue pro;
+    __shared__ int s_last;
+
+    pair_prologue<S>(a.ctl, a.rank_part, a.pair_part, parity, a.trace, &pro, true);
+    if (!__builtin_amdgcn_readfirstlane(pro.go)) return;   // block-uniform exit
+    const double nrm = pro.nrm, s = pro.s;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    double p[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+
+    // XCD-contiguous tile ranges; the tile loop and its barrier are block-uniform
+    const int tstep = gridDim.x >> 3;
+    const int chunk = (a.pair_ntiles + 7) >> 3;
+    const int tbeg = (blockIdx.x & 7) * chunk;
+    const int tend = min(a.pair_ntiles, tbeg + chunk);
+    auto issue = [&](Regs(&R)[Q], int4(&mc)[Q], int tl) {
+#pragma unroll
+        for (int j = 0; j < Q; ++j) mc[j] = ld_uniform(a.slice_meta, min(tl * kPairT + j * kWaves + wave, a.nslices - 1));
+#pragma unroll
+        for (int j = 0; j < Q; ++j)   // past the last slice: reloads it, unused
+            slice_issue<S, KB, false>(a, xin, min(tl * kPairT + j * kWaves + wave, a.nslices - 1), mc[j], R[j]);
+    };
+    // one tile from registers R; the next tile's loads go out into Rn behind the halo slice's
+    auto run = [&](const Regs(&R)[Q], const int4(&mc)[Q], int tl, int b, Regs(&Rn)[Q], int4(&mn)[Q]) {
+        const int4 tm = ld_uniform(a.pair_meta, tl);
+        const int s0 = tl * kPairT, s1 = min(s0 + kPairT, a.nslices);
+        const int hl = s0 - tm.x, nh = hl + (tm.y - s1);   // halo slices: below the tile, in all
+        const int span_lo = tm.x * kSliceRows;
+        S* lw = w1s[b];
+        Regs RH;
+        int4 mh = make_int4(0, 0, 0, 0);
+        const int hs = wave < hl ? tm.x + wave : s1 + (wave - hl);   // wave < nh: this wave's halo slice
+        if (wave < nh) {
+            mh = ld_uniform(a.slice_meta, hs);
+            slice_issue<S, KB, false, false, true>(a, xin, hs, mh, RH, nullptr, min(max(tm.z - hs * kSliceRows, 0), 63),
+                                                   min(max(tm.w - 1 - hs * kSliceRows, 0), 63));
+        }
+        if (kPairPipe && tl + tstep < tend) issue(Rn, mn, tl + tstep);
+#pragma unroll
+        for (int j = 0; j < Q; ++j) {
+            const int sl = s0 + j * kWaves + wave;
+            if (sl < s1)
+                slice_compute<S, true, KB, false, false, 1>(a, xin, out1, nrm, R[j], mc[j], sl, xw_all[wave], p[0], p[1],
+                                                            p[2], nullptr, 0, lw, span_lo, s);
+        }
+        if (wave < nh) {
+            double z0 = 0.0, z1 = 0.0, z2 = 0.0;
+            slice_compute<S, true, KB, false, false, 2>(a, xin, out1, nrm, RH, mh, hs, xw_all[wave], z0, z1, z2, nullptr,
+                                                        0, lw, span_lo, s, tm.z, tm.w);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < Q; ++j) {
+            const int sl = s0 + j * kWaves + wave;
+            if (sl < s1) slice_compute2<S, KB>(a, out2, R[j], mc[j], sl, lw, span_lo, p[3], p[4], p[5]);
+        }
+    };
+    {
+        Regs RA[Q], RB[Q];
+        int4 ma[Q], mb[Q];
+        int tl = tbeg + (blockIdx.x >> 3);
+        if constexpr (kPairPipe) {
+            // unrolled by two so both register sets have static names
+            if (tl < tend) issue(RA, ma, tl);
+            while (tl < tend) {
+                run(RA, ma, tl, 0, RB, mb);
+                tl += tstep;
+                if (tl >= tend) break;
+                run(RB, mb, tl, 1, RA, ma);
+                tl += tstep;
+            }
+        } else {
+            for (int b = 0; tl < tend; tl += tstep, b ^= 1) {
+                issue(RA, ma, tl);
+                run(RA, ma, tl, b, RB, mb);
+            }
+        }
+    }
+    block_sum3(p[0], p[1], p[2], sm);
+    block_sum3(p[3], p[4], p[5], sm);
+    pair_reduce(p, a.blk_part, a.pair_blk, &a.ctl->counter, a.my_part, a.pair_part, sm, &s_last);
 }
 
 // Start of a peer-exchange session (begin(), after the x0 norm partial): x0's halo rows and the
@@ -1295,7 +1474,7 @@ void csr_release(eigsol_csr* A) {
     if (A->val) (void)hipFree(A->val);
     if (A->tile_meta) (void)hipFree(A->tile_meta);
     if (A->tile_win) (void)hipFree(A->tile_win);
-    for (void* q : {(void*)A->slice_meta, A->sval, (void*)A->scol8, (void*)A->scol32, (void*)A->slen})
+    for (void* q : {(void*)A->slice_meta, A->sval, (void*)A->scol8, (void*)A->scol32, (void*)A->slen, (void*)A->pair_meta})
         if (q) (void)hipFree(q);
     if (A->send_idx) (void)hipFree(A->send_idx);
     if (A->send_buf) (void)hipFree(A->send_buf);
@@ -1499,6 +1678,34 @@ static bool build_slices(const int32_t* rowptr, const int32_t* col, const void* 
     return true;
 }
 
+// Tiles of the pair kernel: per tile of kPairT slices the rows its windows read [lo, hi) and the
+// slices [h0, h1) holding them (the tile's own and its halo slices).  False when some slice
+// gathers or a tile's span does not fit the kernel's LDS array (the matrix keeps single launches).
+static bool build_pair_tiles(const SliceLayout& L, int64_t nrows, std::vector<int32_t>& tm) {
+    const int64_t ns = (int64_t)L.meta.size() / 4;
+    if (ns == 0 || L.any_gather) return false;
+    const int64_t nt = (ns + kPairT - 1) / kPairT;
+    tm.assign((size_t)(4 * nt), 0);
+    for (int64_t t = 0; t < nt; ++t) {
+        const int64_t s0 = t * kPairT, s1 = std::min<int64_t>(ns, s0 + kPairT);
+        int64_t lo = s0 * kSliceRows, hi = std::min<int64_t>(nrows, s1 * kSliceRows);
+        for (int64_t sl = s0; sl < s1; ++sl) {
+            const int64_t w0 = L.meta[4 * sl + 1], wl = (L.meta[4 * sl + 2] >> 9) & 0x1ff;
+            if (w0 < 0) return false;
+            lo = std::min(lo, w0);
+            hi = std::max(hi, w0 + wl);
+        }
+        if (lo < 0 || hi > nrows) return false;
+        const int64_t h0 = std::min(s0, lo / kSliceRows), h1 = std::max(s1, (hi + kSliceRows - 1) / kSliceRows);
+        if ((s0 - h0) + (h1 - s1) > kPairHalo || (h1 - h0) * kSliceRows > kPairSpan) return false;
+        tm[4 * t] = (int32_t)h0;
+        tm[4 * t + 1] = (int32_t)h1;
+        tm[4 * t + 2] = (int32_t)lo;
+        tm[4 * t + 3] = (int32_t)hi;
+    }
+    return true;
+}
+
 // xoff: x-space index of local row 0 (0 on one GPU; the lower-ghost count when row-sharded)
 static int build_col_blocks(eigsol_csr* A, const int32_t* rowptr, const int32_t* col, const void* val);
 static int build_bins(eigsol_csr* A, const int32_t* rowptr, const int32_t* col, const void* val);
@@ -1636,6 +1843,17 @@ int csr_upload(eigsol_ctx* ctx, int dtype, int64_t nrows, int64_t ncols, int64_t
             (e = hipStreamSynchronize(s)) != hipSuccess) {
             cleanup();
             return fail(EIGSOL_E_HIP, std::string("eigsol_csr_create: slice upload: ") + hipGetErrorString(e));
+        }
+        // pair path: decided here, once; square single-GPU f64 matrices of window slices only
+        std::vector<int32_t> ptm;
+        if (dtype == EIGSOL_F64 && nrows == ncols && xoff == 0 && !A->slice_gather && build_pair_tiles(SL, nrows, ptm)) {
+            if ((e = upl((void**)&A->pair_meta, ptm.data(), ptm.size() * 4)) != hipSuccess ||
+                (e = hipStreamSynchronize(s)) != hipSuccess) {
+                cleanup();
+                return fail(EIGSOL_E_HIP, std::string("eigsol_csr_create: pair tile upload: ") + hipGetErrorString(e));
+            }
+            A->pair_ntiles = (int32_t)(ptm.size() / 4);
+            A->pair_ok = 1;
         }
     }
     int rcb = build_bins(A, rowptr, col_use, val_use);
@@ -2031,6 +2249,11 @@ static CsrArgs<S> make_args(const eigsol_csr* A, int64_t xlen) {
     a.cbeg = 0;
     a.cend = A->nchunks;
     a.cont = 0;
+    a.pair_mode = 0;
+    a.pair_ntiles = A->pair_ntiles;
+    a.pair_meta = (const int4*)A->pair_meta;
+    a.pair_part = nullptr;
+    a.pair_blk = nullptr;
     return a;
 }
 
@@ -2157,6 +2380,54 @@ int csr_power_launch(eigsol_csr* A, int64_t xlen, void* buf0, void* buf1, PowerC
                                      trace, parity, grid, peer, part);
     return power_launch_t<double>(A, xlen, buf0, buf1, ctl, rank_part, nranks, my_part, blk_part,
                                   trace, parity, grid, peer, part);
+}
+
+// ---- pair path entry points (power_session.cpp)
+static const void* pair_kernel_ptr(const eigsol_csr* A) {
+    switch (A->slice_kb) {
+        case 4: return reinterpret_cast<const void*>(csr_pair_kernel<double, 4>);
+        case 8: return reinterpret_cast<const void*>(csr_pair_kernel<double, 8>);
+        case 12: return reinterpret_cast<const void*>(csr_pair_kernel<double, 12>);
+        default: return reinterpret_cast<const void*>(csr_pair_kernel<double, 16>);
+    }
+}
+const void* csr_pair_kernel_ptr(const eigsol_csr* A) { return A->pair_ok ? pair_kernel_ptr(A) : nullptr; }
+
+int csr_pair_grid(eigsol_csr* A, int* grid) {
+    return resident_grid(A->ctx, pair_kernel_ptr(A), A->pair_ntiles, grid, kPairBlocksPerCU);
+}
+
+// One launch of a session on the pair carry: pair != 0 runs reference launches t and t + 1 (xin ->
+// out1 -> out2), else one single launch xin -> out1 of the slice kernel with the pair prologue.
+int csr_pair_launch(eigsol_csr* A, int64_t xlen, const void* xin, void* out1, void* out2, PowerCtl* ctl,
+                    void* part1, void* part2, void* blk1, void* blk2, void* trace, int parity, int grid, int pair) {
+    if (!A->pair_ok) return fail(EIGSOL_E_INVALID, "pair launch: the matrix is not eligible");
+    CsrArgs<double> a = make_args<double>(A, xlen);
+    // the slice kernel reads buf[parity ^ 1] and writes buf[parity]
+    a.buf0 = (double*)(parity ? const_cast<void*>(xin) : out1);
+    a.buf1 = (double*)(parity ? out1 : const_cast<void*>(xin));
+    a.ctl = ctl;
+    a.rank_part = (const part4*)part1;
+    a.nranks = 1;
+    a.my_part = (part4*)part1;
+    a.blk_part = (part4*)blk1;
+    a.trace = (double*)trace;
+    a.pair_mode = 1;
+    a.pair_part = (part4*)part2;
+    a.pair_blk = (part4*)blk2;
+    if (!pair) return launch_csr<double>(A, a, true, parity, grid, false);
+    hipStream_t s = A->ctx->stream;
+    const double* xi = (const double*)xin;
+    double* o1 = (double*)out1;
+    double* o2 = (double*)out2;
+    switch (A->slice_kb) {
+        case 4: hipLaunchKernelGGL((csr_pair_kernel<double, 4>), dim3(grid), dim3(kThreads), 0, s, a, parity, xi, o1, o2); break;
+        case 8: hipLaunchKernelGGL((csr_pair_kernel<double, 8>), dim3(grid), dim3(kThreads), 0, s, a, parity, xi, o1, o2); break;
+        case 12: hipLaunchKernelGGL((csr_pair_kernel<double, 12>), dim3(grid), dim3(kThreads), 0, s, a, parity, xi, o1, o2); break;
+        default: hipLaunchKernelGGL((csr_pair_kernel<double, 16>), dim3(grid), dim3(kThreads), 0, s, a, parity, xi, o1, o2); break;
+    }
+    EIGSOL_HIP(hipGetLastError());
+    return EIGSOL_OK;
 }
 
 // Own rows in the first part of a split iteration (binned layout): whole chunks of the first half.

@@ -285,6 +285,11 @@ struct eigsol_csr {
     uint8_t* slen = nullptr;       // device, per row (ragged slices)
     int32_t nseg = 1;              // stream segments (see kSliceSegShift): element offsets of each
     int64_t seg_val[16] = {0}, seg_c8[16] = {0}, seg_c32[16] = {0};
+    // pair path (csr_pair_kernel): eligible when square, f64, xoff == 0, every slice a window slice
+    // and every tile's span fits the kernel's LDS array; decided at upload
+    int32_t pair_ok = 0;
+    int32_t pair_ntiles = 0;
+    int32_t* pair_meta = nullptr;  // device, 4 ints per tile
     // Row-sharded (multi-GPU) layout: this rank owns global rows [row_begin, row_begin + nrows);
     // local columns are [own rows | ghosts grouped by owner rank, ascending global index].
     int dist = 0;

@@ -393,6 +393,149 @@ __device__ __forceinline__ T ldg_stream(const T* base, uint32_t i) {
 #endif
 }
 
+// Pair launches of the power iteration (csr_power.hip, csr_pair_kernel): one pass over the matrix
+// runs reference launches t and t+1.  w1 = A x is launch t's product exactly as a single launch
+// computes it; w2 = A (s w1), s = 2^-e an exact power of two near 1 / ||w1|| (e from the previous
+// launch's growth), is launch t+1's product with its normalisation deferred by linearity:
+//     y_{t+1} = A (w1 / ||w1||) = w2 / (s ||w1||)
+// which moves only the rounding of the division by the norm (the same construction as
+// shift_multi_prologue below).  Partials: part1 = {||w1||^2, x^H w1} as a single launch leaves
+// them, part2 = {||w2||^2, (s w1)^H w2}, so
+//     rho_{t+1} = (s w1)^H w2 / (s^2 ||w1||^2),   ||y_{t+1}|| = ||w2|| / (s ||w1||)
+// and the next input is w2 / ||w2||.  y_v lives in vector buffer (v + 3) % 3 (x0 in buffer 2), so
+// a pair never overwrites an iterate a stopping decision can still return.
+//
+// This prologue serves every launch of a session on the pair path, single launches included
+// (this_pair == false), so the two kinds interleave freely on one carry.  It first applies
+// power_decide to the deferred launch of a preceding pair (carry.pad != 0), then to its own first
+// launch, in order: ctl->launches, ntrace, the trace, iters and converged take the single path's
+// values, and work past the stopping launch is discarded.  A decision that stops at launch v
+// returns y_{v-2} / ||y_{v-2}||: final_parity = kPairCode + (v + 1) % 3.
+// Carry: rho = the last Rayleigh quotient, nrm = the norm of this launch's input buffer,
+// t = the last reference launch this launch runs, pad = 0 (single) or kPairFlag | (e + 1024).
+constexpr int32_t kPairFlag = 1 << 16;
+constexpr int32_t kPairCode = 4;
+template <class S>
+__device__ __forceinline__ void pair_prologue(PowerCtl* ctl, const part4* part1, const part4* part2,
+                                              int parity, S* trace, Prologue* out, bool this_pair) {
+    if (threadIdx.x == 0) {
+        Prologue pr{0.0, 0, 0, 1.0};
+        const int done = __hip_atomic_load(&ctl->done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (!done) {
+            const PowerCarry in = ctl->st[parity];
+            const int32_t t = in.t + 1;   // this launch's (first) reference launch
+            const bool cplx_ = is_cplx_v<S>;
+            const bool w0 = blockIdx.x == 0;
+            const part4 p1 = part1[0];
+            bool fin = false;
+            int32_t fcode = 0;
+            double fnorm = 0.0, rho_re = in.rho_re, rho_im = in.rho_im, nrm = 0.0, g = 0.0;
+            PowerDecision d;
+            // one reference launch v: the single path's bookkeeping
+            auto apply = [&](int32_t v, double nv, double rr, double ri, double pre, double pim, double fn) {
+                d = power_decide(v, ctl->max_iter, ctl->tol, cplx_, nv, rr, ri, pre, pim);
+                if (w0) {
+                    ctl->launches = v + 1;
+                    if (d.record) ctl->ntrace = d.k + 1;
+                    if (d.record && trace && d.k < ctl->trace_cap) set_re_im(trace[d.k], d.lam_re, d.lam_im);
+                }
+                if (d.done) {
+                    fin = true;
+                    fcode = kPairCode + (v + 1) % 3;
+                    fnorm = fn;
+                }
+            };
+            if (!(in.pad & kPairFlag)) {
+                nrm = sqrt(p1.a);
+                apply(t, nrm, p1.b, p1.c, in.rho_re, in.rho_im, in.nrm);
+                rho_re = p1.b;
+                rho_im = p1.c;
+                g = nrm;
+            } else {
+                const double sp = ldexp(1.0, -((in.pad & 0xffff) - 1024));
+                const double n1 = sqrt(p1.a);
+                apply(t - 1, n1, p1.b, p1.c, in.rho_re, in.rho_im, in.nrm);
+                if (!fin) {   // n1 > 0 here
+                    const part4 p2 = part2[0];
+                    const double den = sp * sp * p1.a;
+                    rho_re = p2.b / den;
+                    rho_im = p2.c / den;
+                    nrm = sqrt(p2.a);
+                    g = nrm / (sp * n1);
+                    apply(t, g, rho_re, rho_im, p1.b, p1.c, n1);
+                }
+            }
+            // growth of the last product from a unit input: the scale of this launch's second product
+            int32_t e = 0;
+            if (this_pair && g > 0.0 && g < INFINITY) e = min(max(ilogb(g), -900), 900);
+            if (w0) {
+                PowerCarry o;
+                o.rho_re = rho_re;
+                o.rho_im = rho_im;
+                o.nrm = nrm;
+                o.t = this_pair ? t + 1 : t;
+                o.pad = this_pair ? (kPairFlag | (e + 1024)) : 0;
+                ctl->st[parity ^ 1] = o;
+                if (fin) {
+                    ctl->lam_re = d.lam_re;
+                    ctl->lam_im = d.lam_im;
+                    ctl->iters = d.iters;
+                    ctl->converged = d.converged ? 1 : 0;
+                    ctl->final_parity = fcode;
+                    ctl->final_norm = fnorm;
+                    __hip_atomic_store(&ctl->done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+            pr.go = fin ? 0 : 1;
+            pr.nrm = nrm;
+            pr.t = t;
+            pr.s = ldexp(1.0, -e);
+        }
+        *out = pr;
+    }
+    __syncthreads();
+}
+
+// last_arriver_reduce for the two partial records of a pair launch: one ticket, both records
+// summed in block order by the last-arriving block.  Values valid in thread 0.
+__device__ __forceinline__ void pair_reduce(const double (&v)[6], part4* blk1, part4* blk2, uint32_t* counter,
+                                            part4* out1, part4* out2, double* sm, int* s_last) {
+    const uint32_t G = gridDim.x;
+    if (threadIdx.x == 0) {
+        part4* p = blk1 + blockIdx.x;
+        part4* q = blk2 + blockIdx.x;
+        st_agent(&p->a, v[0]);
+        st_agent(&p->b, v[1]);
+        st_agent(&p->c, v[2]);
+        st_agent(&q->a, v[3]);
+        st_agent(&q->b, v[4]);
+        st_agent(&q->c, v[5]);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const uint32_t tk = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *s_last = (tk == G - 1) ? 1 : 0;
+    }
+    __syncthreads();
+    if (!*s_last) return;
+    for (int h = 0; h < 2; ++h) {
+        const part4* blk = h ? blk2 : blk1;
+        double sa = 0.0, sb = 0.0, sc = 0.0;
+        for (uint32_t i = threadIdx.x; i < G; i += kThreads) {
+            sa += ld_agent(&blk[i].a);
+            sb += ld_agent(&blk[i].b);
+            sc += ld_agent(&blk[i].c);
+        }
+        block_sum3(sa, sb, sc, sm);
+        if (threadIdx.x == 0) {
+            part4* out = h ? out2 : out1;
+            out->a = sa;
+            out->b = sb;
+            out->c = sc;
+            out->d = 0.0;
+        }
+    }
+    if (threadIdx.x == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 }  // namespace dev
 }  // namespace eigsol
 

@@ -25,6 +25,10 @@ const void* csr_power_kernel(const eigsol_csr* A, bool peer);
 int csr_power_launch(eigsol_csr* A, int64_t xlen, void* buf0, void* buf1, PowerCtl* ctl,
                      const void* rank_part, int nranks, void* my_part, void* blk_part, void* trace,
                      int parity, int grid, const dev::PeerArgs* peer = nullptr, int part = -1);
+const void* csr_pair_kernel_ptr(const eigsol_csr* A);
+int csr_pair_grid(eigsol_csr* A, int* grid);
+int csr_pair_launch(eigsol_csr* A, int64_t xlen, const void* xin, void* out1, void* out2, PowerCtl* ctl,
+                    void* part1, void* part2, void* blk1, void* blk2, void* trace, int parity, int grid, int pair);
 int64_t csr_bin_split_row(const eigsol_csr* A);
 int dist_exchange_part(eigsol_csr* A, void* y, void* rank_part, int part, const std::vector<int64_t>& split,
                        hipStream_t comm_st, hipEvent_t* ev);
@@ -80,7 +84,7 @@ struct eigsol_power {
     int64_t nbuf = 0;         // own + ghost entries (x-space)
     int64_t xoff = 0;         // x-space index of own row 0 (row-sharded: lower ghosts first)
     bool dist = false;
-    void* buf[2] = {nullptr, nullptr};
+    void* buf[3] = {nullptr, nullptr, nullptr};   // the third: sessions on the pair path only
     PowerCtl* ctl = nullptr;
     void* rank_part = nullptr;   // part4[nranks]
     void* my_part = nullptr;     // part4 (== rank_part on one GPU)
@@ -105,6 +109,14 @@ struct eigsol_power {
     hipStream_t comm = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     WideSession* wide = nullptr;   // EIGSOL_DD / EIGSOL_CDD: the double-double session (wide.hip)
+    // Pair path (csr_pair_kernel; pair_prologue in kernels_common.hpp): two reference launches per
+    // pass over the matrix.  y_v lives in buf[(v + 3) % 3] (x0 = y_{-1} in buf[2]); vt is the next
+    // reference launch.  Launch 0 is single (no growth estimate yet), as is an odd remainder.
+    bool pair = false;
+    int pair_grid = 8;
+    int64_t vt = 0;
+    void* pair_part = nullptr;   // part4: partials of a pair launch's second product
+    void* pair_blk = nullptr;    // part4[pair_grid]
 };
 
 static constexpr size_t kPart = 32;
@@ -112,18 +124,25 @@ static constexpr size_t kPart = 32;
 static int session_alloc(eigsol_power* s, int32_t trace_cap) {
     const size_t sb = scalar_bytes(s->dtype);
     EIGSOL_HIP(hipSetDevice(s->ctx->device));
-    for (int i = 0; i < 2; ++i) EIGSOL_HIP(hipMalloc(&s->buf[i], std::max<int64_t>(s->nbuf, 1) * sb + 64));
+    for (int i = 0; i < (s->pair ? 3 : 2); ++i) EIGSOL_HIP(hipMalloc(&s->buf[i], std::max<int64_t>(s->nbuf, 1) * sb + 64));
     EIGSOL_HIP(hipMalloc(&s->ctl, sizeof(PowerCtl)));
     EIGSOL_HIP(hipMalloc(&s->rank_part, kPart * std::max(1, s->ctx->nranks)));
     // rank partials are all-gathered in place: this rank's slot is rank_part[rank]
     s->my_part = static_cast<char*>(s->rank_part) + kPart * (s->dist ? s->ctx->rank : 0);
-    EIGSOL_HIP(hipMalloc(&s->blk_part, kPart * std::max(8, s->grid)));
+    const int nblk = std::max({8, s->grid, s->pair ? s->pair_grid : 0});
+    EIGSOL_HIP(hipMalloc(&s->blk_part, kPart * nblk));
+    if (s->pair) {
+        EIGSOL_HIP(hipMalloc(&s->pair_part, kPart));
+        EIGSOL_HIP(hipMalloc(&s->pair_blk, kPart * nblk));
+        EIGSOL_HIP(hipMemsetAsync(s->pair_part, 0, kPart, s->ctx->stream));
+        EIGSOL_HIP(hipMemsetAsync(s->pair_blk, 0, kPart * nblk, s->ctx->stream));
+    }
     if (trace_cap > 0) EIGSOL_HIP(hipMalloc(&s->trace, (size_t)trace_cap * sb));
     s->trace_cap = std::max(0, trace_cap);
     EIGSOL_HIP(hipHostMalloc(&s->host_ctl, sizeof(PowerCtl), hipHostMallocDefault));
     std::memset(s->host_ctl, 0, sizeof(PowerCtl));
     EIGSOL_HIP(hipMemsetAsync(s->ctl, 0, sizeof(PowerCtl), s->ctx->stream));
-    EIGSOL_HIP(hipMemsetAsync(s->blk_part, 0, kPart * std::max(8, s->grid), s->ctx->stream));
+    EIGSOL_HIP(hipMemsetAsync(s->blk_part, 0, kPart * nblk, s->ctx->stream));
     return EIGSOL_OK;
 }
 
@@ -155,8 +174,8 @@ static void session_free(eigsol_power* s) {
     for (hipEvent_t e : s->ev)
         if (e) hipEventDestroy(e);
     peer_free(s);
-    hipFree(s->buf[0]);
-    hipFree(s->buf[1]);
+    for (void* q : {s->buf[0], s->buf[1], s->buf[2], s->pair_part, s->pair_blk})
+        if (q) hipFree(q);
     hipFree(s->ctl);
     hipFree(s->rank_part);
     hipFree(s->blk_part);
@@ -445,6 +464,11 @@ int eigsol_power_create_csr(eigsol_csr* A, int32_t trace_capacity, eigsol_power*
     s->n = A->nrows;
     s->nbuf = A->ncols;
     int rc = csr_grid(A, &s->grid);
+    // the pair path: eligibility was decided at upload; EIGSOL_POWER_PAIR=0 keeps single launches
+    const char* pair_env = std::getenv("EIGSOL_POWER_PAIR");
+    s->pair = A->pair_ok && !s->dist && s->ctx->nranks == 1 && !A->binned && A->cblk.empty() &&
+              !(pair_env && std::atoi(pair_env) == 0);
+    if (rc == EIGSOL_OK && s->pair) rc = csr_pair_grid(A, &s->pair_grid);
     if (rc == EIGSOL_OK && s->dist) rc = choose_transport(s, trace_capacity);
     if (rc == EIGSOL_OK && s->dist && s->transport == EIGSOL_TRANSPORT_COLLECTIVE) rc = choose_split(s);
     if (rc == EIGSOL_OK && !s->buf[0]) rc = session_alloc(s, trace_capacity);
@@ -489,7 +513,8 @@ int eigsol_power_begin(eigsol_power* s, const eigsol_solver_options* opts, const
     s->opts = *opts;
     s->trivial = opts->max_iterations <= 0;
     // y_{-1} = x0 lives in buf[1] (launch t reads buf[(t-1)&1]); own rows at x-space offset xoff
-    char* x0dst = static_cast<char*>(s->buf[1]) + (size_t)s->xoff * sb;
+    // (pair path: buf[2], launch v reads buf[(v + 2) % 3])
+    char* x0dst = static_cast<char*>(s->buf[s->pair ? 2 : 1]) + (size_t)s->xoff * sb;
     EIGSOL_HIP(hipMemcpyAsync(x0dst, x0, s->n * sb,
                               x0_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     PowerCtl init;
@@ -520,6 +545,7 @@ int eigsol_power_begin(eigsol_power* s, const eigsol_solver_options* opts, const
     EIGSOL_HIP(hipStreamSynchronize(st));   // host_ctl is reused by query()
     s->parity = 0;
     s->launches = 0;
+    s->vt = 0;
     s->begun = true;
     return EIGSOL_OK;
 }
@@ -529,6 +555,20 @@ int eigsol_power_step(eigsol_power* s, int32_t nsteps) {
     if (!s || !s->begun) return fail(EIGSOL_E_INVALID, "eigsol_power_step: session not begun");
     if (s->trivial) return EIGSOL_OK;
     EIGSOL_HIP(hipSetDevice(s->ctx->device));
+    if (s->pair) {
+        // nsteps reference launches: pair launches, single ones for launch 0 and an odd remainder
+        for (int32_t left = nsteps; left > 0;) {
+            const int two = (s->vt > 0 && left >= 2) ? 1 : 0;
+            EIGSOL_TRY(csr_pair_launch(s->csr, s->nbuf, s->buf[(s->vt + 2) % 3], s->buf[s->vt % 3],
+                                       s->buf[(s->vt + 1) % 3], s->ctl, s->rank_part, s->pair_part, s->blk_part,
+                                       s->pair_blk, s->trace, s->parity, two ? s->pair_grid : s->grid, two));
+            s->parity ^= 1;
+            s->vt += 1 + two;
+            s->launches += 1 + two;
+            left -= 1 + two;
+        }
+        return EIGSOL_OK;
+    }
     for (int32_t i = 0; i < nsteps; ++i) {
         EIGSOL_TRY(launch_iteration(s));
         s->parity ^= 1;
@@ -606,7 +646,7 @@ int eigsol_power_finish(eigsol_power* s, void* lambda_out, void* x_out, int x_ou
         double n2 = 0.0;
         for (int r = 0; r < P; ++r) n2 += part[4 * r];   // rank order, as on the device
         fnorm = std::sqrt(n2);
-        parity = 1;
+        parity = s->pair ? 2 : 1;
     } else {
         EIGSOL_TRY(pull_ctl(s));
         if (!s->host_ctl->done)
@@ -623,14 +663,24 @@ int eigsol_power_finish(eigsol_power* s, void* lambda_out, void* x_out, int x_ou
     if (converged) *converged = conv;
     if (x_out) {
         // final_parity 2 + j: solve j of a multi-solve launch (the triangular factor's buffer aux[j])
-        void* src = parity >= 2 ? shift_aux(s->shift, parity - 2)
-                                : static_cast<char*>(s->buf[parity]) + (size_t)s->xoff * sb;
-        if (parity >= 2) parity = 1;   // scratch below: buf[0]
+        // pair path: final_parity 4 + b names buf[b] (pair_prologue); scratch below: the next buffer
+        void* src;
+        void* scratch;
+        if (s->pair) {
+            const int b = parity >= 4 ? parity - 4 : parity;
+            src = s->buf[b];
+            scratch = s->buf[(b + 1) % 3];
+        } else {
+            src = parity >= 2 ? shift_aux(s->shift, parity - 2)
+                              : static_cast<char*>(s->buf[parity]) + (size_t)s->xoff * sb;
+            if (parity >= 2) parity = 1;   // scratch: buf[0]
+            scratch = s->buf[parity ^ 1];
+        }
         if (x_out_on_device) {
             EIGSOL_TRY(scale_out_launch(s->ctx, s->dtype, src, fnorm, x_out, s->n));
             EIGSOL_HIP(hipStreamSynchronize(st));
         } else {
-            void* tmp = s->buf[parity ^ 1];
+            void* tmp = scratch;
             EIGSOL_TRY(scale_out_launch(s->ctx, s->dtype, src, fnorm, tmp, s->n));
             EIGSOL_HIP(hipMemcpyAsync(x_out, tmp, s->n * sb, hipMemcpyDeviceToHost, st));
             EIGSOL_HIP(hipStreamSynchronize(st));
@@ -702,13 +752,20 @@ int eigsol_power_kernel_name(eigsol_power* s, char* buf, size_t cap) {
     if (!s || !buf || cap == 0) return fail(EIGSOL_E_INVALID, "eigsol_power_kernel_name: null argument");
     buf[0] = 0;
     if (s->wide || s->shift || !s->csr) return EIGSOL_OK;   // named for CSR power sessions only
-    const void* k = csr_power_kernel(s->csr, s->transport == EIGSOL_TRANSPORT_PEER);
+    const void* k = s->pair ? csr_pair_kernel_ptr(s->csr) : csr_power_kernel(s->csr, s->transport == EIGSOL_TRANSPORT_PEER);
     const char* m = k ? hipKernelNameRefByPtr(k, s->ctx->stream) : nullptr;
     if (!m) return EIGSOL_OK;
     int st = 0;
     char* d = abi::__cxa_demangle(m, nullptr, nullptr, &st);
     std::snprintf(buf, cap, "%s", (st == 0 && d) ? d : m);
     std::free(d);
+    return EIGSOL_OK;
+}
+
+// Reference iterations one pass over the matrix runs: 2 for sessions on the pair path, else 1.
+int eigsol_power_iterations_per_pass(eigsol_power* s, int32_t* n) {
+    if (!s || !n) return fail(EIGSOL_E_INVALID, "eigsol_power_iterations_per_pass: null argument");
+    *n = s->pair ? 2 : 1;
     return EIGSOL_OK;
 }
 
