@@ -1,7 +1,12 @@
 // Dense real symmetric / complex Hermitian eigensolver (gfx950): all or a selected range of the
 // eigenvalues, and an orthonormal set of eigenvectors, of A (n x n, EIGSOL_F64 / EIGSOL_C128).
 //
-//   a. the lower triangle is mirrored on the device (eigh_symmetrise), so the matrix reduced is Hermitian;
+//   a. the largest modulus in the lower triangle is found (eigh_absmax) and, only where it lies outside
+//      [2^-410, 2^410], the triangle is multiplied by the power of two that brings it into [1, 2)
+//      (eigh_rescale; dsyevx's scaling, exact here): the squares the later steps form (Householder norms, e^2
+//      in the Sturm count and the split rule, the norm of an iterate) then neither overflow nor underflow.
+//      Only the returned eigenvalues and the comparison with a value range are scaled back.  Then the lower
+//      triangle is mirrored on the device (eigh_symmetrise), so the matrix reduced is Hermitian;
 //   b. hessenberg_blocked<S> (hessenberg.hip) reduces it; on a Hermitian matrix H is tridiagonal, and the
 //      reduction keeps every panel's V and T;
 //   c. d_i = Re h_ii, e_i = |h_{i+1,i}| and the phases h_{i+1,i} / |h_{i+1,i}| (eigh_extract); the host
@@ -52,6 +57,62 @@ __global__ __launch_bounds__(256) void eigh_symmetrise(S* A, int n) {
         set_re_im(v, *reinterpret_cast<const double*>(&v), 0.0);
         A[idx] = v;
     }
+}
+
+// ------------------------------------------------------------------ scaling
+constexpr int kAbsmaxBlocks = 256;    // partial maxima, reduced again by every block of eigh_rescale
+constexpr int kRescaleBlocks = 1024;
+constexpr double kScaleMin = 0x1p-410, kScaleMax = 0x1p410;   // the range taken as it is
+
+__device__ __forceinline__ double absmax_of(double a, bool /*diag*/) { return fabs(a); }
+__device__ __forceinline__ double absmax_of(cplx a, bool diag) { return diag ? fabs(a.re) : fmax(fabs(a.re), fabs(a.im)); }
+__device__ __forceinline__ double scale_by(double a, int k) { return ldexp(a, k); }
+__device__ __forceinline__ cplx scale_by(cplx a, int k) { return cplx{ldexp(a.re, k), ldexp(a.im, k)}; }
+
+// max of 256 threads' values (a maximum does not depend on the order it is taken in)
+__device__ __forceinline__ double block_max_256(double v, double* sm) {
+    sm[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sm[threadIdx.x] = fmax(sm[threadIdx.x], sm[threadIdx.x + s]);
+        __syncthreads();
+    }
+    return sm[0];
+}
+
+// partial[blockIdx.x] = max over this block's share of the lower triangle of |re|, |im| (the diagonal's
+// imaginary part is not part of the matrix).  fmax drops a NaN: the reduction reports it, as before.
+template <class S>
+__global__ __launch_bounds__(256) void eigh_absmax(const S* A, int n, double* partial) {
+    __shared__ double sm[256];
+    const int64_t nn = (int64_t)n * n;
+    double v = 0.0;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < nn; idx += (int64_t)gridDim.x * 256) {
+        const int64_t i = idx % n, j = idx / n;
+        if (i >= j) v = fmax(v, absmax_of(A[idx], i == j));
+    }
+    v = block_max_256(v, sm);
+    if (threadIdx.x == 0) partial[blockIdx.x] = v;
+}
+
+// The exponent k (A <- 2^k A): 0 inside [kScaleMin, kScaleMax], and for a zero or a non-finite maximum.
+__device__ __forceinline__ int scale_exponent(double amax) {
+    if (!(amax > 0.0) || isinf(amax) || (amax >= kScaleMin && amax <= kScaleMax)) return 0;
+    return -ilogb(amax);
+}
+
+// Every block takes the maximum of the np <= 256 partial maxima and the exponent from it; where that is not
+// zero the lower triangle is scaled (exactly: ldexp).  *kexp receives the exponent.
+template <class S>
+__global__ __launch_bounds__(256) void eigh_rescale(S* A, int n, const double* partial, int np, int* kexp) {
+    __shared__ double sm[256];
+    const double amax = block_max_256((int)threadIdx.x < np ? partial[threadIdx.x] : 0.0, sm);
+    const int k = scale_exponent(amax);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *kexp = k;
+    if (k == 0) return;
+    const int64_t nn = (int64_t)n * n;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < nn; idx += (int64_t)gridDim.x * 256)
+        if (idx % n >= idx / n) A[idx] = scale_by(A[idx], k);
 }
 
 __device__ __forceinline__ void phase_of(double h, double& a, double& ph) {
@@ -666,7 +727,10 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
     for (auto& x : E.ev) EIGSOL_HIP(hipEventCreate(&x));
     DevBuf dV, dT, dd, de, dph;
     EIGSOL_HIP(dd.alloc((size_t)n * sizeof(double)));
-    EIGSOL_HIP(de.alloc((size_t)n * sizeof(double)));
+    // e (n entries), then the scaling's scratch: kAbsmaxBlocks partial maxima and the exponent
+    EIGSOL_HIP(de.alloc((size_t)(n + dev::kAbsmaxBlocks + 1) * sizeof(double)));
+    double* const dmax = de.as<double>() + n;
+    int* const dkexp = reinterpret_cast<int*>(dmax + dev::kAbsmaxBlocks);
     EIGSOL_HIP(dph.alloc((size_t)n * sizeof(S)));
     if (vectors && npan) {
         EIGSOL_HIP(dV.alloc((size_t)npan * n * NB * sizeof(S)));
@@ -674,6 +738,10 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
     }
     EIGSOL_HIP(hipEventRecord(E.ev[0], st));
     const unsigned gnn = (unsigned)(((int64_t)n * n + 255) / 256);
+    const unsigned gmax = std::min<unsigned>(gnn, dev::kAbsmaxBlocks);
+    hipLaunchKernelGGL(dev::eigh_absmax<S>, dim3(gmax), dim3(256), 0, st, dA.as<S>(), (int)n, dmax);
+    hipLaunchKernelGGL(dev::eigh_rescale<S>, dim3(std::min<unsigned>(gnn, dev::kRescaleBlocks)), dim3(256), 0, st, dA.as<S>(),
+                       (int)n, dmax, (int)gmax, dkexp);
     hipLaunchKernelGGL(dev::eigh_symmetrise<S>, dim3(gnn), dim3(256), 0, st, dA.as<S>(), (int)n);
     EIGSOL_TRY(Ops::reduce(st, dA.as<S>(), n, dV.as<S>(), dT.as<S>()));
     hipLaunchKernelGGL(dev::eigh_extract<S>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dA.as<S>(), (int)n,
@@ -686,6 +754,8 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
         EIGSOL_HIP(hipMemcpyAsync(e.data(), de.p, (size_t)(n - 1) * sizeof(double), hipMemcpyDeviceToHost, st));
         EIGSOL_HIP(hipMemcpyAsync(ph.data(), dph.p, (size_t)(n - 1) * sizeof(S), hipMemcpyDeviceToHost, st));
     }
+    int kexp = 0;   // the matrix reduced is 2^kexp A
+    EIGSOL_HIP(hipMemcpyAsync(&kexp, dkexp, sizeof(int), hipMemcpyDeviceToHost, st));
     EIGSOL_HIP(hipEventRecord(E.ev[1], st));
     EIGSOL_HIP(hipStreamSynchronize(st));
     for (int64_t i = 0; i < n; ++i)
@@ -746,13 +816,17 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
         s1 = iu + 1;
     } else if (select == EIGSOL_EIGH_VALUE) {
         s0 = 0;
-        while (s0 < n && !(all[s0].lam > vl)) ++s0;
+        while (s0 < n && !(std::ldexp(all[s0].lam, -kexp) > vl)) ++s0;   // vl, vu are on the caller's scale
         s1 = s0;
-        while (s1 < n && all[s1].lam <= vu) ++s1;
+        while (s1 < n && std::ldexp(all[s1].lam, -kexp) <= vu) ++s1;
     }
     const int64_t m = s1 - s0;
     *m_out = m;
-    for (int64_t j = 0; j < m; ++j) w_out[j] = all[s0 + j].lam;
+    std::vector<double> ws(m);   // the selected eigenvalues of the scaled matrix, which the vectors are computed from
+    for (int64_t j = 0; j < m; ++j) {
+        ws[j] = all[s0 + j].lam;
+        w_out[j] = std::ldexp(ws[j], -kexp);   // exact; kexp = 0 leaves the bits
+    }
     if (not_converged) *not_converged = 0;
     float ms[4] = {0.f, 0.f, 0.f, 0.f};
     if (!vectors || m == 0) {
@@ -766,7 +840,7 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
     std::vector<int64_t> owner(m), cluster_of(m);
     for (int64_t j = 0; j < m; ++j) owner[j] = all[s0 + j].block;
     int64_t ncl = 0;
-    EIGSOL_TRY(tridiag_plan_impl(n, d.data(), e.data(), m, w_out, owner.data(), nullptr, cluster_of.data(), nullptr, B, &ncl));
+    EIGSOL_TRY(tridiag_plan_impl(n, d.data(), e.data(), m, ws.data(), owner.data(), nullptr, cluster_of.data(), nullptr, B, &ncl));
     std::vector<dev::SteinCluster> cls(ncl, dev::SteinCluster{0, 0, 0, 0, 0.0});
     for (int64_t j = 0; j < m; ++j) {
         dev::SteinCluster& c = cls[cluster_of[j]];
@@ -811,7 +885,7 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
     EIGSOL_HIP(dfail.alloc(64));
     EIGSOL_HIP(dD.alloc((size_t)n * sizeof(S)));
     EIGSOL_HIP(dZ.alloc((size_t)n * m * sizeof(S)));
-    EIGSOL_HIP(hipMemcpyAsync(dw.p, w_out, (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
+    EIGSOL_HIP(hipMemcpyAsync(dw.p, ws.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
     EIGSOL_HIP(hipMemcpyAsync(dcl.p, sorted.data(), (size_t)ncl * sizeof(dev::SteinCluster), hipMemcpyHostToDevice, st));
     EIGSOL_HIP(hipMemcpyAsync(dit.p, items.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
     EIGSOL_HIP(hipMemcpyAsync(dik.p, item_k.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));

@@ -134,6 +134,30 @@ def test_plan_loose72_one_cluster_of_twelve():
     assert len(set(cluster_of[60:])) == 1 and cluster_of[59] != cluster_of[60]
 
 
+@pytest.mark.parametrize("name", R.STRUCTURED)
+def test_structured_matrices_have_their_structure(name):
+    """weak*: one block, one cluster of n; twins1040: 520 clusters of 2; pairs2200: 2200 clusters of 1 in 1100
+    blocks; mixed2100: 2100 clusters of 1 in 700 blocks of order 1 and 700 of order 2; wilk41: a pair closer than 10 eps |lambda| in one block; glued105: unsplit, clusters of 5."""
+    R.check_structure(name)
+
+
+CLOSED_FORM = {"twins1040": R.twins1040_closed_form, "pairs2200": R.pairs2200_closed_form,
+               "mixed2100": R.mixed2100_closed_form}
+
+
+@pytest.mark.parametrize("name", ["weak600", "twins1040", "pairs2200", "mixed2100"])
+def test_large_restatement_bounds(name):
+    """The large matrices (not in NAMES) under the conditions of test_restatement_bounds."""
+    A = R.matrix(name)
+    w, Z, wl = R.reference(name)
+    r, o = R.r_figure(A, w, Z), R.o_figure(Z)
+    dw = float(np.abs(w - wl).max())
+    print(f"{name}: r={r:.3f} o={o:.3f} |w-w_lapack|={dw:.3e} (bound {R.value_bound(A):.3e})")
+    assert r <= 2 and o <= 2 and dw <= R.value_bound(A)
+    if name in CLOSED_FORM:
+        assert np.abs(wl - CLOSED_FORM[name]()).max() <= R.value_bound(A)
+
+
 def test_plan_hand_made():
     # rows 0-2 and 3-5: e[2] = 1e-18 <= eps sqrt(|2 * 3|) is negligible.  ||T_0||_1 = 1 + 4 + 1 = 6 (row 1),
     # ||T_1||_1 = 0.01 + 7 = 7.01 (row 5).  Eigenvalues of block 1, [[3, 1e-4, 0], [1e-4, 3, 0.01], [0, 0.01, -7]]:

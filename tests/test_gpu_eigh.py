@@ -6,6 +6,7 @@ Accuracy conditions, with "ref" the CPU restatement's figure on the same matrix 
 profiles/eigh_accuracy.json."""
 import json
 import os
+import types
 
 import numpy as np
 import pytest
@@ -80,6 +81,8 @@ def check_phase(Z):
 @pytest.mark.parametrize("name", R.NAMES)
 def test_all_eigenpairs(ctx, name):
     A = R.matrix(name)
+    if name in R.STRUCTURED:
+        R.check_structure(name)
     w_ref, Z_ref, w_lapack = R.reference(name)
     check_conditions(name, A, full_run(ctx, name), w_ref, Z_ref, w_lapack)
 
@@ -113,6 +116,130 @@ def test_sym1030_selected_pairs(ctx):
     res = E.eigh(ctx, A, select=sel)
     w_ref, Z_ref = R.restatement(A, sel)
     check_conditions("sym1030[i,500,531]", A, res, w_ref, Z_ref, np.linalg.eigvalsh(A)[500:532])
+
+
+# weak600: one block, one cluster of 600, three projection batches (256 + 256 + 88).  twins1040: 520 clusters of
+# two, more than the 512 workgroups the cluster kernel gets.  pairs2200: 2200 clusters of one in blocks of
+# order 2, more than the 2048 waves the single-eigenvalue kernel gets.  mixed2100: 2100 clusters of one, every
+# third a 1 x 1 block, so a wave that takes a second cluster meets the unit-vector shortcut beside real blocks.
+# check_structure asserts each of these.
+CLOSED_FORM = {"twins1040": R.twins1040_closed_form, "pairs2200": R.pairs2200_closed_form,
+               "mixed2100": R.mixed2100_closed_form}
+
+
+@pytest.mark.parametrize("name", ["weak600", "twins1040", "pairs2200", "mixed2100"])
+def test_large_structured(ctx, name):
+    A = R.matrix(name)
+    R.check_structure(name)
+    w_ref, Z_ref, w_lapack = R.reference(name)
+    res = full_run(ctx, name)
+    check_conditions(name, A, res, w_ref, Z_ref, w_lapack)
+    if name in CLOSED_FORM:
+        closed = CLOSED_FORM[name]()
+        dc = float(np.abs(res.eigenvalues - closed).max())
+        print(f"{name}: |w - closed form| = {dc:.3e}")
+        assert dc <= R.value_bound(A)
+
+
+# a selection projects only against the selected members of the cluster: 13 of them (one batch, cut out of the
+# middle), and all 600 through the index path
+@pytest.mark.parametrize("il,iu", [(250, 262), (0, 599)])
+def test_weak600_selection_cuts_the_cluster(ctx, il, iu):
+    A = R.matrix("weak600")
+    R.check_structure("weak600")
+    full = full_run(ctx, "weak600")
+    res = E.eigh(ctx, A, select=("i", il, iu))
+    assert res.eigenvalues.tobytes() == full.eigenvalues[il:iu + 1].tobytes()
+    w_ref, Z_ref = R.restatement(A, ("i", il, iu))
+    check_conditions(f"weak600[i,{il},{iu}]", A, res, w_ref, Z_ref, R.reference("weak600")[2][il:iu + 1])
+
+
+# block orders around kBisectChunk = 1024 (the staging chunk of the Sturm count): one chunk, one chunk and a
+# row, two chunks and a row (one unsplit block each), and the dense sym1030
+@pytest.mark.parametrize("name", ["sym1030", "lap1024", "lap1025", "lap2049"])
+def test_all_values_past_one_bisection_chunk(ctx, name):
+    A = R.matrix(name)
+    w = E.eigvalsh(ctx, A)
+    w_lapack = np.linalg.eigvalsh(A)
+    assert w.shape == w_lapack.shape and np.all(np.isfinite(w)) and np.all(np.diff(w) >= 0)
+    dw, bound = float(np.abs(w - w_lapack).max()), R.value_bound(A)
+    _record(f"{name}[values]", eigenvalue_difference=dw, eigenvalue_bound=bound)
+    print(f"{name}: |w-w_lapack|={dw:.3e} (bound {bound:.3e})")
+    assert dw <= bound
+
+
+# eigh(s A) for exact scalings s = 2^p: s^-1 w and Z must meet the conditions of A itself (LAPACK returns s w
+# for these, so the references are those of A, and the test's own arithmetic stays in range).  |p| = 400 is
+# inside the range the solver takes as it is (e^2 = 2^+-800 is representable); |p| = 600 is outside it.
+SCALE_SELECTION = {"sym97": (31, 64), "herm70": (10, 30), "cluster99": (72, 80)}
+
+
+def _unscaled(res, s):
+    return types.SimpleNamespace(eigenvalues=res.eigenvalues / s, eigenvectors=res.eigenvectors,
+                                 not_converged=res.not_converged)
+
+
+@pytest.mark.parametrize("p", [-600, -400, 400, 600])
+@pytest.mark.parametrize("name", ["sym97", "herm70", "cluster99"])
+def test_scale_extremes(ctx, name, p):
+    A = R.matrix(name)
+    s = 2.0 ** p
+    sA = s * A
+    assert np.array_equal(sA / s, A)                       # the scaling is exact
+    w_ref, Z_ref, w_lapack = R.reference(name)
+    res = E.eigh(ctx, sA)
+    check_conditions(f"{name}*2^{p}", A, _unscaled(res, s), w_ref, Z_ref, w_lapack)
+    # values only: against s w_LAPACK(A), and the same bits as the full run
+    wv = E.eigvalsh(ctx, sA)
+    assert wv.shape == w_lapack.shape and np.all(np.isfinite(wv))
+    assert np.abs(wv - s * w_lapack).max() <= s * R.value_bound(A)
+    assert wv.tobytes() == res.eigenvalues.tobytes()
+    # an index selection: a slice of the full run, under the conditions of the same selection on A
+    il, iu = SCALE_SELECTION[name]
+    sel = E.eigh(ctx, sA, select=("i", il, iu))
+    assert sel.eigenvalues.tobytes() == res.eigenvalues[il:iu + 1].tobytes()
+    ws_ref, Zs_ref = R.restatement(A, ("i", il, iu))
+    check_conditions(f"{name}*2^{p}[i,{il},{iu}]", A, _unscaled(sel, s), ws_ref, Zs_ref, w_lapack[il:iu + 1])
+
+
+# a value selection is taken on the caller's scale
+@pytest.mark.parametrize("p", [-600, 600])
+def test_scale_extremes_value_selection(ctx, p):
+    A = R.matrix("sym97")
+    s = 2.0 ** p
+    full = full_run(ctx, "sym97").eigenvalues
+    vl, vu = -3.0, 2.5
+    keep = (full > vl) & (full <= vu)
+    assert 0 < keep.sum() < 97
+    res = E.eigh(ctx, s * A, select=("v", s * vl, s * vu))
+    w_ref, Z_ref = R.restatement(A, ("v", vl, vu))
+    check_conditions(f"sym97*2^{p}[v,{vl},{vu}]", A, _unscaled(res, s), w_ref, Z_ref, R.reference("sym97")[2][keep])
+
+
+# both scalings are brought to the same matrix (largest entry in [1, 2)) by exact multiplications, so everything
+# but the eigenvalues' exponent agrees to the bit
+@pytest.mark.parametrize("name", ["sym97", "herm70"])
+def test_scale_extremes_same_bits_up_and_down(ctx, name):
+    A = R.matrix(name)
+    up, down = E.eigh(ctx, 2.0 ** 600 * A), E.eigh(ctx, 2.0 ** -600 * A)
+    assert (up.eigenvalues / 2.0 ** 600).tobytes() == (down.eigenvalues * 2.0 ** 600).tobytes()
+    assert up.eigenvectors.tobytes() == down.eigenvectors.tobytes()
+    assert up.not_converged == down.not_converged == 0
+
+
+@pytest.mark.parametrize("p", [0, 600])
+@pytest.mark.parametrize("bad", [np.inf, np.nan])
+def test_non_finite_entry_fails_at_any_scale(ctx, bad, p):
+    A = 2.0 ** p * R.matrix("sym97")
+    A[50, 3] = bad
+    with pytest.raises(E.EigSolError) as e:
+        E.eigh(ctx, A)
+    assert "non-finite" in str(e.value)
+    H = 2.0 ** p * R.matrix("herm70")
+    H[69, 69] = bad
+    with pytest.raises(E.EigSolError) as e:
+        E.eigvalsh(ctx, H)
+    assert "non-finite" in str(e.value)
 
 
 @pytest.mark.parametrize("name,vl,vu", [("lap300", 4.5, 5.0), ("lap300", -1.0, -0.5), ("wilk21", 0.4, 0.6)])

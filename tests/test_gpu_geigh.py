@@ -7,6 +7,7 @@ w_ref = numpy.linalg.eigvalsh of the restatement's standard form).  Every measur
 profiles/geigh_accuracy.json."""
 import json
 import os
+import types
 
 import numpy as np
 import pytest
@@ -110,6 +111,20 @@ def test_index_selection(ctx, name, il, iu):
     w_np = G.reference(name)[2]
     check_conditions(f"{name}[i,{il},{iu}]", A, B, res, w_ref, X_ref, w_np[il:iu + 1], G.value_bound(A, B, w_np))
     assert E.eigvalsh(ctx, A, select=("i", il, iu), B=B).tobytes() == res.eigenvalues.tobytes()
+
+
+# eigh(s A, B) for the exact scalings s = 2^+-600: s^-1 w and X must meet the conditions of (A, B) itself
+@pytest.mark.parametrize("p", [-600, 600])
+def test_scaled_a(ctx, p):
+    A, B = G.pair("gsym97")
+    s = 2.0 ** p
+    assert np.array_equal((s * A) / s, A)
+    res = E.eigh(ctx, s * A, B=B)
+    w_ref, X_ref, w_np = G.reference("gsym97")
+    back = types.SimpleNamespace(eigenvalues=res.eigenvalues / s, eigenvectors=res.eigenvectors,
+                                 not_converged=res.not_converged)
+    check_conditions(f"gsym97*2^{p}", A, B, back, w_ref, X_ref, w_np, G.value_bound(A, B, w_np))
+    assert E.eigvalsh(ctx, s * A, B=B).tobytes() == res.eigenvalues.tobytes()
 
 
 @pytest.mark.parametrize("name", ["gsym97", "gherm70", "glap300"])
