@@ -570,13 +570,17 @@ struct EighOptions {
     Select select = Select::All;
     std::int64_t il = 0, iu = 0;
     double vl = 0, vu = 0;
+    // the tridiagonal stage: dstein's inverse iteration (the default), or divide and conquer, whose cost does
+    // not depend on how the spectrum clusters (eigsol_eigh_dense_m; eigvalsh ignores it)
+    enum class Method { Stein, DC };
+    Method method = Method::Stein;
 };
 
 template <typename S>
 struct EighResult {
     std::vector<double> eigenvalues;   // ascending
     DenseMatrix<S> eigenvectors;       // n x m, unit columns (with B: B-orthonormal), largest-modulus component real positive
-    std::int64_t notConverged = 0;     // eigenvectors that failed the inverse iteration's growth test
+    std::int64_t notConverged = 0;     // eigenvectors that failed the inverse iteration's growth test (DC: iteration caps hit)
 };
 
 template <typename S>

@@ -445,6 +445,7 @@ KrylovResult<S> krylovSchur_dense(const DenseMatrix<S>& A, const KrylovOptions<S
 // Eigenvalues (ascending) and an orthonormal set of eigenvectors of the real symmetric / complex
 // Hermitian matrix whose lower triangle is A's (eigsol_eigh_dense: blocked Hessenberg reduction,
 // bisection, inverse iteration, back-transformation; the strict upper triangle is not read).
+// EighOptions::method = Method::DC takes the tridiagonal eigenpairs by divide and conquer instead.
 // S = double and std::complex<double>.  eigvalsh returns the eigenvalues alone (no vectors are formed).
 // With a second matrix B (Hermitian positive definite, its lower triangle read): A x = lambda B x
 // (eigsol_geigh_dense: Cholesky B = L L^H, C = L^-1 A L^-H, the solver above, X = L^-H Y); the
@@ -476,12 +477,14 @@ EighResult<S> eigh_run(const DenseMatrix<S>& A, const EighOptions& opts, bool ve
         if (vectors) Z = DenseMatrix<S>(n, n);
         std::int64_t m = 0, nc = 0;
         void* zp = vectors ? static_cast<void*>(Z.data()) : nullptr;
+        const std::int32_t method = opts.method == EighOptions::Method::DC ? EIGSOL_EIGH_METHOD_DC : EIGSOL_EIGH_METHOD_STEIN;
         if (B)
-            check(eigsol_geigh_dense(ctx(), dtype_of<S>(), n, A.data(), B->data(), &o, res.eigenvalues.data(), zp, &m, &nc,
-                                     nullptr),
+            check(eigsol_geigh_dense_m(ctx(), dtype_of<S>(), n, A.data(), B->data(), &o, method, res.eigenvalues.data(), zp,
+                                       &m, &nc, nullptr),
                   who);
         else
-            check(eigsol_eigh_dense(ctx(), dtype_of<S>(), n, A.data(), &o, res.eigenvalues.data(), zp, &m, &nc), who);
+            check(eigsol_eigh_dense_m(ctx(), dtype_of<S>(), n, A.data(), &o, method, res.eigenvalues.data(), zp, &m, &nc),
+                  who);
         res.eigenvalues.resize(static_cast<std::size_t>(m));
         res.notConverged = nc;
         if (vectors) {

@@ -464,7 +464,7 @@ int eigsol_hyman_refine(eigsol_ctx* ctx, int dtype, int64_t n, const void* H_col
  * accepts: 16384 real, 8192 complex).  n == 0: EIGSOL_OK with *m_out = 0.  A non-finite entry in the
  * lower triangle fails with EIGSOL_E_SOLVER.
  * Out of scope: single precision and double-double, row-sharded matrices, a symmetric (sytrd) or
- * two-stage reduction, divide and conquer / MRRR, and high relative accuracy
+ * two-stage reduction, MRRR (divide and conquer: eigsol_eigh_dense_m below), and high relative accuracy
  * of tiny eigenvalues of graded matrices (the Householder reduction loses it; entries are not
  * rescaled, so e_i^2 must neither overflow nor underflow).  The generalised problem A x = lambda B x
  * is eigsol_geigh_dense (below); out of scope there: types 2 and 3 (A B x = lambda x,
@@ -528,6 +528,66 @@ int eigsol_geigh_stage_times(eigsol_ctx* ctx, double* ms7);
  * claims. */
 int eigsol_tridiag_plan(int64_t n, const double* d, const double* e, int64_t m, const double* w,
                         int64_t* block_of, int64_t* cluster_of, int64_t* nblocks, int64_t* nclusters);
+
+/* ---------------------------------------------------------------- eigh by divide and conquer
+ * eigsol_eigh_dense_m / eigsol_geigh_dense_m: eigsol_eigh_dense / eigsol_geigh_dense with the method
+ * of the tridiagonal stage as an argument after opts.  EIGSOL_EIGH_METHOD_STEIN is the existing entry,
+ * bit for bit (the existing entries are method 0).  EIGSOL_EIGH_METHOD_DC replaces bisection and
+ * inverse iteration by Cuppen's divide and conquer with Gu and Eisenstat's stabilisation (LAPACK
+ * dstedc / dlaed1-4's scheme; csrc/eigh_dc.hip): every split block of T is scaled by the power of two
+ * that brings its largest entry into [1, 2) (exact; undone on the eigenvalues), then halved down to leaves of
+ * order <= 64 (EIGSOL_DC_LEAF = 2 .. 64, read per call, overrides the leaf order); at a cut c
+ * rho = e_c is taken off d_c and d_{c+1}; the leaves are solved by implicit QL, one wave each; then,
+ * level by level and all merges of a level in the same launches: dlaed2's deflation on the host
+ * (eigsol_dc_deflate below, one host wait per level), the secular equation's roots one lane each,
+ * relative to the nearer pole, by bisection on the offset; Loewner's recomputed z; the vector matrix U
+ * with unit columns; Q(:, kept) <- Q(:, kept) U on the fp64 matrix cores.  The orthogonality of the
+ * vectors does not depend on how the spectrum clusters.
+ * Under DC: dtypes, order limit, scaling, mirroring, the non-finite check, the phase convention and
+ * (generalised) B-orthonormality are the existing ones.  w holds the divide-and-conquer values: within
+ * 2 n eps ||A||_F of LAPACK's but not bitwise eigsol_eigh_dense's.  A selection computes every pair of
+ * T and takes the selected columns of the sorted list before the back-transformation: it returns
+ * bitwise the full DC call's values, and its vectors too as long as the back-transformation sums in
+ * the same order for both column counts (it does for n <= 4096).  EIGSOL_EIGH_VALUE compares with the
+ * computed values.  A values-only call (Z NULL) is the bisection path whatever the method.
+ * not_converged: leaf eigenvalues (60 QL sweeps) or secular roots (400 bisection steps) that hit
+ * their iteration cap; expected 0.  No floating-point atomics: two calls return the same bits.
+ * Workspace: three n x n real matrices on the device (Q, the permuted Q, U), freed before the
+ * back-transformation.  An unknown method returns EIGSOL_E_INVALID before any device call.
+ * Under DC eigsol_eigh_stage_times reports the whole tridiagonal stage in its third slot and 0 in
+ * the second.  eigsol_eigh_dc_stage_times: the context's last DC call, 6 doubles in ms: reduction,
+ * leaves, host deflation (wall time of the scan alone; the uploads and the wait are in no slot), secular +
+ * Loewner + vector kernels
+ * (with the rotations and the column permutation), merge GEMMs (with the copy of the deflated
+ * columns), back-transformation; by stream events except the host stage. */
+#define EIGSOL_EIGH_METHOD_STEIN 0
+#define EIGSOL_EIGH_METHOD_DC 1
+int eigsol_eigh_dense_m(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor,
+                        const eigsol_eigh_options* opts, int32_t method, double* w, void* Z,
+                        int64_t* m_out, int64_t* not_converged);
+int eigsol_geigh_dense_m(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor, const void* B_colmajor,
+                         const eigsol_eigh_options* opts, int32_t method, double* w, void* Z,
+                         int64_t* m_out, int64_t* not_converged, int64_t* info);
+int eigsol_eigh_dc_stage_times(eigsol_ctx* ctx, double* ms6);
+/* Host only (no device): the deflation step of one divide-and-conquer merge, dlaed2's rules, on
+ * D + rho z z^T with D = diag(d) (n poles in any order: the eigenvalues of the two halves, the first
+ * n1 from the left one; n1 is only checked, 1 <= n1 < n: the poles are sorted whole, not merged from two
+ * sorted halves) and z (n) the halves' boundary rows.  The caller scales the problem so that max |d| is
+ * of order 1, as the driver does: tol below takes |z| <= 1 as the scale of the poles.  z is divided by its 2-norm
+ * and rho multiplied by its square; the poles are sorted (stable); tol = 8 u max(max |d|, max |z|),
+ * u = 2^-53.  In ascending order of the poles: j is dropped when rho |z_j| <= tol; a pole j is rotated
+ * together with the last kept candidate p when |t c s| <= tol (t = d_j - d_p, (c, s) = (z_j, -z_p) /
+ * hypot(z_j, z_p)): columns (p, j) <- (c p + s j, c j - s p), z_j = hypot, z_p = 0, d_p and d_j
+ * replaced by the rotated diagonal, p deflated and j the new candidate.
+ * Out: *k_out kept poles; perm (n): perm[q] = the old index of new place q, the kept poles first and
+ * ascending, then the deflated ones in the order they were dropped; dk (n): the values at the new
+ * places (kept poles, then deflated eigenvalues); zk (n): the kept z, then zeros; *rho_out;
+ * *nrot_out rotations in the order to apply them, rot_cols (2 per rotation, capacity 2 (n - 1)): old
+ * indices (p, j); rot_cs (2 per rotation): (c, s); *tol_out (optional).
+ * EIGSOL_E_INVALID: a null pointer, n < 2, n1 outside 1 .. n - 1, rho <= 0 or a non-finite input. */
+int eigsol_dc_deflate(int64_t n, int64_t n1, const double* d, const double* z, double rho,
+                      int64_t* k_out, int64_t* perm, double* dk, double* zk, double* rho_out,
+                      int64_t* nrot_out, int64_t* rot_cols, double* rot_cs, double* tol_out);
 
 /* ---------------------------------------------------------------- row-sharded power iteration
  * One process per GPU; RCCL over xGMI (the reference has no distribution: SURVEY.md §2.1).

@@ -24,7 +24,7 @@ __all__ = [
     "PowerSession", "power_method", "device_count", "lib", "last_error",
     "SubspaceOptions", "SubspaceResult", "subspace_iteration", "spmm", "dense_mm",
     "KrylovOptions", "KrylovResult", "krylov_schur", "krylov_orth", "krylov_rotate",
-    "EighResult", "eigh", "eigvalsh", "eigh_stage_times", "tridiag_plan",
+    "EighResult", "eigh", "eigvalsh", "eigh_stage_times", "tridiag_plan", "eigh_dc_stage_times", "dc_deflate",
     "cholesky", "geigh_stage_times",
 ]
 
@@ -810,7 +810,8 @@ def qr_eigenvalues(ctx: Context, A, opts: SolverOptions = SolverOptions(), varia
 class EighResult:
     """Result of :func:`eigh`: ``eigenvalues`` ascending (m), ``eigenvectors`` n x m with unit columns
     (column j belongs to eigenvalue j; its largest-modulus component is real and positive),
-    ``not_converged`` the number of vectors that failed the inverse iteration's growth test.
+    ``not_converged`` the number of vectors that failed the inverse iteration's growth test (with
+    ``method="dc"``: the leaf eigenvalues and secular roots that hit their iteration cap; expected 0).
     With ``B`` (A x = lambda B x) the columns are B-orthonormal (X^H B X = I) instead of unit 2-norm."""
 
     eigenvalues: np.ndarray
@@ -818,7 +819,12 @@ class EighResult:
     not_converged: int
 
 
-def _eigh_call(ctx: Context, A, select, vectors: bool, who: str, B=None):
+_EIGH_METHODS = {"stein": 0, "dc": 1}
+
+
+def _eigh_call(ctx: Context, A, select, vectors: bool, who: str, B=None, method="stein"):
+    if method not in _EIGH_METHODS:
+        raise EigSolError(EIGSOL_E_INVALID, f'{who}: method is "stein" or "dc"')
     A = _square_dense(A, who)
     code = _dtype_code(A.dtype)
     n = A.shape[0]
@@ -838,33 +844,39 @@ def _eigh_call(ctx: Context, A, select, vectors: bool, who: str, B=None):
     w = np.zeros(max(n, 1))
     Z = np.zeros((n, max(n, 1)), dtype=A.dtype, order="F") if vectors else None
     m, nc = C.c_int64(0), C.c_int64(0)
+    mcode = _EIGH_METHODS[method]
     if B is None:
-        call("eigsol_eigh_dense", ctx.handle, code, n, _ptr(Af), None if o is None else C.byref(o), _ptr(w),
+        call("eigsol_eigh_dense_m", ctx.handle, code, n, _ptr(Af), None if o is None else C.byref(o), mcode, _ptr(w),
              None if Z is None else _ptr(Z), C.byref(m), C.byref(nc))
     else:
         Bf = np.asfortranarray(B)
-        call("eigsol_geigh_dense", ctx.handle, code, n, _ptr(Af), _ptr(Bf), None if o is None else C.byref(o), _ptr(w),
-             None if Z is None else _ptr(Z), C.byref(m), C.byref(nc), None)
+        call("eigsol_geigh_dense_m", ctx.handle, code, n, _ptr(Af), _ptr(Bf), None if o is None else C.byref(o), mcode,
+             _ptr(w), None if Z is None else _ptr(Z), C.byref(m), C.byref(nc), None)
     k = int(m.value)
     return w[:k].copy(), (None if Z is None else np.asfortranarray(Z[:, :k])), int(nc.value)
 
 
-def eigvalsh(ctx: Context, A, select=None, B=None) -> np.ndarray:
+def eigvalsh(ctx: Context, A, select=None, B=None, method="stein") -> np.ndarray:
     """Eigenvalues (ascending) of the real symmetric / complex Hermitian matrix whose lower triangle
     is that of ``A`` (float64 / complex128; the strict upper triangle is not read), on the device
     (``eigsol_eigh_dense``): Hessenberg reduction, then bisection.  ``select``: ``None`` (all),
     ``("i", il, iu)`` (0-based, inclusive) or ``("v", vl, vu)`` (vl < lambda <= vu).
     With ``B`` (Hermitian positive definite, same shape and dtype; its lower triangle is read): the
-    eigenvalues of A x = lambda B x (``eigsol_geigh_dense``: Cholesky, reduction to standard form)."""
-    return _eigh_call(ctx, A, select, False, "eigvalsh", B)[0]
+    eigenvalues of A x = lambda B x (``eigsol_geigh_dense``: Cholesky, reduction to standard form).
+    ``method`` is accepted and ignored: no vectors are formed, so the values are the bisection path's."""
+    return _eigh_call(ctx, A, select, False, "eigvalsh", B, method)[0]
 
 
-def eigh(ctx: Context, A, select=None, B=None) -> EighResult:
+def eigh(ctx: Context, A, select=None, B=None, method="stein") -> EighResult:
     """:func:`eigvalsh` with an orthonormal set of eigenvectors (inverse iteration on the tridiagonal
     matrix, back-transformed through the reduction's stored reflectors).  With ``B`` the eigenvectors
     of A x = lambda B x, B-orthonormal; a ``B`` that is not positive definite raises with the first
-    failing column's index in the message."""
-    w, Z, nc = _eigh_call(ctx, A, select, True, "eigh", B)
+    failing column's index in the message.
+    ``method="dc"`` (``eigsol_eigh_dense_m``) takes the eigenpairs of the tridiagonal matrix by divide and
+    conquer instead: its cost does not depend on how the spectrum clusters, the eigenvalues are its own
+    (within 2 n eps ||A||_F of LAPACK's, not bitwise :func:`eigvalsh`'s), and a selection returns the bits of
+    the full ``"dc"`` call's columns.  ``EIGSOL_DC_LEAF`` (2 .. 64, default 64) sets the leaf order."""
+    w, Z, nc = _eigh_call(ctx, A, select, True, "eigh", B, method)
     return EighResult(w, Z, nc)
 
 
@@ -894,6 +906,37 @@ def eigh_stage_times(ctx: Context) -> dict:
     ms = (C.c_double * 4)()
     call("eigsol_eigh_stage_times", ctx.handle, ms)
     return {k: ms[i] * 1e-3 for i, k in enumerate(("reduction", "bisection", "inverse_iteration", "back_transform"))}
+
+
+def eigh_dc_stage_times(ctx: Context) -> dict:
+    """The context's last :func:`eigh` call with ``method="dc"``, in seconds (``host_deflation`` is the wall time
+    of the host scans alone)."""
+    ms = (C.c_double * 6)()
+    call("eigsol_eigh_dc_stage_times", ctx.handle, ms)
+    return {k: ms[i] * 1e-3 for i, k in enumerate(("reduction", "leaves", "host_deflation", "secular_vectors",
+                                                   "merge_gemm", "back_transform"))}
+
+
+def dc_deflate(d, z, rho, n1=None):
+    """Host only (``eigsol_dc_deflate``): the deflation of one divide-and-conquer merge D + rho z z^T.
+    Returns a dict: k, perm, dk, zk, rho, rot (list of (a, b, c, s)), tol."""
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    n = d.size
+    if z.size != n:
+        raise EigSolError(EIGSOL_E_SIZE_MISMATCH, "dc_deflate: d and z must have the same length")
+    n1 = n // 2 if n1 is None else int(n1)
+    cap = max(n, 2)
+    perm, cols = np.zeros(cap, dtype=np.int64), np.zeros(2 * cap, dtype=np.int64)
+    dk, zk, cs = np.zeros(cap), np.zeros(cap), np.zeros(2 * cap)
+    k, nrot = C.c_int64(0), C.c_int64(0)
+    rho_out, tol = C.c_double(0.0), C.c_double(0.0)
+    call("eigsol_dc_deflate", n, n1, _ptr(d) if n else _ptr(dk), _ptr(z) if n else _ptr(zk), float(rho), C.byref(k),
+         _ptr(perm), _ptr(dk), _ptr(zk), C.byref(rho_out), C.byref(nrot), _ptr(cols), _ptr(cs), C.byref(tol))
+    r = int(nrot.value)
+    rot = [(int(cols[2 * q]), int(cols[2 * q + 1]), float(cs[2 * q]), float(cs[2 * q + 1])) for q in range(r)]
+    return dict(k=int(k.value), perm=perm[:n].copy(), dk=dk[:n].copy(), zk=zk[:n].copy(), rho=rho_out.value, rot=rot,
+                tol=tol.value)
 
 
 def tridiag_plan(d, e, w):

@@ -163,6 +163,10 @@ SIGNATURES = {
     "eigsol_geigh_dense": [_vp, C.c_int, _i64, _vp, _vp, C.POINTER(EighOptionsC), _vp, _vp, _pi64, _pi64, _pi64],
     "eigsol_geigh_stage_times": [_vp, _pd],
     "eigsol_tridiag_plan": [_i64, _vp, _vp, _i64, _vp, _vp, _vp, _pi64, _pi64],
+    "eigsol_eigh_dense_m": [_vp, C.c_int, _i64, _vp, C.POINTER(EighOptionsC), _i32, _vp, _vp, _pi64, _pi64],
+    "eigsol_geigh_dense_m": [_vp, C.c_int, _i64, _vp, _vp, C.POINTER(EighOptionsC), _i32, _vp, _vp, _pi64, _pi64, _pi64],
+    "eigsol_eigh_dc_stage_times": [_vp, _pd],
+    "eigsol_dc_deflate": [_i64, _i64, _vp, _vp, C.c_double, _pi64, _vp, _vp, _vp, _pd, _pi64, _vp, _vp, _pd],
     "eigsol_hbm_probe": [_vp, C.c_size_t, C.c_int, _pd, _pd, _pd, _pint],
     "eigsol_hbm_probe_mix": [_vp, C.c_size_t, C.c_int, _pd, _pint],
     "eigsol_ctx_info": [_vp, _pint, _pint, _pint, _pint],

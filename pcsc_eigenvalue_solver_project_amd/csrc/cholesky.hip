@@ -298,7 +298,8 @@ int cholesky_host(eigsol_ctx* ctx, int64_t n, const void* B_host, void* L_host, 
 
 template <class S>
 int geigh_host(eigsol_ctx* ctx, int64_t n, const void* A_host, const void* B_host, int select, int64_t il, int64_t iu,
-               double vl, double vu, double* w_out, void* Z_out, int64_t* m_out, int64_t* not_converged, int64_t* info) {
+               double vl, double vu, int method, double* w_out, void* Z_out, int64_t* m_out, int64_t* not_converged,
+               int64_t* info) {
     constexpr int dtype = dtype_of<S>::value;
     hipStream_t st = ctx->stream;
     const bool vectors = Z_out != nullptr;
@@ -345,7 +346,7 @@ int geigh_host(eigsol_ctx* ctx, int64_t n, const void* A_host, const void* B_hos
     if (vectors) conj_transpose<S>(st, n, B, T);   // T = L^H, for step e
     else dT.release();
     // ---- d. the standard problem
-    EIGSOL_TRY(eigh_device(ctx, dtype, n, dA, select, il, iu, vl, vu, w_out, vectors, dZ, m_out, not_converged));
+    EIGSOL_TRY(eigh_device_m(ctx, dtype, n, dA, select, il, iu, vl, vu, method, w_out, vectors, dZ, m_out, not_converged));
     for (int q = 0; q < 4; ++q) g[2 + q] = ctx->eigh_ms[q];
     const int64_t m = *m_out;
     if (!vectors || m == 0) return EIGSOL_OK;
@@ -392,10 +393,12 @@ int eigsol_cholesky_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* B_c
                                 : cholesky_host<double>(ctx, n, B_colmajor, L_colmajor, info);
 }
 
-int eigsol_geigh_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor, const void* B_colmajor,
-                       const eigsol_eigh_options* opts, double* w, void* Z, int64_t* m_out, int64_t* not_converged,
-                       int64_t* info) {
+int eigsol_geigh_dense_m(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor, const void* B_colmajor,
+                         const eigsol_eigh_options* opts, int32_t method, double* w, void* Z, int64_t* m_out,
+                         int64_t* not_converged, int64_t* info) {
     if (info) *info = -1;
+    if (method != EIGSOL_EIGH_METHOD_STEIN && method != EIGSOL_EIGH_METHOD_DC)
+        return fail(EIGSOL_E_INVALID, "eigsol_geigh_dense: unknown method");
     if (n < 0) return fail(EIGSOL_E_INVALID, "eigsol_geigh_dense: negative order");
     if (n == 0) {
         if (m_out) *m_out = 0;
@@ -410,8 +413,15 @@ int eigsol_geigh_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colm
     EIGSOL_TRY(check_dtype_order("eigsol_geigh_dense", dtype, n));
     EIGSOL_HIP(hipSetDevice(ctx->device));
     return dtype == EIGSOL_C128
-               ? geigh_host<cplx>(ctx, n, A_colmajor, B_colmajor, select, il, iu, vl, vu, w, Z, m_out, not_converged, info)
-               : geigh_host<double>(ctx, n, A_colmajor, B_colmajor, select, il, iu, vl, vu, w, Z, m_out, not_converged, info);
+               ? geigh_host<cplx>(ctx, n, A_colmajor, B_colmajor, select, il, iu, vl, vu, method, w, Z, m_out, not_converged, info)
+               : geigh_host<double>(ctx, n, A_colmajor, B_colmajor, select, il, iu, vl, vu, method, w, Z, m_out, not_converged, info);
+}
+
+int eigsol_geigh_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor, const void* B_colmajor,
+                       const eigsol_eigh_options* opts, double* w, void* Z, int64_t* m_out, int64_t* not_converged,
+                       int64_t* info) {
+    return eigsol_geigh_dense_m(ctx, dtype, n, A_colmajor, B_colmajor, opts, EIGSOL_EIGH_METHOD_STEIN, w, Z, m_out,
+                                not_converged, info);
 }
 
 int eigsol_geigh_stage_times(eigsol_ctx* ctx, double* ms7) {

@@ -25,6 +25,8 @@
 //      registers, the scalings, dots and updates run on all threads;
 //   g. Z = Q (D Z_T) with the stored panels, three MFMA GEMMs per panel (hess_backtransform), and each
 //      column's phase fixed so that its largest-modulus component (the first on ties) is real positive.
+// Under EIGSOL_EIGH_METHOD_DC steps e and f are replaced by divide and conquer on T (eigh_dc.hip): all eigenpairs
+// of T, the selection taken from the sorted values and the matching columns.
 // No floating-point atomics; every sum has a fixed order, so two runs give the same bits.
 #include <algorithm>
 #include <cfloat>
@@ -717,9 +719,11 @@ struct EigItem {
 // which is also copied to Z_host where that is given.  fix_phase: apply the phase convention to Z.
 template <class S>
 int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, int64_t iu, double vl, double vu,
-              double* w_out, bool vectors, bool fix_phase, void* Z_host, DevBuf& dZ, int64_t* m_out,
+              int method, double* w_out, bool vectors, bool fix_phase, void* Z_host, DevBuf& dZ, int64_t* m_out,
               int64_t* not_converged) {
     using Ops = EighOps<S>;
+    // divide and conquer forms vectors with its values: a values-only call stays the bisection path
+    const bool dc = method == EIGSOL_EIGH_METHOD_DC && vectors;
     hipStream_t st = ctx->stream;
     const int NB = Ops::nb();
     const int64_t npan = n >= 3 ? (n - 2 + NB - 1) / NB : 0;
@@ -770,7 +774,13 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
     const int64_t nblocks = (int64_t)B.start.size() - 1;
     std::vector<dev::BisectWave> waves;
     std::vector<double> lam(n);
-    for (int64_t b = 0; b < nblocks; ++b) {
+    DevBuf dQdc;        // dc: the eigenvectors of T, column i belongs to lam[i]
+    int64_t ncap = 0;   // dc: leaf eigenvalues and secular roots that hit their iteration cap
+    if (dc) {           // ---- e, f. by divide and conquer (eigh_dc.hip); slot 1 of the stage times stays 0
+        EIGSOL_HIP(hipEventRecord(E.ev[2], st));
+        EIGSOL_TRY(eigh_dc_tridiag(ctx, n, d.data(), e.data(), B.start, dQdc, lam.data(), &ncap));
+    }
+    for (int64_t b = 0; b < nblocks && !dc; ++b) {
         const int64_t b0 = B.start[b], bn = B.start[b + 1] - b0;
         if (bn == 1) {
             lam[b0] = d[b0];
@@ -799,7 +809,7 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
         EIGSOL_HIP(hipGetLastError());
         EIGSOL_HIP(hipMemcpyAsync(lam.data(), dlam.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
     }
-    EIGSOL_HIP(hipEventRecord(E.ev[2], st));
+    if (!dc) EIGSOL_HIP(hipEventRecord(E.ev[2], st));
     EIGSOL_HIP(hipStreamSynchronize(st));
     // ascending; equal values in block order (a fixed order, whatever the selection)
     std::vector<EigItem> all(n);
@@ -832,81 +842,102 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
     if (!vectors || m == 0) {
         (void)hipEventElapsedTime(&ms[0], E.ev[0], E.ev[1]);
         (void)hipEventElapsedTime(&ms[1], E.ev[1], E.ev[2]);
+        if (dc) {   // an empty value range: the whole tridiagonal stage ran
+            ms[1] = 0.f;
+            EIGSOL_HIP(hipEventRecord(E.ev[3], st));
+            EIGSOL_HIP(hipStreamSynchronize(st));
+            (void)hipEventElapsedTime(&ms[2], E.ev[2], E.ev[3]);
+            ctx->eigh_dc_ms[0] = ms[0];
+            ctx->eigh_dc_ms[5] = 0.0;
+        }
         for (int q = 0; q < 4; ++q) ctx->eigh_ms[q] = ms[q];
         return EIGSOL_OK;
     }
 
-    // ---- f. clusters (the same plan eigsol_tridiag_plan returns) and inverse iteration
-    std::vector<int64_t> owner(m), cluster_of(m);
-    for (int64_t j = 0; j < m; ++j) owner[j] = all[s0 + j].block;
-    int64_t ncl = 0;
-    EIGSOL_TRY(tridiag_plan_impl(n, d.data(), e.data(), m, ws.data(), owner.data(), nullptr, cluster_of.data(), nullptr, B, &ncl));
-    std::vector<dev::SteinCluster> cls(ncl, dev::SteinCluster{0, 0, 0, 0, 0.0});
-    for (int64_t j = 0; j < m; ++j) {
-        dev::SteinCluster& c = cls[cluster_of[j]];
-        if (c.cnt == 0) {
-            c.b0 = (int)B.start[owner[j]];
-            c.bn = (int)(B.start[owner[j] + 1] - B.start[owner[j]]);
-            c.onenrm = B.onenrm[owner[j]];
-        }
-        ++c.cnt;
-    }
-    // clusters of one eigenvalue (one wave each) first, then the real clusters (one large workgroup each)
-    std::vector<int64_t> order;
-    for (int pass = 0; pass < 2; ++pass)
-        for (int64_t c = 0; c < ncl; ++c)
-            if ((cls[c].cnt == 1) == (pass == 0)) order.push_back(c);
-    std::vector<dev::SteinCluster> sorted(ncl);
-    std::vector<int64_t> place(ncl);
-    int run = 0;
-    int64_t nsingle = 0;
-    for (int64_t q = 0; q < ncl; ++q) {
-        sorted[q] = cls[order[q]];
-        sorted[q].first = run;
-        run += sorted[q].cnt;
-        place[order[q]] = q;
-        if (sorted[q].cnt == 1) ++nsingle;
-    }
-    std::vector<int> items(m), item_k(m), fill(ncl, 0);
-    for (int64_t j = 0; j < m; ++j) {
-        const int64_t q = place[cluster_of[j]];
-        items[sorted[q].first + fill[q]++] = (int)j;   // ascending within the cluster
-        item_k[j] = (int)all[s0 + j].k;
-    }
-    constexpr int kClusterThreads = 1024;
-    const int slots1 = (int)std::min<int64_t>(nsingle, 2048), slots2 = (int)std::min<int64_t>(ncl - nsingle, 512);
-    DevBuf dw, dcl, dit, dik, dZT, dwork, dfail, dD;
-    EIGSOL_HIP(dw.alloc((size_t)m * sizeof(double)));
-    EIGSOL_HIP(dcl.alloc((size_t)ncl * sizeof(dev::SteinCluster)));
-    EIGSOL_HIP(dit.alloc((size_t)m * sizeof(int)));
-    EIGSOL_HIP(dik.alloc((size_t)m * sizeof(int)));
+    // ---- f. Z_T (n x m): the selected columns of divide and conquer's vector matrix, or inverse iteration
+    DevBuf dZT, dD;
+    DevBuf dw, dcl, dit, dik, dwork, dfail;   // inverse iteration's; with the host arrays its uploads read,
+    std::vector<dev::SteinCluster> sorted;    // they live until the stream is waited for
+    std::vector<int> items, item_k;
     EIGSOL_HIP(dZT.alloc((size_t)n * m * sizeof(double)));
-    EIGSOL_HIP(dwork.alloc((size_t)(slots1 + slots2) * 6 * n * sizeof(double)));
-    EIGSOL_HIP(dfail.alloc(64));
     EIGSOL_HIP(dD.alloc((size_t)n * sizeof(S)));
     EIGSOL_HIP(dZ.alloc((size_t)n * m * sizeof(S)));
-    EIGSOL_HIP(hipMemcpyAsync(dw.p, ws.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
-    EIGSOL_HIP(hipMemcpyAsync(dcl.p, sorted.data(), (size_t)ncl * sizeof(dev::SteinCluster), hipMemcpyHostToDevice, st));
-    EIGSOL_HIP(hipMemcpyAsync(dit.p, items.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
-    EIGSOL_HIP(hipMemcpyAsync(dik.p, item_k.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
-    EIGSOL_HIP(hipMemsetAsync(dZT.p, 0, (size_t)n * m * sizeof(double), st));
-    EIGSOL_HIP(hipMemsetAsync(dfail.p, 0, 64, st));
     std::vector<S> D(n);
     D[0] = Ops::one();
     for (int64_t i = 0; i + 1 < n; ++i) D[i + 1] = Ops::mulp(D[i], ph[i]);
-    EIGSOL_HIP(hipMemcpyAsync(dD.p, D.data(), (size_t)n * sizeof(S), hipMemcpyHostToDevice, st));
-    if (slots2)
-        hipLaunchKernelGGL(dev::eigh_stein<kClusterThreads>, dim3(slots2), dim3(kClusterThreads), 0, st, (int)n,
-                           dd.as<double>(), de.as<double>(), dw.as<double>(), dcl.as<dev::SteinCluster>() + nsingle,
-                           (int)(ncl - nsingle), dit.as<int>(), dik.as<int>(), dZT.as<double>(),
-                           dwork.as<double>() + (size_t)slots1 * 6 * n, dfail.as<int>());
-    if (slots1)
-        hipLaunchKernelGGL(dev::eigh_stein<64>, dim3(slots1), dim3(64), 0, st, (int)n, dd.as<double>(), de.as<double>(),
-                           dw.as<double>(), dcl.as<dev::SteinCluster>(), (int)nsingle, dit.as<int>(), dik.as<int>(),
-                           dZT.as<double>(), dwork.as<double>(), dfail.as<int>());
-    EIGSOL_HIP(hipGetLastError());
     int nfail = 0;
-    EIGSOL_HIP(hipMemcpyAsync(&nfail, dfail.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (dc) {   // the workspace goes before the back-transformation
+        std::vector<int> cols(m);
+        for (int64_t j = 0; j < m; ++j) cols[j] = (int)(B.start[all[s0 + j].block] + all[s0 + j].k);
+        EIGSOL_TRY(eigh_dc_take_columns(st, n, m, dQdc.as<double>(), cols, dZT.as<double>()));
+        dQdc.release();
+        EIGSOL_HIP(hipMemcpyAsync(dD.p, D.data(), (size_t)n * sizeof(S), hipMemcpyHostToDevice, st));
+    } else {    // clusters (the same plan eigsol_tridiag_plan returns) and inverse iteration
+        std::vector<int64_t> owner(m), cluster_of(m);
+        for (int64_t j = 0; j < m; ++j) owner[j] = all[s0 + j].block;
+        int64_t ncl = 0;
+        EIGSOL_TRY(tridiag_plan_impl(n, d.data(), e.data(), m, ws.data(), owner.data(), nullptr, cluster_of.data(), nullptr, B, &ncl));
+        std::vector<dev::SteinCluster> cls(ncl, dev::SteinCluster{0, 0, 0, 0, 0.0});
+        for (int64_t j = 0; j < m; ++j) {
+            dev::SteinCluster& c = cls[cluster_of[j]];
+            if (c.cnt == 0) {
+                c.b0 = (int)B.start[owner[j]];
+                c.bn = (int)(B.start[owner[j] + 1] - B.start[owner[j]]);
+                c.onenrm = B.onenrm[owner[j]];
+            }
+            ++c.cnt;
+        }
+        // clusters of one eigenvalue (one wave each) first, then the real clusters (one large workgroup each)
+        std::vector<int64_t> order;
+        for (int pass = 0; pass < 2; ++pass)
+            for (int64_t c = 0; c < ncl; ++c)
+                if ((cls[c].cnt == 1) == (pass == 0)) order.push_back(c);
+        sorted.resize(ncl);
+        std::vector<int64_t> place(ncl);
+        int run = 0;
+        int64_t nsingle = 0;
+        for (int64_t q = 0; q < ncl; ++q) {
+            sorted[q] = cls[order[q]];
+            sorted[q].first = run;
+            run += sorted[q].cnt;
+            place[order[q]] = q;
+            if (sorted[q].cnt == 1) ++nsingle;
+        }
+        items.assign(m, 0);
+        item_k.assign(m, 0);
+        std::vector<int> fill(ncl, 0);
+        for (int64_t j = 0; j < m; ++j) {
+            const int64_t q = place[cluster_of[j]];
+            items[sorted[q].first + fill[q]++] = (int)j;   // ascending within the cluster
+            item_k[j] = (int)all[s0 + j].k;
+        }
+        constexpr int kClusterThreads = 1024;
+        const int slots1 = (int)std::min<int64_t>(nsingle, 2048), slots2 = (int)std::min<int64_t>(ncl - nsingle, 512);
+        EIGSOL_HIP(dw.alloc((size_t)m * sizeof(double)));
+        EIGSOL_HIP(dcl.alloc((size_t)ncl * sizeof(dev::SteinCluster)));
+        EIGSOL_HIP(dit.alloc((size_t)m * sizeof(int)));
+        EIGSOL_HIP(dik.alloc((size_t)m * sizeof(int)));
+        EIGSOL_HIP(dwork.alloc((size_t)(slots1 + slots2) * 6 * n * sizeof(double)));
+        EIGSOL_HIP(dfail.alloc(64));
+        EIGSOL_HIP(hipMemcpyAsync(dw.p, ws.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
+        EIGSOL_HIP(hipMemcpyAsync(dcl.p, sorted.data(), (size_t)ncl * sizeof(dev::SteinCluster), hipMemcpyHostToDevice, st));
+        EIGSOL_HIP(hipMemcpyAsync(dit.p, items.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
+        EIGSOL_HIP(hipMemcpyAsync(dik.p, item_k.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
+        EIGSOL_HIP(hipMemsetAsync(dZT.p, 0, (size_t)n * m * sizeof(double), st));
+        EIGSOL_HIP(hipMemsetAsync(dfail.p, 0, 64, st));
+        EIGSOL_HIP(hipMemcpyAsync(dD.p, D.data(), (size_t)n * sizeof(S), hipMemcpyHostToDevice, st));
+        if (slots2)
+            hipLaunchKernelGGL(dev::eigh_stein<kClusterThreads>, dim3(slots2), dim3(kClusterThreads), 0, st, (int)n,
+                               dd.as<double>(), de.as<double>(), dw.as<double>(), dcl.as<dev::SteinCluster>() + nsingle,
+                               (int)(ncl - nsingle), dit.as<int>(), dik.as<int>(), dZT.as<double>(),
+                               dwork.as<double>() + (size_t)slots1 * 6 * n, dfail.as<int>());
+        if (slots1)
+            hipLaunchKernelGGL(dev::eigh_stein<64>, dim3(slots1), dim3(64), 0, st, (int)n, dd.as<double>(), de.as<double>(),
+                               dw.as<double>(), dcl.as<dev::SteinCluster>(), (int)nsingle, dit.as<int>(), dik.as<int>(),
+                               dZT.as<double>(), dwork.as<double>(), dfail.as<int>());
+        EIGSOL_HIP(hipGetLastError());
+        EIGSOL_HIP(hipMemcpyAsync(&nfail, dfail.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    }
     EIGSOL_HIP(hipEventRecord(E.ev[3], st));
 
     // ---- g. Z = Q (D Z_T), then the phase convention
@@ -918,28 +949,39 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
     if (Z_host) EIGSOL_HIP(hipMemcpyAsync(Z_host, dZ.p, (size_t)n * m * sizeof(S), hipMemcpyDeviceToHost, st));
     EIGSOL_HIP(hipEventRecord(E.ev[4], st));
     EIGSOL_HIP(hipStreamSynchronize(st));
-    if (not_converged) *not_converged = nfail;
+    if (not_converged) *not_converged = dc ? ncap : nfail;
     for (int q = 0; q < 4; ++q) (void)hipEventElapsedTime(&ms[q], E.ev[q], E.ev[q + 1]);
+    if (dc) {
+        ms[1] = 0.f;
+        ctx->eigh_dc_ms[0] = ms[0];
+        ctx->eigh_dc_ms[5] = ms[3];
+    }
     for (int q = 0; q < 4; ++q) ctx->eigh_ms[q] = ms[q];
     return EIGSOL_OK;
 }
 
 template <class S>
 int eigh_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int select, int64_t il, int64_t iu, double vl, double vu,
-              double* w_out, void* Z_out, int64_t* m_out, int64_t* not_converged) {
+              int method, double* w_out, void* Z_out, int64_t* m_out, int64_t* not_converged) {
     DevBuf dA, dZ;
     EIGSOL_HIP(dA.alloc((size_t)n * n * sizeof(S)));
     EIGSOL_HIP(hipMemcpyAsync(dA.p, A_host, (size_t)n * n * sizeof(S), hipMemcpyHostToDevice, ctx->stream));
-    return eigh_core<S>(ctx, n, dA, select, il, iu, vl, vu, w_out, Z_out != nullptr, true, Z_out, dZ, m_out, not_converged);
+    return eigh_core<S>(ctx, n, dA, select, il, iu, vl, vu, method, w_out, Z_out != nullptr, true, Z_out, dZ, m_out, not_converged);
 }
 
 }  // namespace
 
+int eigh_device_m(eigsol_ctx* ctx, int dtype, int64_t n, DevBuf& dA, int select, int64_t il, int64_t iu, double vl,
+                  double vu, int method, double* w_out, bool vectors, DevBuf& dZ, int64_t* m_out, int64_t* not_converged) {
+    return dtype == EIGSOL_C128
+               ? eigh_core<cplx>(ctx, n, dA, select, il, iu, vl, vu, method, w_out, vectors, false, nullptr, dZ, m_out, not_converged)
+               : eigh_core<double>(ctx, n, dA, select, il, iu, vl, vu, method, w_out, vectors, false, nullptr, dZ, m_out, not_converged);
+}
+
 int eigh_device(eigsol_ctx* ctx, int dtype, int64_t n, DevBuf& dA, int select, int64_t il, int64_t iu, double vl,
                 double vu, double* w_out, bool vectors, DevBuf& dZ, int64_t* m_out, int64_t* not_converged) {
-    return dtype == EIGSOL_C128
-               ? eigh_core<cplx>(ctx, n, dA, select, il, iu, vl, vu, w_out, vectors, false, nullptr, dZ, m_out, not_converged)
-               : eigh_core<double>(ctx, n, dA, select, il, iu, vl, vu, w_out, vectors, false, nullptr, dZ, m_out, not_converged);
+    return eigh_device_m(ctx, dtype, n, dA, select, il, iu, vl, vu, EIGSOL_EIGH_METHOD_STEIN, w_out, vectors, dZ, m_out,
+                         not_converged);
 }
 
 int eigh_fix_phase_device(hipStream_t st, int dtype, int64_t n, int64_t m, void* Z) {
@@ -993,8 +1035,10 @@ int eigsol_tridiag_plan(int64_t n, const double* d, const double* e, int64_t m, 
     return EIGSOL_OK;
 }
 
-int eigsol_eigh_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor, const eigsol_eigh_options* opts,
-                      double* w, void* Z, int64_t* m_out, int64_t* not_converged) {
+int eigsol_eigh_dense_m(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor, const eigsol_eigh_options* opts,
+                        int32_t method, double* w, void* Z, int64_t* m_out, int64_t* not_converged) {
+    if (method != EIGSOL_EIGH_METHOD_STEIN && method != EIGSOL_EIGH_METHOD_DC)
+        return fail(EIGSOL_E_INVALID, "eigsol_eigh_dense: unknown method");
     if (n < 0) return fail(EIGSOL_E_INVALID, "eigsol_eigh_dense: negative order");
     if (n == 0) {
         if (m_out) *m_out = 0;
@@ -1013,8 +1057,19 @@ int eigsol_eigh_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colma
         return fail(EIGSOL_E_UNSUPPORTED, "eigsol_eigh_dense: n above the order the blocked Hessenberg reduction accepts");
     EIGSOL_HIP(hipSetDevice(ctx->device));
     return dtype == EIGSOL_C128
-               ? eigh_host<cplx>(ctx, n, A_colmajor, select, il, iu, vl, vu, w, Z, m_out, not_converged)
-               : eigh_host<double>(ctx, n, A_colmajor, select, il, iu, vl, vu, w, Z, m_out, not_converged);
+               ? eigh_host<cplx>(ctx, n, A_colmajor, select, il, iu, vl, vu, method, w, Z, m_out, not_converged)
+               : eigh_host<double>(ctx, n, A_colmajor, select, il, iu, vl, vu, method, w, Z, m_out, not_converged);
+}
+
+int eigsol_eigh_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor, const eigsol_eigh_options* opts,
+                      double* w, void* Z, int64_t* m_out, int64_t* not_converged) {
+    return eigsol_eigh_dense_m(ctx, dtype, n, A_colmajor, opts, EIGSOL_EIGH_METHOD_STEIN, w, Z, m_out, not_converged);
+}
+
+int eigsol_eigh_dc_stage_times(eigsol_ctx* ctx, double* ms6) {
+    if (!ctx || !ms6) return fail(EIGSOL_E_INVALID, "eigsol_eigh_dc_stage_times: null pointer");
+    for (int q = 0; q < 6; ++q) ms6[q] = ctx->eigh_dc_ms[q];
+    return EIGSOL_OK;
 }
 
 int eigsol_eigh_stage_times(eigsol_ctx* ctx, double* ms4) {

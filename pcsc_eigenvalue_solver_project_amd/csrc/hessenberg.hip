@@ -1848,6 +1848,12 @@ int hess_backtransform_f64(hipStream_t st, int64_t n, int64_t m, const double* V
 int hess_backtransform_c128(hipStream_t st, int64_t n, int64_t m, const cplx* V, const cplx* T, cplx* Z, int64_t ldz) {
     return hess_backtransform<cplx>(st, n, m, V, T, Z, ldz);
 }
+int hess_gemm_nn_f64(hipStream_t st, int64_t m, int64_t nn, int64_t kk, const double* A, int64_t lda, const double* B,
+                     int64_t ldb, double* C, int64_t ldc) {
+    gemm<double, false, false>(st, (int)m, (int)nn, (int)kk, 1.0, A, lda, B, ldb, 0.0, C, ldc);
+    EIGSOL_HIP(hipGetLastError());
+    return EIGSOL_OK;
+}
 int hess_panel_width_f64() { return dev::HessCfg<double>::NB; }
 int hess_panel_width_c128() { return dev::HessCfg<cplx>::NB; }
 int hess_max_order_f64() { return dev::HessCfg<double>::kMaxLdsN; }

@@ -96,6 +96,10 @@ int hess_backtransform_f64(hipStream_t st, int64_t n, int64_t m, const double* V
                            int64_t ldz);
 int hess_backtransform_c128(hipStream_t st, int64_t n, int64_t m, const cplx* V, const cplx* T, cplx* Z,
                             int64_t ldz);
+// C (m x nn, ldc) = A (m x kk, lda) B (kk x nn, ldb), column-major on the device: the reduction's own GEMM
+// on the fp64 matrix cores (the divide-and-conquer merges of eigh_dc.hip)
+int hess_gemm_nn_f64(hipStream_t st, int64_t m, int64_t nn, int64_t kk, const double* A, int64_t lda, const double* B,
+                     int64_t ldb, double* C, int64_t ldc);
 int hess_panel_width_f64();
 int hess_panel_width_c128();
 int hess_max_order_f64();
@@ -256,6 +260,9 @@ struct eigsol_ctx {
     // the last eigsol_geigh_dense call's stages in ms (eigsol_geigh_stage_times): cholesky, standardise,
     // the four above, triangular back solve
     double geigh_ms[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    // the last divide-and-conquer eigh call's stages in ms (eigsol_eigh_dc_stage_times): reduction, leaves,
+    // host deflation (wall), secular + vector kernels, merge GEMMs, back-transformation
+    double eigh_dc_ms[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 };
 
 struct eigsol_csr {
