@@ -160,7 +160,7 @@ __device__ __forceinline__ void load_tile(const CsrArgs<S>& a, int4 m, TileRegs<
 }
 
 // Gathers of one tile's x entries (all in flight together; unconditional, see load_tile).
-template <class S, int kMode>
+template <class S>
 __device__ __forceinline__ void issue_gathers(const TileRegs<S>& R, const S* xin,
                                               S (&xg)[TileRegs<S>::P][Slot<S>::kNnz]) {
     constexpr int P = TileRegs<S>::P;
@@ -172,8 +172,8 @@ __device__ __forceinline__ void issue_gathers(const TileRegs<S>& R, const S* xin
         if constexpr (std::is_same_v<S, double>) {
             int c0 = R.s[p].c.x, c1 = R.s[p].c.y;
             asm volatile("" : "+v"(c0), "+v"(c1));
-            xg[p][0] = kMode == 1 ? 1.0 : xin[c0];
-            xg[p][1] = kMode == 1 ? 1.0 : xin[c1];
+            xg[p][0] = xin[c0];
+            xg[p][1] = xin[c1];
         } else {
             int c0 = R.s[p].c;
             asm volatile("" : "+v"(c0));
@@ -184,10 +184,10 @@ __device__ __forceinline__ void issue_gathers(const TileRegs<S>& R, const S* xin
 
 // products a_ij * x_j (x_j = y_j / nrm, the reference's x = y / normY) -> LDS.  Slots outside
 // the tile write to the scratch element `dummy`.
-template <class S, bool kPower, int kMode>
+template <class S, bool kPower>
 __device__ __forceinline__ void write_products(const TileRegs<S>& R, int4 m,
                                                const S (&xg)[TileRegs<S>::P][Slot<S>::kNnz],
-                                               double nrm, double rnrm, S* prod, int dummy) {
+                                               double nrm, double /*rnrm*/, S* prod, int dummy) {
     constexpr int P = TileRegs<S>::P;
     constexpr int NPS = Slot<S>::kNnz;
     const int tid = threadIdx.x;
@@ -197,10 +197,7 @@ __device__ __forceinline__ void write_products(const TileRegs<S>& R, int4 m,
         const int qb = q0 + NPS * (tid + p * kThreads);
         if constexpr (std::is_same_v<S, double>) {
             double x0 = xg[p][0], x1 = xg[p][1];
-            if constexpr (kPower && kMode == 2) {
-                x0 = x0 * rnrm;
-                x1 = x1 * rnrm;
-            } else if constexpr (kPower) {
+            if constexpr (kPower) {
                 x0 = scale_in(x0, nrm);
                 x1 = scale_in(x1, nrm);
             }
@@ -252,28 +249,13 @@ __device__ __forceinline__ void long_rows_pass(const CsrArgs<S>& a, const S* xin
     }
 }
 
-// Sequential ascending-column sum of one row's products from LDS (the reference's order).
-template <class S, int kMode = 0>
-__device__ __forceinline__ S row_sum(const S* pb, int k0, int k1) {
-    S sacc = s_zero<S>();
-    if constexpr (kMode == 3) {
-        if (k1 > k0) sacc = pb[lds_idx(k0)];
-    } else {
-        for (int k = k0; k < k1; ++k) sacc = add(sacc, pb[lds_idx(k)]);
-    }
-    return sacc;
-}
-
-// kMode (diagnostic ablations, EIGSOL_CSR_ABLATION): 0 full; 1 no x gather; 2 reciprocal scaling;
-// 3 no phase-2 row sums.  Only mode 0 is a product path.
-//
 // Short tiles run as a software pipeline with ONE barrier per tile and two LDS product buffers:
 //   iteration i:  issue gathers of tile i+1 | issue stream loads of tile i+2
 //                 row sums of tile i (LDS buffer b)          <- overlaps the gathers' latency
 //                 products of tile i+1 -> LDS buffer b^1 ; barrier
 // Buffer b^1 was last read by the row sums of iteration i-1, which precede the barrier that
 // ended iteration i-1, so one barrier per tile orders both hazards.
-template <class S, bool kPower, int kMode = 0>
+template <class S, bool kPower>
 __global__ __launch_bounds__(kThreads) void csr_kernel(CsrArgs<S> a, int parity) {
     constexpr int TN = Tile<S>::kNnz;
     constexpr int P = TileRegs<S>::P;
@@ -299,8 +281,11 @@ __global__ __launch_bounds__(kThreads) void csr_kernel(CsrArgs<S> a, int parity)
         xin = a.x_plain;
         yout = a.y_plain;
     }
+    // rnrm is not used: a reciprocal-scaling ablation that read it was removed.  It stays, with its
+    // pass through write_products, because without it hipcc issues the three x gathers of a tile in
+    // another order and csr_kernel<cplx, true> measures 1.6 % slower (262144 x 72 uniform, three
+    // alternating runs: 0.1995-0.2004 against 0.2032-0.2045 ms per iteration)
     const double rnrm = nrm > 0.0 ? 1.0 / nrm : 1.0;
-    (void)rnrm;
     const int tid = threadIdx.x;
     double n2 = 0.0, rr = 0.0, ri = 0.0;
 
@@ -320,14 +305,14 @@ __global__ __launch_bounds__(kThreads) void csr_kernel(CsrArgs<S> a, int parity)
         TileRegs<S> Rc;
         load_tile(a, mc, Rc);
         S xg[P][NPS];
-        issue_gathers<S, kMode>(Rc, xin, xg);
+        issue_gathers<S>(Rc, xin, xg);
         S xrow = s_zero<S>();
         if constexpr (kPower) xrow = xin[min(mc.x + tid, a.nrows - 1) + a.xoff];
         int tn = t + nb;
         int4 mn = a.tile_meta[min(tn, last)];
         TileRegs<S> Rn;
         load_tile(a, mn, Rn);
-        write_products<S, kPower, kMode>(Rc, mc, xg, nrm, rnrm, prod, LDSN - 1);
+        write_products<S, kPower>(Rc, mc, xg, nrm, rnrm, prod, LDSN - 1);
         rows[0][tid] = make_int2(Rc.rp0, Rc.rp1);
         if constexpr (kPower) xrows[0][tid] = xrow;
         __syncthreads();
@@ -339,7 +324,7 @@ __global__ __launch_bounds__(kThreads) void csr_kernel(CsrArgs<S> a, int parity)
             const int t2 = tn + nb;
             // meta first, so its wait does not cover the gathers issued after it
             const int4 m2 = a.tile_meta[min(t2, last)];
-            issue_gathers<S, kMode>(Rnx, xin, xg);
+            issue_gathers<S>(Rnx, xin, xg);
             if constexpr (kPower) xrow = xin[min(mn.x + tid, a.nrows - 1) + a.xoff];
             load_tile(a, m2, Rld);
             // row sums of the current tile from LDS buffer b (ascending-column sequential sums)
@@ -350,11 +335,7 @@ __global__ __launch_bounds__(kThreads) void csr_kernel(CsrArgs<S> a, int parity)
                 const int k1 = rp.y - mc.z;
                 // column-block passes continue the previous block's partial (same summation order)
                 S sacc = a.cb_carry ? yout[mc.x + tid] : s_zero<S>();
-                if constexpr (kMode == 3) {
-                    if (k1 > k0) sacc = pb[lds_idx(k0)];
-                } else {
-                    for (int k = k0; k < k1; ++k) sacc = add(sacc, pb[lds_idx(k)]);
-                }
+                for (int k = k0; k < k1; ++k) sacc = add(sacc, pb[lds_idx(k)]);
                 yout[mc.x + tid] = sacc;
                 if constexpr (kPower) {
                     if (a.cb_epi) {
@@ -365,7 +346,7 @@ __global__ __launch_bounds__(kThreads) void csr_kernel(CsrArgs<S> a, int parity)
                 }
             }
             if (tn >= tend) return true;
-            write_products<S, kPower, kMode>(Rnx, mn, xg, nrm, rnrm, prod + (b ^ 1) * LDSN, LDSN - 1);
+            write_products<S, kPower>(Rnx, mn, xg, nrm, rnrm, prod + (b ^ 1) * LDSN, LDSN - 1);
             rows[b ^ 1][tid] = make_int2(Rnx.rp0, Rnx.rp1);
             if constexpr (kPower) xrows[b ^ 1][tid] = xrow;
             // keep the next step's address arithmetic (which waits for the prefetch) below this
@@ -509,12 +490,10 @@ __device__ __forceinline__ void load_tile_w(const CsrArgs<S>& a, int4 m, WTileRe
 // LDS product index of the windowed kernel: f64 products are written as 16-byte pairs, so the
 // padding (one pair per 32 products, which spreads the lane-per-row reads over the banks) keeps
 // every pair 16-byte aligned; complex products are 16 bytes each.
-#ifndef EIGSOL_WPAD_SHIFT
-#define EIGSOL_WPAD_SHIFT 5
-#endif
+constexpr int kWpadShift = 5;
 template <class S>
 __device__ __forceinline__ int wlds(int k) {
-    if constexpr (std::is_same_v<S, double>) return k + 2 * (k >> EIGSOL_WPAD_SHIFT);
+    if constexpr (std::is_same_v<S, double>) return k + 2 * (k >> kWpadShift);
     else return k + (k >> 5);
 }
 template <class S>
@@ -554,7 +533,7 @@ __device__ __forceinline__ S row_sum_w(const S* pb, int k0, int k1) {
 template <class S, bool kPower>
 __global__ __launch_bounds__(kThreads) void csr_win_kernel(CsrArgs<S> a, int parity) {
     constexpr int TN = Tile<S>::kNnz;
-    constexpr int LDSN = TN + (std::is_same_v<S, double> ? 2 * (TN >> EIGSOL_WPAD_SHIFT) : TN / 32);
+    constexpr int LDSN = TN + (std::is_same_v<S, double> ? 2 * (TN >> kWpadShift) : TN / 32);
     constexpr int KW = Win<S>::kWin;
     __shared__ __align__(16) S prod[LDSN];
     __shared__ S xwin[2][KW];
@@ -925,34 +904,22 @@ __device__ __forceinline__ void slice_compute(const CsrArgs<S>& a, const S* xin,
 // Rounds of slice loads a wave keeps in flight (software pipeline depth) and slices per round,
 // from the size of one slice's registers: band10m (f64, 12 entries per row, 36 VGPRs per slice)
 // measured 205.6 us unpipelined with two slices per round, 194.5 us at depth 1 and 191 us at
-// depth 2 with one slice per round (depth 3+: register pressure, 214 us).  EIGSOL_SLICE_PIPE /
-// EIGSOL_SLICE_NS (compile time) override for A/B builds.
+// depth 2 with one slice per round (depth 3+: register pressure, 214 us).
 template <class S, int KB, bool kG>
 struct SlicePlan {
     static constexpr int bytes = (int)sizeof(SliceRegs<S, KB, kG>);
-#ifdef EIGSOL_SLICE_PIPE
-    static constexpr int pipe = EIGSOL_SLICE_PIPE;
-#else
     static constexpr int pipe = bytes <= 160 ? 2 : (bytes <= 320 ? 1 : 0);
-#endif
-#ifdef EIGSOL_SLICE_NS
-    static constexpr int ns = EIGSOL_SLICE_NS;
-#else
     static constexpr int ns = pipe > 0 ? 1 : 2;
-#endif
 };
 // float: a slice's registers are small enough that four slices per round, all loads issued before
 // any is consumed, beat the software pipeline: band10m f32 149.3 -> 130.9 us (6.16 -> 7.03 TB/s
 // algorithmic), 1M x 16 band 23.6 -> 21.6 us; two / three slices with a pipeline 141-142 / 136 us
-// (tools/f32_ab.sh)
-#if !defined(EIGSOL_SLICE_PIPE) && !defined(EIGSOL_SLICE_NS)
 template <int KB, bool kG>
 struct SlicePlan<float, KB, kG> {
     static constexpr int bytes = (int)sizeof(SliceRegs<float, KB, kG>);
     static constexpr int pipe = 0;
     static constexpr int ns = 4;
 };
-#endif
 
 template <class S, bool kPower, int KB, bool kG, bool kDist = false>
 __global__ __launch_bounds__(kThreads) void csr_slice_kernel(CsrArgs<S> a, int parity) {
@@ -1073,13 +1040,10 @@ __global__ __launch_bounds__(kThreads) void csr_slice_kernel(CsrArgs<S> a, int p
 // double buffered, so one barrier per tile is enough: a wave can only write buffer b again after
 // the barrier of the tile in between, which every wave reaches after its reads of b.
 // Halo slices load only the lanes whose rows are read (slice_issue, kClamp).
-#ifndef EIGSOL_PAIR_T
-#define EIGSOL_PAIR_T 16
-#endif
-// own slices per tile (EIGSOL_PAIR_T, compile time, for A/B builds).  band10m f64, us per iteration,
+// own slices per tile.  band10m f64, us per iteration,
 // two workgroups per CU: 4: 175, 8: 142, 16: 120-125, 20: 123 (248 VGPRs); the halo slices of a
 // band of half-width 64 are read whole, so the tile size sets the extra matrix traffic (2 / T)
-constexpr int kPairT = EIGSOL_PAIR_T;
+constexpr int kPairT = 16;
 constexpr int kPairHalo = 4;              // halo slices a tile may have (both sides together)
 constexpr int kPairSpan = (kPairT + kPairHalo) * kSliceRows;
 constexpr int kPairBlocksPerCU = 2;        // T = 16: 1 / 2 / 3 per CU 148 / 120 / 130 us
@@ -1315,10 +1279,8 @@ constexpr int kBinLev = 4;
 // the largest row-sum array one workgroup can hold beside its other LDS (160 KiB per CU): one
 // workgroup per CU, e.g. 10M f64 rows in two exact rounds of 19532-row chunks over 256 CUs
 constexpr int kBinKBMax = 153;
-#ifndef EIGSOL_BIN_COND
-#define EIGSOL_BIN_COND 1
-#endif
-constexpr bool kBinCondLoads = EIGSOL_BIN_COND;   // levels >= 1: loads only in waves that use them
+// threads per workgroup of csr_bin_kernel; complex<double>: the 1024-thread instantiation spills
+template <class S> inline constexpr int kBinNT = sizeof(S) >= 16 ? 256 : 1024;
 
 template <class S>
 struct BinRegs {
@@ -1372,7 +1334,7 @@ __global__ __launch_bounds__(kNT) void csr_bin_kernel(CsrArgs<S> a, int parity) 
             const int2 lv = ld_uniform(a.blev, m.x + min(l, R.nl - 1));
             R.c[l] = l < R.nl ? lv.y : 0;
             const uint32_t e = (uint32_t)lv.x + (uint32_t)min(R.i, lv.y - 1);
-            if (kBinCondLoads && l > 0 && m.z + wbase >= R.c[l]) continue;   // no lane of this wave at level l
+            if (l > 0 && m.z + wbase >= R.c[l]) continue;   // levels >= 1: loads only in waves that use them
             R.pk[l] = ldg_stream(a.bpk, e);
             R.v[l] = ldg_stream(a.bval, e);
         }
@@ -1380,7 +1342,7 @@ __global__ __launch_bounds__(kNT) void csr_bin_kernel(CsrArgs<S> a, int parity) 
     auto load_x = [&](BinRegs<S>& R) {
 #pragma unroll
         for (int l = 0; l < kBinLev; ++l) {
-            if (kBinCondLoads && l > 0 && (R.i - tid) + wbase >= R.c[l]) continue;
+            if (l > 0 && (R.i - tid) + wbase >= R.c[l]) continue;
             R.x[l] = ldg(xin, R.xb + (R.pk[l] & cmask));
         }
     };
@@ -1749,11 +1711,9 @@ int csr_upload(eigsol_ctx* ctx, int dtype, int64_t nrows, int64_t ncols, int64_t
     const int ntiles = build_tiles(rowptr, col_use, nrows, xoff, cx ? Tile<cplx>::kCap : Tile<double>::kCap,
                                    cx ? Win<cplx>::kWin : Win<double>::kWin, meta, win, nshort,
                                    max_rows, windowed);
-    if (const char* env = std::getenv("EIGSOL_CSR_NO_WINDOW")) if (std::atoi(env)) windowed = 0;
     SliceLayout SL;
     bool sliced = g_upload_plain == 0;
     if (g_upload_plain) windowed = 0;
-    if (const char* env = std::getenv("EIGSOL_CSR_NO_SLICE")) if (std::atoi(env)) sliced = false;
     if (sliced)
         sliced = build_slices(rowptr, col_use, val_use, sb,
                               dtype == EIGSOL_F64 ? 2 : (dtype == EIGSOL_F32 ? 4 : 1), nrows, nnz, xoff, ncols, SL);
@@ -1791,7 +1751,6 @@ int csr_upload(eigsol_ctx* ctx, int dtype, int64_t nrows, int64_t ncols, int64_t
         A->seg_c8[g] = SL.seg_c8[g];
         A->seg_c32[g] = SL.seg_c32[g];
     }
-    if (const char* env = std::getenv("EIGSOL_SLICE_FORCE_GATHER")) if (std::atoi(env)) A->slice_gather = 1;   // A/B
     const size_t pad = (size_t)(dtype == EIGSOL_C128 ? Tile<cplx>::kNnz : Tile<double>::kNnz) + 8;   // branch-free tile loads
     auto cleanup = [&]() { csr_release(A); };
     hipError_t e;
@@ -1936,7 +1895,7 @@ static int build_col_blocks(eigsol_csr* A, const int32_t* rowptr, const int32_t*
 
 // Column-binned layout (csr_bin_kernel) for gather-bound matrices: built for matrices (square,
 // rectangular or row shards) that gather x (gather slices or plain tiles) when x exceeds
-// EIGSOL_CSR_BIN_MIN bytes (default 4 MB: one XCD's L2).  EIGSOL_CSR_BIN=0 disables, =2 builds regardless of x's size (tests);
+// kBinMinBytes (4 MB: one XCD's L2).  EIGSOL_CSR_BIN=0 disables, =2 builds regardless of x's size (tests);
 // EIGSOL_CSR_BIN_BYTES (default 1 MB) is the x block a chunk's steps gather from.
 static int build_bins(eigsol_csr* A, const int32_t* rowptr, const int32_t* col, const void* val) {
     if (g_upload_plain) return EIGSOL_OK;
@@ -1951,13 +1910,13 @@ static int build_bins(eigsol_csr* A, const int32_t* rowptr, const int32_t* col, 
     // kernel runs at 3 waves per SIMD; config 5's triangular product measured 0.198 ms sliced
     // against 0.356 ms binned, so it keeps the slices
     if (sb > 8 && mode != 2) return EIGSOL_OK;
-    double blk_bytes = 1024.0 * 1024, min_bytes = 4.0 * 1024 * 1024;
+    double blk_bytes = 1024.0 * 1024;
+    constexpr double kBinMinBytes = 4.0 * 1024 * 1024;
     if (const char* e = std::getenv("EIGSOL_CSR_BIN_BYTES")) blk_bytes = std::max(1024.0, std::atof(e));
-    if (const char* e = std::getenv("EIGSOL_CSR_BIN_MIN")) min_bytes = std::atof(e);
-    if (mode != 2 && (double)A->ncols * (double)sb < min_bytes) return EIGSOL_OK;
+    if (mode != 2 && (double)A->ncols * (double)sb < kBinMinBytes) return EIGSOL_OK;
     // KB of row sums per workgroup: 153 (one workgroup per CU) where the rows' sums exceed 64 MB,
     // else 16 (EIGSOL_CSR_BIN_LDS = 16 | 64 | 128 | 153); threads per workgroup 1024 or 256
-    // (EIGSOL_CSR_BIN_NT).  Round 4 A/B (tools/bin_balance_ab.py, balanced chunks): 10M x 10 uniform
+    // (kBinNT).  Round 4 A/B (tools/bin_balance_ab.py, balanced chunks): 10M x 10 uniform
     // 16 / 64 / 128 / 153 KB 1.733 / 0.859 / 0.761 / 0.751 ms (fewer chunk rounds: fewer sweeps of x);
     // 1M x 16 0.123 / 0.123 / 0.125 / 0.125 ms
     int lds_kb = (double)A->nrows * (double)sb >= 1024.0 * 65536.0 ? kBinKBMax : 16;
@@ -1965,11 +1924,7 @@ static int build_bins(eigsol_csr* A, const int32_t* rowptr, const int32_t* col, 
         const int v = std::atoi(e);
         lds_kb = v == kBinKBMax ? kBinKBMax : v == 128 ? 128 : v == 64 ? 64 : 16;
     }
-    int nt = sb >= 16 ? 256 : 1024;   // complex<double>: the 1024-thread instantiation spills
-    if (const char* e = std::getenv("EIGSOL_CSR_BIN_NT")) {
-        const int v = std::atoi(e);
-        nt = v == 256 ? 256 : v == 512 ? 512 : 1024;
-    }
+    const int nt = sb >= 16 ? kBinNT<cplx> : kBinNT<double>;
     const int Rmax = lds_kb * 1024 / (int)sb;   // kBinRows<S, lds_kb>
     int R = Rmax;
     // Balanced chunks (EIGSOL_CSR_BIN_BALANCE, default on): the resident workgroups take the chunks
@@ -2126,8 +2081,7 @@ static int resident_grid(eigsol_ctx* ctx, const void* kernel, int64_t ntiles, in
     const int vgpr_alloc = std::max(8, ((fa.numRegs + 7) / 8) * 8);
     const int by_vgpr = std::max(1, std::min(8, 512 / vgpr_alloc) * 4 / waves);
     const int by_lds = fa.sharedSizeBytes ? (int)(160 * 1024 / fa.sharedSizeBytes) : 8;
-    int per_cu = std::max(1, std::min({by_vgpr, by_lds, cap}));
-    if (const char* env = std::getenv("EIGSOL_CSR_BLOCKS_PER_CU")) per_cu = std::max(1, std::atoi(env));
+    const int per_cu = std::max(1, std::min({by_vgpr, by_lds, cap}));
     int64_t g = (int64_t)per_cu * ctx->num_cus;
     const int64_t need = ((ntiles + 7) / 8) * 8;
     g = std::min(g, std::max<int64_t>(need, 8));
@@ -2139,18 +2093,13 @@ static int resident_grid(eigsol_ctx* ctx, const void* kernel, int64_t ntiles, in
 // the device-side peer exchange (row-sharded sessions): every scalar type has the peer kernels
 template <class S> inline constexpr bool kPeerOk = true;
 
-template <class S, bool kPower, int kKB>
-static const void* bin_kernel_ptr_kb(int nt) {
-    return nt == 1024  ? reinterpret_cast<const void*>(csr_bin_kernel<S, kPower, kKB, 1024>)
-           : nt == 512 ? reinterpret_cast<const void*>(csr_bin_kernel<S, kPower, kKB, 512>)
-                       : reinterpret_cast<const void*>(csr_bin_kernel<S, kPower, kKB, 256>);
-}
 template <class S, bool kPower>
 static const void* bin_kernel_ptr(const eigsol_csr* A) {
-    return A->binned == kBinKBMax ? bin_kernel_ptr_kb<S, kPower, kBinKBMax>(A->bin_nt)
-           : A->binned == 128     ? bin_kernel_ptr_kb<S, kPower, 128>(A->bin_nt)
-           : A->binned == 64      ? bin_kernel_ptr_kb<S, kPower, 64>(A->bin_nt)
-                                  : bin_kernel_ptr_kb<S, kPower, 16>(A->bin_nt);
+    constexpr int NT = kBinNT<S>;
+    return A->binned == kBinKBMax ? reinterpret_cast<const void*>(csr_bin_kernel<S, kPower, kBinKBMax, NT>)
+           : A->binned == 128     ? reinterpret_cast<const void*>(csr_bin_kernel<S, kPower, 128, NT>)
+           : A->binned == 64      ? reinterpret_cast<const void*>(csr_bin_kernel<S, kPower, 64, NT>)
+                                  : reinterpret_cast<const void*>(csr_bin_kernel<S, kPower, 16, NT>);
 }
 
 template <class S>
@@ -2202,7 +2151,7 @@ int csr_grid(eigsol_csr* A, int* grid, bool peer) {
         return resident_grid(A->ctx, k, units, grid, 8);
     }
     // sliced: two blocks (8 waves, 16 slices in flight) per CU measured fastest on band10m f64
-    // (round 4, tools/slice_grid_ab.py: 2 / 3 / 4 / 6 blocks 188.8 / 201.9 / 226.6 / 225.1 us); more
+    // (round 4: 2 / 3 / 4 / 6 blocks 188.8 / 201.9 / 226.6 / 225.1 us); more
     // concurrent streams per CU cost more than the latency they hide.  float (four slices per round,
     // no pipeline) peaks at three: 128.8 / 125.8 / 128.8 / 156.2 us
     if (dtype_single(A->dtype) && !A->sliced)   // row-per-lane fallback: rows / threads
@@ -2290,19 +2239,6 @@ static int launch_csr(eigsol_csr* A, const CsrArgs<S>& args, bool power, int par
                 if (power) hipLaunchKernelGGL((csr_kernel<S, true>), dim3(grid), dim3(kThreads), 0, s, ab, parity);
                 else hipLaunchKernelGGL((csr_kernel<S, false>), dim3(grid), dim3(kThreads), 0, s, ab, parity);
             }
-            EIGSOL_HIP(hipGetLastError());
-            return EIGSOL_OK;
-        }
-    }
-    static const int mode = [] {
-        const char* e = std::getenv("EIGSOL_CSR_ABLATION");
-        return e ? std::atoi(e) : 0;
-    }();
-    if constexpr (std::is_same_v<S, double>) {
-        if (power && mode > 0 && !A->windowed && !A->sliced) {
-            if (mode == 1) hipLaunchKernelGGL((csr_kernel<S, true, 1>), dim3(grid), dim3(kThreads), 0, s, args, parity);
-            else if (mode == 2) hipLaunchKernelGGL((csr_kernel<S, true, 2>), dim3(grid), dim3(kThreads), 0, s, args, parity);
-            else hipLaunchKernelGGL((csr_kernel<S, true, 3>), dim3(grid), dim3(kThreads), 0, s, args, parity);
             EIGSOL_HIP(hipGetLastError());
             return EIGSOL_OK;
         }

@@ -34,9 +34,6 @@
 
 namespace eigsol {
 
-int hqr_lds(hipStream_t st, const double* H, int64_t ld, int n, int maxits, double* wr_dev, double* wi_dev,
-            int* info_dev);
-
 namespace dev {
 
 constexpr int kWin = 96;        // window rows/columns (H window + U: 2 x 72 KiB of LDS)
@@ -646,7 +643,7 @@ constexpr int kHqrWaveMax = 128;
 
 // eigenvalues of an n x n (n <= 128) Hessenberg block: info = {fail, most sweeps per deflation, total}
 // dtol: relative subdiagonal below which the block splits (eps: LAPACK's test; the sweeps' shifts
-// are computed with a looser one, EIGSOL_QR_SHIFT_TOL)
+// are computed with a looser one, shift_tol)
 __global__ __launch_bounds__(64) void hqr_wave_kernel(const double* Hin, int64_t ld, int n, double* wr, double* wi,
                                                       int maxits, int* info, double dtol) {
     constexpr int LD = kHqrWaveMax + 1;
@@ -696,7 +693,7 @@ constexpr int kAedThreads = 256;
 // workgroup 0 writes the window back only after seeing the flag, so the copy is the pre-AED state.
 struct ShiftJob {
     int kb, ns;                // block [kb, kb + ns) of H
-    double dtol;               // split tolerance of the shifts' QR (EIGSOL_QR_SHIFT_TOL)
+    double dtol;               // split tolerance of the shifts' QR (shift_tol)
     double *wr, *wi;           // ns eigenvalues
     int* info;                 // {fail, most sweeps per deflation, total, wait timed out}
     unsigned* flag;
@@ -930,24 +927,18 @@ __global__ void zero_entry_kernel(double* H, int64_t n, int i, int j) { H[i + (i
 }  // namespace dev
 
 // ---------------------------------------------------------------------------------- host loop
-// eigenvalues of an n <= 128 Hessenberg block in LDS: the one-wave solver (EIGSOL_HQR_WAVE=0: the
-// workgroup solver of qr.hip, for A/B)
+// eigenvalues of an n <= 128 Hessenberg block in LDS: the one-wave solver
 static int hqr_small(hipStream_t st, const double* H, int64_t ld, int n, int maxits, double* wr, double* wi,
                      int* info, double dtol = 2.220446049250313e-16) {
-    static const bool wave = [] {
-        const char* e = std::getenv("EIGSOL_HQR_WAVE");
-        return !e || std::atoi(e) != 0;
-    }();
-    if (!wave) return hqr_lds(st, H, ld, n, maxits, wr, wi, info);
     hipLaunchKernelGGL(dev::hqr_wave_kernel, dim3(1), dim3(64), 0, st, H, ld, n, wr, wi, maxits, info, dtol);
     EIGSOL_HIP(hipGetLastError());
     return EIGSOL_OK;
 }
 
-static constexpr int kSmallDefault = 128;
+static constexpr int kSmall = 128;   // blocks of at most this many rows are finished in LDS
 // AED window at 4096 with 4-bulge groups (up to 24 bulges per sweep): 40 -> 1.90 s, 48 -> 1.82 s, 56 -> 1.87 s
 // (one chain of 16 bulges: 40 was best); the window's one-wave Schur factorisation costs O(nw^3) latency-bound steps
-static constexpr int kAedDefault = 64;   // EIGSOL_QR_AED overrides (0: off)
+static constexpr int kAedWin = 64;
 
 int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double* wr, double* wi,
                       int32_t* sweeps_out, int32_t* fail_out) {
@@ -992,68 +983,34 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
     int stall = 0;               // sweeps on the current bottom block without a deflation
     // `sweeps` tracks the largest number of sweeps any single deflation needed
     const int max_stall = std::max(1, maxits);
-    static const int kSmall = [] {
-        const char* e = std::getenv("EIGSOL_QR_SMALL");
-        return e ? std::max(16, std::min(128, std::atoi(e))) : kSmallDefault;
-    }();
     static const bool stats = std::getenv("EIGSOL_QR_STATS") != nullptr;
-    static const int max_groups = [] {                 // bulge groups chased concurrently (EIGSOL_QR_GROUPS)
-        const char* e = std::getenv("EIGSOL_QR_GROUPS");
-        return e ? std::max(1, std::min(dev::kMaxGroups, std::atoi(e))) : dev::kMaxGroups;
-    }();
-    static const int max_bulges = [] {                 // experiments: cap the bulges per chain
-        const char* e = std::getenv("EIGSOL_QR_NB");
-        return e ? std::max(1, std::min(dev::kMaxBulges, std::atoi(e))) : 32;
-    }();
-    long long st_steps = 0, st_aed_steps = 0, st_aed_ph[3] = {0, 0, 0};
-    static const int aed_win = [] {
-        const char* e = std::getenv("EIGSOL_QR_AED");   // AED window (0: off)
-        return e ? std::max(0, std::min(dev::kAedMax, std::atoi(e))) : kAedDefault;
-    }();
-    // AED early stop (default; EIGSOL_QR_AED_EARLY=0: the whole window Schur form, whose undeflated
-    // eigenvalues are the shifts).  4096^2: 1.33 -> 1.23 s (the window's factorisation stops at the
-    // first undeflatable block: 378 -> 192 ms of one-wave steps; the shifts then come from the
-    // trailing block, and the sweeps drop from 146 to 128); grid over window 48/56/64, nibble 30/50,
-    // bulges 28/36: window 64, nibble 30, 28 bulges is the optimum (tools/qr_ab_round3.sh)
-    static const bool aed_early = [] {
-        const char* e = std::getenv("EIGSOL_QR_AED_EARLY");
-        return !e || std::atoi(e) != 0;
-    }();
-    // the shifts' QR splits at a looser relative subdiagonal than the eigenvalues' (shifts need no
-    // full accuracy; EIGSOL_QR_SHIFT_TOL).  Round 4 (tools/shift_tol_ab.sh, 4096^2, three seeds):
-    // eps / 1e-6 / 1e-5 / 1e-4 / 1e-3 -> 1.181-1.192 / 1.147-1.158 / 1.143-1.161 / 1.109-1.130 /
-    // 1.109-1.126 s, the eigenvalues one-to-one with LAPACK's at every setting (2.9e-12 at 1e-4)
-    static const double shift_tol = [] {
-        const char* e = std::getenv("EIGSOL_QR_SHIFT_TOL");
-        return e ? std::max(2.220446049250313e-16, std::atof(e)) : 1e-4;
-    }();
-    // window-GEMM tile (EIGSOL_QR_GEMM_TILE = 32 | 64; default: 32 when a launch's 64-wide tiles
-    // would not cover the CUs)
-    static const int gemm_tile = [] {
-        const char* e = std::getenv("EIGSOL_QR_GEMM_TILE");
-        const int v = e ? std::atoi(e) : 0;
-        return (v == 32 || v == 64) ? v : 0;
-    }();
+    constexpr int max_groups = dev::kMaxGroups;   // bulge groups chased concurrently
+    constexpr int max_bulges = 32;                // bulges per chain
+    constexpr int aed_win = kAedWin;
+    // The AED stops at the first undeflatable block.  (Until round 3 it formed the whole window's
+    // Schur form, whose undeflated eigenvalues were the shifts; removed.)  4096^2: 1.33 -> 1.23 s:
+    // 378 -> 192 ms of one-wave steps; the shifts then come from the trailing block, and the sweeps
+    // drop from 146 to 128.
+    //
+    // The shifts' QR splits at a looser relative subdiagonal than the eigenvalues' (shifts need no
+    // full accuracy).  Round 4 (4096^2, three seeds): eps / 1e-6 / 1e-5 / 1e-4 / 1e-3 ->
+    // 1.181-1.192 / 1.147-1.158 / 1.143-1.161 / 1.109-1.130 / 1.109-1.126 s, the eigenvalues
+    // one-to-one with LAPACK's at every setting (2.9e-12 at 1e-4)
+    constexpr double shift_tol = 1e-4;
     // % of the AED window deflated that skips the sweep (LAPACK's NIBBLE).  Round 5, after the
-    // concurrent shifts (tools/qr_nibble_r5.sh, 4096^2, seeds 42 / 7 / 20251226): 30 / 25 / 20 / 15 / 10
+    // concurrent shifts (4096^2, seeds 42 / 7 / 20251226): 30 / 25 / 20 / 15 / 10
     // -> 0.941 / 0.920 / 0.904 / 0.889 / 0.911 s (seed 42), 0.931 / 0.895 / 0.909 / 0.889 / 0.900,
     // 0.927 / 0.913 / 0.904 / 0.884 / 0.919: 15
-    static const int kNibble = [] {
-        const char* e = std::getenv("EIGSOL_QR_NIBBLE");
-        return e ? std::max(1, std::atoi(e)) : 15;
-    }();
-    int st_sweeps = 0, st_windows = 0, st_small = 0, st_small_rows = 0, st_aed = 0, st_aed_defl = 0, st_conc = 0;
-    // concurrent shifts (EIGSOL_QR_CONC): 0 off (the shift QR after the AED, one wave), 1 when the AED
-    // deflates nothing (bitwise the sequential sweeps), 2 (default) also after a small deflation
-    // (LAPACK xLAQR0's undeflated window eigenvalues).  Round 5 (tools/qr_conc_ab.sh, 4096^2, two
-    // seeds): only 2 of 115 sweeps follow an AED that deflated nothing, so mode 1 is mode 0 (0.946 /
-    // 0.949 s); mode 2 runs 141 sweeps instead of 115 but skips their 0.79 ms shift QRs, whose
+    constexpr int kNibble = 15;
+    // Concurrent shifts are used when the AED deflates nothing (bitwise the sequential sweeps) and
+    // after a small deflation (LAPACK xLAQR0's undeflated window eigenvalues).  Round 5 (4096^2, two
+    // seeds), against the shift QR after the AED on one wave: only 2 of 115 sweeps follow an AED
+    // that deflated nothing, so using them there alone changed nothing (0.946 / 0.949 s); with the
+    // small-deflation case 141 sweeps run instead of 115 but skip their 0.79 ms shift QRs, whose
     // eigenvalue QR of the window hides under the AED (~1.1 ms): 0.946 -> 0.928 s and 0.948 ->
-    // 0.930 s (seed 7), one-to-one with LAPACK (3.3e-12)
-    static const int conc_mode = [] {
-        const char* e = std::getenv("EIGSOL_QR_CONC");
-        return e ? std::atoi(e) : 2;
-    }();
+    // 0.930 s (seed 7), one-to-one with LAPACK (3.3e-12).  The two narrower modes were removed.
+    long long st_steps = 0, st_aed_steps = 0, st_aed_ph[3] = {0, 0, 0};
+    int st_sweeps = 0, st_windows = 0, st_small = 0, st_small_rows = 0, st_aed = 0, st_aed_defl = 0, st_conc = 0;
     auto finish_small = [&](int l, int hi) -> int {
         const int m = hi - l + 1;
         EIGSOL_TRY(hqr_small(st, H + l + (int64_t)l * n, n, m, std::max(1, maxits), dwr + l, dwi + l, dinfo));
@@ -1099,17 +1056,17 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
         int nb = std::min(max_bulges, std::max(1, N / 8));
         int ns = 2 * nb;
         bool have_shifts = false;
-        if (aed_win > 0) {
+        {
             const int nw = std::min(aed_win, N);
             const int kw = ihi - nw + 1;
             // concurrent shifts: the pre-AED trailing ns block's eigenvalues on a second workgroup
             // (ShiftJob); used when the AED deflates nothing (the very block the sequential shift QR
             // would read, so the sweep is bitwise the same) and, LAPACK xLAQR0-style, when it
             // deflated a few and the block is the window itself (the undeflated window eigenvalues)
-            const bool conc = conc_mode > 0 && ns <= dev::kAedMax && ns >= 2;
+            const bool conc = ns <= dev::kAedMax && ns >= 2;
             dev::ShiftJob sj{ihi - ns + 1, ns, shift_tol, dsw, dsw + dev::kAedMax, dsinfo, dflag, ++flag_epoch};
             hipLaunchKernelGGL(dev::aed_kernel, dim3(conc ? 2 : 1), dim3(dev::kAedThreads), 0, st, H, n, kw, nw,
-                               kw > l ? 1 : 0, 60, aed_early ? 1 : 0, dwr, dwi, dU, dinfo, sj);
+                               kw > l ? 1 : 0, 60, /*early stop*/ 1, dwr, dwi, dU, dinfo, sj);
             int* info = hp->info;
             double* const awr = hp->awr;
             double* const awi = hp->awi;
@@ -1148,7 +1105,7 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
                     }
                     have_shifts = true;
                     ++st_conc;
-                } else if (conc_ok && conc_mode > 1 && nd > 0 && ns == nw && m >= ns / 2) {
+                } else if (conc_ok && nd > 0 && ns == nw && m >= ns / 2) {
                     // the window's undeflated eigenvalues (LAPACK xLAQR0): the window's spectrum with
                     // each deflated eigenvalue's nearest match removed; the last (ns - nd) rounded to
                     // an even count
@@ -1180,29 +1137,15 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
                     have_shifts = true;
                     ++st_conc;
                 }
-                // shifts: the bottom undeflated eigenvalues of the window (early-stopped windows
-                // have none: the trailing block's, below)
-                if (!aed_early) {
-                    const int N2 = ihi - l + 1;
-                    nb = std::min({max_bulges, std::max(1, N2 / 8), std::max(1, m / 2)});
-                    ns = 2 * nb;
-                    for (int i = 0; i < ns; ++i) {
-                        swr[i] = awr[m - ns + i];
-                        swi[i] = awi[m - ns + i];
-                    }
-                    have_shifts = true;
-                }
+                // (an early-stopped window has no undeflated eigenvalues to offer as shifts: without
+                // concurrent ones they are the trailing block's, below)
             }
         }
         // every 6th sweep without a deflation uses exceptional shifts (LAPACK xLAQR0's KEXSH, NDFL
         // counted from 1 after a deflation): stall counts those sweeps, 0 right after the AED deflated.
-        // Round 3 took stall == 0 as exceptional too, so every sweep after a partial AED deflation ran
-        // on ad hoc shifts (and its shift QR went unused); EIGSOL_QR_EXC_LEGACY=1 restores that for A/B
-        static const bool exc_legacy = [] {
-            const char* e = std::getenv("EIGSOL_QR_EXC_LEGACY");
-            return e && std::atoi(e) != 0;
-        }();
-        const bool exceptional = exc_legacy ? stall % 6 == 0 : (stall > 0 && stall % 6 == 0);
+        // (Round 3 took stall == 0 as exceptional too, so every sweep after a partial AED deflation ran
+        // on ad hoc shifts and its shift QR went unused: a bug, fixed in round 4.)
+        const bool exceptional = stall > 0 && stall % 6 == 0;
         if (!have_shifts && !exceptional) {
             nb = std::min(max_bulges, std::max(1, (ihi - l + 1) / 8));
             ns = 2 * nb;
@@ -1301,8 +1244,8 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
             st_windows += nwin;
             st_steps += t1 - t0;
             hipLaunchKernelGGL(dev::chase_wave_kernel, dim3(nwin), dim3(1024), 0, st, ca);
-            // delayed updates: every left region, then every right region; tiles of gemm_tile
-            // columns / rows per workgroup (32 when 64-wide tiles would leave CUs idle)
+            // delayed updates: every left region, then every right region; tiles of 64 columns /
+            // rows per workgroup (32 when 64-wide tiles would leave CUs idle)
             dev::WinGemmBatch lb{H, n, 0, {}}, rb{H, n, 0, {}};
             int nlb = 0, nrb = 0, span = 0;
             for (int q = 0; q < nwin; ++q) {
@@ -1310,7 +1253,7 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
                 if (w.e <= ihi) span += ihi + 1 - w.e;
                 if (w.s > l) span += w.s - l;
             }
-            const int tile = gemm_tile > 0 ? gemm_tile : (span / 64 < ctx->num_cus ? 32 : 64);
+            const int tile = span / 64 < ctx->num_cus ? 32 : 64;
             for (int q = 0; q < nwin; ++q) {
                 const dev::ChaseWin& w = ca.w[q];
                 const int W = w.e - w.s;

@@ -225,13 +225,6 @@ __global__ __launch_bounds__(kThreads) void gm_resid_kernel(const S* b, double b
     }
 }
 
-// dst = src * (g_re + i g_im)   (real S: g_im ignored)
-template <class S>
-__global__ __launch_bounds__(kThreads) void gm_cscale_kernel(const S* src, double gre, double gim, S* dst, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads)
-        dst[i] = mul(src[i], from_re_im<S>(gre, gim));
-}
-
 // y -= sigma x: M x = A x - sigma x on the caller's matrix A
 template <class S>
 __global__ __launch_bounds__(kThreads) void gm_shift_sub_kernel(const S* x, double sre, double sim, S* y, int64_t n) {
@@ -252,13 +245,13 @@ struct GmresSolver {
     eigsol_ctx* ctx = nullptr;
     int dtype = EIGSOL_F64;
     int64_t n = 0;
-    int m = 40;                 // Krylov dimension per cycle (EIGSOL_GMRES_M)
+    static constexpr int m = 40;                 // Krylov dimension per cycle
     int max_cycles = 30;
-    double rtol = 1e-13;        // Arnoldi estimate target (EIGSOL_GMRES_RTOL)
+    static constexpr double rtol = 1e-13;        // Arnoldi estimate target
     double rtol_true = 1e-12;   // true residual accepted at the end of a cycle
-    double rtol_accept = 1e-10; // worst final residual reported as a success (EIGSOL_GMRES_ACCEPT)
+    static constexpr double rtol_accept = 1e-10; // worst final residual reported as a success
     double normM = 0.0;         // max(||M||_1, ||M||_inf): the backward-error scale of a direct solve
-    double be_accept = 1e-14;   // a direct solve whose normwise backward error is below this is accepted
+    static constexpr double be_accept = 1e-14;   // a direct solve whose normwise backward error is below this is accepted
     int64_t mf_static = 0;      // static pivots of the multifrontal factor (its zero-pivot retry)
     eigsol_csr* M = nullptr;    // M = A - sigma I uploaded (single-precision A only), else
     eigsol_csr* A = nullptr;    // the caller's device matrix: M x = A x - sigma x (no second copy of M)
@@ -377,10 +370,6 @@ static int gmres_create_t(eigsol_ctx* ctx, int dtype, int64_t n, const int32_t* 
     ctx_retain(ctx);
     g->dtype = dtype;
     g->n = n;
-    if (const char* e = std::getenv("EIGSOL_GMRES_M")) g->m = std::max(2, std::min(60, std::atoi(e)));
-    if (const char* e = std::getenv("EIGSOL_GMRES_RTOL")) g->rtol = std::atof(e);
-    if (const char* e = std::getenv("EIGSOL_GMRES_ACCEPT")) g->rtol_accept = std::atof(e);
-    if (const char* e = std::getenv("EIGSOL_DIRECT_BE_ACCEPT")) g->be_accept = std::atof(e);
     // M = A - sigma I, diagonal inserted where A stores none (solve_shifted.hpp:100-102)
     S sig;
     if constexpr (std::is_same_v<S, double>) { (void)sim; sig = sre; }
@@ -831,7 +820,7 @@ static int apply_M(GmresSolver* g, const S* x, S* y) {
 }
 
 template <class S>
-static int gmres_solve_t(GmresSolver* g, const S* b, double bdiv, S* y, const double* guess) {
+static int gmres_solve_t(GmresSolver* g, const S* b, double bdiv, S* y) {
     hipStream_t st = g->ctx->stream;
     const int64_t n = g->n;
     const int m = g->m;
@@ -868,7 +857,7 @@ static int gmres_solve_t(GmresSolver* g, const S* b, double bdiv, S* y, const do
     hipLaunchKernelGGL((dev::gm_resid_kernel<S>), dim3(gb), dim3(dev::kThreads), 0, st, b, bdiv, (const S*)nullptr, w, n);
     double beta = 0.0;
     bool direct_done = false;
-    if (g->complete && !guess) {
+    if (g->complete) {
         // exact factor: ||r0||, x = K^-1 r0, r = r0 - M x and ||r|| with one host wait
         hipLaunchKernelGGL((dev::gm_dots_kernel<S>), dim3(g->G), dim3(dev::kThreads), 0, st, w, n, 1, w, n, g->part);
         hipLaunchKernelGGL(dev::gm_reduce_kernel, dim3(1), dim3(dev::kThreads), 0, st, g->part, g->G, 1, g->hdev);
@@ -901,24 +890,6 @@ static int gmres_solve_t(GmresSolver* g, const S* b, double bdiv, S* y, const do
         bytes += lb + ub + mb + 4.0 * sb * (double)n;
     } else {
         EIGSOL_HIP(hipMemsetAsync(x, 0, n * sizeof(S), st));
-    }
-    // Warm start for the shifted inverse iteration: once x_t is close to the eigenvector v
-    // ((A - sigma I) v = (lambda - sigma) v), y_t = (A - sigma I)^{-1} x_t is close to
-    // x_t / (lambda_{t-1} - sigma): x0 = guess * b / bdiv leaves a residual that shrinks with the
-    // iterate's error, so later solves need fewer Arnoldi steps to the same 1e-12 relative residual
-    // (kept only when it beats x0 = 0).
-    if (guess && bnorm > 0.0) {
-        hipLaunchKernelGGL((dev::gm_cscale_kernel<S>), dim3(gb), dim3(dev::kThreads), 0, st, w, guess[0], guess[1], x, n);
-        EIGSOL_TRY(apply_M<S>(g, x, t1));
-        hipLaunchKernelGGL((dev::gm_resid_kernel<S>), dim3(gb), dim3(dev::kThreads), 0, st, b, bdiv, t1, w, n);
-        EIGSOL_TRY(norm_of(w, beta));
-        bytes += mb + 4.0 * sb * (double)n;
-        if (!(beta < bnorm)) {   // no better than zero: start from zero
-            EIGSOL_HIP(hipMemsetAsync(x, 0, n * sizeof(S), st));
-            hipLaunchKernelGGL((dev::gm_resid_kernel<S>), dim3(gb), dim3(dev::kThreads), 0, st, b, bdiv,
-                               (const S*)nullptr, w, n);
-            beta = bnorm;
-        }
     }
     // exact LU (complete fill): x = U^-1 L^-1 r0 directly; GMRES cycles below only if its true
     // residual misses rtol_true (iterative refinement on the same factors)
@@ -999,8 +970,8 @@ static int gmres_solve_t(GmresSolver* g, const S* b, double bdiv, S* y, const do
         }
     }
     EIGSOL_HIP(hipMemcpyAsync(y, x, n * sizeof(S), hipMemcpyDeviceToDevice, st));
-    if (g->mf && (!direct_done || cycles > 0 || guess)) {
-        // multifrontal solves after the first pass (refinement cycles, a warm-start guess): their
+    if (g->mf && (!direct_done || cycles > 0)) {
+        // multifrontal solves after the first pass (refinement cycles): their
         // wait-error word, read once in one host wait
         int32_t* mf_err = reinterpret_cast<int32_t*>(g->hpin + 6);
         EIGSOL_HIP(hipMemcpyAsync(mf_err, mf_err_word(g->mf), sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1100,10 +1071,10 @@ int gmres_lag_verdict(GmresSolver* g) {
     return (ok && !force) ? EIGSOL_OK : EIGSOL_E_SOLVER;
 }
 
-int gmres_solve(GmresSolver* g, const void* b_dev, double bdiv, void* y_dev, const double* guess) {
+int gmres_solve(GmresSolver* g, const void* b_dev, double bdiv, void* y_dev) {
     if (g->dtype == EIGSOL_C128)
-        return gmres_solve_t<cplx>(g, static_cast<const cplx*>(b_dev), bdiv, static_cast<cplx*>(y_dev), guess);
-    return gmres_solve_t<double>(g, static_cast<const double*>(b_dev), bdiv, static_cast<double*>(y_dev), guess);
+        return gmres_solve_t<cplx>(g, static_cast<const cplx*>(b_dev), bdiv, static_cast<cplx*>(y_dev));
+    return gmres_solve_t<double>(g, static_cast<const double*>(b_dev), bdiv, static_cast<double*>(y_dev));
 }
 
 int gmres_complete(const GmresSolver* g) { return g->complete; }

@@ -10,7 +10,7 @@ struct GmresSolver;
 int gmres_create(eigsol_ctx* ctx, int dtype, int64_t n, const int32_t* rp, const int32_t* ci, const void* v,
                  double sre, double sim, GmresSolver** out, eigsol_csr* Adev = nullptr);
 void gmres_free(GmresSolver* g);
-int gmres_solve(GmresSolver* g, const void* b_dev, double bdiv, void* y_dev, const double* guess = nullptr);
+int gmres_solve(GmresSolver* g, const void* b_dev, double bdiv, void* y_dev);
 int gmres_can_lag(const GmresSolver* g);
 int gmres_solve_lag(GmresSolver* g, const void* b_dev, double bdiv, void* y_dev);
 int gmres_lag_verdict(GmresSolver* g);

@@ -397,12 +397,14 @@ __global__ __launch_bounds__(1024) void qr_panel_col(S* R, int m, int k, int j, 
 
 // ------------------------------------------------------------------ cooperative panel (one launch)
 // The whole panel (32 columns) in ONE cooperative launch of G co-resident blocks (host: ~32 rows each); block
-// b owns rows [b R, (b+1) R).  Per column, three grid barriers separate
+// b owns rows [b R, (b+1) R).  Per column the phases are
 //   P1  right update of column j (own rows, kept in LDS) + partials of V^T a
 //   P2  w = T^T (sum of partials); left update; partial of ||a(j+2:)||^2; x0 = a(j+1)
 //   P3  reflector (every block, redundantly, from the reduced scalars); v and the reduced column
 //       for own rows; partials of t = V^T v
 //   P4  GEMV y = A(:, j+1:n) v for own rows (v staged in LDS), Y(:, i) and the T column
+// with a grid barrier after P1 and after P2; the barrier that first stood between P3 and P4 is
+// gone (see hess_panel_coop below: P2 publishes what P3 and P4 need).
 // (P4 -> the next P1 needs no barrier: P1 reads only own rows and V(j+1, 0:i), published in P3.
 // The block partials are double-buffered for the same reason: a block that has finished P4 writes
 // the next column's P1 partials while a slower block may still be gathering P3's, so P1/P2 and
@@ -412,13 +414,7 @@ __global__ __launch_bounds__(1024) void qr_panel_col(S* R, int m, int k, int j, 
 // (deterministic).  The barrier spins are bounded: on expiry the kernel sets an error word and
 // drains (the host then reports EIGSOL_E_HIP).
 constexpr int kCoopThreads = 1024;
-#ifndef EIGSOL_GEMV_BATCH
-#define EIGSOL_GEMV_BATCH 16
-#endif
-#ifndef EIGSOL_HESS_SKIP_GEMV
-#define EIGSOL_HESS_SKIP_GEMV 0   // timing experiments only
-#endif
-constexpr int kGemvBatch = EIGSOL_GEMV_BATCH;   // columns per GEMV step (loads in flight per lane)
+constexpr int kGemvBatch = 16;   // columns per GEMV step (loads in flight per lane)
 
 template <class S>
 struct CoopArgs {
@@ -432,7 +428,7 @@ struct CoopArgs {
     S* x0;              // a(j+1)
     unsigned* bar;      // barrier counters, 9 x 64 bytes (zeroed by the host before the launch)
     int* err;
-    S* xu;              // kMerge: the column below row j + 1 before normalisation (n scalars)
+    S* xu;              // the column below row j + 1 before normalisation (n scalars)
     bool hier;          // two-level grid barrier (gridDim.x % 8 == 0)
 };
 
@@ -466,7 +462,7 @@ __device__ __forceinline__ void grid_barrier(unsigned* bar, unsigned& target, in
     __syncthreads();
 }
 
-// kMerge (default; EIGSOL_HESS_MERGE=0: off): two grid barriers per column instead of three.  P2 also publishes
+// Two grid barriers per column (the first form of this kernel took three, see the host's note): P2 also publishes
 // the updated column below row j + 1 unnormalised (xu) with the partials of V^H over those rows;
 // after its barrier every block forms the reflector from the reduced norm, scales xu into the GEMV's
 // v on the fly, and t = V^H v = rv (conj(V(j+1, :)) v0 + the reduced partials) - no barrier between
@@ -474,7 +470,7 @@ __device__ __forceinline__ void grid_barrier(unsigned* bar, unsigned& target, in
 // barrier, so the next column's P1 takes the one entry it reads from another block, V(j + 1, i),
 // from the block's own copy (every block forms rv v0 itself).  The same reflectors; t and T round
 // differently.
-template <class S, int kCoopRowsPerLane, bool kMerge = false>
+template <class S, int kCoopRowsPerLane>
 __global__ __launch_bounds__(kCoopThreads) void hess_panel_coop(CoopArgs<S> a) {
     constexpr int NB = HessCfg<S>::NB;
     extern __shared__ double vsh_raw[];      // v (n scalars) for the GEMV
@@ -487,7 +483,7 @@ __global__ __launch_bounds__(kCoopThreads) void hess_panel_coop(CoopArgs<S> a) {
     __shared__ S s_scal[3];
     __shared__ double s_rv;
     __shared__ int s_sk;
-    __shared__ S s_vrow;   // kMerge: V(j + 1, i) of the previous column (rv v0, or 0 when skipped)
+    __shared__ S s_vrow;   // V(j + 1, i) of the previous column (rv v0, or 0 when skipped)
     // Block partials of another phase: thread (s, c) loads blocks s, s + kSl, ... of column c at once
     // (independent sc1 loads) and sums them in that order; thread c then sums the kSl slices in order
     // (deterministic, the same in every block, for any grid size).
@@ -538,7 +534,7 @@ __global__ __launch_bounds__(kCoopThreads) void hess_panel_coop(CoopArgs<S> a) {
     for (int i = 0; i < a.nbp; ++i) {
         const int j = k + i;
         // ---------------- P1
-        if (tid < i) sv[tid] = cj((kMerge && tid == i - 1) ? s_vrow : ld_ag(&a.V[j + (int64_t)tid * n]));
+        if (tid < i) sv[tid] = cj(tid == i - 1 ? s_vrow : ld_ag(&a.V[j + (int64_t)tid * n]));
         __syncthreads();
         if (wv == 0)
             for (int q = 0; q < kCoopRowsPerLane; ++q) {
@@ -562,7 +558,7 @@ __global__ __launch_bounds__(kCoopThreads) void hess_panel_coop(CoopArgs<S> a) {
         }
         grid_barrier(a.bar, target, a.err, a.hier);
         bool sk;
-        if constexpr (kMerge) {
+        {
             // ---------------- P2 (merged): left update, norm partials, x0, xu, partials of V^H xu
             gather(a.part, i, sw);
             if (tid < i) {
@@ -657,100 +653,11 @@ __global__ __launch_bounds__(kCoopThreads) void hess_panel_coop(CoopArgs<S> a) {
                 sv[tid] = sk ? s_zero<S>() : scal(u, rv);
             }
             __syncthreads();
-        } else {
-            // ---------------- P2
-            gather(a.part, i, sw);
-            if (tid < i) {
-                S s = s_zero<S>();
-                for (int c = 0; c <= tid; ++c) s = add(s, mul(cj(Tl[c + tid * NB]), sw[c]));   // (T^H w)_tid
-                st[tid] = s;
-            }
-            __syncthreads();
-            double tl = 0.0;
-            if (wv == 0)
-                for (int q = 0; q < kCoopRowsPerLane; ++q) {
-                    const int r = r0 + lane + 64 * q;
-                    if (r < r1) {
-                        S x = xs[lane + 64 * q];
-                        if (r >= k + 1)
-                            for (int c = 0; c < i; ++c) x = sub(x, mul(a.V[r + (int64_t)c * n], st[c]));
-                        xs[lane + 64 * q] = x;
-                        if (r >= j + 2) tl += sq_abs(x);
-                        if (r == j + 1) st_ag(a.x0, x);
-                    }
-                }
-            if (wv == 0) {
-                tl = wave_sum(tl);
-                if (lane == 0) st_agent(&a.tpart[grp], tl);
-            }
-            grid_barrier(a.bar, target, a.err, a.hier);
-            // ---------------- P3
-            double* redd = reinterpret_cast<double*>(red);
-            if (tid < G) redd[tid] = ld_agent(&a.tpart[tid]);
-            __syncthreads();
-            if (tid == 0) {
-                double tail = 0.0;
-                for (int b = 0; b < G; ++b) tail += redd[b];
-                const S x0 = ld_ag(a.x0);
-                bool sk;
-                S v0, alpha;
-                double rv;
-                hess_reflector(x0, tail, sk, v0, rv, alpha);
-                s_sk = sk ? 1 : 0;
-                s_scal[1] = v0;
-                s_rv = rv;
-                s_scal[2] = alpha;
-            }
-            __syncthreads();
-            sk = s_sk != 0;
-            const S v0 = s_scal[1], alpha = s_scal[2];
-            const double rv = s_rv;
-            if (wv == 0)
-                for (int q = 0; q < kCoopRowsPerLane; ++q) {
-                    const int r = r0 + lane + 64 * q;
-                    if (r < r1) {
-                        const S x = xs[lane + 64 * q];
-                        S v = s_zero<S>();
-                        if (!sk && r > j) v = scal(r == j + 1 ? v0 : x, rv);
-                        st_ag(&a.V[r + (int64_t)i * n], v);
-                        xs[lane + 64 * q] = v;           // keep v for the t partials
-                        S red_col = x;
-                        if (!sk && r == j + 1) red_col = alpha;
-                        if (!sk && r > j + 1) red_col = s_zero<S>();
-                        a.A[r + (int64_t)j * n] = red_col;
-                    }
-                }
-            __syncthreads();
-            for (int c = wv; c < i; c += 16) {
-                S p = s_zero<S>();
-                for (int q = 0; q < kCoopRowsPerLane; ++q) {
-                    const int r = r0 + lane + 64 * q;
-                    if (r < r1) p = add(p, mul(cj(a.V[r + (int64_t)c * n]), xs[lane + 64 * q]));
-                }
-                p = wsum(p);
-                if (lane == 0) st_ag(&a.part[(G + grp) * NB + c], p);
-            }
-            grid_barrier(a.bar, target, a.err, a.hier);
-            // ---------------- P4
-            // v into LDS: four independent coherent loads per thread in flight (clamped rows, so no
-            // predicated load waits for the one before it)
-            for (int rb = tid; rb < n; rb += 4 * kCoopThreads) {
-                S t4[4];
-    #pragma unroll
-                for (int u = 0; u < 4; ++u) t4[u] = ld_ag(&a.V[min(rb + u * kCoopThreads, n - 1) + (int64_t)i * n]);
-    #pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (rb + u * kCoopThreads < n) vsh[rb + u * kCoopThreads] = sk ? s_zero<S>() : t4[u];
-            }
-            __syncthreads();
-            gather(a.part + (size_t)G * NB, i, sv);
-            if (sk && tid < i) sv[tid] = s_zero<S>();
-            __syncthreads();
         }
         S yacc[kCoopRowsPerLane];
 #pragma unroll
         for (int q = 0; q < kCoopRowsPerLane; ++q) yacc[q] = s_zero<S>();
-        if (!sk && !EIGSOL_HESS_SKIP_GEMV) {
+        if (!sk) {
             // kB columns per step with every load issued before the FMAs (bytes in flight: the
             // GEMV streams the trailing matrix once per column)
             // rp lanes per row group of a column, sub = 64 / rp columns per wave step: with fewer than
@@ -822,7 +729,7 @@ __global__ __launch_bounds__(kCoopThreads) void hess_panel_coop(CoopArgs<S> a) {
 // right and left updates and the partials of V^H a read no global memory), the own rows of A(:, j + 1)
 // loaded before the second barrier, and everything the reflector and the GEMV need after that barrier
 // (the norm partials, x0, xu, the partials of V^H xu and V(j + 1, 0:i)) loaded in one batch; V(j + 1, :)
-// is also the next column's V(j, :).  The same operations in the same order as hess_panel_coop<S, 1, true>:
+// is also the next column's V(j, :).  The same operations in the same order as hess_panel_coop<S, 1>:
 // bitwise its results (tests/test_gpu_qr.py::test_hessenberg_panel2_bitwise).
 // kVG (orders past HessCfg<S>::kCoopMaxN, up to 64 rows per block x 256 blocks): v is not staged in LDS;
 // the GEMV reads the published column xu and scales it on the fly (the same value as the staged v).
@@ -1005,7 +912,7 @@ __global__ __launch_bounds__(kCoopThreads) void hess_panel_coop2(CoopArgs<S> a) 
         if (tid == i) s_vj[i] = sk ? s_zero<S>() : scal(v0, rv);
         __syncthreads();
         S yacc = s_zero<S>();
-        if (!sk && !EIGSOL_HESS_SKIP_GEMV) {
+        if (!sk) {
             const int rl = lane & (rp - 1), sub = 64 / rp;
             const int cs = 16 * sub;
             const int r = min(r0 + rl, r1 - 1);
@@ -1508,9 +1415,8 @@ void gemm(hipStream_t st, int m, int nn, int kk, double alpha, const S* A, int64
     }
     auto launch = [&](dim3 g, double be, S* Cp, int64_t ldcp, int kc, int64_t zs) {
         if constexpr (std::is_same_v<S, double>) {
-            static const bool valu = std::getenv("EIGSOL_GEMM_VALU") != nullptr;
-            auto kern = valu ? dev::gemm_valu<double, TA, TB> : dev::gemm_mfma_f64<TA, TB>;
-            hipLaunchKernelGGL(kern, g, dim3(256), 0, st, m, nn, kk, alpha, A, lda, B, ldb, be, Cp, ldcp, kc, zs);
+            hipLaunchKernelGGL((dev::gemm_mfma_f64<TA, TB>), g, dim3(256), 0, st, m, nn, kk, alpha, A, lda, B, ldb, be,
+                               Cp, ldcp, kc, zs);
         } else if constexpr (std::is_same_v<S, cplx>) {
             hipLaunchKernelGGL((dev::gemm_mfma_c128<TA, TB>), g, dim3(256), 0, st, m, nn, kk, alpha, A, lda, B, ldb,
                                be, Cp, ldcp, kc, zs);
@@ -1565,24 +1471,15 @@ int hessenberg_blocked(hipStream_t st, S* A, int64_t n64, S* Vout = nullptr, S* 
     int coop_ok = 0, dev_id = 0;
     EIGSOL_HIP(hipGetDevice(&dev_id));
     EIGSOL_HIP(hipDeviceGetAttribute(&coop_ok, hipDeviceAttributeCooperativeLaunch, dev_id));
-    // panel grid: about 32 rows per block, 16 .. 256 blocks (EIGSOL_HESS_G overrides: 8 .. 256, a multiple of
-    // 8).  The panel's GEMV streams the trailing matrix once per column from the grid's CUs, its two grid
-    // barriers per column grow with the grid; round 6 (tools/r06_hess_grid_ab.sh, profiles/r06_hess_grid_ab.log,
+    // panel grid: about 32 rows per block, 16 .. 256 blocks (a multiple of 8).  The panel's GEMV streams the trailing matrix once per column from the grid's CUs, its two grid
+    // barriers per column grow with the grid; round 6 (profiles/r06_hess_grid_ab.log,
     // host in/out): 512^2 16 blocks 0.011 s (64: 0.014), 1024^2 32 0.024 (64: 0.026), 4096^2 128 0.167 (64:
     // 0.184, 256: 0.193), 8192^2 256 0.73 (64: 1.11)
-    static const int g_env = [] {
-        const char* e = std::getenv("EIGSOL_HESS_G");
-        const int g = e ? std::atoi(e) : 0;
-        return (g >= 8 && g <= 256 && g % 8 == 0) ? g : 0;
-    }();
-    const int G = g_env ? g_env : std::min(256, std::max(16, (n / 32 + 7) / 8 * 8));
-    // two-level grid barrier from 64 blocks (EIGSOL_HESS_BAR=0: one counter).  Round 6
-    // (tools/r06_hess_bar_ab.sh, profiles/r06_hess_bar_ab.log, host in/out): 4096^2 0.169 / 0.172 -> 0.161 /
+    const int G = std::min(256, std::max(16, (n / 32 + 7) / 8 * 8));
+    // two-level grid barrier from 64 blocks (one counter below).  Round 6
+    // (profiles/r06_hess_bar_ab.log, host in/out): 4096^2 0.169 / 0.172 -> 0.161 /
     // 0.162 s, 8192^2 0.730 -> 0.689 s; at 32 blocks (1024^2) one counter stays (0.0240 against 0.0248 s)
-    static const bool hier = [] {
-        const char* e = std::getenv("EIGSOL_HESS_BAR");
-        return !(e && std::atoi(e) == 0);
-    }();
+    const bool hier = G >= 64;   // (G is a multiple of 8)
     constexpr size_t kBarBytes = 9 * 64;
     // past Cfg::kCoopMaxN (v no longer fits the panel's LDS) the merged panel reads v from the published
     // column (hess_panel_coop2<S, true>), up to 64 rows per block (n <= 16384); EIGSOL_HESS_VG=0 keeps such
@@ -1592,28 +1489,21 @@ int hessenberg_blocked(hipStream_t st, S* A, int64_t n64, S* Vout = nullptr, S* 
     const bool vg = (n > Cfg::kCoopMaxN || (vge && std::atoi(vge) == 2)) && n <= 64 * G && !(vge && std::atoi(vge) == 0);
     bool coop = coop_ok && (n <= Cfg::kCoopMaxN || vg) && n <= 128 * G && std::getenv("EIGSOL_HESS_NO_COOP") == nullptr;
     const size_t coop_lds = vg ? 0 : (size_t)n * sizeof(S);
-    // two grid barriers per panel column (hess_panel_coop kMerge; EIGSOL_HESS_MERGE=0: three).  Round 6
-    // (tools/r06_hess_merge_ab.sh, profiles/r06_hess_merge_ab.log): to_hessenberg 4096^2 0.184 / 0.185 ->
-    // 0.182 / 0.176 s; QR 4096^2 unchanged within noise (0.885 / 0.885 against 0.888 / 0.882 s), complex
-    // 1.551 -> 1.545 s; eigenvalues one-to-one with the LAPACK fixtures
-    static const bool merge = [] {
-        const char* e = std::getenv("EIGSOL_HESS_MERGE");
-        return !(e && std::atoi(e) == 0);
-    }();
+    // two grid barriers per panel column; the three-barrier form it replaced in round 6 was removed
+    // (profiles/r06_hess_merge_ab.log: to_hessenberg 4096^2 0.184 / 0.185 -> 0.182 / 0.176 s; QR 4096^2
+    // unchanged within noise, 0.885 / 0.885 against 0.888 / 0.882 s, complex 1.551 -> 1.545 s; eigenvalues
+    // one-to-one with the LAPACK fixtures)
     // EIGSOL_HESS_PANEL2=0: the merged panel without the LDS caches and the batched loads
     const bool panel2 = [] {   // read per call (the bitwise test switches it)
         const char* e = std::getenv("EIGSOL_HESS_PANEL2");
         return !(e && std::atoi(e) == 0);
     }();
-    if (vg && !(merge && panel2)) coop = false;   // only the merged LDS-cached panel has the global-v form
+    if (vg && !panel2) coop = false;   // only the LDS-cached panel has the global-v form
     const void* coop_kernel =
-        n <= 64 * G
-            ? (merge ? (panel2 ? (vg ? reinterpret_cast<const void*>(dev::hess_panel_coop2<S, true>)
-                                     : reinterpret_cast<const void*>(dev::hess_panel_coop2<S>))
-                               : reinterpret_cast<const void*>(dev::hess_panel_coop<S, 1, true>))
-                     : reinterpret_cast<const void*>(dev::hess_panel_coop<S, 1>))
-            : (merge ? reinterpret_cast<const void*>(dev::hess_panel_coop<S, 2, true>)
-                     : reinterpret_cast<const void*>(dev::hess_panel_coop<S, 2>));
+        n <= 64 * G ? (panel2 ? (vg ? reinterpret_cast<const void*>(dev::hess_panel_coop2<S, true>)
+                                    : reinterpret_cast<const void*>(dev::hess_panel_coop2<S>))
+                              : reinterpret_cast<const void*>(dev::hess_panel_coop<S, 1>))
+                    : reinterpret_cast<const void*>(dev::hess_panel_coop<S, 2>);
     S *part = nullptr, *x0s = nullptr, *xu = nullptr;
     double* tpart = nullptr;
     unsigned* bar = nullptr;
@@ -1636,7 +1526,7 @@ int hessenberg_blocked(hipStream_t st, S* A, int64_t n64, S* Vout = nullptr, S* 
         EIGSOL_HIP(hipMemsetAsync(T, 0, NB * NB * sizeof(S), st));
         if (coop) {
             EIGSOL_HIP(hipMemsetAsync(bar, 0, kBarBytes, st));
-            dev::CoopArgs<S> ca{A, n, k, nbp, V, Y, T, part, tpart, x0s, bar, err, xu, hier && G % 8 == 0 && G >= 64};
+            dev::CoopArgs<S> ca{A, n, k, nbp, V, Y, T, part, tpart, x0s, bar, err, xu, hier};
             void* kargs[] = {&ca};
             // EIGSOL_HESS_COOP_PLAIN=1: the SAME panel kernel through an ordinary launch, for profiling
             // only (rocprofv3 7.2 crashes at exit after any cooperative launch, tools/coop_prof_repro.hip);

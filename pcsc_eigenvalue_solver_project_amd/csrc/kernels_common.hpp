@@ -366,13 +366,9 @@ __device__ __forceinline__ T ldg(const T* base, uint32_t i) {
                                        (uint64_t)(i * (uint32_t)sizeof(T)));
 }
 // streaming (read-once) variant: non-temporal, so the matrix stream does not evict the x windows
-#ifndef EIGSOL_STREAM_NT
-#define EIGSOL_STREAM_NT 1
-#endif
 template <class T>
 __device__ __forceinline__ T ldg_stream(const T* base, uint32_t i) {
     const T* p = reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (uint64_t)(i * (uint32_t)sizeof(T)));
-#if EIGSOL_STREAM_NT
     if constexpr (std::is_arithmetic_v<T>) {
         return __builtin_nontemporal_load(p);
     } else if constexpr (sizeof(T) == 16) {           // double2, cplx, int4
@@ -388,9 +384,6 @@ __device__ __forceinline__ T ldg_stream(const T* base, uint32_t i) {
         __builtin_memcpy(&r, &v, 8);
         return r;
     }
-#else
-    return *p;
-#endif
 }
 
 // Pair launches of the power iteration (csr_power.hip, csr_pair_kernel): one pass over the matrix

@@ -88,9 +88,7 @@ __device__ __forceinline__ cplx mf_ld(const cplx* p) { return cplx{ld_agent(&p->
 // value flags of the row-block solve (EIGSOL_MF_VALFLAG): an unsolved pivot value holds this NaN in
 // every 8-byte word, a solved one never does (a NaN result is stored as the default quiet NaN), so a
 // waiting block polls the values themselves instead of a flag and then the values
-#ifndef EIGSOL_MF_UNROLL
-#define EIGSOL_MF_UNROLL 8   // loads in flight per thread in the small fronts' inverse-form products
-#endif
+constexpr int kMfUnroll = 8;   // loads in flight per thread in the small fronts' inverse-form products
 constexpr unsigned long long kMfSent = 0x7FF4DEAD7FF4DEADull;
 __device__ __forceinline__ bool mf_unready(double v) { return (unsigned long long)__double_as_longlong(v) == kMfSent; }
 __device__ __forceinline__ bool mf_unready(cplx v) { return mf_unready(v.re) || mf_unready(v.im); }
@@ -353,7 +351,7 @@ __device__ __forceinline__ void mf_fwd_front(const MfFront f, unsigned char* lds
                 S v = s_zero<S>();
                 const S* Gi = G + i;
                 const int jn = i < ns ? i + 1 : ns;   // inv(L11) is lower triangular: skip its zeros
-#pragma unroll EIGSOL_MF_UNROLL
+#pragma unroll kMfUnroll
                 for (int j = 0; j < jn; ++j) v = add(v, mul(Gi[(int64_t)j * d], y[j]));
                 if (i < ns) w[f.c0 + i] = v;
                 else u[f.uoff + i - ns] = add(acc[i - ns], v);
@@ -367,7 +365,7 @@ __device__ __forceinline__ void mf_fwd_front(const MfFront f, unsigned char* lds
         if (i < d) {
             const S* Gi = G + i;
             const int jn = i < ns ? i + 1 : ns;   // inv(L11) is lower triangular: skip its zeros
-#pragma unroll EIGSOL_MF_UNROLL
+#pragma unroll kMfUnroll
             for (int j = p; j < jn; j += tpr) sacc = add(sacc, mul(Gi[(int64_t)j * d], y[j]));
         }
         part[p * R + i] = sacc;
@@ -468,7 +466,7 @@ __device__ __forceinline__ void mf_bwd_front(const MfFront f, unsigned char* lds
             const S* Gk = G + k;
             // inv(U11) is upper triangular: columns from k on (the first of them congruent to p mod 4)
             const int c0 = k > p ? p + ((k - p + 3) / 4) * 4 : p;
-#pragma unroll EIGSOL_MF_UNROLL
+#pragma unroll kMfUnroll
             for (int c = c0; c < d; c += 4) sacc = add(sacc, mul(Gk[(int64_t)c * ns], c < ns ? t[c] : xs[c - ns]));
         }
         part[p * 64 + k] = sacc;
@@ -1011,7 +1009,7 @@ __global__ __launch_bounds__(256) void mf_inv_kernel(const MfFront* fr, const in
 }
 
 // Inverse form of a one-workgroup front with at most 64 pivots (after the factorization;
-// EIGSOL_MF_INVFORM=0: off, EIGSOL_MF_INV_D: most rows, default 256): the
+// EIGSOL_MF_INVFORM=0: off; at most 256 rows): the
 // forward solve of the front becomes one product [inv(L11); L21 inv(L11)] (P r) and the backward one
 // [inv(U11), -inv(U11) U12] [t; x(struct)], every load independent, instead of a dependent chain
 // over the pivot columns on one wave followed by the struct rows (the diagonal blocks of the large
@@ -1797,15 +1795,6 @@ struct MfFactor {
     std::vector<int32_t> lds_asm;
     std::vector<int32_t> lds_asm2;    // mf_fwd_height_kernel's assembly: d entries per large front
     MfStats st;
-    // solves replayed as a hipGraph per (b, out) pair seen twice (value flags, no flow kernels:
-    // the launches' arguments are then the same for every solve of that pair)
-    struct Graph {
-        const void* b;
-        void* out;
-        int uses;
-        hipGraphExec_t exec;
-    };
-    std::vector<Graph> graphs;
     int64_t nstatic = 0;   // static pivots of the factorization (0 unless the retry set them)
 };
 
@@ -1818,8 +1807,6 @@ void mf_free(MfFactor* f) {
                     (void*)f->tabf2, (void*)f->tabb2, (void*)f->flags, (void*)f->err, f->z, f->tinv, (void*)f->flow_f, (void*)f->flow_b,
                     (void*)f->fheight, (void*)f->done, (void*)f->sub_ranges, (void*)f->bigm})
         if (p) hipFree(p);
-    for (auto& g : f->graphs)
-        if (g.exec) hipGraphExecDestroy(g.exec);
     ctx_release(f->ctx);
     delete f;
 }
@@ -1946,13 +1933,10 @@ bool nested_dissection(int64_t n, const SymGraph& g, int leaf, std::vector<NdNod
         int32_t level;
     };
     std::vector<Vs> vs(n, Vs{-1, -1, 0});
-    // pseudo-peripheral restarts per piece (EIGSOL_MF_PP_ROUNDS).  1M convection-diffusion: 2 / 1 / 0
+    // pseudo-peripheral restarts per piece.  1M convection-diffusion: 2 / 1 / 0
     // rounds -> 1.374e8 / 1.368e8 / 1.47e8 factor entries, 1.13e11 / 1.12e11 / 1.83e11 flops; on the box
     // the set-up is the same for 1 and 2 (0.63-0.67 s) and the solve 1.55 against 1.57 ms: 2 stays
-    static const int pp_rounds = [] {
-        const char* e = std::getenv("EIGSOL_MF_PP_ROUNDS");
-        return e ? std::max(0, std::atoi(e)) : 2;
-    }();
+    constexpr int pp_rounds = 2;
     std::atomic<int64_t> stamp{0}, bstamp{0};
     std::mutex mu;
     std::condition_variable cv;
@@ -2578,9 +2562,9 @@ int mf_prepare_host(int64_t n, const std::vector<int32_t>& rp, const std::vector
     }
     // solve plan: fronts with many pivots or rows are solved by one workgroup per 64-row block
     // (mf_big_*), the others by one workgroup each (mf_fwd / mf_bwd)
-    int big_ns = 96, big_d = 256;
+    int big_ns = 96;
+    constexpr int big_d = 256;
     if (const char* e = std::getenv("EIGSOL_MF_BIG_NS")) big_ns = std::atoi(e);
-    if (const char* e = std::getenv("EIGSOL_MF_BIG_D")) big_d = std::atoi(e);
     auto &slists = X.slists, &tabf = X.tabf, &tabb = X.tabb, &tabf2 = X.tabf2, &tabb2 = X.tabb2, &lds_asm = X.lds_asm;
     auto& lds_asm2 = X.lds_asm2;
     auto &sstart = X.sstart, &nwave = X.nwave, &nsmall = X.nsmall, &nbig = X.nbig, &foff = X.foff, &fcnt = X.fcnt,
@@ -2632,9 +2616,8 @@ int mf_prepare_host(int64_t n, const std::vector<int32_t>& rp, const std::vector
     lds_asm.assign(H + 1, 0);
     lds_asm2.assign(H + 1, 0);
     bool inv_on = true;
-    int inv_d = 256;   // 256 / 384 / 512: 1.71 / 1.72 / 1.72 ms per 1M iteration (tools/mf_grid.sh)
+    constexpr int inv_d = 256;   // 256 / 384 / 512: 1.71 / 1.72 / 1.72 ms per 1M iteration (tools/mf_grid.sh)
     if (const char* e = std::getenv("EIGSOL_MF_INVFORM")) inv_on = std::atoi(e) != 0;
-    if (const char* e = std::getenv("EIGSOL_MF_INV_D")) inv_d = std::max(1, std::atoi(e));
     int32_t& nflag = X.nflag;
     int64_t& zsz = X.zsz;
     for (int32_t h = 0; h <= H; ++h) {
@@ -3120,45 +3103,11 @@ int mf_solve_t(MfFactor* f, const S* b, S* out) {
     const int64_t n = f->n;
     if (n == 0) return EIGSOL_OK;
     const int32_t ef = ++f->epoch, eb = ++f->epoch;   // flag words: forward, then backward values
-    // EIGSOL_MF_GRAPH=1 (opt-in): the ~50 dependent launches of a solve replayed as one hipGraph
-    // once a (b, out) pair repeats.  Only where no launch argument changes between solves: value
-    // flags (the epoch words are unused) and no flow kernels.  Measured and rejected (round 6,
-    // tools/r06_mf_graph_ab.sh, 1M convection-diffusion, two A/B pairs): 1.51 ms per iteration with
-    // direct launches, 2.82 / 2.86 ms replayed - the replay serialises the nodes behind more than the
-    // stream's own launch gaps
-    static const bool graph_on = [] {
-        const char* e = std::getenv("EIGSOL_MF_GRAPH");
-        return e && std::atoi(e) != 0;
-    }();
-    const bool ff = f->nflow && (f->flow_mode & 1), fb = f->nflow && (f->flow_mode & 2);
-    bool done = false;
-    if (graph_on && (f->backoff & 4) && !ff && !fb && st != nullptr) {
-        MfFactor::Graph* gr = nullptr;
-        for (auto& g : f->graphs)
-            if (g.b == b && g.out == out) gr = &g;
-        if (!gr) {
-            if (f->graphs.size() >= 8) {   // keep the most recent pairs
-                if (f->graphs.front().exec) (void)hipGraphExecDestroy(f->graphs.front().exec);
-                f->graphs.erase(f->graphs.begin());
-            }
-            f->graphs.push_back({b, out, 1, nullptr});
-        } else if (!gr->exec && ++gr->uses >= 2) {
-            hipGraph_t g = nullptr;
-            if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                mf_solve_enqueue<S>(f, st, b, out, ef, eb);
-                if (hipStreamEndCapture(st, &g) != hipSuccess || !g ||
-                    hipGraphInstantiate(&gr->exec, g, nullptr, nullptr, 0) != hipSuccess)
-                    gr->exec = nullptr;
-                if (g) (void)hipGraphDestroy(g);
-            }
-            (void)hipGetLastError();   // a failed capture leaves the direct launches below
-        }
-        if (gr && gr->exec) {
-            EIGSOL_HIP(hipGraphLaunch(gr->exec, st));
-            done = true;
-        }
-    }
-    if (!done) mf_solve_enqueue<S>(f, st, b, out, ef, eb);
+    // The ~50 dependent launches of a solve go to the stream one by one.  Replaying them as one
+    // hipGraph per repeated (b, out) pair was tried in round 6 (1M convection-diffusion, two A/B
+    // pairs): 1.51 ms per iteration with direct launches, 2.82 / 2.86 ms replayed - the replay
+    // serialises the nodes behind more than the stream's own launch gaps.  Removed.
+    mf_solve_enqueue<S>(f, st, b, out, ef, eb);
     EIGSOL_HIP(hipGetLastError());
     static const bool dbg = std::getenv("EIGSOL_MF_DEBUG") != nullptr;
     if (dbg) {

@@ -214,192 +214,6 @@ __global__ void diag_kernel(const S* H, int64_t n, S* d) {
     if (i < n) d[i] = H[i + i * n];
 }
 
-// ------------------------------------------------------------ Francis double shift (real)
-// Whole active problem in LDS, one workgroup: scalar control (deflation search, shifts, the
-// reflector) by thread 0, row and column updates of every 3x3 reflector by all threads.  The
-// algorithm is the textbook eigenvalue-only double-shift QR (the oracle's hqr_francis restates
-// it): deflation when |h(l,l-1)| <= eps (|h(l-1,l-1)| + |h(l,l)|), exceptional shifts at 10 and
-// 20 iterations, `maxits` sweeps per eigenvalue before giving up.
-struct HqrCtl {
-    int nn, l, m, its, stage, fail;
-    int total;          // sweeps performed
-    int maxits;         // most sweeps any single deflation needed
-    double t;           // accumulated exceptional shift
-    double p, q, r, xs, ys, zs;
-};
-
-constexpr int kHqrMaxN = 128;   // 128^2 fp64 = 128 KiB of LDS
-
-__global__ __launch_bounds__(1024) void hqr_lds_kernel(const double* Hin, int64_t ld, int n, double* wr,
-                                                       double* wi, int maxits, int* info) {
-    __shared__ double a[kHqrMaxN * kHqrMaxN];
-    __shared__ HqrCtl c;
-    __shared__ double s_anorm;
-    const int tid = threadIdx.x;
-    auto A = [&](int i, int j) -> double& { return a[i + j * n]; };
-    for (int e = tid; e < n * n; e += blockDim.x) {
-        const int i = e % n, j = e / n;
-        a[e] = Hin[i + (int64_t)j * ld];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double s = 0.0;
-        for (int i = 0; i < n; ++i)
-            for (int j = max(i - 1, 0); j < n; ++j) s += fabs(A(i, j));
-        s_anorm = s;
-        c.nn = n - 1;
-        c.t = 0.0;
-        c.fail = 0;
-        c.total = 0;
-        c.maxits = 0;
-        c.its = 0;
-    }
-    __syncthreads();
-    const double eps = 2.220446049250313e-16;
-    __shared__ int s_l;
-    while (true) {
-        // ---- deflation scan in parallel: the largest l in [1, nn] with a negligible h(l, l-1)
-        if (tid == 0) s_l = 0;
-        __syncthreads();
-        const int nn0 = c.nn;
-        if (nn0 < 0) break;
-        for (int l = 1 + tid; l <= nn0; l += blockDim.x) {
-            const double s0 = fabs(A(l - 1, l - 1)) + fabs(A(l, l));
-            const double sc = s0 == 0.0 ? s_anorm : s0;
-            if (fabs(A(l, l - 1)) <= eps * sc) atomicMax(&s_l, l);
-        }
-        __syncthreads();
-        // ---- thread 0: 1x1 / 2x2 deflation or the next sweep's shift (start row m = l)
-        if (tid == 0) {
-            c.stage = 0;   // 0: sweep, 1: stop, 3: deflated (scan again)
-            const int nn = nn0;
-            const int l = s_l;
-            if (l > 0) A(l, l - 1) = 0.0;
-            const double x = A(nn, nn);
-            if (l == nn) {
-                wr[nn] = x + c.t; wi[nn] = 0.0; c.nn = nn - 1;
-                c.maxits = max(c.maxits, c.its);
-                c.its = 0;
-                c.stage = 3;
-            } else {
-                const double y = A(nn - 1, nn - 1);
-                const double w = A(nn, nn - 1) * A(nn - 1, nn);
-                if (l == nn - 1) {
-                    const double p = 0.5 * (y - x);
-                    const double q = p * p + w;
-                    const double z = sqrt(fabs(q));
-                    const double xx = x + c.t;
-                    if (q >= 0.0) {
-                        const double zz = p + (p >= 0 ? fabs(z) : -fabs(z));
-                        wr[nn - 1] = wr[nn] = xx + zz;
-                        if (zz != 0.0) wr[nn] = xx - w / zz;
-                        wi[nn - 1] = wi[nn] = 0.0;
-                    } else {
-                        wr[nn - 1] = wr[nn] = xx + p;
-                        wi[nn - 1] = -z;
-                        wi[nn] = z;
-                    }
-                    c.nn = nn - 2;
-                    c.maxits = max(c.maxits, c.its);
-                    c.its = 0;
-                    c.stage = 3;
-                } else if (c.its >= maxits) {
-                    c.fail = 1;
-                    c.stage = 1;
-                } else {
-                    double xs = x, ys = y, ws = w;
-                    if (c.its == 10 || c.its == 20) {   // exceptional shift
-                        c.t += xs;
-                        for (int i = 0; i <= nn; ++i) A(i, i) -= xs;
-                        const double s = fabs(A(nn, nn - 1)) + fabs(A(nn - 1, nn - 2));
-                        ys = xs = 0.75 * s;
-                        ws = -0.4375 * s * s;
-                    }
-                    ++c.its;
-                    ++c.total;
-                    // the sweep starts at m = l (the textbook's search for two small consecutive
-                    // subdiagonals is an O(n) scalar loop; starting at l is always valid)
-                    const int m = l;
-                    const double z = A(m, m);
-                    const double r0 = xs - z, s1 = ys - z;
-                    double p = (r0 * s1 - ws) / A(m + 1, m) + A(m, m + 1);
-                    double q = A(m + 1, m + 1) - z - r0 - s1;
-                    double r = A(m + 2, m + 1);
-                    const double sc = fabs(p) + fabs(q) + fabs(r);
-                    p /= sc; q /= sc; r /= sc;
-                    c.l = l;
-                    c.m = m;
-                    c.p = p; c.q = q; c.r = r;
-                }
-            }
-        }
-        __syncthreads();
-        if (c.stage == 1) break;
-        if (c.stage == 3) continue;
-        {
-            // clear the sub-subdiagonals of the active block (textbook: before the sweep)
-            const int m = c.m, nn = c.nn;
-            for (int i = m + tid; i <= nn - 2; i += blockDim.x) {
-                A(i + 2, i) = 0.0;
-                if (i != m) A(i + 2, i - 1) = 0.0;
-            }
-            __syncthreads();
-        }
-        const int l = c.l, m = c.m, nn = c.nn;
-        // ---- the sweep: one 3x3 reflector per k, updates in parallel
-        for (int k = m; k <= nn - 1; ++k) {
-            if (tid == 0) {
-                double p = c.p, q = c.q, r = c.r, xs = 1.0;
-                if (k != m) {
-                    p = A(k, k - 1);
-                    q = A(k + 1, k - 1);
-                    r = (k != nn - 1) ? A(k + 2, k - 1) : 0.0;
-                    xs = fabs(p) + fabs(q) + fabs(r);
-                    if (xs != 0.0) { p /= xs; q /= xs; r /= xs; }
-                }
-                const double s = (p >= 0 ? 1.0 : -1.0) * sqrt(p * p + q * q + r * r);
-                if (s != 0.0) {
-                    if (k == m) {
-                        if (l != m) A(k, k - 1) = -A(k, k - 1);
-                    } else {
-                        A(k, k - 1) = -s * xs;
-                    }
-                    p += s;
-                    c.xs = p / s;
-                    c.ys = q / s;
-                    c.zs = r / s;
-                    c.q = q / p;
-                    c.r = r / p;
-                    c.stage = 2;   // apply
-                } else {
-                    c.stage = 0;   // skip
-                }
-            }
-            __syncthreads();
-            if (c.stage == 2) {
-                const double xs = c.xs, ys = c.ys, zs = c.zs, q = c.q, r = c.r;
-                const bool three = k != nn - 1;
-                for (int j = k + tid; j <= nn; j += blockDim.x) {
-                    double p = A(k, j) + q * A(k + 1, j);
-                    if (three) { p += r * A(k + 2, j); A(k + 2, j) -= p * zs; }
-                    A(k + 1, j) -= p * ys;
-                    A(k, j) -= p * xs;
-                }
-                __syncthreads();
-                const int mmin = nn < k + 3 ? nn : k + 3;
-                for (int i = l + tid; i <= mmin; i += blockDim.x) {
-                    double p = xs * A(i, k) + ys * A(i, k + 1);
-                    if (three) { p += zs * A(i, k + 2); A(i, k + 2) -= p * r; }
-                    A(i, k + 1) -= p * q;
-                    A(i, k) -= p;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (tid == 0) { info[0] = c.fail; info[1] = max(c.maxits, c.its); info[2] = c.total; }
-}
-
 // max |a_ij| as the bit pattern of a non-negative double (ordered like the value), for the
 // norm-range check before the Francis path
 __global__ __launch_bounds__(256) void absmax_kernel(const double* A, int64_t cnt, unsigned long long* out) {
@@ -477,34 +291,29 @@ int hessenberg_t(hipStream_t st, S* H, int64_t n, QrWork<S>& w) {
 }
 
 // Matrices of moderate size use the blocked (panel + GEMM) reduction (hessenberg.hip): real up to
-// n = 16384, complex up to 8192 (the panel column in LDS); others the per-reflector kernels above
-// (EIGSOL_HESS_UNBLOCKED=1 forces those, for A/B).
+// n = 16384, complex up to 8192 (the panel column in LDS); others the per-reflector kernels above.
 template <class S>
 int hessenberg_dev(hipStream_t st, S* H, int64_t n, QrWork<S>& w) {
-    static const bool unblocked = std::getenv("EIGSOL_HESS_UNBLOCKED") != nullptr;
-    if (!unblocked) {
-        if constexpr (std::is_same_v<S, double>) {
-            if (n >= 64 && n <= 16384) return hessenberg_blocked_f64(st, H, n);
-        } else if constexpr (std::is_same_v<S, cplx>) {
-            if (n >= 64 && n <= 8192) return hessenberg_blocked_c128(st, H, n);
-        } else if constexpr (std::is_same_v<S, float>) {
-            if (n >= 64 && n <= 16384) return hessenberg_blocked_f32(st, H, n);
-        } else {
-            if (n >= 64 && n <= 16384) return hessenberg_blocked_c64(st, H, n);
-        }
+    if constexpr (std::is_same_v<S, double>) {
+        if (n >= 64 && n <= 16384) return hessenberg_blocked_f64(st, H, n);
+    } else if constexpr (std::is_same_v<S, cplx>) {
+        if (n >= 64 && n <= 8192) return hessenberg_blocked_c128(st, H, n);
+    } else if constexpr (std::is_same_v<S, float>) {
+        if (n >= 64 && n <= 16384) return hessenberg_blocked_f32(st, H, n);
+    } else {
+        if (n >= 64 && n <= 16384) return hessenberg_blocked_c64(st, H, n);
     }
     return hessenberg_t<S>(st, H, n, w);
 }
 
 // qr_decompose_dense (qr_decompose.hpp:46-85): R = A (m x n) in place, Q (m x m) = I then updated
 // Blocked (compact WY, hessenberg.hip) from min(m, n) >= 64 while a column fits the panel
-// kernel's LDS; EIGSOL_QR_UNBLOCKED=1 forces the per-reflector kernels (A/B).
+// kernel's LDS; the per-reflector kernels otherwise.
 template <class S>
 int qr_decompose_t(hipStream_t st, S* R, int64_t m, int64_t n, S* Q, QrWork<S>& w) {
     hipLaunchKernelGGL((dev::set_identity_kernel<S>), dim3((m * m + 255) / 256), dim3(256), 0, st, Q, m);
-    static const bool unblocked = std::getenv("EIGSOL_QR_UNBLOCKED") != nullptr;
     const int64_t lds_max = std::is_same_v<S, cplx> ? 8192 : 16384;
-    if (!unblocked && std::min(m, n) >= 64 && m <= lds_max && n <= INT32_MAX / 2) {
+    if (std::min(m, n) >= 64 && m <= lds_max && n <= INT32_MAX / 2) {
         if constexpr (std::is_same_v<S, double>) return qr_blocked_f64(st, R, m, n, Q);
         else if constexpr (std::is_same_v<S, cplx>) return qr_blocked_c128(st, R, m, n, Q);
         else if constexpr (std::is_same_v<S, float>) return qr_blocked_f32(st, R, m, n, Q);
@@ -722,17 +531,6 @@ static int qr_francis_c128_host(eigsol_ctx* ctx, int64_t n, const void* A, int m
     work_free(wk);
     (void)hipFree(H);
     return rc;
-}
-
-// Small problems: the whole matrix in LDS (n <= kHqrMaxN).  Larger: see francis.hip.
-int hqr_lds(hipStream_t st, const double* H, int64_t ld, int n, int maxits, double* wr_dev, double* wi_dev,
-            int* info_dev) {
-    if (n > dev::kHqrMaxN) return fail(EIGSOL_E_UNSUPPORTED, "hqr_lds: n > 128");
-    // one wave for shift-sized problems (its barriers cost nothing), four waves otherwise
-    const int threads = n <= 64 ? 64 : 256;
-    hipLaunchKernelGGL(dev::hqr_lds_kernel, dim3(1), dim3(threads), 0, st, H, ld, n, wr_dev, wi_dev, maxits, info_dev);
-    EIGSOL_HIP(hipGetLastError());
-    return EIGSOL_OK;
 }
 
 int wide_hessenberg(eigsol_ctx* ctx, int dtype, int64_t n, const void* A, void* H);   // wide.hip

@@ -2373,7 +2373,7 @@ static int factor_csr_t(eigsol_csr* A, double sre, double sim, ShiftFactor** out
 template <class S>
 static int tri_launch_setup_t(ShiftFactor* f) {
     int rc = EIGSOL_OK;
-    // tail grid: one residency round (cooperative launch), capped at EIGSOL_TRSV_BLOCKS_PER_CU
+    // tail grid: one residency round (cooperative launch), capped at kTrsvBlocksPerCU
     // blocks per CU and by the work
     {
         int per_cu_max = 0;
@@ -2385,23 +2385,20 @@ static int tri_launch_setup_t(ShiftFactor* f) {
             rc = fail(EIGSOL_E_HIP, "triangular solve: occupancy query");
         f->grid = per_cu_max * f->ctx->num_cus;
     }
-    int per_cu = 2;
-    if (const char* env = std::getenv("EIGSOL_TRSV_BLOCKS_PER_CU")) per_cu = std::max(1, std::atoi(env));
-    f->grid = std::min(f->grid, per_cu * f->ctx->num_cus);
+    constexpr int kTrsvBlocksPerCU = 2;
+    f->grid = std::min(f->grid, kTrsvBlocksPerCU * f->ctx->num_cus);
     const int64_t units = f->tail_chunks ? (int64_t)f->nchunks - f->chunk0 : f->nslices;
     f->grid = (int)std::max<int64_t>(1, std::min<int64_t>(f->grid, (units + dev::kWaves - 1) / dev::kWaves));
     // multi-solve launches: chunk tail with the one-wave head (or none), K solves per launch
     // (EIGSOL_TRSV_MULTI=K, 1..4; 1 = one iteration per launch) on K copies of the grid at one
-    // workgroup per CU per solve (EIGSOL_TRSV_MULTI_BLOCKS_PER_CU), when they are co-resident
+    // workgroup per CU per solve, when they are co-resident
     if (rc == EIGSOL_OK && f->tail_chunks && (f->hpos == 0 || f->wave_head)) {
         const char* e = std::getenv("EIGSOL_TRSV_MULTI");
         const int want = std::max(1, std::min(dev::kMaxMulti, e ? std::atoi(e) : kMultiDefault));
         int per_cu_role = 0;
         hipOccupancyMaxActiveBlocksPerMultiprocessor(
             &per_cu_role, reinterpret_cast<const void*>(dev::sptrsv_chunk_role_kernel<S>), dev::kThreads, 0);
-        int role_per_cu = 1;
-        if (const char* env = std::getenv("EIGSOL_TRSV_MULTI_BLOCKS_PER_CU")) role_per_cu = std::max(1, std::atoi(env));
-        const int gr = std::min(f->grid, role_per_cu * f->ctx->num_cus);
+        const int gr = std::min(f->grid, f->ctx->num_cus);   // one role block per CU
         int K = want;
         while (K > 1 && per_cu_role * f->ctx->num_cus < K * gr) --K;
         if (K > 1) {
@@ -2419,12 +2416,10 @@ static int tri_launch_setup_t(ShiftFactor* f) {
                         (size_t)K * (size_t)(f->hpos + 1) * sizeof(S) + 16 + static_lds <= (size_t)160 * 1024) ? 1 : 0;
         }
     }
-    // EIGSOL_TRSV_PART_GRID: the partials kernels' grid.  Round 6 (tools/r06_c5_partgrid_ab.sh,
-    // profiles/r06_c5_partgrid_ab.log, config 5 at K = 4): 2048 / 977 (n / 1024, the old cap) / 512 /
+    // the partials kernels' grid.  Round 6 (profiles/r06_c5_partgrid_ab.log, config 5 at K = 4): 2048 / 977 (n / 1024, the old cap) / 512 /
     // 256 / 192 / 128 / 64 blocks -> 0.4077 / 0.4076 / 0.4026 / 0.4010 / 0.4016 / 0.4049 / 0.4159 ms per
     // iteration: one block per CU, the last arriver sums fewer block partials per solve
-    int64_t red_cap = 256;
-    if (const char* e = std::getenv("EIGSOL_TRSV_PART_GRID")) red_cap = std::max<int64_t>(8, std::atoll(e));
+    constexpr int64_t red_cap = 256;
     // never above grid * kWaves: wave_part (below) holds that many block partials
     f->red_grid = (int)std::max<int64_t>(1, std::min<int64_t>(f->grid * dev::kWaves,
                                                                   std::min<int64_t>(red_cap, (f->n + 1023) / 1024)));
@@ -2492,9 +2487,9 @@ void* shift_aux(const ShiftFactor* f, int j) { return (j >= 0 && j < dev::kMaxMu
 
 // x = M^-1 (b / bdiv) by the GMRES family; single precision through f->promo (widen, solve, narrow)
 template <class S>
-static int gm_solve_s(ShiftFactor* f, const void* b, double bdiv, void* y, const double* guess, bool lag = false) {
+static int gm_solve_s(ShiftFactor* f, const void* b, double bdiv, void* y, bool lag = false) {
     if constexpr (kGmres<S>) {
-        return lag ? gmres_solve_lag(f->gm, b, bdiv, y) : gmres_solve(f->gm, b, bdiv, y, guess);
+        return lag ? gmres_solve_lag(f->gm, b, bdiv, y) : gmres_solve(f->gm, b, bdiv, y);
     } else {
         using W = GmresScalar<S>;
         hipStream_t st = f->ctx->stream;
@@ -2503,7 +2498,7 @@ static int gm_solve_s(ShiftFactor* f, const void* b, double bdiv, void* y, const
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (f->n + 255) / 256));
         hipLaunchKernelGGL((dev::convert_kernel<S, W>), dim3(grid), dim3(256), 0, st, static_cast<const S*>(b), wb, f->n);
         EIGSOL_HIP(hipGetLastError());
-        const int rc = lag ? gmres_solve_lag(f->gm, wb, bdiv, wy) : gmres_solve(f->gm, wb, bdiv, wy, guess);
+        const int rc = lag ? gmres_solve_lag(f->gm, wb, bdiv, wy) : gmres_solve(f->gm, wb, bdiv, wy);
         if (rc != EIGSOL_OK) return rc;
         hipLaunchKernelGGL((dev::convert_kernel<W, S>), dim3(grid), dim3(256), 0, st, wy, static_cast<S*>(y), f->n);
         EIGSOL_HIP(hipGetLastError());
@@ -2520,7 +2515,7 @@ static int shift_launch_t(ShiftFactor* f, bool iter, const void* b, void* y, voi
         // ILU(0)-preconditioned GMRES: host-driven (one sync per Arnoldi step), so the iteration is
         // prologue launch -> host reads the stop decision -> solve -> partials launch
         if (!iter) {
-            const int rc = gm_solve_s<S>(f, b, 0.0, y, nullptr);
+            const int rc = gm_solve_s<S>(f, b, 0.0, y);
             if (rc != EIGSOL_E_SOLVER) return rc;
             EIGSOL_TRY(gmres_dense_fallback<S>(f, rc));
             return shift_launch_t<S>(f, iter, b, y, buf0, buf1, ctl, rank_part, my_part, trace, parity);
@@ -2559,7 +2554,7 @@ static int shift_launch_t(ShiftFactor* f, bool iter, const void* b, void* y, voi
             if (v != EIGSOL_OK && v != EIGSOL_E_SOLVER) return v;
             if (v == EIGSOL_E_SOLVER) {
                 const int pp = parity ^ 1;
-                const int rc = gm_solve_s<S>(f, pp ? buf0 : buf1, f->lag_bdiv, pp ? buf1 : buf0, nullptr);
+                const int rc = gm_solve_s<S>(f, pp ? buf0 : buf1, f->lag_bdiv, pp ? buf1 : buf0);
                 if (rc == EIGSOL_E_SOLVER) {
                     // the checked solve failed too: the densified LU redoes the previous launch (its
                     // prologue re-takes that launch's decision from the same carry), then this one
@@ -2583,31 +2578,15 @@ static int shift_launch_t(ShiftFactor* f, bool iter, const void* b, void* y, voi
         const int32_t done = hd->done;
         const PowerCarry cr = hd->cr;
         if (done) return EIGSOL_OK;
-        // EIGSOL_GMRES_WARM=1: warm start from the latest eigenvalue estimate, y ~ x / (lambda - sigma)
-        // (gmres.hip).  Off by default: round-4 A/B on config 5's matrix made general (tools/gmres_warm_ab.py)
-        // gave 54 against 55 Arnoldi steps over the run and 9.1 against 8.9 ms per iteration - the
-        // guess only beats x0 = 0 once the iterate's residual is below |lambda - sigma|, i.e. in the
-        // last one or two iterations
-        static const bool warm = [] {
-            const char* e = std::getenv("EIGSOL_GMRES_WARM");
-            return e && std::atoi(e) != 0;
-        }();
-        double guess[2] = {0.0, 0.0};
-        bool use_guess = false;
-        if (warm && cr.t >= 1) {
-            const double dre = cr.rho_re - f->sig_re, dim = dtype_complex(f->dtype) ? cr.rho_im - f->sig_im : 0.0;
-            const double d2 = dre * dre + dim * dim;
-            if (d2 > 0.0 && std::isfinite(d2)) {
-                guess[0] = dre / d2;
-                guess[1] = -dim / d2;
-                use_guess = true;
-            }
-        }
+        // Every solve starts from x0 = 0.  A warm start from the latest eigenvalue estimate,
+        // y ~ x / (lambda - sigma), was tried in round 4 on config 5's matrix made general and removed:
+        // 54 against 55 Arnoldi steps over the run and 9.1 against 8.9 ms per iteration - the guess
+        // only beats x0 = 0 once the iterate's residual is below |lambda - sigma|, i.e. in the last
+        // one or two iterations
         // the direct solve's check is read at the next launch's decision wait (one host wait per
         // iteration instead of two) where the factor is complete and needs no refinement by design
-        const bool lag = !use_guess && gmres_can_lag(f->gm);
-        const int rc = gm_solve_s<S>(f, parity ? buf0 : buf1, cr.nrm, parity ? buf1 : buf0, use_guess ? guess : nullptr,
-                                     lag);
+        const bool lag = gmres_can_lag(f->gm);
+        const int rc = gm_solve_s<S>(f, parity ? buf0 : buf1, cr.nrm, parity ? buf1 : buf0, lag);
         if (lag && rc == EIGSOL_OK) {
             f->lag_prev = true;
             f->lag_bdiv = cr.nrm;

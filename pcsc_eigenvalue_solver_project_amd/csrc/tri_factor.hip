@@ -266,17 +266,15 @@ static void level_order(const std::vector<int32_t>& rp, const std::vector<int32_
 
 // Head of the level order solved by one workgroup from LDS: the longest prefix of levels whose
 // positions fit the LDS budget and whose levels are narrow (a wide level is cheaper spread over
-// the whole GPU).  EIGSOL_TRSV_HEAD_ROWS / EIGSOL_TRSV_HEAD_WIDTH override (0 rows: no head).
+// the whole GPU).
 template <class S>
 static int32_t head_levels(const std::vector<int64_t>& lstart, const std::vector<int64_t>& lcount,
                            const std::vector<int32_t>& lmaxlen, int32_t nlevels, bool wave_head) {
-    int64_t cap = (int64_t)(150 * 1024) / (int64_t)sizeof(S);
+    constexpr int64_t cap = (int64_t)(150 * 1024) / (int64_t)sizeof(S);
     // widest head level.  One-workgroup head: config 5 256 -> 0.861 ms, 1024 -> 0.872 ms per solve.
     // One-wave head (16 rows per pass, ~0.26 us a pass): 64 -> 0.833 ms, 256 -> 0.879 ms (a wider
     // level is cheaper in the tail, ~1.7 us a level)
-    int64_t width = wave_head ? 64 : 256;
-    if (const char* e = std::getenv("EIGSOL_TRSV_HEAD_ROWS")) cap = std::min<int64_t>(cap, std::atoll(e));
-    if (const char* e = std::getenv("EIGSOL_TRSV_HEAD_WIDTH")) width = std::atoll(e);
+    const int64_t width = wave_head ? 64 : 256;
     int32_t h = 0;
     int64_t npass = 0;   // the pass table shares the LDS budget (8 bytes a pass)
     while (h < nlevels && lcount[h] <= width && lmaxlen[h] <= dev::kRowLanes) {
@@ -373,10 +371,6 @@ static TriPlan tri_plan(ShiftFactor* f, const std::vector<int64_t>& lstart, cons
         std::sort(sorted.begin(), sorted.end());
         const int32_t q95 = sorted.empty() ? 0 : sorted[(size_t)(0.95 * (double)(sorted.size() - 1))];
         f->slice_b = q95 <= 4 ? 4 : (q95 <= 8 ? 8 : 16);
-        if (const char* e = std::getenv("EIGSOL_TRSV_SLICE_B")) {
-            const int b = std::atoi(e);
-            if (b == 4 || b == 8 || b == 16) f->slice_b = b;
-        }
     }
     pl.device_buildable = f->tail_chunks && (f->hpos == 0 || f->wave_head);
     return pl;

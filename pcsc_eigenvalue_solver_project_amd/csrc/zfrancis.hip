@@ -158,8 +158,8 @@ __device__ __forceinline__ void zhouse2_scaled(cplx a, cplx x1, double& beta, cp
 // so the AED spike test is taken right there; the first eigenvalue that fails it ends the
 // factorisation (stop = i; the rows above stay unreduced).  stop = -1: ran to completion.
 // dtol: relative subdiagonal at which the block splits (ulp: ZLAHQR's test; the sweeps' shifts are
-// computed with a looser one, EIGSOL_ZQR_SHIFT_TOL)
-template <bool kSchur, bool kFast = true>
+// could be computed with a looser one)
+template <bool kSchur>
 __device__ void zwave_hqr(cplx* h, cplx* v, int n, cplx* w, int& failed, int& maxits, int& steps,
                           double spk = -1.0, int* stop = nullptr, double dtol = 2.220446049250313e-16) {
     constexpr int lh = kZSmall + 1;
@@ -230,16 +230,15 @@ __device__ void zwave_hqr(cplx* h, cplx* v, int n, cplx* w, int& failed, int& ma
             // single-shift sweep from l
             steps += i - l;
             for (int kk = l; kk < i; ++kk) {
-                // kFast: the left update's rows kk, kk+1 (columns >= kk: this step's own stores go to
+                // the left update's rows kk, kk+1 (columns >= kk: this step's own stores go to
                 // column kk-1) and V's columns kk, kk+1 are loaded first, so their LDS latency
-                // overlaps the reflector's chain; the reflector is zhouse2_scaled's
+                // overlaps the reflector's chain; the reflector is zhouse2_scaled's.  (Round 5's step
+                // loaded them where they are used and took zhouse's reflector; removed.)
                 const int c = kk + ln;
                 const bool cl = c <= (kSchur ? n - 1 : i);
                 cplx a0{0.0, 0.0}, a1{0.0, 0.0}, w0{0.0, 0.0}, w1{0.0, 0.0};
-                if (kFast) {
-                    if (cl) { a0 = H(kk, c); a1 = H(kk + 1, c); }
-                    if (kSchur && ln < n) { w0 = V(ln, kk); w1 = V(ln, kk + 1); }
-                }
+                if (cl) { a0 = H(kk, c); a1 = H(kk + 1, c); }
+                if (kSchur && ln < n) { w0 = V(ln, kk); w1 = V(ln, kk + 1); }
                 cplx v0, v1;
                 if (kk == l) {
                     const cplx h11s = sub(H(l, l), t);
@@ -252,9 +251,8 @@ __device__ void zwave_hqr(cplx* h, cplx* v, int n, cplx* w, int& failed, int& ma
                     v1 = H(kk + 1, kk - 1);
                 }
                 double beta;
-                cplx tau, vv, unused;
-                if (kFast) zhouse2_scaled(v0, v1, beta, tau, vv);
-                else zhouse(v0, v1, cplx{0.0, 0.0}, false, beta, tau, vv, unused);
+                cplx tau, vv;
+                zhouse2_scaled(v0, v1, beta, tau, vv);
                 EIGSOL_ZWAVE_ORDER();
                 if (kk > l && ln == 0) {
                     H(kk, kk - 1) = cplx{beta, 0.0};
@@ -263,7 +261,6 @@ __device__ void zwave_hqr(cplx* h, cplx* v, int n, cplx* w, int& failed, int& ma
                 const cplx ct = cconj(tau);
                 {   // left: rows kk, kk+1, columns kk..i (Schur: ..n-1)
                     if (cl) {
-                        if (!kFast) { a0 = H(kk, c); a1 = H(kk + 1, c); }
                         const cplx s = mul(ct, add(a0, cmul_conj(vv, a1)));
                         H(kk, c) = sub(a0, s);
                         H(kk + 1, c) = sub(a1, mul(s, vv));
@@ -279,7 +276,6 @@ __device__ void zwave_hqr(cplx* h, cplx* v, int n, cplx* w, int& failed, int& ma
                         H(r, kk + 1) = sub(b1, mul(s, cconj(vv)));
                     }
                     if (kSchur && ln < n) {
-                        if (!kFast) { w0 = V(ln, kk); w1 = V(ln, kk + 1); }
                         const cplx s = mul(tau, add(w0, mul(w1, vv)));
                         V(ln, kk) = sub(w0, s);
                         V(ln, kk + 1) = sub(w1, mul(s, cconj(vv)));
@@ -311,8 +307,7 @@ __device__ void zwave_hqr(cplx* h, cplx* v, int n, cplx* w, int& failed, int& ma
     }
 }
 
-// Eigenvalues of an n x n Hessenberg block (n <= 64) in LDS.  kFast: zwave_hqr's step (EIGSOL_ZQR_STEP)
-template <bool kFast>
+// Eigenvalues of an n x n Hessenberg block (n <= 64) in LDS.
 __global__ __launch_bounds__(64) void zhqr_wave_kernel(const cplx* Hin, int64_t ld, int n, cplx* w, int* info,
                                                        double dtol) {
     __shared__ cplx h[kZSmall * (kZSmall + 1)];
@@ -321,7 +316,7 @@ __global__ __launch_bounds__(64) void zhqr_wave_kernel(const cplx* Hin, int64_t 
     for (int idx = ln; idx < n * n; idx += 64) h[(idx % n) + (idx / n) * lh] = Hin[(idx % n) + (int64_t)(idx / n) * ld];
     __syncthreads();
     int failed, maxits, steps;
-    zwave_hqr<false, kFast>(h, nullptr, n, w, failed, maxits, steps, -1.0, nullptr, dtol);
+    zwave_hqr<false>(h, nullptr, n, w, failed, maxits, steps, -1.0, nullptr, dtol);
     if (ln == 0) {
         info[0] = failed;
         info[1] = maxits;
@@ -339,7 +334,8 @@ __global__ __launch_bounds__(64) void zhqr_wave_kernel(const cplx* Hin, int64_t 
 // spike is reduced back to Hessenberg form by complex Householder reflectors (ZLARFG convention,
 // accumulated into V), the window and the new spike are written back, and the caller applies V to
 // the rows of the block above the window (H[l:kw, kw:kw+nw] V).  w[kw + i] = S(i, i): the
-// deflated eigenvalues are final, the undeflated ones are the next sweep's shifts.
+// deflated eigenvalues are final.  The factorisation stops at the first eigenvalue that does not
+// deflate (zwave_hqr's early stop), so the next sweep's shifts come from the trailing block.
 // info = {fail, deflated, iterations, undeflated, steps}.
 struct ZAedCtl {
     cplx tau, spike;
@@ -357,22 +353,14 @@ __device__ __forceinline__ cplx quad_sum(cplx sq, int q) {   // (s0 + s1) + (s2 
     const cplx o2{__shfl_xor(pr.re, 2, 64), __shfl_xor(pr.im, 2, 64)};
     return (q & 2) ? add(o2, pr) : add(pr, o2);
 }
-// Concurrent shifts (round 5, as francis.hip's ShiftJob): workgroup 1 of the launch copies the
-// pre-AED trailing ns x ns block [kb, kb + ns) into its LDS, raises flag = epoch, and computes its
-// eigenvalues on one wave while workgroup 0 runs the AED; workgroup 0 writes the window back only
-// after the flag.
-struct ZShiftJob {
-    int kb, ns;
-    double dtol;
-    cplx* w;
-    int* info;            // {fail, most sweeps per deflation, -, wait timed out}
-    unsigned* flag;
-    unsigned epoch;
-};
-
-template <bool kFast>
+// Concurrent shifts (round 5, as francis.hip's ShiftJob: a second workgroup of the launch solving
+// the pre-AED trailing block for the next sweep's shifts) were measured and removed: a launch ends
+// with its slower workgroup, and the 64 x 64 complex shift QR (~2.5 ms) outlasts the AED (~1 ms),
+// so every AED - also the 70 % after which the sweep is skipped - waited for it: 4096^2 1.569 s ->
+// 2.285 s (used only when the AED deflates nothing: same 122 sweeps, bitwise the same eigenvalues),
+// 2.085 s (also after a deflation, 131 sweeps).
 __global__ __launch_bounds__(kZAedThreads) void zaed_kernel(cplx* Hg, int64_t n, int kw, int nw, int spike_valid,
-                                                            int early, cplx* w, cplx* Vout, int* info, ZShiftJob sj) {
+                                                            cplx* w, cplx* Vout, int* info) {
     constexpr int lh = kZSmall + 1;
     constexpr int NT = kZAedThreads;
     __shared__ cplx t[kZSmall * lh];
@@ -381,21 +369,6 @@ __global__ __launch_bounds__(kZAedThreads) void zaed_kernel(cplx* Hg, int64_t n,
     __shared__ cplx sp[kZSmall];
     __shared__ ZAedCtl c;
     const int tid = threadIdx.x, ln = tid & 63, wv0 = tid < 64;
-    if (blockIdx.x == 1) {   // the concurrent shifts
-        const int ns = sj.ns;
-        for (int e = tid; e < ns * ns; e += NT) t[(e % ns) + (e / ns) * lh] = Hg[(sj.kb + e % ns) + (int64_t)(sj.kb + e / ns) * n];
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(sj.flag, sj.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        if (wv0) {
-            int fail, maxsw, steps;
-            zwave_hqr<false, kFast>(t, nullptr, ns, sj.w, fail, maxsw, steps, -1.0, nullptr, sj.dtol);
-            if (ln == 0) {
-                sj.info[0] = fail;
-                sj.info[1] = maxsw;
-            }
-        }
-        return;
-    }
     const int grp = tid >> 2, q = tid & 3;   // 64 groups of four lanes
     auto T = [&](int i, int j) -> cplx& { return t[i + j * lh]; };
     auto V = [&](int i, int j) -> cplx& { return v[i + j * lh]; };
@@ -408,22 +381,10 @@ __global__ __launch_bounds__(kZAedThreads) void zaed_kernel(cplx* Hg, int64_t n,
     __syncthreads();
     if (wv0) {
         int fail, maxsw, steps, stop = -1;
-        zwave_hqr<true, kFast>(t, v, nw, w + kw, fail, maxsw, steps, early ? cabs1(spike) : -1.0, &stop);
-        // spike test, one window row per lane; deflated = the trailing run of negligible entries
-        const double ulp = 2.220446049250313e-16, smlnum = 2.2250738585072014e-308 * ((double)nw / ulp);
-        int nd = 0;
-        if (early) {
-            nd = fail ? 0 : nw - 1 - stop;   // the spike test ran inside the factorisation
-        } else if (!fail) {
-            bool keep = false;
-            if (ln < nw) {
-                double foo = cabs1(T(ln, ln));
-                if (foo == 0.0) foo = cabs1(spike);
-                keep = cabs1(spike) * cabs1(V(0, ln)) > fmax(smlnum, ulp * foo);
-            }
-            const unsigned long long km = __ballot(keep);
-            nd = km ? nw - 1 - (63 - __clzll(km)) : nw;
-        }
+        zwave_hqr<true>(t, v, nw, w + kw, fail, maxsw, steps, cabs1(spike), &stop);
+        // deflated = the trailing run of negligible spike entries (the spike test ran inside the
+        // factorisation, which stopped at the first eigenvalue that failed it)
+        const int nd = fail ? 0 : nw - 1 - stop;
         if (ln == 0) {
             c.fail = fail;
             c.maxsw = maxsw;
@@ -509,20 +470,6 @@ __global__ __launch_bounds__(kZAedThreads) void zaed_kernel(cplx* Hg, int64_t n,
         c.spike = cplx{0.0, 0.0};
     }
     __syncthreads();
-    if (gridDim.x > 1) {   // the concurrent shifts' copy is taken before the write-back (bounded wait)
-        if (tid == 0) {
-            int timed_out = 0;
-            if (nd > 0) {
-                const long long t0 = wall_clock64();
-                while (__hip_atomic_load(sj.flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != sj.epoch) {
-                    if (wall_clock64() - t0 > 100000000ll) { timed_out = 1; break; }
-                    __builtin_amdgcn_s_sleep(2);
-                }
-            }
-            sj.info[3] = timed_out;
-        }
-        __syncthreads();
-    }
     if (nd > 0) {
         for (int e = tid; e < nw * nw; e += NT) {
             const int i = e % nw, j = e / nw;
@@ -672,13 +619,7 @@ __global__ __launch_bounds__(1024) void zchase_kernel(ZChaseBatch b) {
 }
 
 // Delayed window updates.  left: H(s:s+W, cols) <- U^H H(s:s+W, cols) for the columns [lo, hi);
-// right: H(rows, s:s+W) <- H(rows, s:s+W) U for the rows [lo, hi).  8 output columns (rows) per
-// workgroup of 128 threads; U and the panel staged in LDS, each thread a 4 x 1 register tile of
-// the output (the LDS pitches keep a wave's 16-byte reads on distinct banks).  The regions are a
-// few hundred columns, so narrow workgroups are what spreads a launch over the CUs: 32 columns per
-// workgroup 0.436 s, 16: 0.39 s, 8: 0.37 s for the 1024^2 complex QR.
-constexpr int kZG = 8;   // output columns (left) / rows (right) per workgroup
-constexpr int kZB = kZG / 8;   // register-tile columns per thread
+// right: H(rows, s:s+W) <- H(rows, s:s+W) U for the rows [lo, hi).
 struct ZWinGemm {
     int s, W;          // window rows/columns [s, s + W)
     int64_t lo, hi;    // left: columns [lo, hi); right: rows [lo, hi)
@@ -691,69 +632,8 @@ struct ZWinGemmBatch {   // left regions of different windows own disjoint rows,
     int nw;
     ZWinGemm w[kZMaxGroups];
 };
-template <bool kLeft>
-__global__ __launch_bounds__(128) void zwin_gemm_kernel(ZWinGemmBatch bt) {
-    int g = 0;
-#pragma unroll
-    for (int q = 1; q < kZMaxGroups; ++q)
-        if (q < bt.nw && (int)blockIdx.x >= bt.w[q].blk0) g = q;
-    cplx* H = bt.H;
-    const int64_t n = bt.n;
-    const int s = bt.w[g].s, W = bt.w[g].W;
-    const int64_t lo = bt.w[g].lo, hi = bt.w[g].hi;
-    const cplx* U = bt.w[g].U;
-    constexpr int LU = kZWin + 1;    // U pitch
-    constexpr int LX = kZWin + 1;    // panel pitch
-    __shared__ cplx us[kZWin * LU];
-    __shared__ cplx xs[kZG * LX];
-    const int tid = threadIdx.x;
-    const int64_t b0 = lo + (int64_t)(blockIdx.x - bt.w[g].blk0) * kZG;
-    const int nb = (int)std::min<int64_t>(kZG, hi - b0);
-    for (int idx = tid; idx < W * W; idx += 128) us[(idx % W) + (idx / W) * LU] = U[idx];
-    if (kLeft) {   // xs[r + c LX] = H(s + r, b0 + c)
-        for (int idx = tid; idx < W * kZG; idx += 128) {
-            const int r = idx % W, c = idx / W;
-            xs[r + c * LX] = c < nb ? H[(s + r) + (b0 + c) * n] : cplx{0.0, 0.0};
-        }
-    } else {       // xs[r + c LX] = H(b0 + c, s + r)  (row c of the block, transposed)
-        for (int idx = tid; idx < W * kZG; idx += 128) {
-            const int c = idx % kZG, r = idx / kZG;
-            xs[r + c * LX] = c < nb ? H[(b0 + c) + (int64_t)(s + r) * n] : cplx{0.0, 0.0};
-        }
-    }
-    __syncthreads();
-    // output tile: 4 window indices (i0 + 16 a) x 4 block columns/rows (c0 + 8 b)
-    const int i0 = tid & 15, c0 = tid >> 4;   // 16 x 8 threads
-    cplx acc[4][kZB];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < kZB; ++b) acc[a][b] = cplx{0.0, 0.0};
-    for (int r = 0; r < W; ++r) {
-        cplx uu[4], xx[kZB];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) uu[a] = kLeft ? us[r + (i0 + 16 * a) * LU] : us[r + (i0 + 16 * a) * LU];
-#pragma unroll
-        for (int b = 0; b < kZB; ++b) xx[b] = xs[r + (c0 + 8 * b) * LX];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < kZB; ++b)
-                acc[a][b] = add(acc[a][b], kLeft ? cmul_conj(uu[a], xx[b]) : mul(xx[b], uu[a]));
-    }
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < kZB; ++b) {
-            const int i = i0 + 16 * a, c = c0 + 8 * b;
-            if (i < W && c < nb) {
-                if (kLeft) H[(s + i) + (b0 + c) * n] = acc[a][b];          // (U^H X)(i, c)
-                else H[(b0 + c) + (int64_t)(s + i) * n] = acc[a][b];       // (X U)(c, i)
-            }
-        }
-}
-
-// The same delayed updates on the fp64 matrix cores (v_mfma_f64_16x16x4_f64): a complex tile
+// On the fp64 matrix cores (v_mfma_f64_16x16x4_f64; the VALU kernel that preceded this one, 8 output
+// columns per 128-thread workgroup, was removed): a complex tile
 // product is four real ones on split re/im planes.  64 output columns (left) / rows (right) per
 // workgroup of 4 waves, each wave a 16-wide strip against the window's 4 row tiles; U (and the
 // left panel) staged in LDS as re/im planes at a pitch of kZWin + 2 (the real kernel's
@@ -898,10 +778,11 @@ __global__ void zdiag_sub_kernel(const cplx* H, int64_t n, int ihi, cplx* out) {
 
 static double cabs1_h(const cplx& a) { return std::fabs(a.re) + std::fabs(a.im); }
 
-// AED window (EIGSOL_ZQR_AED overrides, 0: off).  Early-stop AED, 32 bulges in 4 chains: window
+// AED window.  Early-stop AED, 32 bulges in 4 chains: window
 // 32 / 48 / 64 at 1024^2 0.292 / 0.287 / 0.320 s; 48 vs 64 at 4096^2 2.65 / 2.75 s.  Without the
-// AED: 1024^2 0.37-0.42 s, 4096^2 4.4 s; the full-Schur AED (EIGSOL_ZQR_AED_FULL=1) 0.54 / 4.4 s.
-static constexpr int kZAedDefault = 48;
+// AED: 1024^2 0.37-0.42 s, 4096^2 4.4 s; an AED over the window's whole Schur form (LAPACK's, the
+// undeflated eigenvalues becoming the shifts) 0.54 / 4.4 s.  Both were removed.
+static constexpr int kZAedWin = 48;
 
 // eigenvalues of the complex Hessenberg matrix H (device, n x n, leading dimension n; destroyed)
 int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_host, int32_t* sweeps_out,
@@ -918,21 +799,11 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
     cplx* dV = nullptr;   // the AED window's unitary factor
     if (rc == EIGSOL_OK && hipMalloc(&dV, (size_t)dev::kZSmall * dev::kZSmall * sizeof(cplx)) != hipSuccess)
         rc = fail(EIGSOL_E_HIP, "complex QR: hipMalloc");
-    cplx* dsw = nullptr;       // concurrent shifts
-    int* dsinfo = nullptr;
-    unsigned* dflag = nullptr;
-    unsigned flag_epoch = 0;
-    if (rc == EIGSOL_OK && (hipMalloc(&dsw, dev::kZSmall * sizeof(cplx)) != hipSuccess || hipMalloc(&dsinfo, 64) != hipSuccess ||
-                            hipMalloc(&dflag, 64) != hipSuccess || hipMemsetAsync(dflag, 0, 64, st) != hipSuccess))
-        rc = fail(EIGSOL_E_HIP, "complex QR: hipMalloc");
     // every per-sweep transfer goes through pinned host memory: a pageable hipMemcpyAsync is staged
     // by the runtime and waited for with a sleeping wait, ~1 ms per copy (round-4 kernel trace of
     // 4096^2: 1.12 s of 2.8 s idle after such copies, tools/gap_analysis.py)
     struct Staging {
         int info[8];
-        int cinfo[4];
-        cplx aw[dev::kZSmall];
-        cplx cw[dev::kZSmall];   // concurrent shifts
         cplx sh[2 * dev::kZMaxBulges];
     };
     Staging* hp = nullptr;
@@ -940,38 +811,17 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
     if (rc == EIGSOL_OK && (hipHostMalloc(&hp, sizeof(Staging), hipHostMallocDefault) != hipSuccess ||
                             hipHostMalloc(&ds, 2 * n * sizeof(cplx), hipHostMallocDefault) != hipSuccess))
         rc = fail(EIGSOL_E_HIP, "complex QR: hipHostMalloc");
-    cplx* const aw = hp ? hp->aw : nullptr;
     int sweeps = 0, failed = 0, stall = 0;
-    int st_sweeps = 0, st_aed = 0, st_aed_defl = 0, st_small = 0, st_conc = 0;
-    // concurrent shifts (EIGSOL_ZQR_CONC): 0 off (default), 1 when the AED deflates nothing (bitwise
-    // the sequential sweeps), 2 also after a deflation (the pre-AED block's spectrum without the
-    // deflated eigenvalues, LAPACK xLAQR0's undeflated shifts).  Measured and left off (round 5,
-    // tools/zqr_conc_ab.sh, 4096^2): a launch ends with its slower workgroup, and the 64 x 64
-    // complex shift QR (~2.5 ms) outlasts the AED (~1 ms), so every AED - also the 70 % after which
-    // the sweep is skipped - waits for it: 1.569 s -> 2.285 s (mode 1, same 122 sweeps, bitwise the
-    // same eigenvalues), 2.085 s (mode 2, 131 sweeps)
-    static const int conc_mode = [] {
-        const char* e = std::getenv("EIGSOL_ZQR_CONC");
-        return e ? std::atoi(e) : 0;
-    }();
+    int st_sweeps = 0, st_aed = 0, st_aed_defl = 0, st_small = 0;
     static const bool stats = std::getenv("EIGSOL_QR_STATS") != nullptr;
-    // the one-wave QR's step (zwave_hqr kFast, EIGSOL_ZQR_STEP): 1 loads ahead and takes the scaled
-    // reflector (default), 0 the round-5 step
-    static const bool fast_step = [] {
-        const char* e = std::getenv("EIGSOL_ZQR_STEP");
-        return !(e && !std::strcmp(e, "0"));
-    }();
     int ihi = (int)n - 1;
     const int max_stall = std::max(1, maxits);
-    // the shifts' QR splits at a looser relative subdiagonal than the eigenvalues' (EIGSOL_ZQR_SHIFT_TOL;
-    // the real path's round-4 grid, francis.hip, put its optimum at 1e-4)
-    static const double shift_tol = [] {
-        const char* e = std::getenv("EIGSOL_ZQR_SHIFT_TOL");
-        return e ? std::max(2.220446049250313e-16, std::atof(e)) : 2.220446049250313e-16;
-    }();
+    // the shifts' QR splits at the eigenvalues' own relative subdiagonal (the real path's round-4
+    // grid, francis.hip, put its optimum at a looser 1e-4; not adopted here)
+    constexpr double shift_tol = 2.220446049250313e-16;
     auto small = [&](int l, int hi, cplx* wdst, int info[2], double dtol = 2.220446049250313e-16) -> int {
-        hipLaunchKernelGGL(fast_step ? dev::zhqr_wave_kernel<true> : dev::zhqr_wave_kernel<false>, dim3(1), dim3(64), 0,
-                           st, H + l + (int64_t)l * n, (int64_t)n, hi - l + 1, wdst, dinfo, dtol);
+        hipLaunchKernelGGL(dev::zhqr_wave_kernel, dim3(1), dim3(64), 0, st, H + l + (int64_t)l * n, (int64_t)n,
+                           hi - l + 1, wdst, dinfo, dtol);
         EIGSOL_HIP(hipMemcpyAsync(hp->info, dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
         EIGSOL_HIP(stream_wait(st));
         info[0] = hp->info[0];
@@ -1010,86 +860,33 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
         // up to 32 bulges per sweep (64 shifts) in C chains of at most 8 (a chain's 3 nb rows must
         // leave its 64-row window room to advance), the chains chased concurrently in disjoint
         // windows.  With the AED (round 3) 32 bulges in 4 chains beat 16 in 2: 1024^2 0.31 -> 0.29 s,
-        // 2048^2 0.93 -> 0.77 s, 4096^2 3.28 -> 2.65 s (tools/qr_ab_round3.sh)
-        static const int max_nb = [] {
-            const char* e = std::getenv("EIGSOL_ZQR_NB");
-            return e ? std::max(1, std::min(dev::kZMaxBulges, std::atoi(e))) : 32;
-        }();
-        static const int max_groups = [] {
-            const char* e = std::getenv("EIGSOL_ZQR_GROUPS");
-            return e ? std::max(1, std::min(dev::kZMaxGroups, std::atoi(e))) : 4;
-        }();
-        // aggressive early deflation on the trailing window; its undeflated eigenvalues are the shifts
-        static const int aed_win = [] {
-            const char* e = std::getenv("EIGSOL_ZQR_AED");   // AED window (0: off)
-            return e ? std::max(0, std::min(dev::kZSmall, std::atoi(e))) : kZAedDefault;
-        }();
-        static const int nibble = [] {   // % of the window deflated that skips the sweep (LAPACK's NIBBLE)
-            const char* e = std::getenv("EIGSOL_ZQR_NIBBLE");
-            return e ? std::max(1, std::atoi(e)) : 14;
-        }();
-        // EIGSOL_ZQR_AED_FULL=1: the window's whole Schur form (LAPACK's AED, the undeflated
-        // eigenvalues become the shifts); default: early stop at the first undeflatable eigenvalue,
-        // shifts from the trailing block afterwards
-        static const bool aed_full = [] {
-            const char* e = std::getenv("EIGSOL_ZQR_AED_FULL");
-            return e && std::atoi(e) != 0;
-        }();
+        // 2048^2 0.93 -> 0.77 s, 4096^2 3.28 -> 2.65 s
+        constexpr int max_nb = 32, max_groups = 4;
+        // aggressive early deflation on the trailing window, stopped at the first undeflatable
+        // eigenvalue; the shifts come from the trailing block afterwards
+        constexpr int aed_win = kZAedWin;
+        constexpr int nibble = 14;   // % of the window deflated that skips the sweep (LAPACK's NIBBLE)
         // bulges of a sweep on an active block of Nact rows (C chains of nbg): the shift count 2 nb
-        auto plan = [&](int Nact, int cap, int& C, int& nbg) {
-            int nb = std::min(max_nb, std::max(1, Nact / 16));
-            if (cap >= 2) nb = std::min(nb, cap / 2);
+        auto plan = [&](int Nact, int& C, int& nbg) {
+            const int nb = std::min(max_nb, std::max(1, Nact / 16));
             C = std::max(1, std::min({max_groups, (nb + 7) / 8, 1 + Nact / (4 * (dev::kZWin + 12))}));
             nbg = std::max(1, std::min(8, nb / C));
             return nbg * C;
         };
-        int m_aed = 0;
-        int conc_n = 0;            // candidate shifts from the concurrent workgroup (in hp->cw)
-        if (aed_win >= 4) {
+        {
             const int nw = std::min(aed_win, N);
             const int kw = ihi - nw + 1;
-            int C0, nbg0;
-            const int ns0 = 2 * plan(N, 0, C0, nbg0);   // the shift block if the AED deflates nothing
-            const bool conc = conc_mode > 0 && !aed_full && ns0 >= 2 && ns0 <= dev::kZSmall;
-            dev::ZShiftJob sj{ihi - ns0 + 1, ns0, shift_tol, dsw, dsinfo, dflag, ++flag_epoch};
-            hipLaunchKernelGGL(fast_step ? dev::zaed_kernel<true> : dev::zaed_kernel<false>, dim3(conc ? 2 : 1),
-                               dim3(dev::kZAedThreads), 0, st, H, (int64_t)n, kw, nw,
-                               kw > l ? 1 : 0, aed_full ? 0 : 1, dw, dV, dinfo, sj);
+            hipLaunchKernelGGL(dev::zaed_kernel, dim3(1), dim3(dev::kZAedThreads), 0, st, H, (int64_t)n, kw, nw,
+                               kw > l ? 1 : 0, dw, dV, dinfo);
             int* info = hp->info;
             if (hipMemcpyAsync(info, dinfo, 5 * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipMemcpyAsync(aw, dw + kw, nw * sizeof(cplx), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                (conc && (hipMemcpyAsync(hp->cinfo, dsinfo, 4 * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                          hipMemcpyAsync(hp->cw, dsw, ns0 * sizeof(cplx), hipMemcpyDeviceToHost, st) != hipSuccess)) ||
                 stream_wait(st) != hipSuccess) {
                 rc = fail(EIGSOL_E_HIP, "complex QR: aed");
                 break;
             }
             ++st_aed;
-            const bool conc_ok = conc && !hp->cinfo[0] && !hp->cinfo[3];
-            if (conc_ok && !info[0] && info[1] == 0) conc_n = ns0;   // pre-AED block = post-AED block
-            if (conc_ok && conc_mode > 1 && !info[0] && info[1] > 0 && ns0 >= nw) {
-                // the deflated eigenvalues (bottom of the window) removed from the block's spectrum by
-                // nearest match; the rest keep their order
-                const int nd = info[1];
-                std::vector<int> used(ns0, 0);
-                for (int j = nw - nd; j < nw; ++j) {
-                    int best = -1;
-                    double bd = 0.0;
-                    for (int i = 0; i < ns0; ++i) {
-                        if (used[i]) continue;
-                        const double d = std::hypot(hp->cw[i].re - aw[j].re, hp->cw[i].im - aw[j].im);
-                        if (best < 0 || d < bd) { best = i; bd = d; }
-                    }
-                    if (best >= 0) used[best] = 1;
-                }
-                int k = 0;
-                for (int i = 0; i < ns0; ++i)
-                    if (!used[i]) hp->cw[k++] = hp->cw[i];
-                conc_n = k;
-            }
             if (!info[0]) {
                 const int nd = info[1];
-                m_aed = aed_full ? info[3] : 0;   // early-stopped windows carry no shifts
                 if (nd > 0) {
                     st_aed_defl += nd;
                     if (kw > l) {   // rows of the block above the window: H[l, kw) x [kw, kw + nw) V
@@ -1108,31 +905,14 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
         }
         const int Nact = ihi - l + 1;   // after the AED's deflations
         int C, nbg;
-        int nb = plan(Nact, m_aed >= 2 ? m_aed : (conc_n >= 2 ? conc_n : 0), C, nbg);
+        const int nb = plan(Nact, C, nbg);
         const int ns = 2 * nb;
         cplx* const sh = hp->sh;   // ns values; the chase reads them from dsh
         // every 6th sweep without a deflation: exceptional shifts (LAPACK's KEXSH; stall is 0 right
-        // after the AED deflated, and such a sweep takes the regular shifts).  EIGSOL_ZQR_EXC_LEGACY=1:
-        // round 3's test, which also took stall == 0 (ad hoc shifts after every partial deflation)
-        static const bool exc_legacy = [] {
-            const char* e = std::getenv("EIGSOL_ZQR_EXC_LEGACY");
-            return e && std::atoi(e) != 0;
-        }();
-        bool exceptional = exc_legacy ? stall % 6 == 0 : (stall > 0 && stall % 6 == 0);
-        if (!exceptional && m_aed >= 2) {   // the bottom undeflated eigenvalues of the AED window
-            for (int i = 0; i < ns; ++i) sh[i] = aw[m_aed - ns + i];
-            if (hipMemcpyAsync(dsh, sh, ns * sizeof(cplx), hipMemcpyHostToDevice, st) != hipSuccess) {
-                rc = fail(EIGSOL_E_HIP, "complex QR: shift upload");
-                break;
-            }
-        } else if (!exceptional && conc_n >= ns) {   // the concurrent workgroup's (bottom ns of them)
-            for (int i = 0; i < ns; ++i) sh[i] = hp->cw[conc_n - ns + i];
-            ++st_conc;
-            if (hipMemcpyAsync(dsh, sh, ns * sizeof(cplx), hipMemcpyHostToDevice, st) != hipSuccess) {
-                rc = fail(EIGSOL_E_HIP, "complex QR: shift upload");
-                break;
-            }
-        } else if (!exceptional) {
+        // after the AED deflated, and such a sweep takes the regular shifts; round 3's test also took
+        // stall == 0, i.e. ad hoc shifts after every partial deflation: a bug, fixed in round 4)
+        bool exceptional = stall > 0 && stall % 6 == 0;
+        if (!exceptional) {
             int info[2];
             if ((rc = small(ihi - ns + 1, ihi, dsh, info, shift_tol)) != EIGSOL_OK) break;   // shifts written to dsh
             if (info[0]) exceptional = true;
@@ -1187,12 +967,8 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
             if (rc != EIGSOL_OK) break;
             hipLaunchKernelGGL(dev::zchase_kernel, dim3(nwin), dim3(1024), 0, st, cb);
             // delayed updates: every left region, then every right region (U_a^H X U_b = (U_a^H X) U_b)
-            // on the matrix cores by default; EIGSOL_ZGEMM_VALU=1: the VALU kernel (8-column workgroups)
-            static const bool valu = [] {
-                const char* e = std::getenv("EIGSOL_ZGEMM_VALU");
-                return e && std::atoi(e) != 0;
-            }();
-            const int per = valu ? dev::kZG : dev::kZMG;
+            // on the matrix cores
+            constexpr int per = dev::kZMG;
             dev::ZWinGemmBatch lb{H, (int64_t)n, 0, {}}, rb{H, (int64_t)n, 0, {}};
             int nlb = 0, nrb = 0;
             for (int q = 0; q < nwin; ++q) {
@@ -1207,13 +983,8 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
                     nrb += (w.s - l + per - 1) / per;
                 }
             }
-            if (valu) {
-                if (nlb > 0) hipLaunchKernelGGL(dev::zwin_gemm_kernel<true>, dim3(nlb), dim3(128), 0, st, lb);
-                if (nrb > 0) hipLaunchKernelGGL(dev::zwin_gemm_kernel<false>, dim3(nrb), dim3(128), 0, st, rb);
-            } else {
-                if (nlb > 0) hipLaunchKernelGGL(dev::zwin_gemm_mfma<true>, dim3(nlb), dim3(dev::kZMT), 0, st, lb);
-                if (nrb > 0) hipLaunchKernelGGL(dev::zwin_gemm_mfma<false>, dim3(nrb), dim3(dev::kZMT), 0, st, rb);
-            }
+            if (nlb > 0) hipLaunchKernelGGL(dev::zwin_gemm_mfma<true>, dim3(nlb), dim3(dev::kZMT), 0, st, lb);
+            if (nrb > 0) hipLaunchKernelGGL(dev::zwin_gemm_mfma<false>, dim3(nrb), dim3(dev::kZMT), 0, st, rb);
             t0 = t1;
         }
         if (hipGetLastError() != hipSuccess) { rc = fail(EIGSOL_E_HIP, "complex QR: launch"); break; }
@@ -1232,10 +1003,9 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
             rc = fail(EIGSOL_E_HIP, "complex QR: download");
     }
     if (stats)
-        std::fprintf(stderr, "complex francis: n=%lld sweeps=%d small_blocks=%d aed=%d aed_deflated=%d conc_shifts=%d\n",
-                     (long long)n, st_sweeps, st_small, st_aed, st_aed_defl, st_conc);
-    for (void* p : {(void*)dw, (void*)dds, (void*)dU, (void*)dsh, (void*)dinfo, (void*)dV, (void*)dsw, (void*)dsinfo,
-                    (void*)dflag})
+        std::fprintf(stderr, "complex francis: n=%lld sweeps=%d small_blocks=%d aed=%d aed_deflated=%d\n",
+                     (long long)n, st_sweeps, st_small, st_aed, st_aed_defl);
+    for (void* p : {(void*)dw, (void*)dds, (void*)dU, (void*)dsh, (void*)dinfo, (void*)dV})
         if (p) (void)hipFree(p);
     if (ds) (void)hipHostFree(ds);
     if (hp) (void)hipHostFree(hp);

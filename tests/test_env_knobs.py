@@ -1,0 +1,86 @@
+"""The EIGSOL_* environment variables the sources read are exactly the ones INTEGRATION.md §4 lists."""
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "pcsc_eigenvalue_solver_project_amd")
+QUOTED = re.compile(r'"(EIGSOL_[A-Z0-9_]+)"')
+KEPT_UNTESTED = ("diagnostic", "profiling", "operational")
+MAX_KNOBS = 62   # the library read 116 before the rejected variants' switches and the tuning values went
+
+
+def _quoted_names(paths):
+    names = set()
+    for path in paths:
+        with open(path, encoding="utf-8") as f:
+            names.update(QUOTED.findall(f.read()))
+    return names
+
+
+def _files(top, suffixes, recurse=True):
+    out = []
+    for d, dirs, fs in os.walk(top):
+        if not recurse:
+            dirs[:] = []
+        dirs[:] = [x for x in dirs if x != "build"]
+        out += [os.path.join(d, f) for f in fs if f.endswith(suffixes)]
+    return out
+
+
+def _library_names():
+    return _quoted_names(_files(os.path.join(PKG, "csrc"), (".hip", ".cpp", ".hpp")))
+
+
+def _names_read_elsewhere():
+    """The same search over the public headers and the Python package (EIGSOL_DEVICE, EIGSOL_LIB_PATH)."""
+    return _quoted_names(_files(os.path.join(ROOT, "include"), (".h", ".hpp")) + _files(PKG, (".py",), recurse=False))
+
+
+def _table():
+    """{name: last cell} of the rows of the §4 table."""
+    with open(os.path.join(ROOT, "INTEGRATION.md"), encoding="utf-8") as f:
+        text = f.read()
+    sec = text[text.index("## 4. Environment knobs"):]
+    nxt = re.search(r"^## ", sec[3:], re.M)
+    if nxt:
+        sec = sec[:3 + nxt.start()]
+    rows = {}
+    for line in sec.splitlines():
+        if not line.startswith("| `EIGSOL_"):
+            continue
+        cells = [c.strip() for c in re.split(r"(?<!\\)\|", line.strip().strip("|"))]
+        names = re.findall(r"`(EIGSOL_[A-Z0-9_]+)`", cells[0])
+        assert len(names) == 1 and len(cells) == 4, line
+        assert names[0] not in rows, f"{names[0]} has two rows"
+        rows[names[0]] = cells[3]
+    return rows
+
+
+def test_table_lists_exactly_the_names_the_sources_read():
+    lib, elsewhere, table = _library_names(), _names_read_elsewhere(), set(_table())
+    assert lib, "no getenv names found: the search is broken"
+    assert table - elsewhere == lib - elsewhere, (sorted(table - lib - elsewhere), sorted(lib - table))
+    assert elsewhere - lib <= table, sorted(elsewhere - lib - table)
+
+
+def test_every_library_name_is_passed_to_getenv():
+    src = "".join(open(p, encoding="utf-8").read() for p in _files(os.path.join(PKG, "csrc"), (".hip", ".cpp", ".hpp")))
+    for name in _library_names():
+        assert f'getenv("{name}")' in src, name
+
+
+def test_rows_cite_an_existing_test_that_mentions_the_name():
+    for name, cell in _table().items():
+        cited = re.findall(r"`(tests/[\w/]+\.py)", cell)
+        if not cited:
+            assert cell.startswith(KEPT_UNTESTED), (name, cell)
+            continue
+        for rel in cited:
+            path = os.path.join(ROOT, rel)
+            assert os.path.isfile(path), (name, rel)
+            with open(path, encoding="utf-8") as f:
+                assert re.search(rf"\b{name}\b", f.read()), (name, rel)
+
+
+def test_knob_count_does_not_grow_back():
+    assert len(_library_names()) <= MAX_KNOBS

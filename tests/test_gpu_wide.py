@@ -462,8 +462,8 @@ def test_wide_francis_split_and_triangular(ctx):
 
 @pytest.mark.parametrize("k", [3, 20, 40])
 def test_wide_power_fused_group_widths(ctx, k):
-    """The one-pass double-double power iteration (power_fused_kernel) picks 4 / 16 / 32 lanes per row
-    from the mean row length: uniform matrices of 3, 20 and 40 entries per row, with 50 empty rows
+    """The one-pass double-double power iteration (power_fused2_kernel) picks 2 to 32 lanes per row
+    from the mean row length (more lanes above 5, 20, 48 and 96 entries): uniform matrices of 3, 20 and 40 entries per row, with 50 empty rows
     and one 3000-entry row, against the x87 oracle (lambda within 1e-17 (1 + |lambda|), equal
     iteration counts, the same eigenvector)."""
     n = 20000

@@ -8,5 +8,5 @@ run() { echo "== $*" >> $OUT; env "$@" timeout -k 10 120 python -u tools/mf_prob
 if [ $# -gt 0 ]; then for cfg in "$@"; do run $cfg; done; exit 0; fi
 run EIGSOL_MF_BACKOFF=0
 run EIGSOL_MF_BACKOFF=2
-run EIGSOL_MF_BACKOFF=2 EIGSOL_MF_BIG_NS=64 EIGSOL_MF_BIG_D=256
-run EIGSOL_MF_BACKOFF=2 EIGSOL_MF_BIG_NS=48 EIGSOL_MF_BIG_D=192
+run EIGSOL_MF_BACKOFF=2 EIGSOL_MF_BIG_NS=64
+run EIGSOL_MF_BACKOFF=2 EIGSOL_MF_BIG_NS=48

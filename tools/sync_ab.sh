@@ -8,7 +8,6 @@ for v in 0 1; do
   EIGSOL_SYNC_SPIN=$v timeout -k 10 120 python -u tools/bench_qr.py 4096 > gpurun_out/sync_ab/qr_$v.log 2>&1
   EIGSOL_SYNC_SPIN=$v timeout -k 10 120 python -u tools/bench_qrc.py 4096 > gpurun_out/sync_ab/qrc_$v.log 2>&1
   EIGSOL_SYNC_SPIN=$v timeout -k 10 200 python -u tools/gmres_warm_ab.py > gpurun_out/sync_ab/gmres_$v.log 2>&1
-  EIGSOL_GMRES_WARM=0 EIGSOL_SYNC_SPIN=$v timeout -k 10 200 python -u tools/gmres_warm_ab.py > gpurun_out/sync_ab/gmres_cold_$v.log 2>&1
 done
 ROOTD=$(pwd)
 cd /tmp && export TMPDIR=/tmp && cd $ROOTD

@@ -1,6 +1,6 @@
 """Config-5 triangular solve under factor-time knobs: one line per variant.
 
-usage: python tools/trsv_variants.py 'EIGSOL_TRSV_HEAD_ROWS=0' 'EIGSOL_TRSV_BLOCKS_PER_CU=4' ...
+usage: python tools/trsv_variants.py 'EIGSOL_TRSV_HEAD=block' 'EIGSOL_TRSV_TWO=0' ...
 (each argument is a space-separated list of VAR=value applied before the factor is built)."""
 import json, os, sys
 import numpy as np
