@@ -583,6 +583,24 @@ struct EighResult {
     std::int64_t notConverged = 0;     // eigenvectors that failed the inverse iteration's growth test (DC: iteration caps hit)
 };
 
+// General dense eigenpairs (eig, solvers.hpp; no counterpart in the reference): the eigenvalues by the Francis
+// sweeps, the right eigenvectors by inverse iteration on the Hessenberg matrix (eigsol_eig_dense).
+struct EigOptions {
+    int maxIterations = 1000;            // the Francis sweeps' limit (SolverOptions::maxIterations)
+    int batch = 0;                       // eigenvalues resident in one launch; 0: as many as the workspace cap holds
+    bool vectors = true;                 // false: the eigenvalues alone
+    std::vector<std::int64_t> select;    // indices into eigenvalues, in the order of the columns wanted; empty: all
+};
+
+template <typename S>
+struct EigResult {
+    std::vector<std::complex<double>> eigenvalues;       // all n, in qr_eigenvalues' Francis order
+    DenseMatrix<std::complex<double>> eigenvectors;      // n x m, unit columns, largest-modulus component real positive
+    int iterations = 0;                                  // the sweeps', as QRResult reports them
+    bool converged = false;
+    std::int64_t notConverged = 0;                       // eigenvalues no start vector passed the growth test for
+};
+
 template <typename S>
 struct QRResult {
     Vector<S> eigenvalues;

@@ -513,6 +513,43 @@ template <ScalarConcept S>
 std::vector<double> eigvalsh(const DenseMatrix<S>& A, const DenseMatrix<S>& B, const EighOptions& opts = {}) {
     return detail::eigh_run<S>(A, opts, false, "eigvalsh", &B).eigenvalues;
 }
+// ------------------------------------------------------------------------------------------- eig
+// Eigenvalues and right eigenvectors of a general dense matrix (eigsol_eig_dense: blocked Hessenberg reduction,
+// the Francis sweeps of qr_eigenvalues on a copy of H, inverse iteration on H, back-transformation).
+// S = double and std::complex<double>; the vectors are complex for both.  Column j of eigenvectors belongs
+// to eigenvalues[select[j]] (eigenvalues[j] without a selection); a selection returns the full call's bits.
+template <ScalarConcept S>
+EigResult<S> eig(const DenseMatrix<S>& A, const EigOptions& opts = {}) {
+    EigResult<S> res;
+    const std::int64_t n = A.rows();
+    if (n != A.cols()) throw std::runtime_error("eig: matrix must be square");
+    if (n == 0) throw std::runtime_error("eig: matrix has zero size");
+    if constexpr (!DeviceScalar<S>) {
+        throw std::runtime_error("eig: scalar type not supported by the device path (double, std::complex<double>)");
+    } else {
+        eigsol_eig_options o;
+        o.max_iterations = opts.maxIterations;
+        o.batch = opts.batch;
+        o.nsel = static_cast<std::int64_t>(opts.select.size());
+        o.sel = opts.select.empty() ? nullptr : opts.select.data();
+        const std::int64_t cap = opts.select.empty() ? n : o.nsel;
+        res.eigenvalues.assign(static_cast<std::size_t>(n), std::complex<double>(0.0, 0.0));
+        DenseMatrix<std::complex<double>> V;
+        if (opts.vectors) V = DenseMatrix<std::complex<double>>(n, cap);
+        std::int64_t m = 0, nc = 0;
+        std::int32_t it = 0, conv = 0;
+        detail::check(eigsol_eig_dense(detail::ctx(), detail::dtype_of<S>(), n, A.data(), &o,
+                                       reinterpret_cast<double*>(res.eigenvalues.data()),
+                                       opts.vectors ? static_cast<void*>(V.data()) : nullptr, &m, &it, &conv, &nc),
+                      "eig");
+        res.iterations = it;
+        res.converged = conv != 0;
+        res.notConverged = nc;
+        if (opts.vectors) res.eigenvectors = std::move(V);
+    }
+    return res;
+}
+
 // L of B = L L^H (eigsol_cholesky_dense): zero strict upper triangle, real positive diagonal.
 template <ScalarConcept S>
 DenseMatrix<S> cholesky(const DenseMatrix<S>& B) {

@@ -486,6 +486,61 @@ int eigsol_eigh_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colma
                       int64_t* not_converged);
 int eigsol_eigh_stage_times(eigsol_ctx* ctx, double* ms4);
 
+/* ---------------------------------------------------------------- general dense eigenpairs
+ * eigsol_eig_dense: the eigenvalues of a general real (EIGSOL_F64) or complex (EIGSOL_C128) dense matrix
+ * and, for all or a selection of them, the right eigenvectors (csrc/eig.hip).  The reference has no such
+ * solver.
+ * Algorithm: the power-of-two range guard of eigsol_qr_eigenvalues_dense; the blocked Hessenberg
+ * reduction with its panels kept (n >= 3; H = A for n <= 2); the Francis sweeps of
+ * eigsol_qr_eigenvalues_dense(EIGSOL_QR_FRANCIS) on a copy of H; every eigenvector by inverse iteration on
+ * H (LAPACK xHSEIN / xLAEIN's scheme), one workgroup per eigenvalue: H splits where h(i+1, i) == 0 exactly,
+ * the vector of an eigenvalue of the block of rows [kl, kr) comes from the partial-pivot LU of
+ * H(0:kr, 0:kr) - lambda I (pivots below eps3 = eps ||H_block||_1 replaced by eps3) and is zero below
+ * row kr; eigenvalues of one block closer than eps3 are moved apart by eps3 for the vector's shift only;
+ * xLAEIN's start vectors on the block's own rows (zero above them), accepted at ||x||_1 >= 0.1 / sqrt(kr),
+ * at most kr - kl starts; x = Q y with the stored panels on the fp64 matrix cores.  A real matrix's real
+ * eigenvalue runs in real arithmetic, a conjugate pair once in complex arithmetic.  No floating-point
+ * atomics and fixed summation orders: two calls return the same bits, and a selection or another batch
+ * size returns the bits of the full call.
+ * Read: A_colmajor (host, n x n, column-major).  opts (NULL: 1000 sweeps, batch 0, all vectors):
+ * max_iterations is the Francis sweeps' limit per deflation (as eigsol_solver_options'); batch > 0 is
+ * the number of eigenvalues resident in one launch (each holds kr (kr + 1) / 2 scalars of U), 0 takes
+ * as many as 32 GiB (or half of the free device memory) hold; sel (NULL: all) lists nsel indices into
+ * w, in the order the columns of V are wanted; selecting one eigenvalue of a real matrix's conjugate
+ * pair does not select the other.
+ * Out: w, n complex eigenvalues as (re, im) pairs (2 n doubles), always all of them.  For
+ * 64 <= n <= 16384 (real) / 8192 (complex) they are bitwise eigsol_qr_eigenvalues_dense's Francis
+ * values in its order; below 64 that entry point reduces with per-reflector kernels and eig with the
+ * blocked ones, so the bits may differ.  V (NULL: eigenvalues only): n x *m_out complex doubles (both
+ * dtypes), column-major with leading dimension n; column j belongs to w[sel[j]] (w[j] without sel), has
+ * unit 2-norm, and its largest-modulus component (the first on ties) is real and positive.  For a real
+ * matrix the vector of a real eigenvalue has imaginary part exactly 0, and the vectors of a conjugate
+ * pair are bitwise conjugates.  iterations / converged (optional): the Francis sweeps', as
+ * eigsol_qr_eigenvalues_dense reports them.  not_converged (optional): eigenvalues whose every start
+ * failed the growth test (their last iterate is returned; expected 0).
+ * Status, decided before any device call: EIGSOL_E_INVALID (n < 0; with n > 0 a null ctx, A, w or m_out;
+ * max_iterations < 1; batch < 0; nsel != 0 without sel; nsel < 0; a selected index outside 0 .. n-1;
+ * unknown dtype), EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD; n above the order the blocked reduction
+ * accepts: 16384 real, 8192 complex).  n == 0: EIGSOL_OK with *m_out = 0.  A non-finite eigenvalue or
+ * entry of H fails with EIGSOL_E_SOLVER.
+ * Out of scope: left eigenvectors and balancing (xGEBAL); the Schur form (no Schur vectors are
+ * accumulated); a basis for a multiple semisimple eigenvalue whose copies land in one unreduced block
+ * of H (xHSEIN's known limit: the vectors returned for it satisfy the residual bound but may be
+ * parallel); single precision and double-double.
+ * eigsol_eig_stage_times: the context's last eigsol_eig_dense call by stream events, 4 doubles in ms:
+ * reduction (guard, Hessenberg, copy), Francis, inverse iteration (with its plan), back-transformation
+ * (with the normalisation and the copy of V to the host); stages that did not run are 0. */
+typedef struct eigsol_eig_options {
+    int32_t max_iterations;
+    int32_t batch;
+    int64_t nsel;
+    const int64_t* sel;
+} eigsol_eig_options;
+int eigsol_eig_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor,
+                     const eigsol_eig_options* opts, double* w, void* V, int64_t* m_out,
+                     int32_t* iterations, int32_t* converged, int64_t* not_converged);
+int eigsol_eig_stage_times(eigsol_ctx* ctx, double* ms4);
+
 /* ---------------------------------------------------------------- Cholesky and A x = lambda B x (dense)
  * eigsol_cholesky_dense: B = L L^H of a real symmetric / complex Hermitian positive definite B
  * (EIGSOL_F64 / EIGSOL_C128; host, n x n, column-major; ONLY the lower triangle is read, and for

@@ -18,6 +18,7 @@ from ._capi import (EIGSOL_C64, EIGSOL_C128, EIGSOL_CDD, EIGSOL_DD, EIGSOL_E_INV
                     EIGSOL_F64, EIGSOL_KRYLOV_LM, EIGSOL_KRYLOV_SHIFT_INVERT, EigSolError, KrylovOptionsC, SolverOptionsC,
                     SubspaceOptionsC, call, check, last_error, lib)
 from ._capi import EIGSOL_EIGH_INDEX, EIGSOL_EIGH_VALUE, EighOptionsC
+from ._capi import EigOptionsC
 
 __all__ = [
     "EigSolError", "SolverOptions", "EigenResult", "Context", "CsrMatrix", "DenseMatrix",
@@ -25,7 +26,7 @@ __all__ = [
     "SubspaceOptions", "SubspaceResult", "subspace_iteration", "spmm", "dense_mm",
     "KrylovOptions", "KrylovResult", "krylov_schur", "krylov_orth", "krylov_rotate",
     "EighResult", "eigh", "eigvalsh", "eigh_stage_times", "tridiag_plan", "eigh_dc_stage_times", "dc_deflate",
-    "cholesky", "geigh_stage_times",
+    "cholesky", "geigh_stage_times", "EigResult", "eig", "eig_stage_times",
 ]
 
 
@@ -878,6 +879,59 @@ def eigh(ctx: Context, A, select=None, B=None, method="stein") -> EighResult:
     the full ``"dc"`` call's columns.  ``EIGSOL_DC_LEAF`` (2 .. 64, default 64) sets the leaf order."""
     w, Z, nc = _eigh_call(ctx, A, select, True, "eigh", B, method)
     return EighResult(w, Z, nc)
+
+
+@dataclass
+class EigResult:
+    """Result of :func:`eig`: ``values`` all n eigenvalues (complex128, :func:`qr_eigenvalues`' Francis order),
+    ``vectors`` n x m complex128 with unit columns (column j belongs to ``values[select[j]]``, or to
+    ``values[j]`` without a selection; its largest-modulus component is real and positive), ``iterations`` /
+    ``converged`` the Francis sweeps' as :class:`QRResult` reports them, ``not_converged`` the eigenvalues
+    whose inverse iteration failed the growth test from every start vector (expected 0)."""
+
+    values: np.ndarray
+    vectors: np.ndarray
+    iterations: int
+    converged: bool
+    not_converged: int
+
+
+def eig(ctx: Context, A, select=None, opts: SolverOptions = SolverOptions(), batch: int = 0) -> EigResult:
+    """Eigenvalues and right eigenvectors of a general dense matrix (float64 / complex128) on the device
+    (``eigsol_eig_dense``): blocked Hessenberg reduction, the Francis sweeps of :func:`qr_eigenvalues` on a
+    copy of H, every eigenvector by inverse iteration on H (LAPACK xHSEIN's scheme, one workgroup per
+    eigenvalue), back-transformed through the reduction's stored reflectors.  ``select``: ``None`` (all) or a
+    sequence of indices into ``values``; a selection returns the bits of the full call's columns.
+    ``opts.maxIterations`` limits the sweeps; ``batch`` > 0 fixes how many eigenvalues are resident at once
+    (0: as many as the workspace cap holds)."""
+    A = _square_dense(A, "eig")
+    code = _dtype_code(A.dtype)
+    n = A.shape[0]
+    Af = np.asfortranarray(A)
+    sel = None
+    if select is not None:
+        sel = np.ascontiguousarray(np.asarray(select, dtype=np.int64).ravel())
+    o = EigOptionsC(int(opts.maxIterations), int(batch), 0 if sel is None else int(sel.size),
+                    None if sel is None else sel.ctypes.data_as(C.POINTER(C.c_int64)))
+    if sel is not None and sel.size == 0:   # an empty selection: the eigenvalues alone
+        o.sel = None
+    m_cap = n if sel is None else int(sel.size)
+    w = np.zeros(max(n, 1), dtype=np.complex128)
+    want = m_cap > 0
+    V = np.zeros((n, max(m_cap, 1)), dtype=np.complex128, order="F")
+    m, nc = C.c_int64(0), C.c_int64(0)
+    it, conv = C.c_int32(0), C.c_int32(0)
+    call("eigsol_eig_dense", ctx.handle, code, n, _ptr(Af), C.byref(o), _ptr(w), _ptr(V) if want else None, C.byref(m),
+         C.byref(it), C.byref(conv), C.byref(nc))
+    k = int(m.value)
+    return EigResult(w[:n].copy(), np.asfortranarray(V[:, :k]), int(it.value), bool(conv.value), int(nc.value))
+
+
+def eig_stage_times(ctx: Context) -> dict:
+    """The context's last :func:`eig` call by stream events, in seconds."""
+    ms = (C.c_double * 4)()
+    call("eigsol_eig_stage_times", ctx.handle, ms)
+    return {k: ms[i] * 1e-3 for i, k in enumerate(("reduction", "francis", "inverse_iteration", "back_transform"))}
 
 
 def cholesky(ctx: Context, B) -> np.ndarray:

@@ -104,6 +104,9 @@ int hess_panel_width_f64();
 int hess_panel_width_c128();
 int hess_max_order_f64();
 int hess_max_order_c128();
+// qr.hip: the power-of-two range guard of the Francis paths on a device matrix read as cnt doubles
+// (A <- 2^escale A where its largest entry lies outside [smlnum, 1 / smlnum]; else *escale = 0)
+int qr_range_guard(hipStream_t st, double* A, int64_t cnt, int* escale);
 
 inline bool dtype_complex(int dtype) { return dtype == EIGSOL_C128 || dtype == EIGSOL_C64 || dtype == EIGSOL_CDD; }
 inline bool dtype_single(int dtype) { return dtype == EIGSOL_F32 || dtype == EIGSOL_C64; }
@@ -263,6 +266,9 @@ struct eigsol_ctx {
     // the last divide-and-conquer eigh call's stages in ms (eigsol_eigh_dc_stage_times): reduction, leaves,
     // host deflation (wall), secular + vector kernels, merge GEMMs, back-transformation
     double eigh_dc_ms[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    // the last eigsol_eig_dense call's stages in ms (eigsol_eig_stage_times): reduction, Francis, inverse
+    // iteration, back-transformation
+    double eig_ms[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 struct eigsol_csr {

@@ -424,6 +424,32 @@ static int qr_unshifted_host(eigsol_ctx* ctx, int64_t n, const void* A, int max_
     return rc;
 }
 
+// LAPACK xGEEV's range guard, shared by the Francis paths and eig (eig.hip): a matrix whose largest
+// entry (max |Re|, |Im| for a complex one: A is read as cnt doubles) lies outside [smlnum, bignum]
+// (smlnum = sqrt(safe min) / eps) is scaled into range first, here by an exact power of two, and the
+// caller scales the eigenvalues back by 2^-escale; squared norms in the reflectors would under- or
+// overflow otherwise.  Matrices inside the range are untouched (*escale = 0).
+int qr_range_guard(hipStream_t st, double* A, int64_t cnt, int* escale) {
+    *escale = 0;
+    unsigned long long bits = 0;   // max |a_ij| as its bit pattern (nonnegative doubles order as integers)
+    unsigned long long* dmax = nullptr;
+    if (hipMallocAsync(reinterpret_cast<void**>(&dmax), sizeof(bits), st) != hipSuccess)
+        return fail(EIGSOL_E_HIP, "qr_eigenvalues: hipMallocAsync");
+    hipMemsetAsync(dmax, 0, sizeof(bits), st);
+    hipLaunchKernelGGL(dev::absmax_kernel, dim3(1024), dim3(256), 0, st, A, cnt, dmax);
+    hipMemcpyAsync(&bits, dmax, sizeof(bits), hipMemcpyDeviceToHost, st);
+    (void)hipFreeAsync(dmax, st);
+    if (stream_wait(st) != hipSuccess) return fail(EIGSOL_E_HIP, "qr_eigenvalues: norm-range check");
+    double amax;
+    std::memcpy(&amax, &bits, sizeof(amax));
+    const double smlnum = std::sqrt(std::numeric_limits<double>::min()) / std::numeric_limits<double>::epsilon();
+    if (std::isfinite(amax) && amax > 0.0 && (amax < smlnum || amax > 1.0 / smlnum)) {
+        *escale = -std::ilogb(amax);
+        hipLaunchKernelGGL(dev::scale_pow2_kernel, dim3(1024), dim3(256), 0, st, A, cnt, *escale);
+    }
+    return EIGSOL_OK;
+}
+
 // Francis double shift on a real matrix (Hessenberg on the device, then the sweeps)
 int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double* wr, double* wi,
                       int32_t* sweeps, int32_t* fail_out);
@@ -438,33 +464,9 @@ static int qr_francis_host(eigsol_ctx* ctx, int64_t n, const double* A, int max_
     if (rc == EIGSOL_OK) rc = work_alloc(w, n);
     if (rc == EIGSOL_OK && hipMemcpyAsync(H, A, n * n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
         rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: upload");
-    // LAPACK xGEEV's range guard: a matrix whose largest entry lies outside [smlnum, bignum]
-    // (smlnum = sqrt(safe min) / eps) is scaled into range first, here by an exact power of two, and
-    // the eigenvalues are scaled back; squared norms in the reflectors would under- or overflow
-    // otherwise.  Matrices inside the range are untouched (bit-identical path).
+    // the range guard (qr_range_guard above); matrices inside the range are untouched (bit-identical path)
     int escale = 0;
-    unsigned long long bits = 0;   // max |a_ij| as its bit pattern (nonnegative doubles order as integers)
-    if (rc == EIGSOL_OK) {
-        unsigned long long* dmax = nullptr;
-        if (hipMallocAsync(reinterpret_cast<void**>(&dmax), sizeof(bits), st) != hipSuccess) {
-            rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: hipMallocAsync");
-        } else {
-            hipMemsetAsync(dmax, 0, sizeof(bits), st);
-            hipLaunchKernelGGL(dev::absmax_kernel, dim3(1024), dim3(256), 0, st, H, n * n, dmax);
-            hipMemcpyAsync(&bits, dmax, sizeof(bits), hipMemcpyDeviceToHost, st);
-            (void)hipFreeAsync(dmax, st);
-            if (stream_wait(st) != hipSuccess) rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: norm-range check");
-        }
-    }
-    if (rc == EIGSOL_OK) {
-        double amax;
-        std::memcpy(&amax, &bits, sizeof(amax));
-        const double smlnum = std::sqrt(std::numeric_limits<double>::min()) / std::numeric_limits<double>::epsilon();
-        if (std::isfinite(amax) && amax > 0.0 && (amax < smlnum || amax > 1.0 / smlnum)) {
-            escale = -std::ilogb(amax);
-            hipLaunchKernelGGL(dev::scale_pow2_kernel, dim3(1024), dim3(256), 0, st, H, n * n, escale);
-        }
-    }
+    if (rc == EIGSOL_OK) rc = qr_range_guard(st, H, n * n, &escale);
     if (rc == EIGSOL_OK) rc = hessenberg_dev<double>(st, H, n, w);
     int32_t sweeps = 0, failed = 0;
     if (rc == EIGSOL_OK) rc = francis_large_f64(ctx, H, n, max_iter, wr, wi, &sweeps, &failed);
@@ -497,27 +499,7 @@ static int qr_francis_c128_host(eigsol_ctx* ctx, int64_t n, const void* A, int m
     if (rc == EIGSOL_OK && hipMemcpyAsync(H, A, n * n * sizeof(cplx), hipMemcpyHostToDevice, st) != hipSuccess)
         rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: upload");
     int escale = 0;
-    if (rc == EIGSOL_OK) {
-        unsigned long long* dmax = nullptr;
-        unsigned long long bits = 0;
-        if (hipMallocAsync(reinterpret_cast<void**>(&dmax), sizeof(bits), st) != hipSuccess) {
-            rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: hipMallocAsync");
-        } else {
-            double* Hd = reinterpret_cast<double*>(H);
-            hipMemsetAsync(dmax, 0, sizeof(bits), st);
-            hipLaunchKernelGGL(dev::absmax_kernel, dim3(1024), dim3(256), 0, st, Hd, 2 * n * n, dmax);
-            hipMemcpyAsync(&bits, dmax, sizeof(bits), hipMemcpyDeviceToHost, st);
-            (void)hipFreeAsync(dmax, st);
-            if (stream_wait(st) != hipSuccess) rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: norm-range check");
-            double amax;
-            std::memcpy(&amax, &bits, sizeof(amax));
-            const double smlnum = std::sqrt(std::numeric_limits<double>::min()) / std::numeric_limits<double>::epsilon();
-            if (rc == EIGSOL_OK && std::isfinite(amax) && amax > 0.0 && (amax < smlnum || amax > 1.0 / smlnum)) {
-                escale = -std::ilogb(amax);
-                hipLaunchKernelGGL(dev::scale_pow2_kernel, dim3(1024), dim3(256), 0, st, Hd, 2 * n * n, escale);
-            }
-        }
-    }
+    if (rc == EIGSOL_OK) rc = qr_range_guard(st, reinterpret_cast<double*>(H), 2 * n * n, &escale);
     if (rc == EIGSOL_OK) rc = hessenberg_dev<cplx>(st, H, n, wk);
     int32_t sweeps = 0, failed = 0;
     if (rc == EIGSOL_OK) rc = francis_large_c128(ctx, H, n, max_iter, w, &sweeps, &failed);
