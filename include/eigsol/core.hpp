@@ -601,6 +601,21 @@ struct EigResult {
     std::int64_t notConverged = 0;                       // eigenvalues no start vector passed the growth test for
 };
 
+// Thin singular value decomposition (svd / svdvals, solvers.hpp; no counterpart in the reference): block
+// one-sided Jacobi on the device (eigsol_svd_dense).
+struct SvdOptions {
+    int maxSweeps = 60;                  // the Jacobi sweeps' limit
+};
+
+template <typename S>
+struct SvdResult {
+    std::vector<double> s;               // k = min(m, n) singular values, descending
+    DenseMatrix<S> U;                    // m x k, orthonormal columns
+    DenseMatrix<S> V;                    // n x k (V, not V^H), orthonormal columns, largest-modulus component real positive
+    int sweeps = 0;
+    std::int64_t not_converged = 0;      // pairs of column blocks above the tolerance when maxSweeps ran out
+};
+
 template <typename S>
 struct QRResult {
     Vector<S> eigenvalues;

@@ -550,6 +550,53 @@ EigResult<S> eig(const DenseMatrix<S>& A, const EigOptions& opts = {}) {
     return res;
 }
 
+// ------------------------------------------------------------------------------------------- svd
+// Thin singular value decomposition A = U diag(s) V^H of a dense m x n matrix (eigsol_svd_dense: block one-sided
+// Jacobi on the fp64 matrix cores).  S = double and std::complex<double>.  svdvals returns the bits of svd's s.
+namespace detail {
+template <ScalarConcept S>
+SvdResult<S> svd_run(const DenseMatrix<S>& A, const SvdOptions& opts, bool vectors, const char* who) {
+    SvdResult<S> res;
+    const std::int64_t m = A.rows(), n = A.cols();
+    if (m == 0 || n == 0) throw std::runtime_error(std::string(who) + ": matrix has zero size");
+    if constexpr (!DeviceScalar<S>) {
+        throw std::runtime_error(std::string(who) +
+                                 ": scalar type not supported by the device path (double, std::complex<double>)");
+    } else {
+        const std::int64_t k = std::min(m, n);
+        eigsol_svd_options o;
+        o.max_sweeps = opts.maxSweeps;
+        res.s.assign(static_cast<std::size_t>(k), 0.0);
+        DenseMatrix<S> U, V;
+        if (vectors) {
+            U = DenseMatrix<S>(m, k);
+            V = DenseMatrix<S>(n, k);
+        }
+        std::int32_t sw = 0;
+        std::int64_t nc = 0;
+        detail::check(eigsol_svd_dense(detail::ctx(), detail::dtype_of<S>(), m, n, A.data(), &o, res.s.data(),
+                                       vectors ? static_cast<void*>(U.data()) : nullptr,
+                                       vectors ? static_cast<void*>(V.data()) : nullptr, &sw, &nc),
+                      who);
+        res.sweeps = sw;
+        res.not_converged = nc;
+        if (vectors) {
+            res.U = std::move(U);
+            res.V = std::move(V);
+        }
+    }
+    return res;
+}
+}  // namespace detail
+template <ScalarConcept S>
+SvdResult<S> svd(const DenseMatrix<S>& A, const SvdOptions& opts = {}) {
+    return detail::svd_run<S>(A, opts, true, "svd");
+}
+template <ScalarConcept S>
+std::vector<double> svdvals(const DenseMatrix<S>& A, const SvdOptions& opts = {}) {
+    return detail::svd_run<S>(A, opts, false, "svdvals").s;
+}
+
 // L of B = L L^H (eigsol_cholesky_dense): zero strict upper triangle, real positive diagonal.
 template <ScalarConcept S>
 DenseMatrix<S> cholesky(const DenseMatrix<S>& B) {

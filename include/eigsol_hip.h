@@ -541,6 +541,50 @@ int eigsol_eig_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmaj
                      int32_t* iterations, int32_t* converged, int64_t* not_converged);
 int eigsol_eig_stage_times(eigsol_ctx* ctx, double* ms4);
 
+/* ---------------------------------------------------------------- singular value decomposition (dense)
+ * eigsol_svd_dense: the thin singular value decomposition A = U diag(s) V^H of a real (EIGSOL_F64) or
+ * complex (EIGSOL_C128) dense m x n matrix, k = min(m, n) (csrc/svd.hip).  The reference has no such solver.
+ * Algorithm: block one-sided Jacobi (Hestenes).  m < n works on A^H with the roles of U and V swapped.  The
+ * matrix is scaled by a power of two so that its largest component lies in [1, 2), and s is scaled back.
+ * The columns are cut into blocks of 32 (real) / 16 (complex); a sweep visits every pair of blocks once in
+ * a round-robin schedule whose steps hold disjoint pairs, and each step is three launches: the pairs' Gram
+ * matrices on the fp64 matrix cores (row chunks, partials added in a fixed order); per pair one workgroup
+ * that skips the pair where max |g_ij| / sqrt(g_ii g_jj) <= tol = sqrt(max(m, n)) eps, else diagonalises G
+ * by cyclic two-sided Jacobi to the same tolerance (Rutishauser's rotation, parallel disjoint rotations)
+ * and polishes the accumulated rotation J by one Newton-Schulz step; X <- X J on the matrix cores for the
+ * pair's columns of W and, where accumulated, of V.  The host reads the pairs' maxima once per sweep and
+ * stops where none exceeds tol.  Then s_j = ||w_j||_2 sorted descending (stable), u_j = w_j / s_j.  No
+ * floating-point atomics and fixed summation orders: two calls return the same bits, and s does not
+ * depend on which of U and V are asked for.
+ * Read: A_colmajor (host, m x n, column-major, leading dimension m).  opts (NULL: 60): max_sweeps.
+ * Out: s, k singular values, descending.  U (NULL: not wanted): m x k; V (NULL: not wanted): n x k, V
+ * itself and not V^H; both column-major with orthonormal columns.  Column j of V has its
+ * largest-modulus component (the first on ties) real and positive, and U's phase follows from
+ * A V = U diag(s).  A column of U (for m < n: of V) whose singular value is exactly 0 completes the
+ * orthonormal set: unit vectors e_k in ascending k, each orthogonalised twice against all columns,
+ * accepted at norm >= 0.5; that loop is serial over such columns, which is acceptable because exact
+ * zeros are rare.  sweeps (optional): the sweeps run, the last of which rotated nothing where the call
+ * converged.  not_converged (optional): the pairs of blocks still above tol when max_sweeps ran out (the
+ * result so far is returned; expected 0).
+ * Status, decided before any device call: EIGSOL_E_INVALID (m < 0 or n < 0; with m, n > 0 a null ctx, A
+ * or s; max_sweeps < 1; unknown dtype), EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD; more than 2^31
+ * entries).  m == 0 or n == 0: EIGSOL_OK, nothing written but *sweeps = 0 and *not_converged = 0.  A
+ * non-finite entry fails with EIGSOL_E_SOLVER.
+ * Out of scope: full_matrices (the square U of a tall matrix); single precision and double-double; QR
+ * preconditioning of tall or ill-conditioned matrices (Drmac-Veselic), which would cut the sweeps of
+ * ill-conditioned matrices; a bidiagonal (gesdd) path; truncated or selected triplets; columns whose
+ * norm lies more than about 2^500 below the largest (their squares underflow in G).
+ * eigsol_svd_stage_times: the context's last eigsol_svd_dense call by stream events, 4 doubles in ms:
+ * Gram, pair Jacobi, apply (each summed over all steps), finish (norms, sort, normalisation, completion,
+ * phases and the copies to the host). */
+typedef struct eigsol_svd_options {
+    int32_t max_sweeps;
+} eigsol_svd_options;
+int eigsol_svd_dense(eigsol_ctx* ctx, int dtype, int64_t m, int64_t n, const void* A_colmajor,
+                     const eigsol_svd_options* opts, double* s, void* U, void* V, int32_t* sweeps,
+                     int64_t* not_converged);
+int eigsol_svd_stage_times(eigsol_ctx* ctx, double* ms4);
+
 /* ---------------------------------------------------------------- Cholesky and A x = lambda B x (dense)
  * eigsol_cholesky_dense: B = L L^H of a real symmetric / complex Hermitian positive definite B
  * (EIGSOL_F64 / EIGSOL_C128; host, n x n, column-major; ONLY the lower triangle is read, and for

@@ -18,7 +18,7 @@ from ._capi import (EIGSOL_C64, EIGSOL_C128, EIGSOL_CDD, EIGSOL_DD, EIGSOL_E_INV
                     EIGSOL_F64, EIGSOL_KRYLOV_LM, EIGSOL_KRYLOV_SHIFT_INVERT, EigSolError, KrylovOptionsC, SolverOptionsC,
                     SubspaceOptionsC, call, check, last_error, lib)
 from ._capi import EIGSOL_EIGH_INDEX, EIGSOL_EIGH_VALUE, EighOptionsC
-from ._capi import EigOptionsC
+from ._capi import EigOptionsC, SvdOptionsC
 
 __all__ = [
     "EigSolError", "SolverOptions", "EigenResult", "Context", "CsrMatrix", "DenseMatrix",
@@ -27,6 +27,7 @@ __all__ = [
     "KrylovOptions", "KrylovResult", "krylov_schur", "krylov_orth", "krylov_rotate",
     "EighResult", "eigh", "eigvalsh", "eigh_stage_times", "tridiag_plan", "eigh_dc_stage_times", "dc_deflate",
     "cholesky", "geigh_stage_times", "EigResult", "eig", "eig_stage_times",
+    "SvdResult", "svd", "svdvals", "svd_stage_times",
 ]
 
 
@@ -932,6 +933,63 @@ def eig_stage_times(ctx: Context) -> dict:
     ms = (C.c_double * 4)()
     call("eigsol_eig_stage_times", ctx.handle, ms)
     return {k: ms[i] * 1e-3 for i, k in enumerate(("reduction", "francis", "inverse_iteration", "back_transform"))}
+
+
+@dataclass
+class SvdResult:
+    """Result of :func:`svd`: ``U`` m x k, ``s`` the k = min(m, n) singular values (descending), ``Vh`` k x n, so
+    that ``A = (U * s) @ Vh`` as with NumPy's thin SVD; column j of ``Vh.conj().T`` has its largest-modulus
+    component real and positive.  ``sweeps`` the Jacobi sweeps run, ``not_converged`` the pairs of column
+    blocks still above the tolerance when ``max_sweeps`` ran out (expected 0).  Without vectors ``U`` and
+    ``Vh`` are ``None``."""
+
+    U: Optional[np.ndarray]
+    s: np.ndarray
+    Vh: Optional[np.ndarray]
+    sweeps: int
+    not_converged: int
+
+
+def _svd_call(ctx: Context, A, want_u: bool, want_v: bool, max_sweeps: int):
+    A = np.asarray(A)
+    if A.ndim != 2:
+        raise ValueError("svd: a two-dimensional matrix is expected")
+    if A.dtype.kind not in "fc":   # integers and booleans; other float widths are the C entry's to refuse
+        A = A.astype(np.float64)
+    code = _dtype_code(A.dtype)
+    m, n = A.shape
+    k = min(m, n)
+    Af = np.asfortranarray(A)
+    s = np.zeros(max(k, 1), dtype=np.float64)
+    U = np.zeros((m, k), dtype=A.dtype, order="F") if want_u else None
+    V = np.zeros((n, k), dtype=A.dtype, order="F") if want_v else None
+    o = SvdOptionsC(int(max_sweeps))
+    sw, nc = C.c_int32(0), C.c_int64(0)
+    call("eigsol_svd_dense", ctx.handle, code, m, n, _ptr(Af), C.byref(o), s.ctypes.data_as(C.POINTER(C.c_double)),
+         _ptr(U) if want_u and U.size else None, _ptr(V) if want_v and V.size else None, C.byref(sw), C.byref(nc))
+    return s[:k].copy(), U, V, int(sw.value), int(nc.value)
+
+
+def svd(ctx: Context, A, vectors: bool = True, max_sweeps: int = 60) -> SvdResult:
+    """Thin singular value decomposition of a dense m x n matrix (float64 / complex128) on the device
+    (``eigsol_svd_dense``): block one-sided Jacobi on the fp64 matrix cores; see :class:`SvdResult`.
+    ``vectors=False`` computes the singular values alone (the same bits)."""
+    s, U, V, sw, nc = _svd_call(ctx, A, vectors, vectors, max_sweeps)
+    if not vectors:
+        return SvdResult(None, s, None, sw, nc)
+    return SvdResult(U, s, np.ascontiguousarray(V.conj().T), sw, nc)
+
+
+def svdvals(ctx: Context, A) -> np.ndarray:
+    """The singular values of a dense m x n matrix, descending (:func:`svd` without vectors)."""
+    return _svd_call(ctx, A, False, False, 60)[0]
+
+
+def svd_stage_times(ctx: Context) -> dict:
+    """The context's last :func:`svd` / :func:`svdvals` call by stream events, in seconds."""
+    ms = (C.c_double * 4)()
+    call("eigsol_svd_stage_times", ctx.handle, ms)
+    return {k: ms[i] * 1e-3 for i, k in enumerate(("gram", "pair_jacobi", "apply", "finish"))}
 
 
 def cholesky(ctx: Context, B) -> np.ndarray:

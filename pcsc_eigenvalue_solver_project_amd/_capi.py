@@ -83,6 +83,10 @@ class EigOptionsC(C.Structure):
     _fields_ = [("max_iterations", C.c_int32), ("batch", C.c_int32), ("nsel", C.c_int64), ("sel", C.POINTER(C.c_int64))]
 
 
+class SvdOptionsC(C.Structure):
+    _fields_ = [("max_sweeps", C.c_int32)]
+
+
 _vp = C.c_void_p
 _i32 = C.c_int32
 _i64 = C.c_int64
@@ -173,6 +177,8 @@ SIGNATURES = {
     "eigsol_dc_deflate": [_i64, _i64, _vp, _vp, C.c_double, _pi64, _vp, _vp, _vp, _pd, _pi64, _vp, _vp, _pd],
     "eigsol_eig_dense": [_vp, C.c_int, _i64, _vp, C.POINTER(EigOptionsC), _vp, _vp, _pi64, _pi32, _pi32, _pi64],
     "eigsol_eig_stage_times": [_vp, _pd],
+    "eigsol_svd_dense": [_vp, C.c_int, _i64, _i64, _vp, C.POINTER(SvdOptionsC), _pd, _vp, _vp, _pi32, _pi64],
+    "eigsol_svd_stage_times": [_vp, _pd],
     "eigsol_hbm_probe": [_vp, C.c_size_t, C.c_int, _pd, _pd, _pd, _pint],
     "eigsol_hbm_probe_mix": [_vp, C.c_size_t, C.c_int, _pd, _pint],
     "eigsol_ctx_info": [_vp, _pint, _pint, _pint, _pint],

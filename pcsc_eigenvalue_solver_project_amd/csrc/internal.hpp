@@ -269,6 +269,8 @@ struct eigsol_ctx {
     // the last eigsol_eig_dense call's stages in ms (eigsol_eig_stage_times): reduction, Francis, inverse
     // iteration, back-transformation
     double eig_ms[4] = {0.0, 0.0, 0.0, 0.0};
+    // the last eigsol_svd_dense call's stages in ms (eigsol_svd_stage_times): Gram, pair Jacobi, apply, finish
+    double svd_ms[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 struct eigsol_csr {
