@@ -20,6 +20,7 @@
 #include "cholesky.hpp"
 #include "kernels_common.hpp"
 #include "mfma_rankk.hpp"
+#include "scratch.hpp"
 
 namespace eigsol {
 namespace dev {
@@ -194,14 +195,6 @@ __global__ __launch_bounds__(256) void zero_strict_upper(S* A, int n) {
 
 namespace {
 
-struct GEvents {
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~GEvents() {
-        for (auto& x : ev)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-
 inline unsigned grid_nn(int64_t n) { return (unsigned)((n * n + 255) / 256); }
 
 // B (n x n, lower triangle) <- L in place; stream-ordered, no host wait.  *info (device, preset to -1)
@@ -278,8 +271,8 @@ template <class S>
 int cholesky_host(eigsol_ctx* ctx, int64_t n, const void* B_host, void* L_host, int64_t* info) {
     hipStream_t st = ctx->stream;
     DevBuf dB, dw;
-    EIGSOL_HIP(dB.alloc((size_t)n * n * sizeof(S)));
-    EIGSOL_HIP(dw.alloc(sizeof(Words)));
+    EIGSOL_TRY(dB.alloc((size_t)n * n * sizeof(S)));
+    EIGSOL_TRY(dw.alloc(sizeof(Words)));
     Words w{-1, 0, 0};
     EIGSOL_HIP(hipMemcpyAsync(dw.p, &w, sizeof(Words), hipMemcpyHostToDevice, st));
     EIGSOL_HIP(hipMemcpyAsync(dB.p, B_host, (size_t)n * n * sizeof(S), hipMemcpyHostToDevice, st));
@@ -304,45 +297,44 @@ int geigh_host(eigsol_ctx* ctx, int64_t n, const void* A_host, const void* B_hos
     hipStream_t st = ctx->stream;
     const bool vectors = Z_out != nullptr;
     const size_t bytes = (size_t)n * n * sizeof(S);
-    GEvents E;
-    for (auto& x : E.ev) EIGSOL_HIP(hipEventCreate(&x));
+    StageClock clock;   // cholesky, standardise, (the standard problem: timed by eigh), back solve, download
+    EIGSOL_TRY(clock.start(5));
     DevBuf dA, dB, dT, dw, dZ;
-    EIGSOL_HIP(dA.alloc(bytes));
-    EIGSOL_HIP(dB.alloc(bytes));
-    EIGSOL_HIP(dT.alloc(bytes));
-    EIGSOL_HIP(dw.alloc(sizeof(Words)));
+    EIGSOL_TRY(dA.alloc(bytes));
+    EIGSOL_TRY(dB.alloc(bytes));
+    EIGSOL_TRY(dT.alloc(bytes));
+    EIGSOL_TRY(dw.alloc(sizeof(Words)));
     Words w{-1, 0, 0};
     EIGSOL_HIP(hipMemcpyAsync(dw.p, &w, sizeof(Words), hipMemcpyHostToDevice, st));
     EIGSOL_HIP(hipMemcpyAsync(dA.p, A_host, bytes, hipMemcpyHostToDevice, st));
     EIGSOL_HIP(hipMemcpyAsync(dB.p, B_host, bytes, hipMemcpyHostToDevice, st));
     Words* W = dw.as<Words>();
     S *A = dA.as<S>(), *B = dB.as<S>(), *T = dT.as<S>();
-    EIGSOL_HIP(hipEventRecord(E.ev[0], st));
+    EIGSOL_TRY(clock.mark(0, st));
     // ---- a, b. mirror both, B = L L^H
     hipLaunchKernelGGL(dev::herm_prepare<S>, dim3(grid_nn(n)), dim3(256), 0, st, A, (int)n, &W->flag_a);
     hipLaunchKernelGGL(dev::herm_prepare<S>, dim3(grid_nn(n)), dim3(256), 0, st, B, (int)n, &W->flag_b);
     EIGSOL_TRY(cholesky_device<S>(st, B, n, &W->info));
     EIGSOL_HIP(hipMemcpyAsync(&w, dw.p, sizeof(Words), hipMemcpyDeviceToHost, st));
-    EIGSOL_HIP(hipEventRecord(E.ev[1], st));
+    EIGSOL_TRY(clock.mark(1, st));
     // ---- c. C = (L^-1 (L^-1 A)^H)^H, left in dA (eigh_device reads its lower triangle)
     EIGSOL_TRY(trsm_left_lower<S>(st, B, n, n, A, n, n));
     conj_transpose<S>(st, n, A, T);
     EIGSOL_TRY(trsm_left_lower<S>(st, B, n, n, T, n, n));
     conj_transpose<S>(st, n, T, A);
     EIGSOL_HIP(hipGetLastError());
-    EIGSOL_HIP(hipEventRecord(E.ev[2], st));
+    EIGSOL_TRY(clock.mark(2, st));
     EIGSOL_HIP(hipStreamSynchronize(st));
     if (w.info >= 0) return not_definite("eigsol_geigh_dense", w.info, info);
     if (w.flag_a || w.flag_b)
         return fail(EIGSOL_E_SOLVER, std::string("eigsol_geigh_dense: the lower triangle of ") + (w.flag_b ? "B" : "A") +
                                          " holds a non-finite entry");
-    float ms = 0.f;
+    double ms[5];
     double* g = ctx->geigh_ms;
     for (int q = 0; q < 7; ++q) g[q] = 0.0;
-    (void)hipEventElapsedTime(&ms, E.ev[0], E.ev[1]);
-    g[0] = ms;
-    (void)hipEventElapsedTime(&ms, E.ev[1], E.ev[2]);
-    g[1] = ms;
+    clock.read(ms, 5);
+    g[0] = ms[0];
+    g[1] = ms[1];
     if (vectors) conj_transpose<S>(st, n, B, T);   // T = L^H, for step e
     else dT.release();
     // ---- d. the standard problem
@@ -351,17 +343,16 @@ int geigh_host(eigsol_ctx* ctx, int64_t n, const void* A_host, const void* B_hos
     const int64_t m = *m_out;
     if (!vectors || m == 0) return EIGSOL_OK;
     // ---- e. X = L^-H Y, then the phase convention
-    EIGSOL_HIP(hipEventRecord(E.ev[3], st));
+    EIGSOL_TRY(clock.mark(3, st));
     EIGSOL_TRY(trsm_left_upper<S>(st, T, n, n, dZ.as<S>(), n, m));
     EIGSOL_TRY(eigh_fix_phase_device(st, dtype, n, m, dZ.p));
-    EIGSOL_HIP(hipEventRecord(E.ev[4], st));
+    EIGSOL_TRY(clock.mark(4, st));
     EIGSOL_HIP(hipMemcpyAsync(Z_out, dZ.p, (size_t)n * m * sizeof(S), hipMemcpyDeviceToHost, st));
-    EIGSOL_HIP(hipEventRecord(E.ev[5], st));
+    EIGSOL_TRY(clock.mark(5, st));
     EIGSOL_HIP(hipStreamSynchronize(st));
-    (void)hipEventElapsedTime(&ms, E.ev[3], E.ev[4]);
-    g[6] = ms;
-    (void)hipEventElapsedTime(&ms, E.ev[4], E.ev[5]);
-    g[5] += ms;
+    clock.read(ms, 5);
+    g[6] = ms[3];
+    g[5] += ms[4];   // the download counts with eigh's back-transformation
     return EIGSOL_OK;
 }
 

@@ -2,26 +2,11 @@
 // driver) and eigh.hip (the standard solver the driver ends in).
 #pragma once
 
-#include <algorithm>
 #include <vector>
 
-#include "internal.hpp"
+#include "scratch.hpp"
 
 namespace eigsol {
-
-struct DevBuf {
-    void* p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    template <class T> T* as() { return static_cast<T*>(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 64)); }
-};
 
 // eigh.hip: eigsol_eigh_dense's solver on a matrix that is already on the device.  dA (n x n, column-major;
 // only its lower triangle is read) is freed once reduced.  w_out (host) receives the m selected eigenvalues;

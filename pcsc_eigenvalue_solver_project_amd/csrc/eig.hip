@@ -38,8 +38,8 @@
 #include <cstring>
 #include <vector>
 
-#include "cholesky.hpp"
 #include "kernels_common.hpp"
+#include "scratch.hpp"
 
 namespace eigsol {
 
@@ -413,14 +413,6 @@ __global__ __launch_bounds__(256) void eig_finish(int n, const double* W, const 
 // ============================================================================ host
 namespace {
 
-struct EigEvents {
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~EigEvents() {
-        for (auto& x : ev)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-
 // The workspace of the resident eigenvalues (U and x) stays below this: a 4096^2 real matrix's complex
 // shifts take 128 MiB of U each, so 32 GiB keeps 256 workgroups, one per CU, resident; half of the free
 // device memory where that is less.
@@ -464,9 +456,9 @@ int run_jobs(hipStream_t st, int n, const HS* Ht, const std::vector<dev::EigJob>
         B = std::max<int64_t>(1, (int64_t)(cap / per));
     }
     B = std::min<int64_t>(B, (int64_t)jobs.size());
-    EIGSOL_HIP(djobs.alloc(jobs.size() * sizeof(dev::EigJob)));
-    EIGSOL_HIP(dU.alloc((size_t)B * ustride * sizeof(T)));
-    EIGSOL_HIP(dx.alloc((size_t)B * n * sizeof(T)));
+    EIGSOL_TRY(djobs.alloc(jobs.size() * sizeof(dev::EigJob)));
+    EIGSOL_TRY(dU.alloc((size_t)B * ustride * sizeof(T)));
+    EIGSOL_TRY(dx.alloc((size_t)B * n * sizeof(T)));
     EIGSOL_HIP(hipMemcpyAsync(djobs.p, jobs.data(), jobs.size() * sizeof(dev::EigJob), hipMemcpyHostToDevice, st));
     for (int64_t q0 = 0; q0 < (int64_t)jobs.size(); q0 += B) {
         const int nb = (int)std::min<int64_t>(B, (int64_t)jobs.size() - q0);
@@ -504,23 +496,23 @@ int eig_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int max_iter, int b
     hipStream_t st = ctx->stream;
     const int NB = Ops::nb();
     const int64_t npan = n >= 3 ? (n - 2 + NB - 1) / NB : 0;
-    EigEvents E;
-    for (auto& x : E.ev) EIGSOL_HIP(hipEventCreate(&x));
+    StageClock clock;
+    EIGSOL_TRY(clock.start(4));
     DevBuf dH, dH2, dV, dT;
-    EIGSOL_HIP(dH.alloc((size_t)n * n * sizeof(S)));
-    EIGSOL_HIP(dH2.alloc((size_t)n * n * sizeof(S)));
+    EIGSOL_TRY(dH.alloc((size_t)n * n * sizeof(S)));
+    EIGSOL_TRY(dH2.alloc((size_t)n * n * sizeof(S)));
     if (V_out && npan) {
-        EIGSOL_HIP(dV.alloc((size_t)npan * n * NB * sizeof(S)));
-        EIGSOL_HIP(dT.alloc((size_t)npan * NB * NB * sizeof(S)));
+        EIGSOL_TRY(dV.alloc((size_t)npan * n * NB * sizeof(S)));
+        EIGSOL_TRY(dT.alloc((size_t)npan * NB * NB * sizeof(S)));
     }
     EIGSOL_HIP(hipMemcpyAsync(dH.p, A_host, (size_t)n * n * sizeof(S), hipMemcpyHostToDevice, st));
-    EIGSOL_HIP(hipEventRecord(E.ev[0], st));
+    EIGSOL_TRY(clock.mark(0, st));
     // ---- a. range guard; b. reduction with the panels kept, Francis on a copy
     int escale = 0;
     EIGSOL_TRY(qr_range_guard(st, dH.as<double>(), (kReal ? 1 : 2) * n * n, &escale));
     if (n >= 3) EIGSOL_TRY(Ops::reduce(st, dH.as<S>(), n, dV.as<S>(), dT.as<S>()));
     EIGSOL_HIP(hipMemcpyAsync(dH2.p, dH.p, (size_t)n * n * sizeof(S), hipMemcpyDeviceToDevice, st));
-    EIGSOL_HIP(hipEventRecord(E.ev[1], st));
+    EIGSOL_TRY(clock.mark(1, st));
     std::vector<double> wr(n), wi(n, 0.0);   // of the (scaled) matrix the vectors are computed from
     int32_t sweeps = 0, failed = 0;
     if constexpr (kReal) {
@@ -531,7 +523,7 @@ int eig_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int max_iter, int b
         for (int64_t i = 0; i < n; ++i) { wr[i] = wc[i].re; wi[i] = wc[i].im; }
     }
     dH2.release();
-    EIGSOL_HIP(hipEventRecord(E.ev[2], st));
+    EIGSOL_TRY(clock.mark(2, st));
     for (int64_t i = 0; i < n; ++i) {
         w_out[2 * i] = escale ? std::ldexp(wr[i], -escale) : wr[i];
         w_out[2 * i + 1] = escale ? std::ldexp(wi[i], -escale) : wi[i];
@@ -541,12 +533,9 @@ int eig_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int max_iter, int b
     if (not_converged) *not_converged = 0;
     const int64_t m = V_out ? (sel ? nsel : n) : 0;
     *m_out = m;
-    float ms[4] = {0.f, 0.f, 0.f, 0.f};
     if (m == 0) {
         EIGSOL_HIP(hipStreamSynchronize(st));
-        (void)hipEventElapsedTime(&ms[0], E.ev[0], E.ev[1]);
-        (void)hipEventElapsedTime(&ms[1], E.ev[1], E.ev[2]);
-        for (int q = 0; q < 4; ++q) ctx->eig_ms[q] = ms[q];
+        clock.read(ctx->eig_ms, 4);   // the two stages marked so far
         return EIGSOL_OK;
     }
     for (int64_t i = 0; i < n; ++i)
@@ -557,12 +546,12 @@ int eig_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int max_iter, int b
     DevBuf dsub, dHt, dkl, dcs;
     std::vector<S> subd(std::max<int64_t>(n, 1));
     if (n > 1) {
-        EIGSOL_HIP(dsub.alloc((size_t)n * sizeof(S)));
+        EIGSOL_TRY(dsub.alloc((size_t)n * sizeof(S)));
         hipLaunchKernelGGL(dev::eig_subdiag<S>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dH.as<S>(), (int)n,
                            dsub.as<S>());
         EIGSOL_HIP(hipMemcpyAsync(subd.data(), dsub.p, (size_t)(n - 1) * sizeof(S), hipMemcpyDeviceToHost, st));
     }
-    EIGSOL_HIP(dHt.alloc((size_t)n * n * sizeof(S)));
+    EIGSOL_TRY(dHt.alloc((size_t)n * n * sizeof(S)));
     {
         const unsigned g = (unsigned)((n + 31) / 32);
         hipLaunchKernelGGL(dev::eig_transpose<S>, dim3(g, g), dim3(256), 0, st, dH.as<S>(), (int)n, dHt.as<S>());
@@ -583,8 +572,8 @@ int eig_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int max_iter, int b
         }
     }
     std::vector<double> colsum(n);
-    EIGSOL_HIP(dkl.alloc((size_t)n * sizeof(int)));
-    EIGSOL_HIP(dcs.alloc((size_t)n * sizeof(double)));
+    EIGSOL_TRY(dkl.alloc((size_t)n * sizeof(int)));
+    EIGSOL_TRY(dcs.alloc((size_t)n * sizeof(double)));
     EIGSOL_HIP(hipMemcpyAsync(dkl.p, kl_of.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(dev::eig_colsum<S>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, dH.as<S>(), (int)n, dkl.as<int>(),
                        dcs.as<double>());
@@ -659,13 +648,13 @@ int eig_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int max_iter, int b
     }
     // ---- d. inverse iteration
     DevBuf dW, dZ, dfail, djr, djc, dUr, dUc, dxr, dxc, dfin;
-    EIGSOL_HIP(dfail.alloc(64));
+    EIGSOL_TRY(dfail.alloc(64));
     EIGSOL_HIP(hipMemsetAsync(dfail.p, 0, 64, st));
-    EIGSOL_HIP(dZ.alloc((size_t)n * m * sizeof(cplx)));
+    EIGSOL_TRY(dZ.alloc((size_t)n * m * sizeof(cplx)));
     int64_t wcols = 0;
     if constexpr (kReal) {
         wcols = (int64_t)ncol + ncolc;
-        EIGSOL_HIP(dW.alloc((size_t)n * wcols * sizeof(double)));
+        EIGSOL_TRY(dW.alloc((size_t)n * wcols * sizeof(double)));
         for (auto& f : fins)
             if (f.colim >= 0) f.colim += ncol;
         dev::EigOut out{dW.as<double>(), dW.as<double>() + (size_t)n * ncol, nullptr};
@@ -677,7 +666,7 @@ int eig_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int max_iter, int b
     }
     int nfail = 0;
     EIGSOL_HIP(hipMemcpyAsync(&nfail, dfail.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    EIGSOL_HIP(hipEventRecord(E.ev[3], st));
+    EIGSOL_TRY(clock.mark(3, st));
     EIGSOL_HIP(hipStreamSynchronize(st));
     for (DevBuf* b : {&dUr, &dUc, &dxr, &dxc, &dHt}) b->release();
 
@@ -692,7 +681,7 @@ int eig_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int max_iter, int b
             EIGSOL_TRY(hess_backtransform_c128(st, n, std::min(kBackChunk, m - c0), dV.as<cplx>(), dT.as<cplx>(),
                                                dZ.as<cplx>() + (size_t)c0 * n, n));
     }
-    EIGSOL_HIP(dfin.alloc(fins.size() * sizeof(dev::EigFin)));
+    EIGSOL_TRY(dfin.alloc(fins.size() * sizeof(dev::EigFin)));
     EIGSOL_HIP(hipMemcpyAsync(dfin.p, fins.data(), fins.size() * sizeof(dev::EigFin), hipMemcpyHostToDevice, st));
     if constexpr (kReal)
         hipLaunchKernelGGL(dev::eig_finish<true>, dim3((unsigned)fins.size()), dim3(256), 0, st, (int)n, dW.as<double>(),
@@ -702,11 +691,10 @@ int eig_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int max_iter, int b
                            dfin.as<dev::EigFin>(), dZ.as<cplx>());
     EIGSOL_HIP(hipGetLastError());
     EIGSOL_HIP(hipMemcpyAsync(V_out, dZ.p, (size_t)n * m * sizeof(cplx), hipMemcpyDeviceToHost, st));
-    EIGSOL_HIP(hipEventRecord(E.ev[4], st));
+    EIGSOL_TRY(clock.mark(4, st));
     EIGSOL_HIP(hipStreamSynchronize(st));
     if (not_converged) *not_converged = nfail;
-    for (int q = 0; q < 4; ++q) (void)hipEventElapsedTime(&ms[q], E.ev[q], E.ev[q + 1]);
-    for (int q = 0; q < 4; ++q) ctx->eig_ms[q] = ms[q];
+    clock.read(ctx->eig_ms, 4);
     return EIGSOL_OK;
 }
 

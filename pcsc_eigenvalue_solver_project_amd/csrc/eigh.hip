@@ -36,6 +36,7 @@
 
 #include "cholesky.hpp"
 #include "kernels_common.hpp"
+#include "scratch.hpp"
 
 namespace eigsol {
 namespace dev {
@@ -676,14 +677,6 @@ int tridiag_plan_impl(int64_t n, const double* d, const double* e, int64_t m, co
     return EIGSOL_OK;
 }
 
-struct Events {
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~Events() {
-        for (auto& x : ev)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-
 template <class S> struct EighOps;
 template <> struct EighOps<double> {
     static int reduce(hipStream_t st, double* A, int64_t n, double* V, double* T) { return hessenberg_blocked_vt_f64(st, A, n, V, T); }
@@ -727,20 +720,20 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
     hipStream_t st = ctx->stream;
     const int NB = Ops::nb();
     const int64_t npan = n >= 3 ? (n - 2 + NB - 1) / NB : 0;
-    Events E;
-    for (auto& x : E.ev) EIGSOL_HIP(hipEventCreate(&x));
+    StageClock clock;
+    EIGSOL_TRY(clock.start(4));
     DevBuf dV, dT, dd, de, dph;
-    EIGSOL_HIP(dd.alloc((size_t)n * sizeof(double)));
+    EIGSOL_TRY(dd.alloc((size_t)n * sizeof(double)));
     // e (n entries), then the scaling's scratch: kAbsmaxBlocks partial maxima and the exponent
-    EIGSOL_HIP(de.alloc((size_t)(n + dev::kAbsmaxBlocks + 1) * sizeof(double)));
+    EIGSOL_TRY(de.alloc((size_t)(n + dev::kAbsmaxBlocks + 1) * sizeof(double)));
     double* const dmax = de.as<double>() + n;
     int* const dkexp = reinterpret_cast<int*>(dmax + dev::kAbsmaxBlocks);
-    EIGSOL_HIP(dph.alloc((size_t)n * sizeof(S)));
+    EIGSOL_TRY(dph.alloc((size_t)n * sizeof(S)));
     if (vectors && npan) {
-        EIGSOL_HIP(dV.alloc((size_t)npan * n * NB * sizeof(S)));
-        EIGSOL_HIP(dT.alloc((size_t)npan * NB * NB * sizeof(S)));
+        EIGSOL_TRY(dV.alloc((size_t)npan * n * NB * sizeof(S)));
+        EIGSOL_TRY(dT.alloc((size_t)npan * NB * NB * sizeof(S)));
     }
-    EIGSOL_HIP(hipEventRecord(E.ev[0], st));
+    EIGSOL_TRY(clock.mark(0, st));
     const unsigned gnn = (unsigned)(((int64_t)n * n + 255) / 256);
     const unsigned gmax = std::min<unsigned>(gnn, dev::kAbsmaxBlocks);
     hipLaunchKernelGGL(dev::eigh_absmax<S>, dim3(gmax), dim3(256), 0, st, dA.as<S>(), (int)n, dmax);
@@ -760,13 +753,12 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
     }
     int kexp = 0;   // the matrix reduced is 2^kexp A
     EIGSOL_HIP(hipMemcpyAsync(&kexp, dkexp, sizeof(int), hipMemcpyDeviceToHost, st));
-    EIGSOL_HIP(hipEventRecord(E.ev[1], st));
+    EIGSOL_TRY(clock.mark(1, st));
     EIGSOL_HIP(hipStreamSynchronize(st));
     for (int64_t i = 0; i < n; ++i)
         if (!std::isfinite(d[i]) || !std::isfinite(e[i]))
             return fail(EIGSOL_E_SOLVER, "eigh: the lower triangle holds a non-finite entry");
-    (void)hipFree(dA.p);   // the reduced matrix is not read again
-    dA.p = nullptr;
+    dA.release();   // the reduced matrix is not read again
 
     // ---- d. split; e. bisection of every block of order >= 2
     TriBlocks B;
@@ -777,7 +769,7 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
     DevBuf dQdc;        // dc: the eigenvectors of T, column i belongs to lam[i]
     int64_t ncap = 0;   // dc: leaf eigenvalues and secular roots that hit their iteration cap
     if (dc) {           // ---- e, f. by divide and conquer (eigh_dc.hip); slot 1 of the stage times stays 0
-        EIGSOL_HIP(hipEventRecord(E.ev[2], st));
+        EIGSOL_TRY(clock.mark(2, st));
         EIGSOL_TRY(eigh_dc_tridiag(ctx, n, d.data(), e.data(), B.start, dQdc, lam.data(), &ncap));
     }
     for (int64_t b = 0; b < nblocks && !dc; ++b) {
@@ -800,8 +792,8 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
     }
     DevBuf dwv, dlam;
     if (!waves.empty()) {
-        EIGSOL_HIP(dwv.alloc(waves.size() * sizeof(dev::BisectWave)));
-        EIGSOL_HIP(dlam.alloc((size_t)n * sizeof(double)));
+        EIGSOL_TRY(dwv.alloc(waves.size() * sizeof(dev::BisectWave)));
+        EIGSOL_TRY(dlam.alloc((size_t)n * sizeof(double)));
         EIGSOL_HIP(hipMemcpyAsync(dwv.p, waves.data(), waves.size() * sizeof(dev::BisectWave), hipMemcpyHostToDevice, st));
         EIGSOL_HIP(hipMemcpyAsync(dlam.p, lam.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(dev::eigh_bisect, dim3((unsigned)waves.size()), dim3(64), 0, st, dd.as<double>(), de.as<double>(),
@@ -809,7 +801,7 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
         EIGSOL_HIP(hipGetLastError());
         EIGSOL_HIP(hipMemcpyAsync(lam.data(), dlam.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
     }
-    if (!dc) EIGSOL_HIP(hipEventRecord(E.ev[2], st));
+    if (!dc) EIGSOL_TRY(clock.mark(2, st));
     EIGSOL_HIP(hipStreamSynchronize(st));
     // ascending; equal values in block order (a fixed order, whatever the selection)
     std::vector<EigItem> all(n);
@@ -838,19 +830,18 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
         w_out[j] = std::ldexp(ws[j], -kexp);   // exact; kexp = 0 leaves the bits
     }
     if (not_converged) *not_converged = 0;
-    float ms[4] = {0.f, 0.f, 0.f, 0.f};
+    double* const ms = ctx->eigh_ms;
     if (!vectors || m == 0) {
-        (void)hipEventElapsedTime(&ms[0], E.ev[0], E.ev[1]);
-        (void)hipEventElapsedTime(&ms[1], E.ev[1], E.ev[2]);
         if (dc) {   // an empty value range: the whole tridiagonal stage ran
-            ms[1] = 0.f;
-            EIGSOL_HIP(hipEventRecord(E.ev[3], st));
+            EIGSOL_TRY(clock.mark(3, st));
             EIGSOL_HIP(hipStreamSynchronize(st));
-            (void)hipEventElapsedTime(&ms[2], E.ev[2], E.ev[3]);
+        }
+        clock.read(ms, 4);   // the stages marked so far
+        if (dc) {
+            ms[1] = 0.0;
             ctx->eigh_dc_ms[0] = ms[0];
             ctx->eigh_dc_ms[5] = 0.0;
         }
-        for (int q = 0; q < 4; ++q) ctx->eigh_ms[q] = ms[q];
         return EIGSOL_OK;
     }
 
@@ -859,9 +850,9 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
     DevBuf dw, dcl, dit, dik, dwork, dfail;   // inverse iteration's; with the host arrays its uploads read,
     std::vector<dev::SteinCluster> sorted;    // they live until the stream is waited for
     std::vector<int> items, item_k;
-    EIGSOL_HIP(dZT.alloc((size_t)n * m * sizeof(double)));
-    EIGSOL_HIP(dD.alloc((size_t)n * sizeof(S)));
-    EIGSOL_HIP(dZ.alloc((size_t)n * m * sizeof(S)));
+    EIGSOL_TRY(dZT.alloc((size_t)n * m * sizeof(double)));
+    EIGSOL_TRY(dD.alloc((size_t)n * sizeof(S)));
+    EIGSOL_TRY(dZ.alloc((size_t)n * m * sizeof(S)));
     std::vector<S> D(n);
     D[0] = Ops::one();
     for (int64_t i = 0; i + 1 < n; ++i) D[i + 1] = Ops::mulp(D[i], ph[i]);
@@ -913,12 +904,12 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
         }
         constexpr int kClusterThreads = 1024;
         const int slots1 = (int)std::min<int64_t>(nsingle, 2048), slots2 = (int)std::min<int64_t>(ncl - nsingle, 512);
-        EIGSOL_HIP(dw.alloc((size_t)m * sizeof(double)));
-        EIGSOL_HIP(dcl.alloc((size_t)ncl * sizeof(dev::SteinCluster)));
-        EIGSOL_HIP(dit.alloc((size_t)m * sizeof(int)));
-        EIGSOL_HIP(dik.alloc((size_t)m * sizeof(int)));
-        EIGSOL_HIP(dwork.alloc((size_t)(slots1 + slots2) * 6 * n * sizeof(double)));
-        EIGSOL_HIP(dfail.alloc(64));
+        EIGSOL_TRY(dw.alloc((size_t)m * sizeof(double)));
+        EIGSOL_TRY(dcl.alloc((size_t)ncl * sizeof(dev::SteinCluster)));
+        EIGSOL_TRY(dit.alloc((size_t)m * sizeof(int)));
+        EIGSOL_TRY(dik.alloc((size_t)m * sizeof(int)));
+        EIGSOL_TRY(dwork.alloc((size_t)(slots1 + slots2) * 6 * n * sizeof(double)));
+        EIGSOL_TRY(dfail.alloc(64));
         EIGSOL_HIP(hipMemcpyAsync(dw.p, ws.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
         EIGSOL_HIP(hipMemcpyAsync(dcl.p, sorted.data(), (size_t)ncl * sizeof(dev::SteinCluster), hipMemcpyHostToDevice, st));
         EIGSOL_HIP(hipMemcpyAsync(dit.p, items.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
@@ -938,7 +929,7 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
         EIGSOL_HIP(hipGetLastError());
         EIGSOL_HIP(hipMemcpyAsync(&nfail, dfail.p, sizeof(int), hipMemcpyDeviceToHost, st));
     }
-    EIGSOL_HIP(hipEventRecord(E.ev[3], st));
+    EIGSOL_TRY(clock.mark(3, st));
 
     // ---- g. Z = Q (D Z_T), then the phase convention
     const unsigned gnm = (unsigned)(((int64_t)n * m + 255) / 256);
@@ -947,16 +938,15 @@ int eigh_core(eigsol_ctx* ctx, int64_t n, DevBuf& dA, int select, int64_t il, in
     if (fix_phase) hipLaunchKernelGGL(dev::eigh_fix_phase<S>, dim3((unsigned)m), dim3(256), 0, st, (int)n, dZ.as<S>(), n);
     EIGSOL_HIP(hipGetLastError());
     if (Z_host) EIGSOL_HIP(hipMemcpyAsync(Z_host, dZ.p, (size_t)n * m * sizeof(S), hipMemcpyDeviceToHost, st));
-    EIGSOL_HIP(hipEventRecord(E.ev[4], st));
+    EIGSOL_TRY(clock.mark(4, st));
     EIGSOL_HIP(hipStreamSynchronize(st));
     if (not_converged) *not_converged = dc ? ncap : nfail;
-    for (int q = 0; q < 4; ++q) (void)hipEventElapsedTime(&ms[q], E.ev[q], E.ev[q + 1]);
+    clock.read(ms, 4);
     if (dc) {
-        ms[1] = 0.f;
+        ms[1] = 0.0;
         ctx->eigh_dc_ms[0] = ms[0];
         ctx->eigh_dc_ms[5] = ms[3];
     }
-    for (int q = 0; q < 4; ++q) ctx->eigh_ms[q] = ms[q];
     return EIGSOL_OK;
 }
 
@@ -964,7 +954,7 @@ template <class S>
 int eigh_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int select, int64_t il, int64_t iu, double vl, double vu,
               int method, double* w_out, void* Z_out, int64_t* m_out, int64_t* not_converged) {
     DevBuf dA, dZ;
-    EIGSOL_HIP(dA.alloc((size_t)n * n * sizeof(S)));
+    EIGSOL_TRY(dA.alloc((size_t)n * n * sizeof(S)));
     EIGSOL_HIP(hipMemcpyAsync(dA.p, A_host, (size_t)n * n * sizeof(S), hipMemcpyHostToDevice, ctx->stream));
     return eigh_core<S>(ctx, n, dA, select, il, iu, vl, vu, method, w_out, Z_out != nullptr, true, Z_out, dZ, m_out, not_converged);
 }

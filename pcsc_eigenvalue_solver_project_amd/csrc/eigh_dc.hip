@@ -33,6 +33,7 @@
 
 #include "cholesky.hpp"
 #include "kernels_common.hpp"
+#include "scratch.hpp"
 
 namespace eigsol {
 namespace dev {
@@ -462,22 +463,6 @@ int dc_leaf_order() {
     return leaf;
 }
 
-struct EventList {
-    std::vector<hipEvent_t> ev;
-    ~EventList() {
-        for (auto x : ev)
-            if (x) (void)hipEventDestroy(x);
-    }
-    int add(hipStream_t st, hipEvent_t* out) {
-        hipEvent_t x = nullptr;
-        EIGSOL_HIP(hipEventCreate(&x));
-        ev.push_back(x);
-        EIGSOL_HIP(hipEventRecord(x, st));
-        *out = x;
-        return EIGSOL_OK;
-    }
-};
-
 }  // namespace
 
 int eigh_dc_tridiag(eigsol_ctx* ctx, int64_t n64, const double* d_in, const double* e_in, const std::vector<int64_t>& starts,
@@ -522,23 +507,23 @@ int eigh_dc_tridiag(eigsol_ctx* ctx, int64_t n64, const double* d_in, const doub
     }
     const size_t nn = (size_t)n * n;
     DevBuf dB, dU, dd, de, dlam, dz, dzrow, dfrom, dmof, dpole, dzk, dporig, dmu, dzh, dmerges, drots, dleaves, dcap;
-    EIGSOL_HIP(dQ.alloc(nn * sizeof(double)));
-    EIGSOL_HIP(dd.alloc((size_t)n * sizeof(double)));
-    EIGSOL_HIP(de.alloc((size_t)n * sizeof(double)));
-    EIGSOL_HIP(dlam.alloc((size_t)n * sizeof(double)));
-    EIGSOL_HIP(dleaves.alloc(leaves.size() * sizeof(DcLeaf)));
-    EIGSOL_HIP(dcap.alloc(64));
+    EIGSOL_TRY(dQ.alloc(nn * sizeof(double)));
+    EIGSOL_TRY(dd.alloc((size_t)n * sizeof(double)));
+    EIGSOL_TRY(de.alloc((size_t)n * sizeof(double)));
+    EIGSOL_TRY(dlam.alloc((size_t)n * sizeof(double)));
+    EIGSOL_TRY(dleaves.alloc(leaves.size() * sizeof(DcLeaf)));
+    EIGSOL_TRY(dcap.alloc(64));
     if (H > 0) {
-        EIGSOL_HIP(dB.alloc(nn * sizeof(double)));
-        EIGSOL_HIP(dU.alloc(nn * sizeof(double)));
-        for (DevBuf* b : {&dz, &dpole, &dzk, &dporig, &dmu, &dzh}) EIGSOL_HIP(b->alloc((size_t)n * sizeof(double)));
-        for (DevBuf* b : {&dzrow, &dfrom, &dmof}) EIGSOL_HIP(b->alloc((size_t)n * sizeof(int)));
-        EIGSOL_HIP(dmerges.alloc((size_t)(n / 2 + 1) * sizeof(DcMerge)));
-        EIGSOL_HIP(drots.alloc((size_t)n * sizeof(DcRot)));
+        EIGSOL_TRY(dB.alloc(nn * sizeof(double)));
+        EIGSOL_TRY(dU.alloc(nn * sizeof(double)));
+        for (DevBuf* b : {&dz, &dpole, &dzk, &dporig, &dmu, &dzh}) EIGSOL_TRY(b->alloc((size_t)n * sizeof(double)));
+        for (DevBuf* b : {&dzrow, &dfrom, &dmof}) EIGSOL_TRY(b->alloc((size_t)n * sizeof(int)));
+        EIGSOL_TRY(dmerges.alloc((size_t)(n / 2 + 1) * sizeof(DcMerge)));
+        EIGSOL_TRY(drots.alloc((size_t)n * sizeof(DcRot)));
     }
-    EventList EV;
-    hipEvent_t t0, t1;
-    EIGSOL_TRY(EV.add(st, &t0));
+    StageClock clock;   // marks 0, 1 around the leaves; level h: 3 h - 1 .. 3 h + 1 around its vector kernels and its GEMMs
+    EIGSOL_TRY(clock.start(1 + 3 * H));
+    EIGSOL_TRY(clock.mark(0, st));
     EIGSOL_HIP(hipMemsetAsync(dQ.p, 0, nn * sizeof(double), st));
     EIGSOL_HIP(hipMemsetAsync(dcap.p, 0, 64, st));
     EIGSOL_HIP(hipMemcpyAsync(dd.p, d.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
@@ -547,11 +532,10 @@ int eigh_dc_tridiag(eigsol_ctx* ctx, int64_t n64, const double* d_in, const doub
     hipLaunchKernelGGL(dc_leaf, dim3((unsigned)leaves.size()), dim3(64), 0, st, n, dd.as<double>(), de.as<double>(),
                        dleaves.as<DcLeaf>(), dQ.as<double>(), dlam.as<double>(), dcap.as<int>());
     EIGSOL_HIP(hipGetLastError());
-    EIGSOL_TRY(EV.add(st, &t1));
+    EIGSOL_TRY(clock.mark(1, st));
 
     // ---- merges, level by level
     double host_ms = 0.0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> span_vec, span_gemm;
     std::vector<double> z(n);
     std::vector<int> zrow(n), from(n), mof(n);
     std::vector<double> pole(n), zk(n);
@@ -608,8 +592,7 @@ int eigh_dc_tridiag(eigsol_ctx* ctx, int64_t n64, const double* d_in, const doub
         EIGSOL_HIP(hipMemcpyAsync(dpole.p, pole.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
         EIGSOL_HIP(hipMemcpyAsync(dzk.p, zk.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
         EIGSOL_HIP(hipMemcpyAsync(dlam.p, lam, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-        hipEvent_t a, b, c;
-        EIGSOL_TRY(EV.add(st, &a));
+        EIGSOL_TRY(clock.mark(3 * h - 1, st));
         if (!rots.empty())
             hipLaunchKernelGGL(dc_rotate, dim3((unsigned)((nmax + 255) / 256), nm), dim3(256), 0, st, n, dQ.as<double>(),
                                dmerges.as<DcMerge>(), drots.as<DcRot>());
@@ -625,7 +608,7 @@ int eigh_dc_tridiag(eigsol_ctx* ctx, int64_t n64, const double* d_in, const doub
                                dpole.as<double>(), dzh.as<double>(), dporig.as<double>(), dmu.as<double>(), dU.as<double>());
         }
         EIGSOL_HIP(hipGetLastError());
-        EIGSOL_TRY(EV.add(st, &b));
+        EIGSOL_TRY(clock.mark(3 * h, st));
         // one GEMM launch per merge: Q(rows, kept) = B(rows, kept) U
         for (const DcMerge& M : merges) {
             if (M.k == 0) continue;
@@ -636,9 +619,7 @@ int eigh_dc_tridiag(eigsol_ctx* ctx, int64_t n64, const double* d_in, const doub
         hipLaunchKernelGGL(dc_copy_deflated, dim3((unsigned)n), dim3(256), 0, st, n, dB.as<double>(), dQ.as<double>(),
                            dmerges.as<DcMerge>(), dmof.as<int>());
         EIGSOL_HIP(hipGetLastError());
-        EIGSOL_TRY(EV.add(st, &c));
-        span_vec.emplace_back(a, b);
-        span_gemm.emplace_back(b, c);
+        EIGSOL_TRY(clock.mark(3 * h + 1, st));
     }
     int ncap = 0;
     EIGSOL_HIP(hipMemcpyAsync(lam, dlam.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -646,17 +627,13 @@ int eigh_dc_tridiag(eigsol_ctx* ctx, int64_t n64, const double* d_in, const doub
     EIGSOL_HIP(hipStreamSynchronize(st));
     for (int i = 0; i < n; ++i) lam[i] = std::ldexp(lam[i], -kexp[i]);   // back to T's scale, exactly
     *ncap_out = ncap;
-    float ms = 0.f;
+    std::vector<double> ms(1 + 3 * H);
+    clock.read(ms.data(), 1 + 3 * H);
     double vec_ms = 0.0, gemm_ms = 0.0;
-    (void)hipEventElapsedTime(&ms, t0, t1);
-    ctx->eigh_dc_ms[1] = ms;
-    for (auto& s : span_vec) {
-        (void)hipEventElapsedTime(&ms, s.first, s.second);
-        vec_ms += ms;
-    }
-    for (auto& s : span_gemm) {
-        (void)hipEventElapsedTime(&ms, s.first, s.second);
-        gemm_ms += ms;
+    ctx->eigh_dc_ms[1] = ms[0];
+    for (int h = 1; h <= H; ++h) {
+        vec_ms += ms[3 * h - 1];
+        gemm_ms += ms[3 * h];
     }
     ctx->eigh_dc_ms[2] = host_ms;
     ctx->eigh_dc_ms[3] = vec_ms;
@@ -667,7 +644,7 @@ int eigh_dc_tridiag(eigsol_ctx* ctx, int64_t n64, const double* d_in, const doub
 int eigh_dc_take_columns(hipStream_t st, int64_t n, int64_t m, const double* Q, const std::vector<int>& cols, double* ZT) {
     if (m <= 0) return EIGSOL_OK;
     DevBuf dcols;
-    EIGSOL_HIP(dcols.alloc((size_t)m * sizeof(int)));
+    EIGSOL_TRY(dcols.alloc((size_t)m * sizeof(int)));
     EIGSOL_HIP(hipMemcpyAsync(dcols.p, cols.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(dev::dc_take_columns, dim3((unsigned)m), dim3(256), 0, st, (int)n, Q, dcols.as<int>(), ZT);
     EIGSOL_HIP(hipGetLastError());

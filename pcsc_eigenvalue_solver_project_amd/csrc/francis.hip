@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "kernels_common.hpp"
+#include "scratch.hpp"
 
 namespace eigsol {
 
@@ -944,21 +945,23 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
                       int32_t* sweeps_out, int32_t* fail_out) {
     hipStream_t st = ctx->stream;
     const double eps = 2.220446049250313e-16;
-    double *dwr = nullptr, *dwi = nullptr, *dds = nullptr, *dU = nullptr, *dsh = nullptr;
-    int* dinfo = nullptr;
-    double* dsw = nullptr;      // concurrent shifts (ShiftJob): re, im
-    int* dsinfo = nullptr;
-    unsigned* dflag = nullptr;
+    DevBuf bsw, bsinfo, bflag, bwr, bwi, bds, bU, bsh, binfo;
+    EIGSOL_TRY(bsw.alloc(2 * dev::kAedMax * sizeof(double)));   // concurrent shifts (ShiftJob): re, im
+    EIGSOL_TRY(bsinfo.alloc(64));
+    EIGSOL_TRY(bflag.alloc(64));
+    EIGSOL_HIP(hipMemsetAsync(bflag.p, 0, 64, st));
+    EIGSOL_TRY(bwr.alloc(n * sizeof(double)));
+    EIGSOL_TRY(bwi.alloc(n * sizeof(double)));
+    EIGSOL_TRY(bds.alloc(2 * n * sizeof(double)));
+    EIGSOL_TRY(bU.alloc(dev::kMaxGroups * dev::kWin * dev::kWin * sizeof(double)));
+    EIGSOL_TRY(bsh.alloc(4 * dev::kMaxBulges * sizeof(double)));
+    EIGSOL_TRY(binfo.alloc(64));
+    double *const dsw = bsw.as<double>(), *const dwr = bwr.as<double>(), *const dwi = bwi.as<double>();
+    double *const dds = bds.as<double>(), *const dU = bU.as<double>(), *const dsh = bsh.as<double>();
+    int *const dsinfo = bsinfo.as<int>(), *const dinfo = binfo.as<int>();
+    unsigned* const dflag = bflag.as<unsigned>();
     unsigned flag_epoch = 0;
     int rc = EIGSOL_OK;
-    if (hipMalloc(&dsw, 2 * dev::kAedMax * sizeof(double)) != hipSuccess || hipMalloc(&dsinfo, 64) != hipSuccess ||
-        hipMalloc(&dflag, 64) != hipSuccess || hipMemsetAsync(dflag, 0, 64, st) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "francis: device workspace");
-    if (rc == EIGSOL_OK && (hipMalloc(&dwr, n * sizeof(double)) != hipSuccess || hipMalloc(&dwi, n * sizeof(double)) != hipSuccess ||
-        hipMalloc(&dds, 2 * n * sizeof(double)) != hipSuccess ||
-        hipMalloc(&dU, dev::kMaxGroups * dev::kWin * dev::kWin * sizeof(double)) != hipSuccess ||
-        hipMalloc(&dsh, 4 * dev::kMaxBulges * sizeof(double)) != hipSuccess || hipMalloc(&dinfo, 64) != hipSuccess))
-        rc = fail(EIGSOL_E_HIP, "francis: device workspace");
     // every per-sweep transfer goes through pinned host memory: a pageable hipMemcpyAsync is staged
     // by the runtime and waited for with a sleeping wait, ~1 ms per copy (round-4 kernel trace,
     // tools/gap_analysis.py), more than a sweep's kernels at the end of the iteration
@@ -969,15 +972,13 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
         double cwr[2 * dev::kAedMax];   // concurrent shifts: re [0, kAedMax), im [kAedMax, 2 kAedMax)
         double swr[2 * dev::kMaxBulges], swi[2 * dev::kMaxBulges], sh[2 * dev::kMaxBulges];
     };
-    Staging* hp = nullptr;
-    double* ds = nullptr;   // deflation scans: diagonal [0, n), subdiagonal [n, 2n)
-    // on any allocation failure rc is set, the loop below never runs and the common cleanup at the
-    // end frees whatever was allocated
-    if (rc == EIGSOL_OK && (hipHostMalloc(&hp, sizeof(Staging), hipHostMallocDefault) != hipSuccess ||
-                            hipHostMalloc(&ds, 2 * n * sizeof(double), hipHostMallocDefault) != hipSuccess))
-        rc = fail(EIGSOL_E_HIP, "francis: pinned staging");
-    double* const swr = hp ? hp->swr : nullptr;
-    double* const swi = hp ? hp->swi : nullptr;
+    PinBuf bhp, bhs;
+    EIGSOL_TRY(bhp.alloc(sizeof(Staging)));
+    EIGSOL_TRY(bhs.alloc(2 * n * sizeof(double)));
+    Staging* const hp = bhp.as<Staging>();
+    double* const ds = bhs.as<double>();   // deflation scans: diagonal [0, n), subdiagonal [n, 2n)
+    double* const swr = hp->swr;
+    double* const swi = hp->swi;
     int sweeps = 0, failed = 0;
     int ihi = (int)n - 1;
     int stall = 0;               // sweeps on the current bottom block without a deflation
@@ -1297,11 +1298,6 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
                      "aed=%d aed_deflated=%d aed_win=%d aed_steps=%lld aed_phase_ms=%.1f/%.1f/%.1f conc_shifts=%d\n",
                      (long long)n, st_sweeps, st_windows, st_steps, st_small, st_small_rows, kSmall, st_aed, st_aed_defl,
                      aed_win, st_aed_steps, st_aed_ph[0] * 1e-5, st_aed_ph[1] * 1e-5, st_aed_ph[2] * 1e-5, st_conc);
-    for (void* p : {(void*)dwr, (void*)dwi, (void*)dds, (void*)dU, (void*)dsh, (void*)dinfo, (void*)dsw, (void*)dsinfo,
-                    (void*)dflag})
-        (void)hipFree(p);
-    if (ds) (void)hipHostFree(ds);
-    if (hp) (void)hipHostFree(hp);
     // iterations reported: sweeps spent on the slowest deflation (>= 1, the final check), so that
     // iterations <= maxIterations exactly when the iteration converged
     *sweeps_out = std::max(1, sweeps);

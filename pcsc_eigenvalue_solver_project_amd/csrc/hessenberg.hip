@@ -19,6 +19,7 @@
 
 #include "kernels_common.hpp"
 #include "mfma_rankk.hpp"
+#include "scratch.hpp"
 
 namespace eigsol {
 namespace dev {
@@ -1450,22 +1451,21 @@ int hessenberg_blocked(hipStream_t st, S* A, int64_t n64, S* Vout = nullptr, S* 
     if (n > Cfg::kMaxLdsN) return fail(EIGSOL_E_UNSUPPORTED, "blocked Hessenberg: n above the LDS panel limit");
     constexpr int NB = Cfg::NB;
     const int maxch = (n + dev::kGemvCols - 1) / dev::kGemvCols;
-    S *V = nullptr, *Y = nullptr, *T = nullptr, *tv = nullptr, *yp = nullptr, *W = nullptr;
-    int* skip = nullptr;
-    EIGSOL_HIP(hipMalloc(&V, (size_t)n * NB * sizeof(S)));
-    S *L = nullptr, *R = nullptr, *M = nullptr;
-    EIGSOL_HIP(hipMalloc(&L, (size_t)n * 2 * NB * sizeof(S)));   // [Y | V zero above the panel]
-    EIGSOL_HIP(hipMalloc(&R, (size_t)n * 2 * NB * sizeof(S)));   // conj of [V(c1:, :) | W2^H]
-    EIGSOL_HIP(hipMalloc(&M, (size_t)NB * NB * sizeof(S)));      // V^H Y
-    Y = L;
-    EIGSOL_HIP(hipMalloc(&T, NB * NB * sizeof(S)));
-    EIGSOL_HIP(hipMalloc(&tv, NB * sizeof(S)));
-    EIGSOL_HIP(hipMalloc(&yp, (size_t)maxch * n * sizeof(S)));
-    EIGSOL_HIP(hipMalloc(&W, (size_t)NB * n * sizeof(S)));
-    S* SK = nullptr;                      // split-K partials of W = V^H A (16 x NB x n)
     const int64_t sk_elems = (int64_t)16 * NB * n;
-    EIGSOL_HIP(hipMalloc(&SK, sk_elems * sizeof(S)));
-    EIGSOL_HIP(hipMalloc(&skip, 64));
+    DevBuf bV, bL, bR, bM, bT, btv, byp, bW, bSK, bskip;
+    EIGSOL_TRY(bV.alloc((size_t)n * NB * sizeof(S)));
+    EIGSOL_TRY(bL.alloc((size_t)n * 2 * NB * sizeof(S)));   // [Y | V zero above the panel]
+    EIGSOL_TRY(bR.alloc((size_t)n * 2 * NB * sizeof(S)));   // conj of [V(c1:, :) | W2^H]
+    EIGSOL_TRY(bM.alloc((size_t)NB * NB * sizeof(S)));      // V^H Y
+    EIGSOL_TRY(bT.alloc(NB * NB * sizeof(S)));
+    EIGSOL_TRY(btv.alloc(NB * sizeof(S)));
+    EIGSOL_TRY(byp.alloc((size_t)maxch * n * sizeof(S)));
+    EIGSOL_TRY(bW.alloc((size_t)NB * n * sizeof(S)));
+    EIGSOL_TRY(bSK.alloc(sk_elems * sizeof(S)));            // split-K partials of W = V^H A (16 x NB x n)
+    EIGSOL_TRY(bskip.alloc(64));
+    S *const V = bV.as<S>(), *const L = bL.as<S>(), *const R = bR.as<S>(), *const M = bM.as<S>(), *const T = bT.as<S>();
+    S *const tv = btv.as<S>(), *const yp = byp.as<S>(), *const W = bW.as<S>(), *const SK = bSK.as<S>(), *const Y = L;
+    int* const skip = bskip.as<int>();
     const size_t lds = (size_t)n * sizeof(S);
     // one cooperative launch per panel when the device supports it and n fits its LDS staging
     int coop_ok = 0, dev_id = 0;
@@ -1504,18 +1504,15 @@ int hessenberg_blocked(hipStream_t st, S* A, int64_t n64, S* Vout = nullptr, S* 
                                     : reinterpret_cast<const void*>(dev::hess_panel_coop2<S>))
                               : reinterpret_cast<const void*>(dev::hess_panel_coop<S, 1>))
                     : reinterpret_cast<const void*>(dev::hess_panel_coop<S, 2>);
-    S *part = nullptr, *x0s = nullptr, *xu = nullptr;
-    double* tpart = nullptr;
-    unsigned* bar = nullptr;
-    int* err = nullptr;
+    DevBuf part, tpart, x0s, xu, bar, err;   // the cooperative panel's (null otherwise)
     if (coop) {
-        EIGSOL_HIP(hipMalloc(&part, 2 * G * NB * sizeof(S)));
-        EIGSOL_HIP(hipMalloc(&tpart, G * sizeof(double)));
-        EIGSOL_HIP(hipMalloc(&x0s, 64));
-        EIGSOL_HIP(hipMalloc(&xu, (size_t)n * sizeof(S)));
-        EIGSOL_HIP(hipMalloc(&bar, kBarBytes));
-        EIGSOL_HIP(hipMalloc(&err, 64));
-        EIGSOL_HIP(hipMemsetAsync(err, 0, 64, st));
+        EIGSOL_TRY(part.alloc(2 * G * NB * sizeof(S)));
+        EIGSOL_TRY(tpart.alloc(G * sizeof(double)));
+        EIGSOL_TRY(x0s.alloc(64));
+        EIGSOL_TRY(xu.alloc((size_t)n * sizeof(S)));
+        EIGSOL_TRY(bar.alloc(kBarBytes));
+        EIGSOL_TRY(err.alloc(64));
+        EIGSOL_HIP(hipMemsetAsync(err.p, 0, 64, st));
         EIGSOL_HIP(hipFuncSetAttribute(coop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)coop_lds));
     }
     EIGSOL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dev::hess_panel_col<S>),
@@ -1525,8 +1522,9 @@ int hessenberg_blocked(hipStream_t st, S* A, int64_t n64, S* Vout = nullptr, S* 
         const int nbp = std::min(NB, last - k + 1);
         EIGSOL_HIP(hipMemsetAsync(T, 0, NB * NB * sizeof(S), st));
         if (coop) {
-            EIGSOL_HIP(hipMemsetAsync(bar, 0, kBarBytes, st));
-            dev::CoopArgs<S> ca{A, n, k, nbp, V, Y, T, part, tpart, x0s, bar, err, xu, hier};
+            EIGSOL_HIP(hipMemsetAsync(bar.p, 0, kBarBytes, st));
+            dev::CoopArgs<S> ca{A, n, k, nbp, V, Y, T, part.as<S>(), tpart.as<double>(), x0s.as<S>(), bar.as<unsigned>(),
+                                err.as<int>(), xu.as<S>(), hier};
             void* kargs[] = {&ca};
             // EIGSOL_HESS_COOP_PLAIN=1: the SAME panel kernel through an ordinary launch, for profiling
             // only (rocprofv3 7.2 crashes at exit after any cooperative launch, tools/coop_prof_repro.hip);
@@ -1592,12 +1590,9 @@ int hessenberg_blocked(hipStream_t st, S* A, int64_t n64, S* Vout = nullptr, S* 
     EIGSOL_HIP(hipGetLastError());
     int errh = 0;
     if (coop) {
-        EIGSOL_HIP(hipMemcpyAsync(&errh, err, sizeof(int), hipMemcpyDeviceToHost, st));
+        EIGSOL_HIP(hipMemcpyAsync(&errh, err.p, sizeof(int), hipMemcpyDeviceToHost, st));
         EIGSOL_HIP(hipStreamSynchronize(st));
     }
-    for (void* p : {(void*)V, (void*)L, (void*)R, (void*)M, (void*)T, (void*)tv, (void*)yp, (void*)W, (void*)skip,
-                    (void*)part, (void*)tpart, (void*)x0s, (void*)xu, (void*)bar, (void*)err, (void*)SK})
-        if (p) (void)hipFree(p);
     if (errh) return fail(EIGSOL_E_HIP, "blocked Hessenberg: grid barrier timed out (internal error)");
     return EIGSOL_OK;
 }
@@ -1611,11 +1606,12 @@ int hess_backtransform(hipStream_t st, int64_t n64, int64_t m64, const S* Vall, 
     constexpr int NB = dev::HessCfg<S>::NB;
     const int n = (int)n64, m = (int)m64;
     if (n < 3 || m < 1) return EIGSOL_OK;
-    S *W1 = nullptr, *W2 = nullptr, *SK = nullptr;
     const int64_t sk_elems = (int64_t)16 * NB * m;
-    EIGSOL_HIP(hipMalloc(&W1, (size_t)NB * m * sizeof(S)));
-    EIGSOL_HIP(hipMalloc(&W2, (size_t)NB * m * sizeof(S)));
-    EIGSOL_HIP(hipMalloc(&SK, sk_elems * sizeof(S)));
+    DevBuf bW1, bW2, bSK;
+    EIGSOL_TRY(bW1.alloc((size_t)NB * m * sizeof(S)));
+    EIGSOL_TRY(bW2.alloc((size_t)NB * m * sizeof(S)));
+    EIGSOL_TRY(bSK.alloc(sk_elems * sizeof(S)));
+    S *const W1 = bW1.as<S>(), *const W2 = bW2.as<S>(), *const SK = bSK.as<S>();
     const int last = n - 3;
     for (int k = last / NB * NB; k >= 0; k -= NB) {
         const int nbp = std::min(NB, last - k + 1);
@@ -1628,7 +1624,6 @@ int hess_backtransform(hipStream_t st, int64_t n64, int64_t m64, const S* Vall, 
     }
     EIGSOL_HIP(hipGetLastError());
     EIGSOL_HIP(hipStreamSynchronize(st));
-    for (void* p : {(void*)W1, (void*)W2, (void*)SK}) (void)hipFree(p);
     return EIGSOL_OK;
 }
 
@@ -1641,16 +1636,18 @@ int qr_blocked(hipStream_t st, S* R, int m, int n, S* Q) {
     constexpr int NB = 32;
     if (m > dev::HessCfg<S>::kMaxLdsN) return fail(EIGSOL_E_UNSUPPORTED, "blocked QR: m above the LDS panel limit");
     const int kmax = std::min(m, n);
-    S *V = nullptr, *Vc = nullptr, *T = nullptr, *W = nullptr, *W2 = nullptr, *Z = nullptr, *Z2 = nullptr, *SK = nullptr;
     const int64_t sk_elems = (int64_t)16 * NB * std::max(m, n);
-    EIGSOL_HIP(hipMalloc(&V, (size_t)m * NB * sizeof(S)));
-    if (kC) EIGSOL_HIP(hipMalloc(&Vc, (size_t)m * NB * sizeof(S)));
-    EIGSOL_HIP(hipMalloc(&T, NB * NB * sizeof(S)));
-    EIGSOL_HIP(hipMalloc(&W, (size_t)NB * std::max(n, 1) * sizeof(S)));
-    EIGSOL_HIP(hipMalloc(&W2, (size_t)NB * std::max(n, 1) * sizeof(S)));
-    EIGSOL_HIP(hipMalloc(&Z, (size_t)m * NB * sizeof(S)));
-    EIGSOL_HIP(hipMalloc(&Z2, (size_t)m * NB * sizeof(S)));
-    EIGSOL_HIP(hipMalloc(&SK, sk_elems * sizeof(S)));
+    DevBuf bV, bVc, bT, bW, bW2, bZ, bZ2, bSK;
+    EIGSOL_TRY(bV.alloc((size_t)m * NB * sizeof(S)));
+    if (kC) EIGSOL_TRY(bVc.alloc((size_t)m * NB * sizeof(S)));
+    EIGSOL_TRY(bT.alloc(NB * NB * sizeof(S)));
+    EIGSOL_TRY(bW.alloc((size_t)NB * std::max(n, 1) * sizeof(S)));
+    EIGSOL_TRY(bW2.alloc((size_t)NB * std::max(n, 1) * sizeof(S)));
+    EIGSOL_TRY(bZ.alloc((size_t)m * NB * sizeof(S)));
+    EIGSOL_TRY(bZ2.alloc((size_t)m * NB * sizeof(S)));
+    EIGSOL_TRY(bSK.alloc(sk_elems * sizeof(S)));
+    S *const V = bV.as<S>(), *const Vc = bVc.as<S>(), *const T = bT.as<S>(), *const W = bW.as<S>(), *const W2 = bW2.as<S>();
+    S *const Z = bZ.as<S>(), *const Z2 = bZ2.as<S>(), *const SK = bSK.as<S>();
     EIGSOL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dev::qr_panel_col<S>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)(m * sizeof(S))));
     // the panel as one cooperative launch (qr_panel_coop) from m >= 256 when the device supports it
@@ -1662,25 +1659,23 @@ int qr_blocked(hipStream_t st, S* R, int m, int n, S* Q) {
     const char* qce = std::getenv("EIGSOL_QR_COOP");
     const int G = std::min(256, std::max(16, (m / 32 + 7) / 8 * 8));
     const bool coop = coop_ok && m >= 256 && m <= 64 * G && !(qce && std::atoi(qce) == 0);
-    S *part = nullptr, *x0s = nullptr;
-    double* tpart = nullptr;
-    unsigned* bar = nullptr;
-    int* err = nullptr;
+    DevBuf part, tpart, x0s, bar, err;   // the cooperative panel's (null otherwise)
     constexpr size_t kBarBytes = 9 * 64;
     if (coop) {
-        EIGSOL_HIP(hipMalloc(&part, 2 * (size_t)G * NB * sizeof(S)));
-        EIGSOL_HIP(hipMalloc(&tpart, G * sizeof(double)));
-        EIGSOL_HIP(hipMalloc(&x0s, 64));
-        EIGSOL_HIP(hipMalloc(&bar, kBarBytes));
-        EIGSOL_HIP(hipMalloc(&err, 64));
-        EIGSOL_HIP(hipMemsetAsync(err, 0, 64, st));
+        EIGSOL_TRY(part.alloc(2 * (size_t)G * NB * sizeof(S)));
+        EIGSOL_TRY(tpart.alloc(G * sizeof(double)));
+        EIGSOL_TRY(x0s.alloc(64));
+        EIGSOL_TRY(bar.alloc(kBarBytes));
+        EIGSOL_TRY(err.alloc(64));
+        EIGSOL_HIP(hipMemsetAsync(err.p, 0, 64, st));
     }
     for (int k = 0; k < kmax; k += NB) {
         const int nbp = std::min(NB, kmax - k);
         EIGSOL_HIP(hipMemsetAsync(T, 0, NB * NB * sizeof(S), st));
         if (coop) {
-            EIGSOL_HIP(hipMemsetAsync(bar, 0, kBarBytes, st));
-            dev::QrCoopArgs<S> ca{R, m, k, nbp, V, T, part, tpart, x0s, bar, err, G >= 64};
+            EIGSOL_HIP(hipMemsetAsync(bar.p, 0, kBarBytes, st));
+            dev::QrCoopArgs<S> ca{R, m, k, nbp, V, T, part.as<S>(), tpart.as<double>(), x0s.as<S>(), bar.as<unsigned>(),
+                                  err.as<int>(), G >= 64};
             void* kargs[] = {&ca};
             static const bool plain = std::getenv("EIGSOL_HESS_COOP_PLAIN") != nullptr;   // profiling only
             if (plain)
@@ -1713,12 +1708,9 @@ int qr_blocked(hipStream_t st, S* R, int m, int n, S* Q) {
     EIGSOL_HIP(hipGetLastError());
     int errh = 0;
     if (coop) {
-        EIGSOL_HIP(hipMemcpyAsync(&errh, err, sizeof(int), hipMemcpyDeviceToHost, st));
+        EIGSOL_HIP(hipMemcpyAsync(&errh, err.p, sizeof(int), hipMemcpyDeviceToHost, st));
         EIGSOL_HIP(hipStreamSynchronize(st));
     }
-    for (void* p : {(void*)V, (void*)Vc, (void*)T, (void*)W, (void*)W2, (void*)Z, (void*)Z2, (void*)SK, (void*)part,
-                    (void*)tpart, (void*)x0s, (void*)bar, (void*)err})
-        if (p) (void)hipFree(p);
     if (errh) return fail(EIGSOL_E_HIP, "blocked QR: grid barrier timed out (internal error)");
     return EIGSOL_OK;
 }

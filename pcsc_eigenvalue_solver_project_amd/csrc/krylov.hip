@@ -29,6 +29,7 @@
 
 #include "kernels_common.hpp"
 #include "linear_op.hpp"
+#include "scratch.hpp"
 #include "shifted.hpp"
 #include "small_eig.hpp"
 
@@ -329,7 +330,6 @@ __global__ __launch_bounds__(kThreads) void ks_resid_kernel(const cplx* __restri
 namespace {
 
 using smalleig::cd;
-using smalleig::DevBuf;
 using smalleig::host_of;
 using smalleig::ritz_order;
 using smalleig::small_eig;

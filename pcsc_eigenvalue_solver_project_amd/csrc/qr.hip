@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "kernels_common.hpp"
+#include "scratch.hpp"
 
 namespace eigsol {
 namespace dev {
@@ -243,39 +244,28 @@ namespace {
 
 template <class S>
 struct QrWork {
-    S* v = nullptr;
-    int* skip = nullptr;
-    double* red = nullptr;
-    double* hred = nullptr;   // pinned host copy of red (a pageable copy sleeps ~1 ms per iteration)
+    DevBuf v, skip, red;   // the reflector (n scalars), its skip flag, the convergence check's two doubles
+    PinBuf hred;           // pinned host copy of red (a pageable copy sleeps ~1 ms per iteration)
+    int alloc(int64_t n) {
+        EIGSOL_TRY(v.alloc(n * sizeof(S)));
+        EIGSOL_TRY(skip.alloc(64));
+        EIGSOL_TRY(red.alloc(64));
+        return hred.alloc(64);
+    }
 };
-
-template <class S>
-int work_alloc(QrWork<S>& w, int64_t n) {
-    EIGSOL_HIP(hipMalloc(&w.v, std::max<int64_t>(n, 1) * sizeof(S)));
-    EIGSOL_HIP(hipMalloc(&w.skip, 64));
-    EIGSOL_HIP(hipMalloc(&w.red, 64));
-    EIGSOL_HIP(hipHostMalloc(&w.hred, 64, hipHostMallocDefault));
-    return EIGSOL_OK;
-}
-template <class S>
-void work_free(QrWork<S>& w) {
-    if (w.v) (void)hipFree(w.v);
-    if (w.skip) (void)hipFree(w.skip);
-    if (w.red) (void)hipFree(w.red);
-    if (w.hred) (void)hipHostFree(w.hred);
-}
 
 // one reflector: x = A(r0 : r0+m, col); left on A(r0 : r0+m, lc0 : lc1); right on B(0 : nr, r0 : r0+m)
 template <class S>
 void reflect(hipStream_t st, S* A, int64_t lda, int64_t r0, int64_t col, int64_t m, int64_t lc0,
              int64_t lc1, S* B, int64_t ldb, int64_t nr, QrWork<S>& w) {
-    hipLaunchKernelGGL((dev::hh_make_kernel<S>), dim3(1), dim3(1024), 0, st, A, lda, r0, col, m, w.v, w.skip);
+    hipLaunchKernelGGL((dev::hh_make_kernel<S>), dim3(1), dim3(1024), 0, st, A, lda, r0, col, m, w.v.template as<S>(),
+                       w.skip.template as<int>());
     if (lc1 > lc0)
         hipLaunchKernelGGL((dev::hh_left_kernel<S>), dim3(lc1 - lc0), dim3(256), 0, st, A, lda, r0, m, lc0,
-                           w.v, w.skip);
+                           w.v.template as<S>(), w.skip.template as<int>());
     if (nr > 0)
         hipLaunchKernelGGL((dev::hh_right_kernel<S>), dim3((nr + 15) / 16), dim3(256), 0, st, B, ldb, nr, r0,
-                           m, w.v, w.skip);
+                           m, w.v.template as<S>(), w.skip.template as<int>());
 }
 
 // to_hessenberg_dense (to_hessenberg.hpp:38-77) on H (device, n x n, in place)
@@ -335,41 +325,38 @@ int qr_decompose_t(hipStream_t st, S* R, int64_t m, int64_t n, S* Q, QrWork<S>& 
 template <class S>
 static int hessenberg_host(eigsol_ctx* ctx, int64_t n, const void* A, void* Hout) {
     hipStream_t st = ctx->stream;
-    S* H = nullptr;
-    EIGSOL_HIP(hipMalloc(&H, std::max<int64_t>(n * n, 1) * sizeof(S)));
+    DevBuf bH;
+    EIGSOL_TRY(bH.alloc(n * n * sizeof(S)));
+    S* const H = bH.as<S>();
     QrWork<S> w;
-    int rc = work_alloc(w, n);
-    if (rc == EIGSOL_OK && hipMemcpyAsync(H, A, n * n * sizeof(S), hipMemcpyHostToDevice, st) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "to_hessenberg: upload");
-    if (rc == EIGSOL_OK) rc = hessenberg_dev<S>(st, H, n, w);
-    if (rc == EIGSOL_OK && hipMemcpyAsync(Hout, H, n * n * sizeof(S), hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "to_hessenberg: download");
-    if (rc == EIGSOL_OK && stream_wait(st) != hipSuccess) rc = fail(EIGSOL_E_HIP, "to_hessenberg: sync");
-    work_free(w);
-    (void)hipFree(H);
-    return rc;
+    EIGSOL_TRY(w.alloc(n));
+    if (hipMemcpyAsync(H, A, n * n * sizeof(S), hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(EIGSOL_E_HIP, "to_hessenberg: upload");
+    EIGSOL_TRY(hessenberg_dev<S>(st, H, n, w));
+    if (hipMemcpyAsync(Hout, H, n * n * sizeof(S), hipMemcpyDeviceToHost, st) != hipSuccess)
+        return fail(EIGSOL_E_HIP, "to_hessenberg: download");
+    if (stream_wait(st) != hipSuccess) return fail(EIGSOL_E_HIP, "to_hessenberg: sync");
+    return EIGSOL_OK;
 }
 
 template <class S>
 static int qr_decompose_host(eigsol_ctx* ctx, int64_t m, int64_t n, const void* A, void* Qout, void* Rout) {
     hipStream_t st = ctx->stream;
-    S *R = nullptr, *Q = nullptr;
-    EIGSOL_HIP(hipMalloc(&R, m * n * sizeof(S)));
-    EIGSOL_HIP(hipMalloc(&Q, m * m * sizeof(S)));
+    DevBuf bR, bQ;
+    EIGSOL_TRY(bR.alloc(m * n * sizeof(S)));
+    EIGSOL_TRY(bQ.alloc(m * m * sizeof(S)));
+    S *const R = bR.as<S>(), *const Q = bQ.as<S>();
     QrWork<S> w;
-    int rc = work_alloc(w, m);
-    if (rc == EIGSOL_OK && hipMemcpyAsync(R, A, m * n * sizeof(S), hipMemcpyHostToDevice, st) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "qr_decompose: upload");
-    if (rc == EIGSOL_OK) rc = qr_decompose_t<S>(st, R, m, n, Q, w);
-    if (rc == EIGSOL_OK && Qout && hipMemcpyAsync(Qout, Q, m * m * sizeof(S), hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "qr_decompose: download Q");
-    if (rc == EIGSOL_OK && Rout && hipMemcpyAsync(Rout, R, m * n * sizeof(S), hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "qr_decompose: download R");
-    if (rc == EIGSOL_OK && stream_wait(st) != hipSuccess) rc = fail(EIGSOL_E_HIP, "qr_decompose: sync");
-    work_free(w);
-    (void)hipFree(R);
-    (void)hipFree(Q);
-    return rc;
+    EIGSOL_TRY(w.alloc(m));
+    if (hipMemcpyAsync(R, A, m * n * sizeof(S), hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(EIGSOL_E_HIP, "qr_decompose: upload");
+    EIGSOL_TRY(qr_decompose_t<S>(st, R, m, n, Q, w));
+    if (Qout && hipMemcpyAsync(Qout, Q, m * m * sizeof(S), hipMemcpyDeviceToHost, st) != hipSuccess)
+        return fail(EIGSOL_E_HIP, "qr_decompose: download Q");
+    if (Rout && hipMemcpyAsync(Rout, R, m * n * sizeof(S), hipMemcpyDeviceToHost, st) != hipSuccess)
+        return fail(EIGSOL_E_HIP, "qr_decompose: download R");
+    if (stream_wait(st) != hipSuccess) return fail(EIGSOL_E_HIP, "qr_decompose: sync");
+    return EIGSOL_OK;
 }
 
 // qr_eigenvalues_dense, reference algorithm (unshifted): Hessenberg, then H <- R Q until
@@ -378,14 +365,16 @@ template <class S>
 static int qr_unshifted_host(eigsol_ctx* ctx, int64_t n, const void* A, int max_iter, double tol,
                              void* eig, int32_t* iters, int32_t* conv) {
     hipStream_t st = ctx->stream;
-    S *H = nullptr, *Q = nullptr, *R = nullptr, *d = nullptr;
-    int rc = EIGSOL_OK;
-    if (hipMalloc(&H, n * n * sizeof(S)) != hipSuccess || hipMalloc(&Q, n * n * sizeof(S)) != hipSuccess ||
-        hipMalloc(&R, n * n * sizeof(S)) != hipSuccess || hipMalloc(&d, n * sizeof(S)) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: hipMalloc");
+    DevBuf bH, bQ, bR, bd;
+    EIGSOL_TRY(bH.alloc(n * n * sizeof(S)));
+    EIGSOL_TRY(bQ.alloc(n * n * sizeof(S)));
+    EIGSOL_TRY(bR.alloc(n * n * sizeof(S)));
+    EIGSOL_TRY(bd.alloc(n * sizeof(S)));
+    S *const H = bH.as<S>(), *const Q = bQ.as<S>(), *const R = bR.as<S>(), *const d = bd.as<S>();
     QrWork<S> w;
-    if (rc == EIGSOL_OK) rc = work_alloc(w, n);
-    if (rc == EIGSOL_OK && hipMemcpyAsync(H, A, n * n * sizeof(S), hipMemcpyHostToDevice, st) != hipSuccess)
+    EIGSOL_TRY(w.alloc(n));
+    int rc = EIGSOL_OK;
+    if (hipMemcpyAsync(H, A, n * n * sizeof(S), hipMemcpyHostToDevice, st) != hipSuccess)
         rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: upload");
     if (rc == EIGSOL_OK) rc = hessenberg_dev<S>(st, H, n, w);
     int iter = 0;
@@ -399,9 +388,9 @@ static int qr_unshifted_host(eigsol_ctx* ctx, int64_t n, const void* A, int max_
         rc = qr_decompose_t<S>(st, R, n, n, Q, w);
         if (rc != EIGSOL_OK) break;
         hipLaunchKernelGGL((dev::gemm_nn_kernel<S>), g, dim3(256), 0, st, R, Q, H, n);
-        hipLaunchKernelGGL((dev::subdiag_frob_kernel<S>), dim3(1), dim3(1024), 0, st, H, n, w.red);
-        const double* red = w.hred;
-        if (hipMemcpyAsync(w.hred, w.red, 2 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipLaunchKernelGGL((dev::subdiag_frob_kernel<S>), dim3(1), dim3(1024), 0, st, H, n, w.red.template as<double>());
+        const double* red = w.hred.template as<double>();
+        if (hipMemcpyAsync(w.hred.p, w.red.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
             stream_wait(st) != hipSuccess) {
             rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: convergence check");
             break;
@@ -419,8 +408,6 @@ static int qr_unshifted_host(eigsol_ctx* ctx, int64_t n, const void* A, int max_
     }
     if (iters) *iters = iter + 1;
     if (conv) *conv = converged ? 1 : 0;
-    work_free(w);
-    for (void* p : {(void*)H, (void*)Q, (void*)R, (void*)d}) (void)hipFree(p);
     return rc;
 }
 
@@ -457,12 +444,13 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
 static int qr_francis_host(eigsol_ctx* ctx, int64_t n, const double* A, int max_iter, double* wr,
                            double* wi, int32_t* iters, int32_t* conv) {
     hipStream_t st = ctx->stream;
-    double* H = nullptr;
-    int rc = EIGSOL_OK;
-    if (hipMalloc(&H, n * n * sizeof(double)) != hipSuccess) rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: hipMalloc");
+    DevBuf bH;
+    EIGSOL_TRY(bH.alloc(n * n * sizeof(double)));
+    double* const H = bH.as<double>();
     QrWork<double> w;
-    if (rc == EIGSOL_OK) rc = work_alloc(w, n);
-    if (rc == EIGSOL_OK && hipMemcpyAsync(H, A, n * n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
+    EIGSOL_TRY(w.alloc(n));
+    int rc = EIGSOL_OK;
+    if (hipMemcpyAsync(H, A, n * n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
         rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: upload");
     // the range guard (qr_range_guard above); matrices inside the range are untouched (bit-identical path)
     int escale = 0;
@@ -477,8 +465,6 @@ static int qr_francis_host(eigsol_ctx* ctx, int64_t n, const double* A, int max_
         }
     if (iters) *iters = sweeps;
     if (conv) *conv = failed ? 0 : 1;
-    work_free(w);
-    (void)hipFree(H);
     return rc;
 }
 
@@ -491,12 +477,13 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
 static int qr_francis_c128_host(eigsol_ctx* ctx, int64_t n, const void* A, int max_iter, cplx* w,
                                 int32_t* iters, int32_t* conv) {
     hipStream_t st = ctx->stream;
-    cplx* H = nullptr;
-    int rc = EIGSOL_OK;
-    if (hipMalloc(&H, n * n * sizeof(cplx)) != hipSuccess) rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: hipMalloc");
+    DevBuf bH;
+    EIGSOL_TRY(bH.alloc(n * n * sizeof(cplx)));
+    cplx* const H = bH.as<cplx>();
     QrWork<cplx> wk;
-    if (rc == EIGSOL_OK) rc = work_alloc(wk, n);
-    if (rc == EIGSOL_OK && hipMemcpyAsync(H, A, n * n * sizeof(cplx), hipMemcpyHostToDevice, st) != hipSuccess)
+    EIGSOL_TRY(wk.alloc(n));
+    int rc = EIGSOL_OK;
+    if (hipMemcpyAsync(H, A, n * n * sizeof(cplx), hipMemcpyHostToDevice, st) != hipSuccess)
         rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: upload");
     int escale = 0;
     if (rc == EIGSOL_OK) rc = qr_range_guard(st, reinterpret_cast<double*>(H), 2 * n * n, &escale);
@@ -510,8 +497,6 @@ static int qr_francis_c128_host(eigsol_ctx* ctx, int64_t n, const void* A, int m
         }
     if (iters) *iters = sweeps;
     if (conv) *conv = failed ? 0 : 1;
-    work_free(wk);
-    (void)hipFree(H);
     return rc;
 }
 

@@ -1,6 +1,6 @@
 // Host-side eigen-decomposition of a small complex matrix and the Ritz-value order, shared by the
 // block subspace iteration (subspace.hip, m <= 32) and the Krylov-Schur solver (krylov.hip,
-// m <= 64), plus the scoped device buffer both drivers allocate their workspaces with.
+// m <= 64).
 #pragma once
 
 #include <algorithm>
@@ -173,21 +173,6 @@ inline std::vector<int> ritz_order(const std::vector<cd>& w) {
     }
     return p;
 }
-
-struct DevBuf {
-    void* p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t bytes) {
-        EIGSOL_HIP(hipMalloc(&p, std::max<size_t>(bytes, 16)));
-        return EIGSOL_OK;
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
 
 template <class T> struct host_of { using type = double; };
 template <> struct host_of<cplx> { using type = cd; };

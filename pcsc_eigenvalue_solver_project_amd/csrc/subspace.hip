@@ -27,6 +27,7 @@
 
 #include "kernels_common.hpp"
 #include "linear_op.hpp"
+#include "scratch.hpp"
 #include "small_eig.hpp"
 
 namespace eigsol {
@@ -373,8 +374,7 @@ int launch_mul(const eigsol_ctx* ctx, const SI* In, int64_t n, int mi, int mo, c
     });
 }
 
-// small_eig, ritz_order, DevBuf and host_of: small_eig.hpp (shared with krylov.hip)
-using smalleig::DevBuf;
+// small_eig, ritz_order and host_of: small_eig.hpp (shared with krylov.hip)
 using smalleig::host_of;
 using smalleig::ritz_order;
 using smalleig::small_eig;

@@ -42,8 +42,8 @@
 #include <numeric>
 #include <vector>
 
-#include "cholesky.hpp"
 #include "mfma_rankk.hpp"
+#include "scratch.hpp"
 
 namespace eigsol {
 namespace dev {
@@ -549,22 +549,6 @@ __global__ __launch_bounds__(256) void svd_phase(S* Z, int len, S* Y, int leny) 
 // ============================================================================ host
 namespace {
 
-struct SvdEvents {
-    std::vector<hipEvent_t> ev;
-    ~SvdEvents() {
-        for (auto& x : ev)
-            if (x) (void)hipEventDestroy(x);
-    }
-    hipError_t create(size_t cnt) {
-        ev.assign(cnt, nullptr);
-        for (auto& x : ev) {
-            const hipError_t e = hipEventCreate(&x);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
-};
-
 constexpr int kSvdInnerSweeps = 30;   // cyclic Jacobi converges quadratically: a bound that ends the kernel, not a knob
 
 // the pairs of one sweep, step by step (first[s] .. first[s + 1])
@@ -598,9 +582,9 @@ void svd_schedule(int n, std::vector<dev::SvdPair>& pairs, std::vector<int>& fir
 template <class S>
 int svd_complete(hipStream_t st, S* Uo, int m, int k, const std::vector<int>& zero_cols) {
     DevBuf dv, dcoef, dnrm;
-    EIGSOL_HIP(dv.alloc((size_t)m * sizeof(S)));
-    EIGSOL_HIP(dcoef.alloc((size_t)k * sizeof(S)));
-    EIGSOL_HIP(dnrm.alloc(sizeof(double)));
+    EIGSOL_TRY(dv.alloc((size_t)m * sizeof(S)));
+    EIGSOL_TRY(dcoef.alloc((size_t)k * sizeof(S)));
+    EIGSOL_TRY(dnrm.alloc(sizeof(double)));
     const unsigned gm = (unsigned)((m + 255) / 256);
     size_t next = 0;
     // 0.5 holds for every matrix met so far; the lower thresholds only guarantee that the loop ends
@@ -651,17 +635,18 @@ int svd_host(eigsol_ctx* ctx, int64_t m0, int64_t n0, const void* A_host, int ma
     for (int s = 0; s < nsteps; ++s) maxnp = std::max(maxnp, first[s + 1] - first[s]);
     const int nchunk = (m + dev::kSvdGramRows - 1) / dev::kSvdGramRows;
 
-    SvdEvents E, T;   // E: start, end of the sweeps, end; T: four per step
-    EIGSOL_HIP(E.create(3));
-    EIGSOL_HIP(T.create((size_t)nsteps * 4));
+    StageClock E, T;   // E: start, end of the sweeps, end; T: four marks per step (Gram, pair Jacobi, apply between them)
+    EIGSOL_TRY(E.start(2));
+    EIGSOL_TRY(T.start(4 * nsteps - 1));
+    std::vector<double> tms((size_t)4 * nsteps);
     DevBuf dA, dW, dV, dpairs, dG, dJ, dpmax, dpflag, dmx;
-    EIGSOL_HIP(dW.alloc((size_t)cnt * sizeof(double)));
-    EIGSOL_HIP(dmx.alloc(2 * 256 * sizeof(double)));
+    EIGSOL_TRY(dW.alloc((size_t)cnt * sizeof(double)));
+    EIGSOL_TRY(dmx.alloc(2 * 256 * sizeof(double)));
     // ---- 0. set-up
     DevBuf& dIn = wide ? dA : dW;
-    if (wide) EIGSOL_HIP(dA.alloc((size_t)cnt * sizeof(double)));
+    if (wide) EIGSOL_TRY(dA.alloc((size_t)cnt * sizeof(double)));
     EIGSOL_HIP(hipMemcpyAsync(dIn.p, A_host, (size_t)cnt * sizeof(double), hipMemcpyHostToDevice, st));
-    EIGSOL_HIP(hipEventRecord(E.ev[0], st));
+    EIGSOL_TRY(E.mark(0, st));
     hipLaunchKernelGGL(dev::svd_absmax, dim3(256), dim3(256), 0, st, dIn.as<double>(), cnt, dmx.as<double>());
     EIGSOL_HIP(hipGetLastError());
     double hmx[512];
@@ -685,16 +670,16 @@ int svd_host(eigsol_ctx* ctx, int64_t m0, int64_t n0, const void* A_host, int ma
     }
     EIGSOL_HIP(hipGetLastError());
     if (accV) {
-        EIGSOL_HIP(dV.alloc((size_t)n * n * sizeof(S)));
+        EIGSOL_TRY(dV.alloc((size_t)n * n * sizeof(S)));
         EIGSOL_HIP(hipMemsetAsync(dV.p, 0, (size_t)n * n * sizeof(S), st));
         hipLaunchKernelGGL(dev::svd_set_identity<S>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dV.as<S>(), n);
     }
-    EIGSOL_HIP(dpairs.alloc((size_t)npair * sizeof(dev::SvdPair)));
+    EIGSOL_TRY(dpairs.alloc((size_t)npair * sizeof(dev::SvdPair)));
     EIGSOL_HIP(hipMemcpyAsync(dpairs.p, pairs.data(), (size_t)npair * sizeof(dev::SvdPair), hipMemcpyHostToDevice, st));
-    EIGSOL_HIP(dG.alloc((size_t)maxnp * nchunk * P * P * sizeof(S)));
-    EIGSOL_HIP(dJ.alloc((size_t)maxnp * P * P * sizeof(S)));
-    EIGSOL_HIP(dpmax.alloc((size_t)npair * sizeof(double)));
-    EIGSOL_HIP(dpflag.alloc((size_t)npair * sizeof(int)));
+    EIGSOL_TRY(dG.alloc((size_t)maxnp * nchunk * P * P * sizeof(S)));
+    EIGSOL_TRY(dJ.alloc((size_t)maxnp * P * P * sizeof(S)));
+    EIGSOL_TRY(dpmax.alloc((size_t)npair * sizeof(double)));
+    EIGSOL_TRY(dpflag.alloc((size_t)npair * sizeof(int)));
     constexpr size_t lds = dev::svd_jacobi_lds<S>();
     EIGSOL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dev::svd_pair_jacobi<S>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -715,28 +700,23 @@ int svd_host(eigsol_ctx* ctx, int64_t m0, int64_t n0, const void* A_host, int ma
             const int f = first[s], np = first[s + 1] - f;
             if (np == 0) continue;
             const dev::SvdPair* pp = dpairs.as<dev::SvdPair>() + f;
-            EIGSOL_HIP(hipEventRecord(T.ev[4 * s], st));
+            EIGSOL_TRY(T.mark(4 * s, st));
             hipLaunchKernelGGL(dev::svd_gram<S>, dim3((unsigned)nchunk, (unsigned)np), dim3(256), 0, st, dW.as<S>(), m, pp, nchunk,
                                dG.as<S>());
-            EIGSOL_HIP(hipEventRecord(T.ev[4 * s + 1], st));
+            EIGSOL_TRY(T.mark(4 * s + 1, st));
             hipLaunchKernelGGL(dev::svd_pair_jacobi<S>, dim3((unsigned)np), dim3(256), lds, st, dG.as<S>(), nchunk, tol,
                                kSvdInnerSweeps, dJ.as<S>(), dpmax.as<double>() + f, dpflag.as<int>() + f);
-            EIGSOL_HIP(hipEventRecord(T.ev[4 * s + 2], st));
+            EIGSOL_TRY(T.mark(4 * s + 2, st));
             hipLaunchKernelGGL(dev::svd_apply<S>, dim3(ga, (unsigned)np, accV ? 2u : 1u), dim3(256), 0, st, dW.as<S>(), m,
                                dV.as<S>(), n, pp, dJ.as<S>(), dpflag.as<int>() + f);
-            EIGSOL_HIP(hipEventRecord(T.ev[4 * s + 3], st));
+            EIGSOL_TRY(T.mark(4 * s + 3, st));
         }
         EIGSOL_HIP(hipGetLastError());
         EIGSOL_HIP(hipMemcpyAsync(pmax.data(), dpmax.p, (size_t)npair * sizeof(double), hipMemcpyDeviceToHost, st));
         EIGSOL_HIP(stream_wait(st));
-        for (int s = 0; s < nsteps; ++s) {
-            if (first[s + 1] == first[s]) continue;
-            for (int q = 0; q < 3; ++q) {
-                float t = 0.f;
-                (void)hipEventElapsedTime(&t, T.ev[4 * s + q], T.ev[4 * s + q + 1]);
-                ms[q] += t;
-            }
-        }
+        T.read(tms.data(), 4 * nsteps - 1);   // a step without pairs was not marked: zeros
+        for (int s = 0; s < nsteps; ++s)
+            for (int q = 0; q < 3; ++q) ms[q] += tms[4 * s + q];
         sweeps = sweep;
         above = 0;
         for (int i = 0; i < npair; ++i) {
@@ -745,12 +725,12 @@ int svd_host(eigsol_ctx* ctx, int64_t m0, int64_t n0, const void* A_host, int ma
         }
         if (above == 0) break;
     }
-    EIGSOL_HIP(hipEventRecord(E.ev[1], st));
+    EIGSOL_TRY(E.mark(1, st));
 
     // ---- 4. finish
     DevBuf dnrm, dperm, dUo, dVo;
     std::vector<double> nrm(n);
-    EIGSOL_HIP(dnrm.alloc((size_t)n * sizeof(double)));
+    EIGSOL_TRY(dnrm.alloc((size_t)n * sizeof(double)));
     hipLaunchKernelGGL(dev::svd_colnorm<S>, dim3((unsigned)n), dim3(256), 0, st, dW.as<S>(), m, (int64_t)m, dnrm.as<double>());
     EIGSOL_HIP(hipGetLastError());
     EIGSOL_HIP(hipMemcpyAsync(nrm.data(), dnrm.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -760,10 +740,10 @@ int svd_host(eigsol_ctx* ctx, int64_t m0, int64_t n0, const void* A_host, int ma
     std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return nrm[a] > nrm[b]; });
     for (int j = 0; j < n; ++j) s_out[j] = std::ldexp(nrm[perm[j]], -escale);
     if (anyvec) {
-        EIGSOL_HIP(dperm.alloc((size_t)n * sizeof(int)));
+        EIGSOL_TRY(dperm.alloc((size_t)n * sizeof(int)));
         EIGSOL_HIP(hipMemcpyAsync(dperm.p, perm.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
-        if (needU) EIGSOL_HIP(dUo.alloc((size_t)m * n * sizeof(S)));
-        if (accV) EIGSOL_HIP(dVo.alloc((size_t)n * n * sizeof(S)));
+        if (needU) EIGSOL_TRY(dUo.alloc((size_t)m * n * sizeof(S)));
+        if (accV) EIGSOL_TRY(dVo.alloc((size_t)n * n * sizeof(S)));
         hipLaunchKernelGGL(dev::svd_gather<S>, dim3((unsigned)n), dim3(256), 0, st, dW.as<S>(), m, dV.as<S>(), n, dperm.as<int>(),
                            dnrm.as<double>(), dUo.as<S>(), dVo.as<S>());
         EIGSOL_HIP(hipGetLastError());
@@ -783,11 +763,11 @@ int svd_host(eigsol_ctx* ctx, int64_t m0, int64_t n0, const void* A_host, int ma
         if (outW) EIGSOL_HIP(hipMemcpyAsync(outW, dUo.p, (size_t)m * n * sizeof(S), hipMemcpyDeviceToHost, st));
         if (outV) EIGSOL_HIP(hipMemcpyAsync(outV, dVo.p, (size_t)n * n * sizeof(S), hipMemcpyDeviceToHost, st));
     }
-    EIGSOL_HIP(hipEventRecord(E.ev[2], st));
+    EIGSOL_TRY(E.mark(2, st));
     EIGSOL_HIP(hipStreamSynchronize(st));
-    float tf = 0.f;
-    (void)hipEventElapsedTime(&tf, E.ev[1], E.ev[2]);
-    ms[3] = tf;
+    double te[2];
+    E.read(te, 2);
+    ms[3] = te[1];
     for (int q = 0; q < 4; ++q) ctx->svd_ms[q] = ms[q];
     if (sweeps_out) *sweeps_out = sweeps;
     if (nc_out) *nc_out = above;

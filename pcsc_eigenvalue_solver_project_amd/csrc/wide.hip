@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "internal.hpp"
+#include "scratch.hpp"
 #include "shifted.hpp"
 #include "wide.hpp"
 
@@ -569,9 +570,9 @@ static int csr_shadow(eigsol_csr* A) {
     const int64_t n = A->nrows, nnz = A->nnz;
     std::vector<int32_t> rp(n + 1), ci(std::max<int64_t>(nnz, 1));
     std::vector<double> hv(std::max<int64_t>(nnz, 1) * (cx ? 2 : 1));
-    double* dv = nullptr;
-    EIGSOL_HIP(hipMalloc(&dv, hv.size() * sizeof(double)));
-    int rc = EIGSOL_OK;
+    DevBuf bdv;
+    EIGSOL_TRY(bdv.alloc(hv.size() * sizeof(double)));
+    double* const dv = bdv.as<double>();
     if (nnz) {
         if (cx)
             hipLaunchKernelGGL((wdev::hi_kernel<cdd>), dim3(nblk(nnz)), dim3(wdev::kT), 0, st, nnz,
@@ -584,9 +585,8 @@ static int csr_shadow(eigsol_csr* A) {
         (nnz && hipMemcpyAsync(ci.data(), A->col, nnz * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess) ||
         (nnz && hipMemcpyAsync(hv.data(), dv, hv.size() * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) ||
         stream_wait(st) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "double-double matrix: fp64 shadow download");
-    (void)hipFree(dv);
-    EIGSOL_TRY(rc);
+        return fail(EIGSOL_E_HIP, "double-double matrix: fp64 shadow download");
+    bdv.release();
     return csr_upload(A->ctx, cx ? EIGSOL_C128 : EIGSOL_F64, n, A->ncols, nnz, rp.data(), ci.data(), hv.data(),
                       &A->shadow, 0);
 }
@@ -985,34 +985,26 @@ namespace {
 
 template <class T>
 struct WQr {
-    T* v = nullptr;
-    int* skip = nullptr;
-    dd* red = nullptr;
+    DevBuf v, skip, red;   // the reflector (n scalars), its skip flag, the convergence check's two dd
+    int alloc(int64_t n) {
+        EIGSOL_TRY(v.alloc(n * sizeof(T)));
+        EIGSOL_TRY(skip.alloc(64));
+        return red.alloc(64);
+    }
 };
-template <class T>
-int wqr_alloc(WQr<T>& w, int64_t n) {
-    EIGSOL_HIP(hipMalloc(&w.v, std::max<int64_t>(n, 1) * sizeof(T)));
-    EIGSOL_HIP(hipMalloc(&w.skip, 64));
-    EIGSOL_HIP(hipMalloc(&w.red, 64));
-    return EIGSOL_OK;
-}
-template <class T>
-void wqr_free(WQr<T>& w) {
-    for (void* p : {(void*)w.v, (void*)w.skip, (void*)w.red})
-        if (p) (void)hipFree(p);
-}
 
 // one reflector: x = A(r0 : r0+m, col); left on A(r0 : r0+m, lc0 : lc1); right on B(0 : nr, r0 : r0+m)
 template <class T>
 void wreflect(hipStream_t st, T* A, int64_t lda, int64_t r0, int64_t col, int64_t m, int64_t lc0, int64_t lc1, T* B,
               int64_t ldb, int64_t nr, WQr<T>& w) {
-    hipLaunchKernelGGL((wdev::hh_make_kernel<T>), dim3(1), dim3(1024), 0, st, A, lda, r0, col, m, w.v, w.skip);
+    hipLaunchKernelGGL((wdev::hh_make_kernel<T>), dim3(1), dim3(1024), 0, st, A, lda, r0, col, m,
+                       w.v.template as<T>(), w.skip.template as<int>());
     if (lc1 > lc0)
-        hipLaunchKernelGGL((wdev::hh_left_kernel<T>), dim3(lc1 - lc0), dim3(wdev::kT), 0, st, A, lda, r0, m, lc0, w.v,
-                           w.skip);
+        hipLaunchKernelGGL((wdev::hh_left_kernel<T>), dim3(lc1 - lc0), dim3(wdev::kT), 0, st, A, lda, r0, m, lc0,
+                           w.v.template as<T>(), w.skip.template as<int>());
     if (nr > 0)
         hipLaunchKernelGGL((wdev::hh_right_kernel<T>), dim3((nr + 15) / 16), dim3(wdev::kT), 0, st, B, ldb, nr, r0, m,
-                           w.v, w.skip);
+                           w.v.template as<T>(), w.skip.template as<int>());
 }
 
 // to_hessenberg_dense (to_hessenberg.hpp:38-77)
@@ -1039,44 +1031,38 @@ int wqr_decompose(hipStream_t st, T* R, int64_t m, int64_t n, T* Q, WQr<T>& w) {
 template <class T>
 int whessenberg_host(eigsol_ctx* ctx, int64_t n, const void* A, void* Hout) {
     hipStream_t st = ctx->stream;
-    T* H = nullptr;
-    EIGSOL_HIP(hipMalloc(&H, std::max<int64_t>(n * n, 1) * sizeof(T)));
+    DevBuf bH;
+    EIGSOL_TRY(bH.alloc(n * n * sizeof(T)));
+    T* const H = bH.as<T>();
     WQr<T> w;
-    int rc = wqr_alloc(w, n);
-    if (rc == EIGSOL_OK && hipMemcpyAsync(H, A, n * n * sizeof(T), hipMemcpyHostToDevice, st) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "to_hessenberg: upload");
-    if (rc == EIGSOL_OK) rc = whessenberg<T>(st, H, n, w);
-    if (rc == EIGSOL_OK && (hipMemcpyAsync(Hout, H, n * n * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                            stream_wait(st) != hipSuccess))
-        rc = fail(EIGSOL_E_HIP, "to_hessenberg: download");
-    wqr_free(w);
-    (void)hipFree(H);
-    return rc;
+    EIGSOL_TRY(w.alloc(n));
+    if (hipMemcpyAsync(H, A, n * n * sizeof(T), hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(EIGSOL_E_HIP, "to_hessenberg: upload");
+    EIGSOL_TRY(whessenberg<T>(st, H, n, w));
+    if (hipMemcpyAsync(Hout, H, n * n * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        stream_wait(st) != hipSuccess)
+        return fail(EIGSOL_E_HIP, "to_hessenberg: download");
+    return EIGSOL_OK;
 }
 
 template <class T>
 int wqr_decompose_host(eigsol_ctx* ctx, int64_t m, int64_t n, const void* A, void* Qout, void* Rout) {
     hipStream_t st = ctx->stream;
-    T *R = nullptr, *Q = nullptr;
-    EIGSOL_HIP(hipMalloc(&R, m * n * sizeof(T)));
-    if (hipMalloc(&Q, m * m * sizeof(T)) != hipSuccess) {
-        (void)hipFree(R);
-        return fail(EIGSOL_E_HIP, "qr_decompose: hipMalloc");
-    }
+    DevBuf bR, bQ;
+    EIGSOL_TRY(bR.alloc(m * n * sizeof(T)));
+    EIGSOL_TRY(bQ.alloc(m * m * sizeof(T)));
+    T *const R = bR.as<T>(), *const Q = bQ.as<T>();
     WQr<T> w;
-    int rc = wqr_alloc(w, m);
-    if (rc == EIGSOL_OK && hipMemcpyAsync(R, A, m * n * sizeof(T), hipMemcpyHostToDevice, st) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "qr_decompose: upload");
-    if (rc == EIGSOL_OK) rc = wqr_decompose<T>(st, R, m, n, Q, w);
-    if (rc == EIGSOL_OK && Qout && hipMemcpyAsync(Qout, Q, m * m * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "qr_decompose: download Q");
-    if (rc == EIGSOL_OK && Rout && hipMemcpyAsync(Rout, R, m * n * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "qr_decompose: download R");
-    if (rc == EIGSOL_OK && stream_wait(st) != hipSuccess) rc = fail(EIGSOL_E_HIP, "qr_decompose: sync");
-    wqr_free(w);
-    (void)hipFree(R);
-    (void)hipFree(Q);
-    return rc;
+    EIGSOL_TRY(w.alloc(m));
+    if (hipMemcpyAsync(R, A, m * n * sizeof(T), hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(EIGSOL_E_HIP, "qr_decompose: upload");
+    EIGSOL_TRY(wqr_decompose<T>(st, R, m, n, Q, w));
+    if (Qout && hipMemcpyAsync(Qout, Q, m * m * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess)
+        return fail(EIGSOL_E_HIP, "qr_decompose: download Q");
+    if (Rout && hipMemcpyAsync(Rout, R, m * n * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess)
+        return fail(EIGSOL_E_HIP, "qr_decompose: download R");
+    if (stream_wait(st) != hipSuccess) return fail(EIGSOL_E_HIP, "qr_decompose: sync");
+    return EIGSOL_OK;
 }
 
 // qr_eigenvalues_dense (qr_eigenvalues.hpp:61-104): Hessenberg, then H <- R Q until
@@ -1085,14 +1071,16 @@ template <class T>
 int wqr_unshifted_host(eigsol_ctx* ctx, int64_t n, const void* A, int max_iter, double tol, void* eig, int32_t* iters,
                        int32_t* conv) {
     hipStream_t st = ctx->stream;
-    T *H = nullptr, *Q = nullptr, *R = nullptr, *d = nullptr;
-    int rc = EIGSOL_OK;
-    if (hipMalloc(&H, n * n * sizeof(T)) != hipSuccess || hipMalloc(&Q, n * n * sizeof(T)) != hipSuccess ||
-        hipMalloc(&R, n * n * sizeof(T)) != hipSuccess || hipMalloc(&d, n * sizeof(T)) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: hipMalloc");
+    DevBuf bH, bQ, bR, bd;
+    EIGSOL_TRY(bH.alloc(n * n * sizeof(T)));
+    EIGSOL_TRY(bQ.alloc(n * n * sizeof(T)));
+    EIGSOL_TRY(bR.alloc(n * n * sizeof(T)));
+    EIGSOL_TRY(bd.alloc(n * sizeof(T)));
+    T *const H = bH.as<T>(), *const Q = bQ.as<T>(), *const R = bR.as<T>(), *const d = bd.as<T>();
     WQr<T> w;
-    if (rc == EIGSOL_OK) rc = wqr_alloc(w, n);
-    if (rc == EIGSOL_OK && hipMemcpyAsync(H, A, n * n * sizeof(T), hipMemcpyHostToDevice, st) != hipSuccess)
+    EIGSOL_TRY(w.alloc(n));
+    int rc = EIGSOL_OK;
+    if (hipMemcpyAsync(H, A, n * n * sizeof(T), hipMemcpyHostToDevice, st) != hipSuccess)
         rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: upload");
     if (rc == EIGSOL_OK) rc = whessenberg<T>(st, H, n, w);
     int iter = 0;
@@ -1106,9 +1094,10 @@ int wqr_unshifted_host(eigsol_ctx* ctx, int64_t n, const void* A, int max_iter, 
         rc = wqr_decompose<T>(st, R, n, n, Q, w);
         if (rc != EIGSOL_OK) break;
         hipLaunchKernelGGL((wdev::gemm_nn_kernel<T>), g, dim3(wdev::kT), 0, st, R, Q, H, n);
-        hipLaunchKernelGGL((wdev::subdiag_frob_kernel<T>), dim3(1), dim3(wdev::kT), 0, st, H, n, w.red);
+        hipLaunchKernelGGL((wdev::subdiag_frob_kernel<T>), dim3(1), dim3(wdev::kT), 0, st, H, n,
+                           w.red.template as<dd>());
         dd red[2];
-        if (hipMemcpyAsync(red, w.red, sizeof(red), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        if (hipMemcpyAsync(red, w.red.p, sizeof(red), hipMemcpyDeviceToHost, st) != hipSuccess ||
             stream_wait(st) != hipSuccess) {
             rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: convergence check");
             break;
@@ -1128,9 +1117,6 @@ int wqr_unshifted_host(eigsol_ctx* ctx, int64_t n, const void* A, int max_iter, 
     }
     if (iters) *iters = iter + 1;
     if (conv) *conv = converged ? 1 : 0;
-    wqr_free(w);
-    for (void* p : {(void*)H, (void*)Q, (void*)R, (void*)d})
-        if (p) (void)hipFree(p);
     return rc;
 }
 
@@ -1449,35 +1435,29 @@ static int hyman_refine(hipStream_t st, const T* H, int64_t n, const cdd* l0, in
     std::vector<int32_t> gptr, gmem, blk(count);
     hyman_groups(l0, count, gptr, gmem);
     const int64_t groups = (int64_t)gptr.size() - 1;
-    cdd *dl0 = nullptr, *dl1 = nullptr;
-    int32_t* di = nullptr;   // steps | blocks | group pointers | group members
-    int rc = EIGSOL_OK;
-    if (hipMalloc(&dl0, count * sizeof(cdd)) != hipSuccess || hipMalloc(&dl1, count * sizeof(cdd)) != hipSuccess ||
-        hipMalloc(&di, (3 * count + groups + 1) * sizeof(int32_t)) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: hipMalloc (refinement)");
+    DevBuf bl0, bl1, bi;   // bi: steps | blocks | group pointers | group members
+    EIGSOL_TRY(bl0.alloc(count * sizeof(cdd)));
+    EIGSOL_TRY(bl1.alloc(count * sizeof(cdd)));
+    EIGSOL_TRY(bi.alloc((3 * count + groups + 1) * sizeof(int32_t)));
+    cdd *const dl0 = bl0.as<cdd>(), *const dl1 = bl1.as<cdd>();
+    int32_t* const di = bi.as<int32_t>();
     int32_t *dsteps = di, *dblk = di + count, *dgptr = di + 2 * count, *dgmem = di + 2 * count + groups + 1;
-    if (rc == EIGSOL_OK &&
-        (hipMemcpyAsync(dl0, l0, count * sizeof(cdd), hipMemcpyHostToDevice, st) != hipSuccess ||
-         hipMemcpyAsync(dgptr, gptr.data(), (groups + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess ||
-         hipMemcpyAsync(dgmem, gmem.data(), count * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess))
-        rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: upload eigenvalues");
-    if (rc == EIGSOL_OK) {
-        const int R = (int)((n + wqdev::kHyT - 1) / wqdev::kHyT);
-        const int ni = (int)n;
-        if (R <= 1) hyman_launch<T, 1>(st, H, ni, dl0, dgptr, dgmem, dl1, dsteps, dblk, groups);
-        else if (R <= 2) hyman_launch<T, 2>(st, H, ni, dl0, dgptr, dgmem, dl1, dsteps, dblk, groups);
-        else if (R <= 4) hyman_launch<T, 4>(st, H, ni, dl0, dgptr, dgmem, dl1, dsteps, dblk, groups);
-        else hyman_launch<T, 8>(st, H, ni, dl0, dgptr, dgmem, dl1, dsteps, dblk, groups);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(l1, dl1, count * sizeof(cdd), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipMemcpyAsync(steps, dsteps, count * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipMemcpyAsync(blk.data(), dblk, count * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            stream_wait(st) != hipSuccess)
-            rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: double-double refinement");
-    }
-    for (void* p : {(void*)dl0, (void*)dl1, (void*)di})
-        if (p) (void)hipFree(p);
-    if (rc != EIGSOL_OK) return rc;
+    if (hipMemcpyAsync(dl0, l0, count * sizeof(cdd), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(dgptr, gptr.data(), (groups + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(dgmem, gmem.data(), count * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(EIGSOL_E_HIP, "qr_eigenvalues: upload eigenvalues");
+    const int R = (int)((n + wqdev::kHyT - 1) / wqdev::kHyT);
+    const int ni = (int)n;
+    if (R <= 1) hyman_launch<T, 1>(st, H, ni, dl0, dgptr, dgmem, dl1, dsteps, dblk, groups);
+    else if (R <= 2) hyman_launch<T, 2>(st, H, ni, dl0, dgptr, dgmem, dl1, dsteps, dblk, groups);
+    else if (R <= 4) hyman_launch<T, 4>(st, H, ni, dl0, dgptr, dgmem, dl1, dsteps, dblk, groups);
+    else hyman_launch<T, 8>(st, H, ni, dl0, dgptr, dgmem, dl1, dsteps, dblk, groups);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(l1, dl1, count * sizeof(cdd), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(steps, dsteps, count * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(blk.data(), dblk, count * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        stream_wait(st) != hipSuccess)
+        return fail(EIGSOL_E_HIP, "qr_eigenvalues: double-double refinement");
     // no silent collisions: of two values that ended on the same root of the same block, the later
     // keeps its start (a value that already kept it has nothing to give back)
     near_pairs(l1, count, 0x1p-96, [&](int32_t i, int32_t j) {
@@ -1496,16 +1476,17 @@ int wqr_francis_host(eigsol_ctx* ctx, int64_t n, const void* A, int max_iter, vo
         return fail(EIGSOL_E_UNSUPPORTED, "qr_eigenvalues: the double-double Francis refinement handles n <= 8192");
     constexpr bool cx = std::is_same_v<T, cdd>;
     hipStream_t st = ctx->stream;
-    T* H = nullptr;
-    double* H64 = nullptr;
-    unsigned long long* damax = nullptr;
-    int rc = EIGSOL_OK;
-    if (hipMalloc(&H, n * n * sizeof(T)) != hipSuccess || hipMalloc(&H64, n * n * (cx ? 16 : 8)) != hipSuccess ||
-        hipMalloc(&damax, 64) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: hipMalloc");
+    DevBuf bH, bH64, bamax;
+    EIGSOL_TRY(bH.alloc(n * n * sizeof(T)));
+    EIGSOL_TRY(bH64.alloc(n * n * (cx ? 16 : 8)));
+    EIGSOL_TRY(bamax.alloc(64));
+    T* const H = bH.as<T>();
+    double* const H64 = bH64.as<double>();
+    unsigned long long* const damax = bamax.as<unsigned long long>();
     WQr<T> w;
-    if (rc == EIGSOL_OK) rc = wqr_alloc(w, n);
-    if (rc == EIGSOL_OK && hipMemcpyAsync(H, A, n * n * sizeof(T), hipMemcpyHostToDevice, st) != hipSuccess)
+    EIGSOL_TRY(w.alloc(n));
+    int rc = EIGSOL_OK;
+    if (hipMemcpyAsync(H, A, n * n * sizeof(T), hipMemcpyHostToDevice, st) != hipSuccess)
         rc = fail(EIGSOL_E_HIP, "qr_eigenvalues: upload");
     if (rc == EIGSOL_OK) rc = whessenberg<T>(st, H, n, w);
     // fp64 rounding of H, with LAPACK xGEEV's range guard (max |h| outside [smlnum, 1 / smlnum]:
@@ -1568,9 +1549,6 @@ int wqr_francis_host(eigsol_ctx* ctx, int64_t n, const void* A, int max_iter, vo
     }
     if (iters) *iters = sweeps;
     if (conv) *conv = failed ? 0 : 1;
-    wqr_free(w);
-    for (void* p : {(void*)H, (void*)H64, (void*)damax})
-        if (p) (void)hipFree(p);
     return rc;
 }
 
@@ -1582,16 +1560,15 @@ int hyman_refine_host(eigsol_ctx* ctx, int64_t n, const void* Hh, int64_t count,
     if (n > (int64_t)wqdev::kHyT * kHyMaxRows)
         return fail(EIGSOL_E_UNSUPPORTED, "eigsol_hyman_refine: the double-double refinement handles n <= 8192");
     hipStream_t st = ctx->stream;
-    T* H = nullptr;
-    int rc = EIGSOL_OK;
-    if (hipMalloc(&H, n * n * sizeof(T)) != hipSuccess) rc = fail(EIGSOL_E_HIP, "eigsol_hyman_refine: hipMalloc");
-    if (rc == EIGSOL_OK && hipMemcpyAsync(H, Hh, n * n * sizeof(T), hipMemcpyHostToDevice, st) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "eigsol_hyman_refine: upload");
-    if (rc == EIGSOL_OK) rc = hyman_refine<T>(st, H, n, starts, count, refined, steps);
-    for (int64_t i = 0; i < count && rc == EIGSOL_OK; ++i)
+    DevBuf bH;
+    EIGSOL_TRY(bH.alloc(n * n * sizeof(T)));
+    T* const H = bH.as<T>();
+    if (hipMemcpyAsync(H, Hh, n * n * sizeof(T), hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(EIGSOL_E_HIP, "eigsol_hyman_refine: upload");
+    EIGSOL_TRY(hyman_refine<T>(st, H, n, starts, count, refined, steps));
+    for (int64_t i = 0; i < count; ++i)
         if (steps[i] < 0) steps[i] = -1;
-    if (H) (void)hipFree(H);
-    return rc;
+    return EIGSOL_OK;
 }
 
 }  // namespace

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "kernels_common.hpp"
+#include "scratch.hpp"
 
 namespace eigsol {
 namespace dev {
@@ -789,16 +790,17 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
                        int32_t* fail_out) {
     hipStream_t st = ctx->stream;
     const double eps = 2.220446049250313e-16;
-    cplx *dw = nullptr, *dds = nullptr, *dU = nullptr, *dsh = nullptr;
-    int* dinfo = nullptr;
+    DevBuf bw, bds, bU, bsh, binfo, bV;
+    EIGSOL_TRY(bw.alloc(n * sizeof(cplx)));
+    EIGSOL_TRY(bds.alloc(2 * n * sizeof(cplx)));
+    EIGSOL_TRY(bU.alloc((size_t)dev::kZMaxGroups * dev::kZWin * dev::kZWin * sizeof(cplx)));
+    EIGSOL_TRY(bsh.alloc(2 * dev::kZMaxBulges * sizeof(cplx)));
+    EIGSOL_TRY(binfo.alloc(64));
+    EIGSOL_TRY(bV.alloc((size_t)dev::kZSmall * dev::kZSmall * sizeof(cplx)));   // the AED window's unitary factor
+    cplx *const dw = bw.as<cplx>(), *const dds = bds.as<cplx>(), *const dU = bU.as<cplx>(), *const dsh = bsh.as<cplx>();
+    cplx* const dV = bV.as<cplx>();
+    int* const dinfo = binfo.as<int>();
     int rc = EIGSOL_OK;
-    if (hipMalloc(&dw, n * sizeof(cplx)) != hipSuccess || hipMalloc(&dds, 2 * n * sizeof(cplx)) != hipSuccess ||
-        hipMalloc(&dU, (size_t)dev::kZMaxGroups * dev::kZWin * dev::kZWin * sizeof(cplx)) != hipSuccess ||
-        hipMalloc(&dsh, 2 * dev::kZMaxBulges * sizeof(cplx)) != hipSuccess || hipMalloc(&dinfo, 64) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "complex QR: hipMalloc");
-    cplx* dV = nullptr;   // the AED window's unitary factor
-    if (rc == EIGSOL_OK && hipMalloc(&dV, (size_t)dev::kZSmall * dev::kZSmall * sizeof(cplx)) != hipSuccess)
-        rc = fail(EIGSOL_E_HIP, "complex QR: hipMalloc");
     // every per-sweep transfer goes through pinned host memory: a pageable hipMemcpyAsync is staged
     // by the runtime and waited for with a sleeping wait, ~1 ms per copy (round-4 kernel trace of
     // 4096^2: 1.12 s of 2.8 s idle after such copies, tools/gap_analysis.py)
@@ -806,11 +808,11 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
         int info[8];
         cplx sh[2 * dev::kZMaxBulges];
     };
-    Staging* hp = nullptr;
-    cplx* ds = nullptr;   // deflation scans: diagonal [0, n), subdiagonal [n, 2n)
-    if (rc == EIGSOL_OK && (hipHostMalloc(&hp, sizeof(Staging), hipHostMallocDefault) != hipSuccess ||
-                            hipHostMalloc(&ds, 2 * n * sizeof(cplx), hipHostMallocDefault) != hipSuccess))
-        rc = fail(EIGSOL_E_HIP, "complex QR: hipHostMalloc");
+    PinBuf bhp, bhs;
+    EIGSOL_TRY(bhp.alloc(sizeof(Staging)));
+    EIGSOL_TRY(bhs.alloc(2 * n * sizeof(cplx)));
+    Staging* const hp = bhp.as<Staging>();
+    cplx* const ds = bhs.as<cplx>();   // deflation scans: diagonal [0, n), subdiagonal [n, 2n)
     int sweeps = 0, failed = 0, stall = 0;
     int st_sweeps = 0, st_aed = 0, st_aed_defl = 0, st_small = 0;
     static const bool stats = std::getenv("EIGSOL_QR_STATS") != nullptr;
@@ -1005,10 +1007,6 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
     if (stats)
         std::fprintf(stderr, "complex francis: n=%lld sweeps=%d small_blocks=%d aed=%d aed_deflated=%d\n",
                      (long long)n, st_sweeps, st_small, st_aed, st_aed_defl);
-    for (void* p : {(void*)dw, (void*)dds, (void*)dU, (void*)dsh, (void*)dinfo, (void*)dV})
-        if (p) (void)hipFree(p);
-    if (ds) (void)hipHostFree(ds);
-    if (hp) (void)hipHostFree(hp);
     *sweeps_out = std::max(1, sweeps);
     *fail_out = failed;
     return rc;
