@@ -616,6 +616,28 @@ struct SvdResult {
     std::int64_t not_converged = 0;      // pairs of column blocks above the tolerance when maxSweeps ran out
 };
 
+// svds (svds / svds_dense, solvers.hpp; no counterpart in the reference): the nsv largest singular triplets of
+// a sparse or a dense M x N matrix by thick-restart Golub-Kahan-Lanczos from bases of ncv vectors
+// (0: min(min(M, N), 64, max(2 nsv + 1, 20))), without forming A^H A (eigsol_svds_csr / eigsol_svds_dense).
+struct SvdsOptions {
+    int maxRestarts = 300;
+    double tolerance = 1e-10;   // < 0: never converges
+    int nsv = 1;
+    int ncv = 0;
+    bool vectors = true;        // false: the values and residuals alone (the same bits)
+};
+
+template <typename S>
+struct SvdsResult {
+    std::vector<double> s;               // nsv singular values, descending
+    DenseMatrix<S> U;                    // M x nsv, orthonormal columns
+    DenseMatrix<S> V;                    // N x nsv, orthonormal columns, largest-modulus component real positive
+    std::vector<double> residuals;       // hypot(||A v - s u||_2, ||A^H u - s v||_2)
+    int restarts = 0;                    // restart cycles run
+    int applications = 0;                // products with A or A^H
+    bool converged = false;
+};
+
 template <typename S>
 struct QRResult {
     Vector<S> eigenvalues;

@@ -9,6 +9,8 @@
 //   qr_eigenvalues<S> / _dense     src/qr_method/qr_eigenvalues.hpp:40-147
 //   subspaceIteration<S> / _dense  new: nev dominant eigenpairs of a sparse matrix (eigsol_subspace_csr)
 //                                  or of a DenseMatrix<S> (eigsol_subspace_dense)
+//   svds<S> / svds_dense<S>        new: nsv largest singular triplets of a sparse or dense matrix (eigsol_svds_csr /
+//                                  eigsol_svds_dense)
 //   krylovSchur<S> / _dense        new: nev eigenpairs, dominant or nearest a shift (eigsol_krylov_csr /
 //                                  eigsol_krylov_dense)
 //
@@ -439,6 +441,103 @@ KrylovResult<S> krylovSchur_dense(const DenseMatrix<S>& A, const KrylovOptions<S
 template <ScalarConcept S>
 KrylovResult<S> krylovSchur_dense(const DenseMatrix<S>& A, const KrylovOptions<S>& opts, const Vector<S>& v0) {
     return detail::krylov_run_dense<S>(A, opts, &v0);
+}
+
+// ------------------------------------------------------------------------------------------ svds
+// opts.nsv largest singular triplets of a sparse matrix of any shape by thick-restart Golub-Kahan-Lanczos
+// (eigsol_svds_csr; the adjoint handle is built and destroyed inside the call).  S = double and
+// std::complex<double>; the default start vector (cols() entries) is drawn with random_vector<S>.
+// svds_dense takes a DenseMatrix<S> instead (eigsol_svds_dense), on the device for the duration of the call.
+namespace detail {
+// entry(o, v0, s, U, V, residuals, restarts, applications, converged) is the C entry bound to its handle
+template <typename S, typename Entry>
+SvdsResult<S> svds_device(std::int64_t rows, std::int64_t cols, const SvdsOptions& opts, const Vector<S>* v0,
+                          const char* who, Entry&& entry) {
+    SvdsResult<S> res;
+    if constexpr (!DeviceScalar<S>) {
+        throw std::runtime_error(std::string(who) + ": scalar type not supported by the device path "
+                                                    "(double, std::complex<double>)");
+    } else {
+        eigsol_svds_options o;
+        o.max_restarts = opts.maxRestarts;
+        o.tolerance = opts.tolerance;
+        o.nsv = opts.nsv;
+        o.ncv = opts.ncv > 0 ? opts.ncv
+                             : static_cast<int>(std::min<std::int64_t>(
+                                   {std::min(rows, cols), 64,
+                                    std::max<std::int64_t>(2 * static_cast<std::int64_t>(opts.nsv) + 1, 20)}));
+        Vector<S> start;
+        if (v0) {
+            if (static_cast<std::int64_t>(v0->size()) != cols)
+                throw std::runtime_error(std::string(who) + ": start vector size mismatch");
+        } else {
+            start = random_vector<S>(static_cast<std::size_t>(cols));
+            v0 = &start;
+        }
+        const std::size_t k = static_cast<std::size_t>(std::max(opts.nsv, 0));
+        res.s.assign(std::max<std::size_t>(k, 1), 0.0);
+        res.residuals.assign(std::max<std::size_t>(k, 1), 0.0);
+        const bool vec = opts.vectors && k > 0;
+        if (vec) {
+            res.U = DenseMatrix<S>(rows, static_cast<std::int64_t>(k));
+            res.V = DenseMatrix<S>(cols, static_cast<std::int64_t>(k));
+        }
+        std::int32_t rs = 0, ap = 0, conv = 0;
+        const int st = entry(&o, v0->data(), res.s.data(), vec ? static_cast<void*>(res.U.data()) : nullptr,
+                             vec ? static_cast<void*>(res.V.data()) : nullptr, res.residuals.data(), &rs, &ap, &conv);
+        check(st, who);
+        res.s.resize(k);
+        res.residuals.resize(k);
+        res.restarts = rs;
+        res.applications = ap;
+        res.converged = conv != 0;
+    }
+    return res;
+}
+
+template <typename S>
+SvdsResult<S> svds_run(const Matrix& M, const SvdsOptions& opts, const Vector<S>* v0) {
+    const char* who = "svds";
+    if (M.scalar_type() != typeid(S)) throw std::runtime_error(std::string(who) + ": scalar type mismatch");
+    if (M.rows() == 0 || M.cols() == 0) throw std::runtime_error(std::string(who) + ": matrix has zero size");
+    if (M.isDense()) throw std::runtime_error(std::string(who) + ": only sparse matrices are supported");
+    return svds_device<S>(M.rows(), M.cols(), opts, v0, who, [&](auto... a) {
+        if constexpr (DeviceScalar<S>) return eigsol_svds_csr(M.device<S>().csr(), nullptr, a...);
+        else return static_cast<int>(EIGSOL_E_UNSUPPORTED);
+    });
+}
+
+template <typename S>
+SvdsResult<S> svds_run_dense(const DenseMatrix<S>& A, const SvdsOptions& opts, const Vector<S>* v0) {
+    const char* who = "svds_dense";
+    if (A.rows() == 0 || A.cols() == 0) throw std::runtime_error(std::string(who) + ": matrix has zero size");
+    return svds_device<S>(A.rows(), A.cols(), opts, v0, who, [&](auto... a) {
+        if constexpr (DeviceScalar<S>) {
+            // on the device for this call: the handle is freed on every return, a throw included
+            const std::shared_ptr<DeviceMatrix> d = DeviceMatrix::dense(dtype_of<S>(), A.rows(), A.cols(), A.data());
+            return eigsol_svds_dense(d->dense(), a...);
+        } else {
+            return static_cast<int>(EIGSOL_E_UNSUPPORTED);
+        }
+    });
+}
+}  // namespace detail
+
+template <ScalarConcept S>
+SvdsResult<S> svds(const Matrix& M, const SvdsOptions& opts = {}) {
+    return detail::svds_run<S>(M, opts, nullptr);
+}
+template <ScalarConcept S>
+SvdsResult<S> svds(const Matrix& M, const SvdsOptions& opts, const Vector<S>& v0) {
+    return detail::svds_run<S>(M, opts, &v0);
+}
+template <ScalarConcept S>
+SvdsResult<S> svds_dense(const DenseMatrix<S>& A, const SvdsOptions& opts = {}) {
+    return detail::svds_run_dense<S>(A, opts, nullptr);
+}
+template <ScalarConcept S>
+SvdsResult<S> svds_dense(const DenseMatrix<S>& A, const SvdsOptions& opts, const Vector<S>& v0) {
+    return detail::svds_run_dense<S>(A, opts, &v0);
 }
 
 // ------------------------------------------------------------------------------------------ eigh

@@ -345,6 +345,78 @@ int eigsol_krylov_orth(eigsol_ctx* ctx, int dtype, int64_t n, int32_t j, const v
 int eigsol_krylov_rotate(eigsol_ctx* ctx, int dtype, int64_t n, int32_t m, int32_t p, void* V_dev,
                          int64_t ldv, const void* Q);
 
+/* ---------------------------------------------------------------- svds (thick-restart Golub-Kahan-Lanczos)
+ * The k = nsv largest singular triplets of a sparse or a dense M x N matrix from bases of m = ncv
+ * vectors (csrc/svds.hip; the reference has no counterpart), without forming A^H A.
+ *
+ * Adjoint products.  eigsol_dense_gemv_h: y = A^H x on device buffers for a column-major dense matrix
+ * of any shape (x: nrows scalars, y: ncols scalars), EIGSOL_F64 / EIGSOL_C128, stream-ordered
+ * (csrc/dense_adjoint.hip).  A is read once; row chunks write partials to a workspace kept on the
+ * matrix and a second kernel adds them in ascending chunk order: no floating-point atomics, the order
+ * of every sum depends on the shape alone, two calls give identical bits.  For a complex matrix the
+ * conjugate is taken on A.  Status: EIGSOL_E_INVALID (null pointer with a non-empty operand),
+ * EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD); ncols == 0 returns EIGSOL_OK, nrows == 0 writes zeros.
+ * eigsol_csr_adjoint: a new eigsol_csr holding A^H (ncols x nrows, values conjugated), built on the
+ * host from A's downloaded arrays (A's CSR arrays are the CSC arrays of its transpose) through
+ * eigsol_csr_create_from_csc, so it gets the layout selection of any uploaded matrix and its product
+ * is eigsol_csr_spmv with its fixed ascending-column sum order.  The caller destroys it with
+ * eigsol_csr_destroy.  Status: EIGSOL_E_INVALID (null pointer), EIGSOL_E_UNSUPPORTED (row-sharded
+ * matrices; F32 / C64 / DD / CDD).
+ *
+ * The driver.  V is N x (m + 1) and U is M x m on the device, column-major, in the matrix dtype; B is
+ * m x m upper triangular on the host.
+ *   v_0 = v0 / ||v0||, p = 0; cycle 1 .. max_restarts:
+ *     steps j = p .. m-1, enqueued without a host wait:
+ *       u = A v_j; twice { c = U_j^H u; u -= U_j c; h += c } (U_j = U[:, :j]; classical Gram-Schmidt
+ *         with one reorthogonalisation); alpha = ||u||; B[:j, j] = h, B[j, j] = alpha, u_j = u / alpha;
+ *       w = A^H u_j; the same against V[:, :j+1], coefficients discarded; beta = ||w||; v_{j+1} = w / beta;
+ *     one host wait (the columns h, alpha, beta, the breakdown word);
+ *     B = X diag(s) Y^H (one-sided Jacobi on the host, s descending); est_i = beta_{m-1} |X[m-1, i]|;
+ *     converged when est_i <= tolerance max(s_i, eps^(2/3) s_0) for every i < k;
+ *     else restart: p = k; V[:, :p] = V[:, :m] Y[:, :p]; U[:, :p] = U[:, :m] X[:, :p]; v_p = v_m; B = 0,
+ *       B[i, i] = s_i for i < p (the spike in column p of B is the h that step p computes).
+ *   u_i = U[:, :m] x_i, v_i = V[:, :m] y_i; column i of V gets its largest-modulus component (the first
+ *   on ties) real and positive, eigsol_svd_dense's convention, and u_i the same unit factor;
+ *   residual_i = hypot(||A v_i - s_i u_i||_2, ||A^H u_i - s_i v_i||_2), formed with A and A^H on the device.
+ * Breakdown: a norm at or below m 2^-52 times the norm before orthogonalisation stores a zero vector
+ * and sets a device word, read at the cycle's wait.  beta_j: U[:, :j+1] and V[:, :j+1] span an
+ * invariant pair of subspaces of dimension d = j + 1, with B[:d, :d].  alpha_j (a rank-deficient A
+ * whose v0 has a null-space component): d = j on the left, j + 1 on the right, and the projected matrix
+ * is the d x (d + 1) block [B[:d, :d] | h_j].  d >= nsv returns the triplets of that block with
+ * converged = 1; d < nsv fails with EIGSOL_E_SOLVER ("svds: invariant subspace of dimension d <
+ * nsv").  No restart with a fresh vector.  A small SVD that does not converge is EIGSOL_E_SOLVER.
+ * restarts counts the cycles run; applications counts the products with A or A^H up to the breakdown
+ * or the last step (max_restarts = 1: restarts = 1, applications = 2 ncv).
+ * Status, all decided before any device call: EIGSOL_E_INVALID (null pointers; nsv < 1;
+ * ncv < nsv + 2; ncv > 64; ncv > min(M, N); max_restarts < 1; an AH whose shape, dtype or context does
+ * not match; a v0 with no finite nonzero norm), EIGSOL_E_ZERO_SIZE, EIGSOL_E_UNSUPPORTED (F32 / C64 /
+ * DD / CDD matrices, row-sharded matrices).
+ * Out of scope: the smallest or interior singular values, block Lanczos, single precision,
+ * double-double, row-sharded matrices, a session / step form and matrix-free operators. */
+typedef struct eigsol_svds_options {
+    int32_t max_restarts; /* 300 */
+    double  tolerance;    /* 1e-10; < 0: never converges */
+    int32_t nsv;          /* k >= 1 */
+    int32_t ncv;          /* m: nsv + 2 <= m <= 64, m <= min(M, N) */
+} eigsol_svds_options;
+
+int eigsol_csr_adjoint(eigsol_csr* A, eigsol_csr** out);
+int eigsol_dense_gemv_h(eigsol_dense* A, const void* x_dev, void* y_dev);
+/* AH: eigsol_csr_adjoint(A), or NULL (built and destroyed inside).  v0: host, ncols scalars of the
+ * matrix dtype.  s: k doubles, descending.  U (optional): M x k, V (optional): N x k, column-major in
+ * the matrix dtype (real for a real matrix).  residuals (optional): k doubles.  restarts /
+ * applications / converged: optional. */
+int eigsol_svds_csr(eigsol_csr* A, eigsol_csr* AH, const eigsol_svds_options* opts, const void* v0, double* s,
+                    void* U, void* V, double* residuals, int32_t* restarts, int32_t* applications,
+                    int32_t* converged);
+/* eigsol_svds_csr on a dense matrix: the same algorithm, arguments, breakdown rules, counters and
+ * status codes; the products are eigsol_dense_gemv and eigsol_dense_gemv_h. */
+int eigsol_svds_dense(eigsol_dense* A, const eigsol_svds_options* opts, const void* v0, double* s, void* U,
+                      void* V, double* residuals, int32_t* restarts, int32_t* applications, int32_t* converged);
+/* The last eigsol_svds_* call's device time by stage, in ms from stream events: products with A,
+ * products with A^H, orthogonalisation, restart + finish. */
+int eigsol_svds_stage_times(eigsol_ctx* ctx, double* ms4);
+
 /* ---------------------------------------------------------------- shifted inverse iteration
  * shiftedInversePowerMethod<S>(M, ShiftedSolverOptions<S>{sigma, maxIter, tol})
  * (shifted_inverse_power_solver.hpp:112-125, impl :21-79).  A - sigma I is factored ONCE at

@@ -18,7 +18,7 @@ from ._capi import (EIGSOL_C64, EIGSOL_C128, EIGSOL_CDD, EIGSOL_DD, EIGSOL_E_INV
                     EIGSOL_F64, EIGSOL_KRYLOV_LM, EIGSOL_KRYLOV_SHIFT_INVERT, EigSolError, KrylovOptionsC, SolverOptionsC,
                     SubspaceOptionsC, call, check, last_error, lib)
 from ._capi import EIGSOL_EIGH_INDEX, EIGSOL_EIGH_VALUE, EighOptionsC
-from ._capi import EigOptionsC, SvdOptionsC
+from ._capi import EigOptionsC, SvdOptionsC, SvdsOptionsC
 
 __all__ = [
     "EigSolError", "SolverOptions", "EigenResult", "Context", "CsrMatrix", "DenseMatrix",
@@ -28,6 +28,7 @@ __all__ = [
     "EighResult", "eigh", "eigvalsh", "eigh_stage_times", "tridiag_plan", "eigh_dc_stage_times", "dc_deflate",
     "cholesky", "geigh_stage_times", "EigResult", "eig", "eig_stage_times",
     "SvdResult", "svd", "svdvals", "svd_stage_times",
+    "SvdsOptions", "SvdsResult", "svds", "svds_stage_times", "dense_mv_h",
 ]
 
 
@@ -272,6 +273,18 @@ class CsrMatrix:
         call("eigsol_csr_download", self.handle, _ptr(rp), _ptr(ci), _ptr(v))
         return rp, ci, from_wire(v, self.dtype)
 
+    def adjoint(self) -> "CsrMatrix":
+        """A new device matrix holding A^H (``eigsol_csr_adjoint``): ncols x nrows, values conjugated, uploaded
+        like any matrix, so its ``spmv`` is the product with A^H.  The caller closes it."""
+        h = C.c_void_p()
+        call("eigsol_csr_adjoint", self.handle, C.byref(h))
+        out = CsrMatrix.__new__(CsrMatrix)
+        out.ctx, out.handle = self.ctx, h
+        out.shape = (self.shape[1], self.shape[0])
+        out.nnz = self.nnz
+        out.dtype = self.dtype
+        return out
+
     def spmv(self, x_dev: int, y_dev: int) -> None:
         call("eigsol_csr_spmv", self.handle, C.c_void_p(x_dev), C.c_void_p(y_dev))
 
@@ -306,6 +319,10 @@ class DenseMatrix:
 
     def gemv(self, x_dev: int, y_dev: int) -> None:
         call("eigsol_dense_gemv", self.handle, C.c_void_p(x_dev), C.c_void_p(y_dev))
+
+    def gemv_h(self, x_dev: int, y_dev: int) -> None:
+        """y = A^H x on device vectors (x: nrows scalars, y: ncols scalars)."""
+        call("eigsol_dense_gemv_h", self.handle, C.c_void_p(x_dev), C.c_void_p(y_dev))
 
     def gemm(self, x_dev: int, y_dev: int, m: int) -> None:
         """Y = A X on row-major interleaved device blocks (X: ncols x m, Y: nrows x m)."""
@@ -990,6 +1007,100 @@ def svd_stage_times(ctx: Context) -> dict:
     ms = (C.c_double * 4)()
     call("eigsol_svd_stage_times", ctx.handle, ms)
     return {k: ms[i] * 1e-3 for i, k in enumerate(("gram", "pair_jacobi", "apply", "finish"))}
+
+
+# ------------------------------------------------------------------------------------------- svds
+def dense_mv_h(matrix: DenseMatrix, x) -> np.ndarray:
+    """``A^H @ x`` for a host vector x (nrows) through ``eigsol_dense_gemv_h`` (double and complex double
+    matrices of any shape); two calls return the same bits."""
+    nrows, ncols = matrix.shape
+    if np.shape(x) != (nrows,):
+        raise EigSolError(EIGSOL_E_SIZE_MISMATCH, f"x has shape {np.shape(x)}, the matrix has {nrows} rows")
+    if is_wide(matrix.dtype):
+        raise EigSolError(EIGSOL_E_UNSUPPORTED, "dense_mv_h: long double matrices are not supported")
+    xh = np.ascontiguousarray(x, dtype=matrix.dtype)
+    y = np.empty(ncols, dtype=matrix.dtype)
+    ctx = matrix.ctx
+    dx, dy = ctx.malloc(max(xh.nbytes, 16)), ctx.malloc(max(y.nbytes, 16))
+    try:
+        if xh.nbytes:
+            ctx.h2d(dx, xh)
+        matrix.gemv_h(dx, dy)
+        if y.nbytes:
+            ctx.d2h(y, dy)
+    finally:
+        ctx.free(dx)
+        ctx.free(dy)
+    return y
+
+
+@dataclass
+class SvdsOptions:
+    """Options of :func:`svds` (``eigsol_svds_options`` without nsv / ncv)."""
+
+    max_restarts: int = 300
+    tolerance: float = 1e-10          # < 0: never converges
+
+
+@dataclass
+class SvdsResult:
+    s: np.ndarray                     # k singular values, descending
+    U: Optional[np.ndarray]           # M x k in the matrix dtype (None without vectors)
+    V: Optional[np.ndarray]           # N x k; the largest-modulus component of every column real and positive
+    residuals: np.ndarray             # k: hypot(||A v - s u||_2, ||A^H u - s v||_2)
+    restarts: int                     # restart cycles run
+    applications: int                 # products with A or A^H
+    converged: bool
+
+
+def default_svds_ncv(shape, nsv: int) -> int:
+    return min(min(shape), 64, max(2 * nsv + 1, 20))
+
+
+def svds(matrix, nsv: int, opts: SvdsOptions = SvdsOptions(), ncv: Optional[int] = None, v0=None, seed: int = 0,
+         vectors: bool = True, adjoint: Optional[CsrMatrix] = None) -> SvdsResult:
+    """The ``nsv`` largest singular triplets of a device-resident CSR or dense matrix by thick-restart
+    Golub-Kahan-Lanczos (``eigsol_svds_csr`` / ``eigsol_svds_dense``), without forming A^H A.  ``ncv``
+    basis vectors (default min(min(M, N), 64, max(2 nsv + 1, 20))); ``v0`` (N entries) defaults to
+    uniform(-1, 1) entries from ``numpy.random.default_rng(seed)`` (complex for complex matrices).  For a
+    CSR matrix ``adjoint`` may be its :meth:`CsrMatrix.adjoint`, kept by a caller who solves more than
+    once; without it the handle is built and destroyed inside.  ``vectors=False`` returns the values and
+    residuals alone (the same bits)."""
+    M, N = matrix.shape
+    nsv = int(nsv)
+    m = default_svds_ncv((M, N), nsv) if ncv is None else int(ncv)
+    if v0 is None:
+        rng = np.random.default_rng(seed)
+        v0 = rng.uniform(-1, 1, N)
+        if np.issubdtype(matrix.dtype, np.complexfloating):
+            v0 = v0 + 1j * rng.uniform(-1, 1, N)
+    if is_wide(matrix.dtype):
+        raise EigSolError(EIGSOL_E_UNSUPPORTED, "svds: long double matrices are not supported")
+    v0 = _vector(v0, matrix.dtype, N, "v0")
+    k = max(nsv, 0)
+    s = np.zeros(max(k, 1))
+    res = np.zeros(max(k, 1))
+    U = np.zeros((M, k), dtype=matrix.dtype, order="F") if vectors else None
+    V = np.zeros((N, k), dtype=matrix.dtype, order="F") if vectors else None
+    rs, ap, conv = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    o = SvdsOptionsC(int(opts.max_restarts), float(opts.tolerance), nsv, m)
+    pd = C.POINTER(C.c_double)
+    tail = (C.byref(o), _ptr(v0), s.ctypes.data_as(pd), _ptr(U) if vectors and U.size else None,
+            _ptr(V) if vectors and V.size else None, res.ctypes.data_as(pd), C.byref(rs), C.byref(ap), C.byref(conv))
+    if isinstance(matrix, DenseMatrix):
+        if adjoint is not None:
+            raise EigSolError(EIGSOL_E_INVALID, "svds: adjoint= applies to CSR matrices")
+        call("eigsol_svds_dense", matrix.handle, *tail)
+    else:
+        call("eigsol_svds_csr", matrix.handle, None if adjoint is None else adjoint.handle, *tail)
+    return SvdsResult(s[:k].copy(), U, V, res[:k].copy(), int(rs.value), int(ap.value), bool(conv.value))
+
+
+def svds_stage_times(ctx: Context) -> dict:
+    """The context's last :func:`svds` call by stream events, in seconds."""
+    ms = (C.c_double * 4)()
+    call("eigsol_svds_stage_times", ctx.handle, ms)
+    return {k: ms[i] * 1e-3 for i, k in enumerate(("product", "adjoint_product", "orthogonalisation", "restart_finish"))}
 
 
 def cholesky(ctx: Context, B) -> np.ndarray:

@@ -87,6 +87,10 @@ class SvdOptionsC(C.Structure):
     _fields_ = [("max_sweeps", C.c_int32)]
 
 
+class SvdsOptionsC(C.Structure):
+    _fields_ = [("max_restarts", C.c_int32), ("tolerance", C.c_double), ("nsv", C.c_int32), ("ncv", C.c_int32)]
+
+
 _vp = C.c_void_p
 _i32 = C.c_int32
 _i64 = C.c_int64
@@ -179,6 +183,11 @@ SIGNATURES = {
     "eigsol_eig_stage_times": [_vp, _pd],
     "eigsol_svd_dense": [_vp, C.c_int, _i64, _i64, _vp, C.POINTER(SvdOptionsC), _pd, _vp, _vp, _pi32, _pi64],
     "eigsol_svd_stage_times": [_vp, _pd],
+    "eigsol_csr_adjoint": [_vp, _ppv],
+    "eigsol_dense_gemv_h": [_vp, _vp, _vp],
+    "eigsol_svds_csr": [_vp, _vp, C.POINTER(SvdsOptionsC), _vp, _pd, _vp, _vp, _pd, _pi32, _pi32, _pi32],
+    "eigsol_svds_dense": [_vp, C.POINTER(SvdsOptionsC), _vp, _pd, _vp, _vp, _pd, _pi32, _pi32, _pi32],
+    "eigsol_svds_stage_times": [_vp, _pd],
     "eigsol_hbm_probe": [_vp, C.c_size_t, C.c_int, _pd, _pd, _pd, _pint],
     "eigsol_hbm_probe_mix": [_vp, C.c_size_t, C.c_int, _pd, _pint],
     "eigsol_ctx_info": [_vp, _pint, _pint, _pint, _pint],

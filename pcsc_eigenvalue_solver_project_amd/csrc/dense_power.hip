@@ -223,6 +223,7 @@ void dense_release(eigsol_dense* A) {
     if (A->ypart) (void)hipFree(A->ypart);
     if (A->tile_cnt) (void)hipFree(A->tile_cnt);
     if (A->gpart) (void)hipFree(A->gpart);
+    if (A->hpart) (void)hipFree(A->hpart);
     if (A->a) (void)hipFree(A->a);
     if (A->shadow) dense_release(A->shadow);
     eigsol_ctx* c = A->ctx;

@@ -271,6 +271,9 @@ struct eigsol_ctx {
     double eig_ms[4] = {0.0, 0.0, 0.0, 0.0};
     // the last eigsol_svd_dense call's stages in ms (eigsol_svd_stage_times): Gram, pair Jacobi, apply, finish
     double svd_ms[4] = {0.0, 0.0, 0.0, 0.0};
+    // the last eigsol_svds_* call's stages in ms (eigsol_svds_stage_times): products with A, products with
+    // A^H, orthogonalisation, restart + finish
+    double svds_ms[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 struct eigsol_csr {
@@ -354,5 +357,7 @@ struct eigsol_dense {
     // block-product workspace (dense_block.hip, allocated on first use): per-chunk partials of Y
     void* gpart = nullptr;
     size_t gpart_bytes = 0;
+    // adjoint-product workspace (dense_adjoint.hip, allocated on first use): per-row-chunk partials of y
+    void* hpart = nullptr;
     eigsol_dense* shadow = nullptr;   // extended precision: the matrix rounded to fp64 (see eigsol_csr)
 };
