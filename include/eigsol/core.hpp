@@ -601,6 +601,22 @@ struct EigResult {
     std::int64_t notConverged = 0;                       // eigenvalues no start vector passed the growth test for
 };
 
+// Schur form A = Z T Z^H (schur, solvers.hpp; no counterpart in the reference): the multishift sweeps of
+// qr_eigenvalues with T and Z kept (eigsol_schur_dense).
+struct SchurOptions {
+    int maxIterations = 1000;            // the sweeps' limit per deflation (SolverOptions::maxIterations)
+    bool vectors = true;                 // false: T and the eigenvalues alone (the same bits)
+};
+
+template <typename S>
+struct SchurResult {
+    DenseMatrix<S> T;                                    // real S: quasi-triangular, standard 2 x 2 blocks; complex S: triangular
+    DenseMatrix<S> Z;                                    // n x n orthogonal / unitary; empty without vectors
+    std::vector<std::complex<double>> eigenvalues;       // in the order of T's diagonal; a pair: Im > 0 first, then its conjugate
+    int iterations = 0;                                  // the sweeps', as QRResult reports them
+    bool converged = false;                              // false: T is upper Hessenberg only, A = Z T Z^H still holds
+};
+
 // Thin singular value decomposition (svd / svdvals, solvers.hpp; no counterpart in the reference): block
 // one-sided Jacobi on the device (eigsol_svd_dense).
 struct SvdOptions {

@@ -649,6 +649,51 @@ EigResult<S> eig(const DenseMatrix<S>& A, const EigOptions& opts = {}) {
     return res;
 }
 
+// ------------------------------------------------------------------------------------------- schur
+// Schur form A = Z T Z^H of a general dense matrix (eigsol_schur_dense: blocked Hessenberg reduction, Q on the
+// matrix cores, the sweeps of qr_eigenvalues applied to the whole of T and to Z, standard 2 x 2 blocks).  A real
+// S gives the real Schur form, a complex S the complex one.  float and std::complex<float> run on their fp64
+// promotion; T and Z are rounded back, the eigenvalues stay in double.
+template <ScalarConcept S>
+SchurResult<S> schur(const DenseMatrix<S>& A, const SchurOptions& opts = {}) {
+    const std::int64_t n = A.rows();
+    if (n != A.cols()) throw std::runtime_error("schur: matrix must be square");
+    if (n == 0) throw std::runtime_error("schur: matrix has zero size");
+    if constexpr (PromotedScalar<S>) {
+        using D = device_scalar_t<S>;
+        SchurResult<D> rd = schur<D>(detail::convert_dense<D>(A), opts);
+        SchurResult<S> rs;
+        rs.T = detail::convert_dense<S>(rd.T);
+        if (opts.vectors) rs.Z = detail::convert_dense<S>(rd.Z);
+        rs.eigenvalues = std::move(rd.eigenvalues);
+        rs.iterations = rd.iterations;
+        rs.converged = rd.converged;
+        return rs;
+    } else if constexpr (!DeviceScalar<S>) {
+        throw std::runtime_error("schur: scalar type not supported by the device path (double, std::complex<double>)");
+    } else {
+        SchurResult<S> res;
+        eigsol_solver_options o{};
+        o.max_iterations = opts.maxIterations;
+        res.T = DenseMatrix<S>(n, n);
+        if (opts.vectors) res.Z = DenseMatrix<S>(n, n);
+        res.eigenvalues.assign(static_cast<std::size_t>(n), std::complex<double>(0.0, 0.0));
+        std::vector<double> wr(static_cast<std::size_t>(n), 0.0), wi(static_cast<std::size_t>(n), 0.0);
+        constexpr bool real = std::is_floating_point_v<S>;
+        std::int32_t it = 0, conv = 0;
+        detail::check(eigsol_schur_dense(detail::ctx(), detail::dtype_of<S>(), n, A.data(), &o, res.T.data(),
+                                         opts.vectors ? static_cast<void*>(res.Z.data()) : nullptr,
+                                         real ? static_cast<void*>(wr.data()) : static_cast<void*>(res.eigenvalues.data()),
+                                         wi.data(), &it, &conv),
+                      "schur");
+        if constexpr (real)
+            for (std::size_t i = 0; i < wr.size(); ++i) res.eigenvalues[i] = std::complex<double>(wr[i], wi[i]);
+        res.iterations = it;
+        res.converged = conv != 0;
+        return res;
+    }
+}
+
 // ------------------------------------------------------------------------------------------- svd
 // Thin singular value decomposition A = U diag(s) V^H of a dense m x n matrix (eigsol_svd_dense: block one-sided
 // Jacobi on the fp64 matrix cores).  S = double and std::complex<double>.  svdvals returns the bits of svd's s.

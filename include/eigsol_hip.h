@@ -596,7 +596,7 @@ int eigsol_eigh_stage_times(eigsol_ctx* ctx, double* ms4);
  * accepts: 16384 real, 8192 complex).  n == 0: EIGSOL_OK with *m_out = 0.  A non-finite eigenvalue or
  * entry of H fails with EIGSOL_E_SOLVER.
  * Out of scope: left eigenvectors and balancing (xGEBAL); the Schur form (no Schur vectors are
- * accumulated); a basis for a multiple semisimple eigenvalue whose copies land in one unreduced block
+ * accumulated here; eigsol_schur_dense computes it); a basis for a multiple semisimple eigenvalue whose copies land in one unreduced block
  * of H (xHSEIN's known limit: the vectors returned for it satisfy the residual bound but may be
  * parallel); single precision and double-double.
  * eigsol_eig_stage_times: the context's last eigsol_eig_dense call by stream events, 4 doubles in ms:
@@ -612,6 +612,58 @@ int eigsol_eig_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmaj
                      const eigsol_eig_options* opts, double* w, void* V, int64_t* m_out,
                      int32_t* iterations, int32_t* converged, int64_t* not_converged);
 int eigsol_eig_stage_times(eigsol_ctx* ctx, double* ms4);
+
+/* ---------------------------------------------------------------- Schur form (dense)
+ * eigsol_schur_dense: the Schur form A = Z T Z^H of a general dense matrix (csrc/schur.hip; the sweeps in
+ * csrc/francis.hip and csrc/zfrancis.hip).  EIGSOL_F64 gives the real Schur form (T quasi-triangular with
+ * 1 x 1 and standard 2 x 2 diagonal blocks, Z orthogonal), EIGSOL_C128 the complex one (T upper
+ * triangular, Z unitary).  The reference has no such solver.
+ * Algorithm: (1) the power-of-two range guard of eigsol_qr_eigenvalues_dense; T and the eigenvalues are
+ * scaled back exactly.  (2) The blocked Hessenberg reduction with its panels kept (n >= 3; H = A and
+ * Q = I for n <= 2), the entries below the sub-diagonal stored as zeros; when Z is wanted, Z = Q by the
+ * stored panels applied to the identity on the fp64 matrix cores, 4096 columns at a time, before the
+ * sweeps.  (3) The multishift sweeps with aggressive early deflation of
+ * eigsol_qr_eigenvalues_dense(EIGSOL_QR_FRANCIS), their chase kernels, shifts and launch geometry
+ * unchanged, in Schur mode: each window's delayed updates reach the whole matrix,
+ * H(s:e, e:n) <- U^H H(s:e, e:n) and H(0:s, s:e) <- H(0:s, s:e) U (every left region before every right
+ * region), and Z(:, s:e) <- Z(:, s:e) U runs as one more launch that T never reads; the deflation
+ * window's factor is applied to the same three ranges.  (4) A diagonal block of at most 96 rows (real:
+ * T and V of the block fill the LDS) or 64 rows (complex) is finished by the one-wave Schur factorisation
+ * with its factor V kept, and V is applied to the three ranges.  (5) Every sub-diagonal entry the
+ * deflation test accepted is stored as 0.0.  (6) Real matrices: every 2 x 2 diagonal block is
+ * standardised by a rotation (LAPACK dlanv2's contract): split into two 1 x 1 blocks with an exactly
+ * zero sub-diagonal entry, or left with equal diagonal entries and off-diagonal entries of opposite
+ * sign; the rotation is applied to the block's rows, its columns and Z's two columns, all row rotations
+ * in one launch and all column rotations in the next.  (7) The eigenvalues are read from T's diagonal
+ * blocks on the device.  No floating-point atomics and fixed summation orders: two calls return the same
+ * bits, and T and the eigenvalues are the same bits with and without Z.
+ * Read: A_colmajor (host, n x n, column-major).  opts (NULL: 1000): max_iterations is the sweeps' limit
+ * per deflation; tolerance is not read.
+ * Out: T_out, n x n in A's scalar type, column-major; nothing below the first sub-diagonal is non-zero.
+ * Z_out (NULL: no Schur vectors), n x n likewise.  The eigenvalues in the order of T's diagonal:
+ * EIGSOL_F64 writes the real parts to eig_re_or_c and the imaginary parts to eig_im (n doubles each); the
+ * two eigenvalues of a 2 x 2 block [a b; c a] are adjacent and bitwise conjugate,
+ * a + i sqrt|b| sqrt|c| first and a - i sqrt|b| sqrt|c| second.  EIGSOL_C128 writes n complex doubles to
+ * eig_re_or_c (T's diagonal) and does not read eig_im.  iterations / converged (optional): as
+ * eigsol_qr_eigenvalues_dense reports them.
+ * Not converged (a deflation took more than max_iterations sweeps): EIGSOL_OK with *converged = 0; T_out
+ * is upper Hessenberg only (its 2 x 2 blocks are not standardised, the eigenvalues are read from what its
+ * diagonal blocks hold), and A = Z T Z^H holds all the same.
+ * Status, decided before any device call: EIGSOL_E_INVALID (n < 0; a null ctx; with n > 0 a null A, T_out
+ * or eig_re_or_c, or a null eig_im with EIGSOL_F64; max_iterations < 1; unknown dtype),
+ * EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD; n above the order the blocked reduction accepts, which is
+ * eigsol_eigh_dense's: 16384 real, 8192 complex).  n == 0: EIGSOL_OK with *converged = 1.  A non-finite
+ * entry of A fails with EIGSOL_E_SOLVER (found on the host, before the upload).
+ * Out of scope: reordering the diagonal blocks (ordschur) and the complex Schur form of a real matrix
+ * (rsf2csf); eigenvectors from T (xTREVC) and any change to eigsol_eig_dense; balancing; single precision
+ * and double-double; any tuning of the deflation window or the chase.
+ * eigsol_schur_stage_times: the context's last eigsol_schur_dense call by stream events, 4 doubles in ms:
+ * reduction (guard, Hessenberg), forming Q, the sweeps with their updates, finish (standardisation,
+ * scaling back, eigenvalues, the copies to the host). */
+int eigsol_schur_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor,
+                       const eigsol_solver_options* opts, void* T_out, void* Z_out, void* eig_re_or_c,
+                       double* eig_im, int32_t* iterations, int32_t* converged);
+int eigsol_schur_stage_times(eigsol_ctx* ctx, double* ms4);
 
 /* ---------------------------------------------------------------- singular value decomposition (dense)
  * eigsol_svd_dense: the thin singular value decomposition A = U diag(s) V^H of a real (EIGSOL_F64) or

@@ -26,7 +26,7 @@ __all__ = [
     "SubspaceOptions", "SubspaceResult", "subspace_iteration", "spmm", "dense_mm",
     "KrylovOptions", "KrylovResult", "krylov_schur", "krylov_orth", "krylov_rotate",
     "EighResult", "eigh", "eigvalsh", "eigh_stage_times", "tridiag_plan", "eigh_dc_stage_times", "dc_deflate",
-    "cholesky", "geigh_stage_times", "EigResult", "eig", "eig_stage_times",
+    "cholesky", "geigh_stage_times", "EigResult", "eig", "eig_stage_times", "SchurResult", "schur", "schur_stage_times",
     "SvdResult", "svd", "svdvals", "svd_stage_times",
     "SvdsOptions", "SvdsResult", "svds", "svds_stage_times", "dense_mv_h",
 ]
@@ -950,6 +950,52 @@ def eig_stage_times(ctx: Context) -> dict:
     ms = (C.c_double * 4)()
     call("eigsol_eig_stage_times", ctx.handle, ms)
     return {k: ms[i] * 1e-3 for i, k in enumerate(("reduction", "francis", "inverse_iteration", "back_transform"))}
+
+
+@dataclass
+class SchurResult:
+    """Result of :func:`schur`: ``A = Z @ T @ Z.conj().T``.  ``T`` n x n in A's dtype, Fortran order (real input:
+    quasi-triangular, every 2 x 2 diagonal block with equal diagonal entries and off-diagonal entries of
+    opposite sign; complex input: upper triangular), ``Z`` n x n orthogonal / unitary or ``None``,
+    ``eigenvalues`` complex128 in the order of T's diagonal (a conjugate pair is adjacent, bitwise conjugate,
+    the member with the positive imaginary part first), ``iterations`` / ``converged`` the sweeps' as
+    :class:`QRResult` reports them.  Not converged: T is upper Hessenberg only; the product still holds."""
+
+    T: np.ndarray
+    Z: Optional[np.ndarray]
+    eigenvalues: np.ndarray
+    iterations: int
+    converged: bool
+
+
+def schur(ctx: Context, A, vectors: bool = True, opts: SolverOptions = SolverOptions()) -> SchurResult:
+    """Schur form of a general dense matrix on the device (``eigsol_schur_dense``): float64 input gives the real
+    Schur form, complex128 input the complex one.  Blocked Hessenberg reduction, Q formed on the matrix cores,
+    the multishift sweeps of :func:`qr_eigenvalues` with every update applied to the whole of T and to Z, the
+    2 x 2 blocks of a real T standardised on the device.  ``vectors=False`` skips Z; T and the eigenvalues
+    are the same bits either way.  ``opts.maxIterations`` limits the sweeps per deflation."""
+    A = _square_dense(A, "schur")
+    code = _dtype_code(A.dtype)
+    n = A.shape[0]
+    Af = np.asfortranarray(A)
+    o = SolverOptionsC(int(opts.maxIterations), float(opts.tolerance))
+    T = np.zeros((n, n), dtype=A.dtype, order="F")
+    Z = np.zeros((n, n), dtype=A.dtype, order="F") if vectors else None
+    real = not np.iscomplexobj(A)
+    wr = np.zeros(max(n, 1), dtype=np.float64 if real else np.complex128)
+    wi = np.zeros(max(n, 1), dtype=np.float64)
+    it, conv = C.c_int32(0), C.c_int32(0)
+    call("eigsol_schur_dense", ctx.handle, code, n, _ptr(Af), C.byref(o), _ptr(T), _ptr(Z) if vectors and n else None,
+         _ptr(wr), wi.ctypes.data_as(C.POINTER(C.c_double)), C.byref(it), C.byref(conv))
+    w = (wr[:n] + 1j * wi[:n]) if real else wr[:n].copy()
+    return SchurResult(T, Z, np.asarray(w, dtype=np.complex128), int(it.value), bool(conv.value))
+
+
+def schur_stage_times(ctx: Context) -> dict:
+    """The context's last :func:`schur` call by stream events, in seconds."""
+    ms = (C.c_double * 4)()
+    call("eigsol_schur_stage_times", ctx.handle, ms)
+    return {k: ms[i] * 1e-3 for i, k in enumerate(("reduction", "form_q", "sweeps", "finish"))}
 
 
 @dataclass

@@ -181,6 +181,8 @@ SIGNATURES = {
     "eigsol_dc_deflate": [_i64, _i64, _vp, _vp, C.c_double, _pi64, _vp, _vp, _vp, _pd, _pi64, _vp, _vp, _pd],
     "eigsol_eig_dense": [_vp, C.c_int, _i64, _vp, C.POINTER(EigOptionsC), _vp, _vp, _pi64, _pi32, _pi32, _pi64],
     "eigsol_eig_stage_times": [_vp, _pd],
+    "eigsol_schur_dense": [_vp, C.c_int, _i64, _vp, C.POINTER(SolverOptionsC), _vp, _vp, _vp, _pd, _pi32, _pi32],
+    "eigsol_schur_stage_times": [_vp, _pd],
     "eigsol_svd_dense": [_vp, C.c_int, _i64, _i64, _vp, C.POINTER(SvdOptionsC), _pd, _vp, _vp, _pi32, _pi64],
     "eigsol_svd_stage_times": [_vp, _pd],
     "eigsol_csr_adjoint": [_vp, _ppv],

@@ -925,6 +925,43 @@ __global__ void diag_sub_kernel(const double* H, int64_t n, int ihi, double* out
 
 __global__ void zero_entry_kernel(double* H, int64_t n, int i, int j) { H[i + (int64_t)j * n] = 0.0; }
 
+// Schur mode: the diagonal block H[l:l+m, l:l+m] (m <= kAedMax: T and V of the block fill the LDS, as the
+// AED's do) finished in one piece: real Schur form T = V^T H V by the one-wave factorisation with V kept.
+// T goes back in place (exact zeros below the sub-diagonal), V to Vout (m x m, column-major); the caller
+// applies V to the columns right of the block, the rows above it and Z.  A factorisation that ran out of
+// sweeps still leaves an orthogonal similarity (T upper Hessenberg): info = {fail, most sweeps, total}.
+__global__ __launch_bounds__(kAedThreads) void schur_block_kernel(double* H, int64_t n, int l, int m, int maxits,
+                                                                  double* Vout, int* info) {
+    constexpr int LD = kAedMax + 1;
+    __shared__ double t[kAedMax * LD];
+    __shared__ double v[kAedMax * LD];
+    __shared__ double wr[kAedMax], wi[kAedMax];
+    __shared__ int bs[kAedMax];
+    const int tid = threadIdx.x, nt = kAedThreads;
+    for (int e = tid; e < m * m; e += nt) {
+        const int i = e % m, j = e / m;
+        t[i + j * LD] = H[(l + i) + (int64_t)(l + j) * n];
+        v[i + j * LD] = i == j ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    if (tid < 64) {
+        int fail = 0, total = 0, maxsw = 0;
+        if (m <= 64) wave_hqr<true, 1>(t, v, m, LD, maxits, wr, wi, bs, fail, total, maxsw);
+        else wave_hqr<true, 2>(t, v, m, LD, maxits, wr, wi, bs, fail, total, maxsw);
+        if (tid == 0) {
+            info[0] = fail;
+            info[1] = maxsw;
+            info[2] = total;
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < m * m; e += nt) {
+        const int i = e % m, j = e / m;
+        H[(l + i) + (int64_t)(l + j) * n] = i > j + 1 ? 0.0 : t[i + j * LD];
+        Vout[e] = v[i + j * LD];
+    }
+}
+
 }  // namespace dev
 
 // ---------------------------------------------------------------------------------- host loop
@@ -941,8 +978,14 @@ static constexpr int kSmall = 128;   // blocks of at most this many rows are fin
 // (one chain of 16 bulges: 40 was best); the window's one-wave Schur factorisation costs O(nw^3) latency-bound steps
 static constexpr int kAedWin = 64;
 
-int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double* wr, double* wi,
-                      int32_t* sweeps_out, int32_t* fail_out) {
+// kSchur = false: the eigenvalue-only iteration (francis_large_f64).  kSchur = true (schur_sweeps_f64): the
+// same sweeps, shifts and launches of the chase, with every delayed update widened to the whole matrix
+// (left regions to column n - 1, right regions from row 0), the window factors also applied to Z (n x n,
+// leading dimension n; null: none), accepted sub-diagonal entries stored as zeros and blocks of at most
+// kAedMax rows finished by schur_block_kernel; wr / wi are not written.
+template <bool kSchur>
+static int francis_impl(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double* wr, double* wi,
+                        int32_t* sweeps_out, int32_t* fail_out, double* Z) {
     hipStream_t st = ctx->stream;
     const double eps = 2.220446049250313e-16;
     DevBuf bsw, bsinfo, bflag, bwr, bwi, bds, bU, bsh, binfo;
@@ -1012,8 +1055,40 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
     // 0.930 s (seed 7), one-to-one with LAPACK (3.3e-12).  The two narrower modes were removed.
     long long st_steps = 0, st_aed_steps = 0, st_aed_ph[3] = {0, 0, 0};
     int st_sweeps = 0, st_windows = 0, st_small = 0, st_small_rows = 0, st_aed = 0, st_aed_defl = 0, st_conc = 0;
+    // Schur mode: the factor U (W x W) of the rows / columns [s, s + W) applied outside them: U^T to the
+    // columns [e, n), U to the rows [0, rhi) and to Z's columns
+    auto apply_outside = [&](int s, int W, int64_t rhi, const double* U) {
+        const int e = s + W;
+        dev::WinGemmBatch gb{H, n, 1, {}};
+        if (e < n) {
+            gb.w[0] = dev::WinGemm{s, W, (int64_t)e, n, 0, U};
+            hipLaunchKernelGGL(dev::win_gemm_mfma<true>, dim3((unsigned)((n - e + 63) / 64)), dim3(256), 0, st, gb);
+        }
+        if (rhi > 0) {
+            gb.w[0] = dev::WinGemm{s, W, 0, rhi, 0, U};
+            hipLaunchKernelGGL(dev::win_gemm_mfma<false>, dim3((unsigned)((rhi + 63) / 64)), dim3(256), 0, st, gb);
+        }
+        if (Z) {
+            dev::WinGemmBatch zb{Z, n, 1, {}};
+            zb.w[0] = dev::WinGemm{s, W, 0, n, 0, U};
+            hipLaunchKernelGGL(dev::win_gemm_mfma<false>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, zb);
+        }
+    };
     auto finish_small = [&](int l, int hi) -> int {
         const int m = hi - l + 1;
+        if constexpr (kSchur) {
+            if (m == 1) return EIGSOL_OK;   // a 1 x 1 block is its own Schur form
+            hipLaunchKernelGGL(dev::schur_block_kernel, dim3(1), dim3(dev::kAedThreads), 0, st, H, n, l, m,
+                               std::max(1, maxits), dU, dinfo);
+            apply_outside(l, m, l, dU);
+            EIGSOL_HIP(hipGetLastError());
+            int* info = hp->info;
+            EIGSOL_HIP(hipMemcpyAsync(info, dinfo, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+            EIGSOL_HIP(stream_wait(st));
+            if (info[0]) failed = 1;
+            sweeps = std::max(sweeps, info[1]);
+            return EIGSOL_OK;
+        }
         EIGSOL_TRY(hqr_small(st, H + l + (int64_t)l * n, n, m, std::max(1, maxits), dwr + l, dwi + l, dinfo));
         int* info = hp->info;
         EIGSOL_HIP(hipMemcpyAsync(info, dinfo, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1043,10 +1118,14 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
             --l;
         }
         const int N = ihi - l + 1;
-        if (N <= kSmall) {
+        if constexpr (kSchur) {   // the accepted sub-diagonal entry becomes an exact zero
+            if (l > 0 && ds[n + l] != 0.0) hipLaunchKernelGGL(dev::zero_entry_kernel, dim3(1), dim3(1), 0, st, H, n, l, l - 1);
+        }
+        if (N <= (kSchur ? dev::kAedMax : kSmall)) {
             ++st_small;
             st_small_rows += N;
             rc = finish_small(l, ihi);
+            if (kSchur && failed) break;   // the block stays unreduced: T is upper Hessenberg there
             ihi = l - 1;
             sweeps = std::max(sweeps, stall);
             stall = 0;
@@ -1089,7 +1168,9 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
                 const int nd = info[1], m = info[3];
                 if (nd > 0) {
                     st_aed_defl += nd;
-                    if (kw > l) {   // rows above the window: H[l, kw) x [kw, kw + nw) V
+                    if constexpr (kSchur) {   // V on the columns right of the window, the rows above it and Z
+                        apply_outside(kw, nw, kw, dU);
+                    } else if (kw > l) {   // rows above the window: H[l, kw) x [kw, kw + nw) V
                         dev::WinGemmBatch gb{H, n, 1, {}};
                         gb.w[0] = dev::WinGemm{kw, nw, (int64_t)l, (int64_t)kw, 0, dU};
                         hipLaunchKernelGGL(dev::win_gemm_mfma<false>, dim3((kw - l + 63) / 64), dim3(256), 0, st, gb);
@@ -1247,24 +1328,33 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
             hipLaunchKernelGGL(dev::chase_wave_kernel, dim3(nwin), dim3(1024), 0, st, ca);
             // delayed updates: every left region, then every right region; tiles of 64 columns /
             // rows per workgroup (32 when 64-wide tiles would leave CUs idle)
-            dev::WinGemmBatch lb{H, n, 0, {}}, rb{H, n, 0, {}};
-            int nlb = 0, nrb = 0, span = 0;
+            // Schur mode: left regions to column n - 1, right regions from row 0 (the window's own rows
+            // from max(l, s) on were updated by the chase), and Z's columns [s, e) as one more right batch
+            dev::WinGemmBatch lb{H, n, 0, {}}, rb{H, n, 0, {}}, zb{Z, n, 0, {}};
+            const int lend = kSchur ? (int)n : ihi + 1;   // left regions: columns [e, lend)
+            auto rlo = [&](const dev::ChaseWin&) { return kSchur ? 0 : l; };                       // right regions: rows
+            auto rhi = [&](const dev::ChaseWin& w) { return kSchur ? std::max(l, w.s) : w.s; };   // [rlo, rhi)
+            int nlb = 0, nrb = 0, nzb = 0, span = 0;
             for (int q = 0; q < nwin; ++q) {
                 const dev::ChaseWin& w = ca.w[q];
-                if (w.e <= ihi) span += ihi + 1 - w.e;
-                if (w.s > l) span += w.s - l;
+                if (w.e < lend) span += lend - w.e;
+                if (rhi(w) > rlo(w)) span += rhi(w) - rlo(w);
             }
             const int tile = span / 64 < ctx->num_cus ? 32 : 64;
             for (int q = 0; q < nwin; ++q) {
                 const dev::ChaseWin& w = ca.w[q];
                 const int W = w.e - w.s;
-                if (w.e <= ihi) {
-                    lb.w[lb.nw++] = dev::WinGemm{w.s, W, (int64_t)w.e, (int64_t)ihi + 1, nlb, w.U};
-                    nlb += (ihi + 1 - w.e + tile - 1) / tile;
+                if (w.e < lend) {
+                    lb.w[lb.nw++] = dev::WinGemm{w.s, W, (int64_t)w.e, (int64_t)lend, nlb, w.U};
+                    nlb += (lend - w.e + tile - 1) / tile;
                 }
-                if (w.s > l) {
-                    rb.w[rb.nw++] = dev::WinGemm{w.s, W, (int64_t)l, (int64_t)w.s, nrb, w.U};
-                    nrb += (w.s - l + tile - 1) / tile;
+                if (rhi(w) > rlo(w)) {
+                    rb.w[rb.nw++] = dev::WinGemm{w.s, W, (int64_t)rlo(w), (int64_t)rhi(w), nrb, w.U};
+                    nrb += (rhi(w) - rlo(w) + tile - 1) / tile;
+                }
+                if (kSchur && Z) {
+                    zb.w[zb.nw++] = dev::WinGemm{w.s, W, 0, n, nzb, w.U};
+                    nzb += (int)((n + 63) / 64);
                 }
             }
             if (tile == 32) {
@@ -1274,6 +1364,7 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
                 if (nlb > 0) hipLaunchKernelGGL(dev::win_gemm_mfma<true>, dim3(nlb), dim3(256), 0, st, lb);
                 if (nrb > 0) hipLaunchKernelGGL(dev::win_gemm_mfma<false>, dim3(nrb), dim3(256), 0, st, rb);
             }
+            if (nzb > 0) hipLaunchKernelGGL(dev::win_gemm_mfma<false>, dim3(nzb), dim3(256), 0, st, zb);
             t0 = t1;
         }
         if (hipGetLastError() != hipSuccess) { rc = fail(EIGSOL_E_HIP, "francis: launch"); break; }
@@ -1287,7 +1378,7 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
                 break;
             }
     }
-    if (rc == EIGSOL_OK) {
+    if (rc == EIGSOL_OK && !kSchur) {
         if (hipMemcpyAsync(wr, dwr, n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipMemcpyAsync(wi, dwi, n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
             stream_wait(st) != hipSuccess)
@@ -1303,6 +1394,19 @@ int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double*
     *sweeps_out = std::max(1, sweeps);
     *fail_out = failed;
     return rc;
+}
+
+int francis_large_f64(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double* wr, double* wi,
+                      int32_t* sweeps_out, int32_t* fail_out) {
+    return francis_impl<false>(ctx, H, n, maxits, wr, wi, sweeps_out, fail_out, nullptr);
+}
+
+// The sweeps in Schur mode (schur.hip): H (upper Hessenberg, exact zeros below the sub-diagonal) becomes a
+// quasi-triangular T whose 2 x 2 blocks are not yet standardised, Z (null: none) becomes Z U for the
+// orthogonal U with T = U^T H U.  *fail_out: T is upper Hessenberg only; the similarity holds all the same.
+int schur_sweeps_f64(eigsol_ctx* ctx, double* H, int64_t n, double* Z, int maxits, int32_t* sweeps_out,
+                     int32_t* fail_out) {
+    return francis_impl<true>(ctx, H, n, maxits, nullptr, nullptr, sweeps_out, fail_out, Z);
 }
 
 }  // namespace eigsol

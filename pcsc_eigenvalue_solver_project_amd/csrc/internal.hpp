@@ -274,6 +274,9 @@ struct eigsol_ctx {
     // the last eigsol_svds_* call's stages in ms (eigsol_svds_stage_times): products with A, products with
     // A^H, orthogonalisation, restart + finish
     double svds_ms[4] = {0.0, 0.0, 0.0, 0.0};
+    // the last eigsol_schur_dense call's stages in ms (eigsol_schur_stage_times): reduction, forming Q, sweeps
+    // with their updates, finish (standardisation, eigenvalues, copies)
+    double schur_ms[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 struct eigsol_csr {

@@ -775,6 +775,44 @@ __global__ void zdiag_sub_kernel(const cplx* H, int64_t n, int ihi, cplx* out) {
     out[n + i] = i > 0 ? H[i + (int64_t)(i - 1) * n] : cplx{0.0, 0.0};
 }
 
+__global__ void zzero_entry_kernel(cplx* H, int64_t n, int i, int j) { H[i + (int64_t)j * n] = cplx{0.0, 0.0}; }
+
+// Schur mode: the diagonal block H[l:l+m, l:l+m] (m <= kZSmall) finished in one piece: complex Schur form
+// T = V^H H V by the one-wave factorisation with V kept.  T goes back in place (exact zeros below the
+// diagonal once it converged, below the sub-diagonal otherwise), V to Vout (m x m, column-major); the
+// caller applies V to the columns right of the block, the rows above it and Z.  info = {fail, most sweeps}.
+__global__ __launch_bounds__(kZAedThreads) void zschur_block_kernel(cplx* Hg, int64_t n, int l, int m, cplx* w,
+                                                                    cplx* Vout, int* info) {
+    constexpr int lh = kZSmall + 1;
+    constexpr int NT = kZAedThreads;
+    __shared__ cplx t[kZSmall * lh];
+    __shared__ cplx v[kZSmall * lh];
+    __shared__ int sfail;
+    const int tid = threadIdx.x;
+    for (int e = tid; e < m * m; e += NT) {
+        const int i = e % m, j = e / m;
+        t[i + j * lh] = Hg[(l + i) + (int64_t)(l + j) * n];
+        v[i + j * lh] = i == j ? cplx{1.0, 0.0} : cplx{0.0, 0.0};
+    }
+    __syncthreads();
+    if (tid < 64) {
+        int fail, maxsw, steps;
+        zwave_hqr<true>(t, v, m, w, fail, maxsw, steps);
+        if (tid == 0) {
+            sfail = fail;
+            info[0] = fail;
+            info[1] = maxsw;
+        }
+    }
+    __syncthreads();
+    const int below = sfail ? 1 : 0;   // converged: triangular, the accepted sub-diagonal entries exact zeros
+    for (int e = tid; e < m * m; e += NT) {
+        const int i = e % m, j = e / m;
+        Hg[(l + i) + (int64_t)(l + j) * n] = i > j + below ? cplx{0.0, 0.0} : t[i + j * lh];
+        Vout[e] = v[i + j * lh];
+    }
+}
+
 }  // namespace dev
 
 static double cabs1_h(const cplx& a) { return std::fabs(a.re) + std::fabs(a.im); }
@@ -785,9 +823,14 @@ static double cabs1_h(const cplx& a) { return std::fabs(a.re) + std::fabs(a.im);
 // undeflated eigenvalues becoming the shifts) 0.54 / 4.4 s.  Both were removed.
 static constexpr int kZAedWin = 48;
 
-// eigenvalues of the complex Hessenberg matrix H (device, n x n, leading dimension n; destroyed)
-int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_host, int32_t* sweeps_out,
-                       int32_t* fail_out) {
+// eigenvalues of the complex Hessenberg matrix H (device, n x n, leading dimension n; destroyed).
+// kSchur = true (schur_sweeps_c128): the same sweeps, shifts and launches of the chase, with every delayed
+// update widened to the whole matrix (left regions to column n - 1, right regions from row 0), the window
+// factors also applied to Z (n x n, leading dimension n; null: none), accepted sub-diagonal entries stored
+// as zeros and blocks of at most kZSmall rows finished by zschur_block_kernel; w_host is not written.
+template <bool kSchur>
+static int zfrancis_impl(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_host, int32_t* sweeps_out,
+                         int32_t* fail_out, cplx* Z) {
     hipStream_t st = ctx->stream;
     const double eps = 2.220446049250313e-16;
     DevBuf bw, bds, bU, bsh, binfo, bV;
@@ -837,6 +880,26 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
         EIGSOL_HIP(stream_wait(st));
         return EIGSOL_OK;
     };
+    // Schur mode: the factor U (W x W) of the rows / columns [s, s + W) applied outside them: U^H to the
+    // columns [e, n), U to the rows [0, rhi) and to Z's columns
+    auto apply_outside = [&](int s, int W, int64_t rhi, const cplx* U) {
+        const int e = s + W;
+        constexpr int per = dev::kZMG;
+        dev::ZWinGemmBatch gb{H, (int64_t)n, 1, {}};
+        if (e < n) {
+            gb.w[0] = dev::ZWinGemm{s, W, (int64_t)e, (int64_t)n, 0, U};
+            hipLaunchKernelGGL(dev::zwin_gemm_mfma<true>, dim3((unsigned)((n - e + per - 1) / per)), dim3(dev::kZMT), 0, st, gb);
+        }
+        if (rhi > 0) {
+            gb.w[0] = dev::ZWinGemm{s, W, 0, rhi, 0, U};
+            hipLaunchKernelGGL(dev::zwin_gemm_mfma<false>, dim3((unsigned)((rhi + per - 1) / per)), dim3(dev::kZMT), 0, st, gb);
+        }
+        if (Z) {
+            dev::ZWinGemmBatch zb{Z, (int64_t)n, 1, {}};
+            zb.w[0] = dev::ZWinGemm{s, W, 0, (int64_t)n, 0, U};
+            hipLaunchKernelGGL(dev::zwin_gemm_mfma<false>, dim3((unsigned)((n + per - 1) / per)), dim3(dev::kZMT), 0, st, zb);
+        }
+    };
     bool scanned = false;   // the previous sweep's closing scan is still current (nothing ran since)
     while (rc == EIGSOL_OK && ihi >= 0) {
         if (!scanned && (rc = scan()) != EIGSOL_OK) break;
@@ -848,12 +911,31 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
             --l;
         }
         const int N = ihi - l + 1;
+        if constexpr (kSchur) {   // the accepted sub-diagonal entry becomes an exact zero
+            if (l > 0 && (ds[n + l].re != 0.0 || ds[n + l].im != 0.0))
+                hipLaunchKernelGGL(dev::zzero_entry_kernel, dim3(1), dim3(1), 0, st, H, (int64_t)n, l, l - 1);
+        }
         if (N <= dev::kZSmall) {
-            int info[2];
+            int info[2] = {0, 0};
             ++st_small;
-            if ((rc = small(l, ihi, dw + l, info)) != EIGSOL_OK) break;
+            if constexpr (kSchur) {
+                if (N > 1) {   // a 1 x 1 block is its own Schur form
+                    hipLaunchKernelGGL(dev::zschur_block_kernel, dim3(1), dim3(dev::kZAedThreads), 0, st, H, (int64_t)n, l, N,
+                                       dw + l, dV, dinfo);
+                    apply_outside(l, N, l, dV);
+                    if (hipGetLastError() != hipSuccess ||
+                        hipMemcpyAsync(hp->info, dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                        stream_wait(st) != hipSuccess) {
+                        rc = fail(EIGSOL_E_HIP, "complex QR: Schur block");
+                        break;
+                    }
+                    info[0] = hp->info[0];
+                    info[1] = hp->info[1];
+                }
+            } else if ((rc = small(l, ihi, dw + l, info)) != EIGSOL_OK) break;
             if (info[0]) failed = 1;
             sweeps = std::max({sweeps, stall, info[1]});
+            if (kSchur && failed) break;   // the block stays unreduced: T is upper Hessenberg there
             stall = 0;
             ihi = l - 1;
             continue;
@@ -891,7 +973,9 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
                 const int nd = info[1];
                 if (nd > 0) {
                     st_aed_defl += nd;
-                    if (kw > l) {   // rows of the block above the window: H[l, kw) x [kw, kw + nw) V
+                    if constexpr (kSchur) {   // V on the columns right of the window, the rows above it and Z
+                        apply_outside(kw, nw, kw, dV);
+                    } else if (kw > l) {   // rows of the block above the window: H[l, kw) x [kw, kw + nw) V
                         dev::ZWinGemmBatch rb{H, (int64_t)n, 1, {}};
                         rb.w[0] = dev::ZWinGemm{kw, nw, (int64_t)l, (int64_t)kw, 0, dV};
                         hipLaunchKernelGGL(dev::zwin_gemm_mfma<false>, dim3((kw - l + dev::kZMG - 1) / dev::kZMG),
@@ -971,22 +1055,31 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
             // delayed updates: every left region, then every right region (U_a^H X U_b = (U_a^H X) U_b)
             // on the matrix cores
             constexpr int per = dev::kZMG;
-            dev::ZWinGemmBatch lb{H, (int64_t)n, 0, {}}, rb{H, (int64_t)n, 0, {}};
-            int nlb = 0, nrb = 0;
+            // Schur mode: left regions to column n - 1, right regions from row 0 (the window's own rows
+            // from max(l, s) on were updated by the chase), and Z's columns [s, e) as one more right batch
+            dev::ZWinGemmBatch lb{H, (int64_t)n, 0, {}}, rb{H, (int64_t)n, 0, {}}, zb{Z, (int64_t)n, 0, {}};
+            const int lend = kSchur ? (int)n : ihi + 1;   // left regions: columns [e, lend)
+            int nlb = 0, nrb = 0, nzb = 0;
             for (int q = 0; q < nwin; ++q) {
                 const dev::ZChaseWin& w = cb.w[q];
                 const int W = w.e - w.s;
-                if (w.e <= ihi) {
-                    lb.w[lb.nw++] = dev::ZWinGemm{w.s, W, (int64_t)w.e, (int64_t)ihi + 1, nlb, w.U};
-                    nlb += (ihi + 1 - w.e + per - 1) / per;
+                const int rlo = kSchur ? 0 : l, rhi = kSchur ? std::max(l, w.s) : w.s;   // right regions: rows [rlo, rhi)
+                if (w.e < lend) {
+                    lb.w[lb.nw++] = dev::ZWinGemm{w.s, W, (int64_t)w.e, (int64_t)lend, nlb, w.U};
+                    nlb += (lend - w.e + per - 1) / per;
                 }
-                if (w.s > l) {
-                    rb.w[rb.nw++] = dev::ZWinGemm{w.s, W, (int64_t)l, (int64_t)w.s, nrb, w.U};
-                    nrb += (w.s - l + per - 1) / per;
+                if (rhi > rlo) {
+                    rb.w[rb.nw++] = dev::ZWinGemm{w.s, W, (int64_t)rlo, (int64_t)rhi, nrb, w.U};
+                    nrb += (rhi - rlo + per - 1) / per;
+                }
+                if (kSchur && Z) {
+                    zb.w[zb.nw++] = dev::ZWinGemm{w.s, W, 0, (int64_t)n, nzb, w.U};
+                    nzb += (int)((n + per - 1) / per);
                 }
             }
             if (nlb > 0) hipLaunchKernelGGL(dev::zwin_gemm_mfma<true>, dim3(nlb), dim3(dev::kZMT), 0, st, lb);
             if (nrb > 0) hipLaunchKernelGGL(dev::zwin_gemm_mfma<false>, dim3(nrb), dim3(dev::kZMT), 0, st, rb);
+            if (nzb > 0) hipLaunchKernelGGL(dev::zwin_gemm_mfma<false>, dim3(nzb), dim3(dev::kZMT), 0, st, zb);
             t0 = t1;
         }
         if (hipGetLastError() != hipSuccess) { rc = fail(EIGSOL_E_HIP, "complex QR: launch"); break; }
@@ -999,7 +1092,7 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
                 break;
             }
     }
-    if (rc == EIGSOL_OK) {
+    if (rc == EIGSOL_OK && !kSchur) {
         if (hipMemcpyAsync(w_host, dw, n * sizeof(cplx), hipMemcpyDeviceToHost, st) != hipSuccess ||
             stream_wait(st) != hipSuccess)
             rc = fail(EIGSOL_E_HIP, "complex QR: download");
@@ -1010,6 +1103,19 @@ int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_
     *sweeps_out = std::max(1, sweeps);
     *fail_out = failed;
     return rc;
+}
+
+int francis_large_c128(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_host, int32_t* sweeps_out,
+                       int32_t* fail_out) {
+    return zfrancis_impl<false>(ctx, H, n, maxits, w_host, sweeps_out, fail_out, nullptr);
+}
+
+// The sweeps in Schur mode (schur.hip): H (upper Hessenberg, exact zeros below the sub-diagonal) becomes the
+// upper triangular T, Z (null: none) becomes Z U for the unitary U with T = U^H H U.  *fail_out: T is upper
+// Hessenberg only; the similarity holds all the same.
+int schur_sweeps_c128(eigsol_ctx* ctx, cplx* H, int64_t n, cplx* Z, int maxits, int32_t* sweeps_out,
+                      int32_t* fail_out) {
+    return zfrancis_impl<true>(ctx, H, n, maxits, nullptr, sweeps_out, fail_out, Z);
 }
 
 }  // namespace eigsol
