@@ -617,6 +617,15 @@ struct SchurResult {
     bool converged = false;                              // false: T is upper Hessenberg only, A = Z T Z^H still holds
 };
 
+// Sylvester and Lyapunov equations (solve_sylvester / solve_lyapunov, solvers.hpp; no counterpart in the
+// reference): Bartels-Stewart on the device (eigsol_sylvester_dense / eigsol_lyapunov_dense).
+template <typename S>
+struct SylvesterResult {
+    DenseMatrix<S> X;                    // m x n
+    int perturbed = 0;                   // diagonal block pairs in which a pivot below smin was replaced by smin
+    bool converged = false;              // both Schur factorisations converged (the solvers throw otherwise)
+};
+
 // Thin singular value decomposition (svd / svdvals, solvers.hpp; no counterpart in the reference): block
 // one-sided Jacobi on the device (eigsol_svd_dense).
 struct SvdOptions {

@@ -13,6 +13,8 @@
 //                                  eigsol_svds_dense)
 //   krylovSchur<S> / _dense        new: nev eigenpairs, dominant or nearest a shift (eigsol_krylov_csr /
 //                                  eigsol_krylov_dense)
+//   solve_sylvester<S> / solve_lyapunov<S>  new: A X + X B = C and A X + X A^H = Q on DenseMatrix<S>
+//                                  (eigsol_sylvester_dense / eigsol_lyapunov_dense)
 //
 // Scalars: double and std::complex<double> natively; float and std::complex<float> natively for the
 // power method and the triangular-CSR shifted inverse, promoted to fp64 for the other solvers
@@ -692,6 +694,66 @@ SchurResult<S> schur(const DenseMatrix<S>& A, const SchurOptions& opts = {}) {
         res.converged = conv != 0;
         return res;
     }
+}
+
+// ------------------------------------------------------------------------------- sylvester, lyapunov
+// A X + X B = C (solve_sylvester, eigsol_sylvester_dense) and A X + X A^H = Q (solve_lyapunov,
+// eigsol_lyapunov_dense) by Bartels-Stewart on the device: the Schur forms by schur's pipeline, the
+// quasi-triangular equation by wavefronts of block solves and rank-K updates, the transforms on the matrix cores.
+// opts.maxIterations bounds the sweeps of each Schur factorisation; opts.vectors is not read.  Throws if a
+// factorisation does not converge.  float and std::complex<float> run on their fp64 promotion; X is rounded back.
+namespace detail {
+template <ScalarConcept S>
+SylvesterResult<S> sylvester_run(const char* who, const DenseMatrix<S>& A, const DenseMatrix<S>* B, const DenseMatrix<S>& C,
+                                 const SchurOptions& opts) {
+    const std::int64_t m = A.rows(), n = B ? B->rows() : A.rows();
+    if (m != A.cols() || (B && n != B->cols())) throw std::runtime_error(std::string(who) + ": matrix must be square");
+    if (C.rows() != m || C.cols() != n) throw std::runtime_error(std::string(who) + ": the right-hand side does not fit");
+    if (m == 0 || n == 0) throw std::runtime_error(std::string(who) + ": matrix has zero size");
+    if constexpr (PromotedScalar<S>) {
+        using D = device_scalar_t<S>;
+        const DenseMatrix<D> Ad = convert_dense<D>(A), Cd = convert_dense<D>(C);
+        SylvesterResult<D> rd;
+        if (B) {
+            const DenseMatrix<D> Bd = convert_dense<D>(*B);
+            rd = sylvester_run<D>(who, Ad, &Bd, Cd, opts);
+        } else {
+            rd = sylvester_run<D>(who, Ad, nullptr, Cd, opts);
+        }
+        SylvesterResult<S> rs;
+        rs.X = convert_dense<S>(rd.X);
+        rs.perturbed = rd.perturbed;
+        rs.converged = rd.converged;
+        return rs;
+    } else if constexpr (!DeviceScalar<S>) {
+        throw std::runtime_error(std::string(who) + ": scalar type not supported by the device path (double, std::complex<double>)");
+    } else {
+        SylvesterResult<S> res;
+        eigsol_solver_options o{};
+        o.max_iterations = opts.maxIterations;
+        res.X = DenseMatrix<S>(m, n);
+        std::int32_t pert = 0, conv = 0;
+        if (B)
+            check(eigsol_sylvester_dense(ctx(), dtype_of<S>(), m, n, A.data(), B->data(), C.data(), &o, res.X.data(), &pert, &conv), who);
+        else
+            check(eigsol_lyapunov_dense(ctx(), dtype_of<S>(), m, A.data(), C.data(), &o, res.X.data(), &pert, &conv), who);
+        if (!conv) throw std::runtime_error(std::string(who) + ": a Schur factorisation did not converge");
+        res.perturbed = pert;
+        res.converged = true;
+        return res;
+    }
+}
+}  // namespace detail
+
+template <ScalarConcept S>
+SylvesterResult<S> solve_sylvester(const DenseMatrix<S>& A, const DenseMatrix<S>& B, const DenseMatrix<S>& C,
+                                   const SchurOptions& opts = {}) {
+    return detail::sylvester_run<S>("solve_sylvester", A, &B, C, opts);
+}
+
+template <ScalarConcept S>
+SylvesterResult<S> solve_lyapunov(const DenseMatrix<S>& A, const DenseMatrix<S>& Q, const SchurOptions& opts = {}) {
+    return detail::sylvester_run<S>("solve_lyapunov", A, nullptr, Q, opts);
 }
 
 // ------------------------------------------------------------------------------------------- svd

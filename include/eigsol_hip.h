@@ -665,6 +665,50 @@ int eigsol_schur_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colm
                        double* eig_im, int32_t* iterations, int32_t* converged);
 int eigsol_schur_stage_times(eigsol_ctx* ctx, double* ms4);
 
+/* ---------------------------------------------------------------- Sylvester and Lyapunov equations (dense)
+ * Bartels-Stewart on the device (csrc/sylvester.hip).  The reference has no such solver; the routines below
+ * correspond to LAPACK xTRSYL and to scipy.linalg.solve_sylvester / solve_continuous_lyapunov.  All matrices
+ * are column-major host arrays of EIGSOL_F64 or EIGSOL_C128 scalars.
+ *
+ * eigsol_trsyl_dense (LAPACK dtrsyl / ztrsyl with isgn = +1, without its scale factor): solves
+ * R Y + Y op(S) = F in place in F_inout (m x n), op(S) = S, or S^H when trans_b != 0.  R (m x m) and S (n x n)
+ * are upper triangular (C128) or real quasi-triangular in eigsol_schur_dense's standard form (F64: 2 x 2
+ * diagonal blocks with equal diagonal entries and off-diagonal entries of opposite sign).  The structure is
+ * checked on the host before the upload: a non-zero below the sub-diagonal, a non-zero complex sub-diagonal
+ * entry, or two consecutive non-zero real sub-diagonal entries fail with EIGSOL_E_INVALID.  The matrices are
+ * cut into blocks of 63 or 64 (F64) / 32 (C128) rows that split no 2 x 2 block; the blocks of one
+ * anti-diagonal wavefront are solved by one launch (one workgroup per block, in LDS) and applied by two
+ * batched rank-K launches on the fp64 matrix cores.  No atomics: two calls give the same bits.
+ * A pivot of a 1 x 1 .. 4 x 4 diagonal system below smin = max(eps max(max|R_ii|, max|S_jj|), 2^-1022 / eps)
+ * in modulus is replaced by smin (dlasy2's rule); *perturbed counts the blocks in which that happened (0: the
+ * equation was solved as posed).  There is no overflow scale factor: an ill-posed equation can give a
+ * non-finite Y.
+ *
+ * eigsol_sylvester_dense (scipy.linalg.solve_sylvester; LAPACK xGEES + xTRSYL): solves A X + X B = C, A m x m,
+ * B n x n, C and X_out m x n: A = U R U^H and B = V S V^H by the pipeline of eigsol_schur_dense, F = U^H C V,
+ * the triangular stage, X = U Y V^H; between the three uploads and the one download everything stays on the
+ * device.  eigsol_lyapunov_dense (scipy.linalg.solve_continuous_lyapunov): solves A X + X A^H = Q with one
+ * Schur form, F = U^H Q U, the triangular stage with op(S) = R^H, X = U Y U^H.  opts->max_iterations bounds the
+ * sweeps of each Schur factorisation (null opts: 1000).  If one does not converge, *converged = 0, X_out is
+ * not written and the call returns EIGSOL_OK; else *converged = 1.
+ * Status: EIGSOL_E_INVALID (null pointers, negative orders, unknown dtype, max_iterations < 1),
+ * EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD; an order above eigsol_schur_dense's: 16384 real, 8192 complex),
+ * EIGSOL_E_SOLVER (a non-finite entry in any input, found on the host before the upload).  m == 0 or n == 0:
+ * EIGSOL_OK with nothing written but *perturbed = 0 and *converged = 1.
+ * Out of scope: discrete-time (Stein) and generalised equations, the sign variant A X - X B, xTRSYL's scale
+ * factor, inputs outside eigsol_schur_dense's range guard, single precision and double-double.
+ * eigsol_sylvester_stage_times: the context's last eigsol_sylvester_dense / eigsol_lyapunov_dense call by
+ * stream events, 5 doubles in ms: Schur of A, Schur of B (0 for Lyapunov), the transforms in, the triangular
+ * stage, the transforms out with the copy to the host. */
+int eigsol_trsyl_dense(eigsol_ctx* ctx, int dtype, int64_t m, int64_t n, const void* R_colmajor,
+                       const void* S_colmajor, int trans_b, void* F_inout, int32_t* perturbed);
+int eigsol_sylvester_dense(eigsol_ctx* ctx, int dtype, int64_t m, int64_t n, const void* A_colmajor,
+                           const void* B_colmajor, const void* C_colmajor, const eigsol_solver_options* opts,
+                           void* X_out, int32_t* perturbed, int32_t* converged);
+int eigsol_lyapunov_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor, const void* Q_colmajor,
+                          const eigsol_solver_options* opts, void* X_out, int32_t* perturbed, int32_t* converged);
+int eigsol_sylvester_stage_times(eigsol_ctx* ctx, double* ms5);
+
 /* ---------------------------------------------------------------- singular value decomposition (dense)
  * eigsol_svd_dense: the thin singular value decomposition A = U diag(s) V^H of a real (EIGSOL_F64) or
  * complex (EIGSOL_C128) dense m x n matrix, k = min(m, n) (csrc/svd.hip).  The reference has no such solver.

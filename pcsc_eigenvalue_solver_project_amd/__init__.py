@@ -8,13 +8,15 @@ No CPU fallback exists: without the library or a gfx950 device every call raises
 """
 from __future__ import annotations
 
+import ctypes   # by its own name where a parameter is called C (solve_sylvester)
 import ctypes as C
 from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
 
-from ._capi import (EIGSOL_C64, EIGSOL_C128, EIGSOL_CDD, EIGSOL_DD, EIGSOL_E_INVALID, EIGSOL_E_SIZE_MISMATCH, EIGSOL_E_UNSUPPORTED, EIGSOL_F32,
+from ._capi import (EIGSOL_C64, EIGSOL_C128, EIGSOL_CDD, EIGSOL_DD, EIGSOL_E_INVALID, EIGSOL_E_SIZE_MISMATCH, EIGSOL_E_SOLVER,
+                    EIGSOL_E_UNSUPPORTED, EIGSOL_F32,
                     EIGSOL_F64, EIGSOL_KRYLOV_LM, EIGSOL_KRYLOV_SHIFT_INVERT, EigSolError, KrylovOptionsC, SolverOptionsC,
                     SubspaceOptionsC, call, check, last_error, lib)
 from ._capi import EIGSOL_EIGH_INDEX, EIGSOL_EIGH_VALUE, EighOptionsC
@@ -27,6 +29,7 @@ __all__ = [
     "KrylovOptions", "KrylovResult", "krylov_schur", "krylov_orth", "krylov_rotate",
     "EighResult", "eigh", "eigvalsh", "eigh_stage_times", "tridiag_plan", "eigh_dc_stage_times", "dc_deflate",
     "cholesky", "geigh_stage_times", "EigResult", "eig", "eig_stage_times", "SchurResult", "schur", "schur_stage_times",
+    "SylvesterResult", "solve_sylvester", "solve_continuous_lyapunov", "trsyl", "sylvester_stage_times",
     "SvdResult", "svd", "svdvals", "svd_stage_times",
     "SvdsOptions", "SvdsResult", "svds", "svds_stage_times", "dense_mv_h",
 ]
@@ -996,6 +999,93 @@ def schur_stage_times(ctx: Context) -> dict:
     ms = (C.c_double * 4)()
     call("eigsol_schur_stage_times", ctx.handle, ms)
     return {k: ms[i] * 1e-3 for i, k in enumerate(("reduction", "form_q", "sweeps", "finish"))}
+
+
+@dataclass
+class SylvesterResult:
+    """Result of :func:`solve_sylvester` / :func:`solve_continuous_lyapunov`: ``X`` m x n, Fortran order, float64
+    (all inputs real) or complex128; ``perturbed`` the number of diagonal block pairs of the triangular stage in
+    which a pivot below LAPACK's ``smin`` was replaced by it (0: the equation was solved as posed; positive: A
+    and -B share an eigenvalue to working precision and X solves a nearby equation); ``converged`` both Schur
+    factorisations converged (a result is only returned when they did)."""
+
+    X: np.ndarray
+    perturbed: int
+    converged: bool
+
+
+def _syl_operands(who: str, *mats):
+    mats = [np.asarray(M) for M in mats]
+    dt = np.complex128 if any(np.iscomplexobj(M) for M in mats) else np.float64
+    for M in mats:
+        if M.ndim != 2:
+            raise EigSolError(EIGSOL_E_SIZE_MISMATCH, f"{who}: every operand is a matrix, got shape {M.shape}")
+    return [np.asfortranarray(M, dtype=dt) for M in mats], dt
+
+
+def _syl_finish(who: str, X, pert, conv) -> SylvesterResult:
+    if not conv.value:
+        raise EigSolError(EIGSOL_E_SOLVER, f"{who}: a Schur factorisation did not converge")
+    return SylvesterResult(X, int(pert.value), True)
+
+
+def solve_sylvester(ctx: Context, A, B, C, opts: SolverOptions = SolverOptions()) -> SylvesterResult:
+    """Solves ``A X + X B = C`` on the device by Bartels-Stewart (``eigsol_sylvester_dense``; SciPy's
+    ``solve_sylvester``): the Schur forms of A (m x m) and B (n x n) by :func:`schur`'s pipeline, the
+    quasi-triangular equation by anti-diagonal wavefronts of block solves in LDS and rank-K updates on the
+    matrix cores, the four transforms on the matrix cores.  Complex input anywhere promotes every operand to
+    complex128, else float64.  Raises :class:`EigSolError` if a Schur factorisation does not converge."""
+    (A, B, Cm), dt = _syl_operands("solve_sylvester", A, B, C)
+    m, n = A.shape[0], B.shape[0]
+    if A.shape != (m, m) or B.shape != (n, n) or Cm.shape != (m, n):
+        raise EigSolError(EIGSOL_E_SIZE_MISMATCH,
+                          f"solve_sylvester: A {A.shape}, B {B.shape} and C {Cm.shape} do not form A X + X B = C")
+    o = SolverOptionsC(int(opts.maxIterations), float(opts.tolerance))
+    X = np.zeros((m, n), dtype=dt, order="F")
+    pert, conv = ctypes.c_int32(0), ctypes.c_int32(0)
+    call("eigsol_sylvester_dense", ctx.handle, _dtype_code(dt), m, n, _ptr(A), _ptr(B), _ptr(Cm), ctypes.byref(o), _ptr(X),
+         ctypes.byref(pert), ctypes.byref(conv))
+    return _syl_finish("solve_sylvester", X, pert, conv)
+
+
+def solve_continuous_lyapunov(ctx: Context, A, Q, opts: SolverOptions = SolverOptions()) -> SylvesterResult:
+    """Solves ``A X + X A^H = Q`` on the device (``eigsol_lyapunov_dense``; SciPy's
+    ``solve_continuous_lyapunov``): one Schur form serves both sides.  Otherwise as :func:`solve_sylvester`."""
+    (A, Qm), dt = _syl_operands("solve_continuous_lyapunov", A, Q)
+    n = A.shape[0]
+    if A.shape != (n, n) or Qm.shape != (n, n):
+        raise EigSolError(EIGSOL_E_SIZE_MISMATCH,
+                          f"solve_continuous_lyapunov: A {A.shape} and Q {Qm.shape} must be square and of one order")
+    o = SolverOptionsC(int(opts.maxIterations), float(opts.tolerance))
+    X = np.zeros((n, n), dtype=dt, order="F")
+    pert, conv = C.c_int32(0), C.c_int32(0)
+    call("eigsol_lyapunov_dense", ctx.handle, _dtype_code(dt), n, _ptr(A), _ptr(Qm), C.byref(o), _ptr(X), C.byref(pert),
+         C.byref(conv))
+    return _syl_finish("solve_continuous_lyapunov", X, pert, conv)
+
+
+def trsyl(ctx: Context, R, S, F, trans_b: bool = False):
+    """The triangular stage alone (``eigsol_trsyl_dense``; LAPACK ``xTRSYL`` without its scale factor): solves
+    ``R Y + Y op(S) = F`` with op(S) = S, or S^H when ``trans_b``.  R and S are upper triangular (complex) or
+    quasi-triangular in :func:`schur`'s standard form (real); anything else raises ``EIGSOL_E_INVALID``.
+    Returns ``(Y, perturbed)``, Y m x n in Fortran order."""
+    (R, S, Fm), dt = _syl_operands("trsyl", R, S, F)
+    m, n = R.shape[0], S.shape[0]
+    if R.shape != (m, m) or S.shape != (n, n) or Fm.shape != (m, n):
+        raise EigSolError(EIGSOL_E_SIZE_MISMATCH, f"trsyl: R {R.shape}, S {S.shape} and F {Fm.shape} do not fit")
+    Y = np.array(Fm, dtype=dt, order="F", copy=True)
+    pert = C.c_int32(0)
+    call("eigsol_trsyl_dense", ctx.handle, _dtype_code(dt), m, n, _ptr(R), _ptr(S), 1 if trans_b else 0, _ptr(Y),
+         C.byref(pert))
+    return Y, int(pert.value)
+
+
+def sylvester_stage_times(ctx: Context) -> dict:
+    """The context's last :func:`solve_sylvester` / :func:`solve_continuous_lyapunov` call by stream events, in
+    seconds."""
+    ms = (C.c_double * 5)()
+    call("eigsol_sylvester_stage_times", ctx.handle, ms)
+    return {k: ms[i] * 1e-3 for i, k in enumerate(("schur_a", "schur_b", "transform_in", "triangular", "transform_out"))}
 
 
 @dataclass

@@ -183,6 +183,10 @@ SIGNATURES = {
     "eigsol_eig_stage_times": [_vp, _pd],
     "eigsol_schur_dense": [_vp, C.c_int, _i64, _vp, C.POINTER(SolverOptionsC), _vp, _vp, _vp, _pd, _pi32, _pi32],
     "eigsol_schur_stage_times": [_vp, _pd],
+    "eigsol_trsyl_dense": [_vp, C.c_int, _i64, _i64, _vp, _vp, C.c_int, _vp, _pi32],
+    "eigsol_sylvester_dense": [_vp, C.c_int, _i64, _i64, _vp, _vp, _vp, C.POINTER(SolverOptionsC), _vp, _pi32, _pi32],
+    "eigsol_lyapunov_dense": [_vp, C.c_int, _i64, _vp, _vp, C.POINTER(SolverOptionsC), _vp, _pi32, _pi32],
+    "eigsol_sylvester_stage_times": [_vp, _pd],
     "eigsol_svd_dense": [_vp, C.c_int, _i64, _i64, _vp, C.POINTER(SvdOptionsC), _pd, _vp, _vp, _pi32, _pi64],
     "eigsol_svd_stage_times": [_vp, _pd],
     "eigsol_csr_adjoint": [_vp, _ppv],

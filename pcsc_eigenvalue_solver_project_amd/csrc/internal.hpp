@@ -277,6 +277,10 @@ struct eigsol_ctx {
     // the last eigsol_schur_dense call's stages in ms (eigsol_schur_stage_times): reduction, forming Q, sweeps
     // with their updates, finish (standardisation, eigenvalues, copies)
     double schur_ms[4] = {0.0, 0.0, 0.0, 0.0};
+    // the last eigsol_sylvester_dense / eigsol_lyapunov_dense call's stages in ms
+    // (eigsol_sylvester_stage_times): Schur of A, Schur of B, transforms in, triangular stage, transforms
+    // out with the copies
+    double sylvester_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 };
 
 struct eigsol_csr {

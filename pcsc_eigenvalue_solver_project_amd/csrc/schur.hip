@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "kernels_common.hpp"
+#include "schur.hpp"
 #include "scratch.hpp"
 
 namespace eigsol {
@@ -245,24 +246,18 @@ template <> struct SchurOps<cplx> {
 
 constexpr int64_t kQChunk = 4096;   // columns per application of Q, as eig.hip's back-transformation
 
+}  // namespace
+
 template <class S>
-int schur_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int max_iter, void* T_out, void* Z_out, void* eig_re_or_c,
-               double* eig_im, int32_t* iterations, int32_t* converged) {
+int schur_device(eigsol_ctx* ctx, int64_t n, const void* A_host, int max_iter, bool wantz, SchurDevice& out,
+                 StageClock& clock) {
     constexpr bool kReal = std::is_same_v<S, double>;
     using Ops = SchurOps<S>;
-    {
-        const double* a = static_cast<const double*>(A_host);
-        const int64_t cnt = (kReal ? 1 : 2) * n * n;
-        for (int64_t i = 0; i < cnt; ++i)
-            if (!std::isfinite(a[i])) return fail(EIGSOL_E_SOLVER, "eigsol_schur_dense: the matrix holds a non-finite entry");
-    }
     hipStream_t st = ctx->stream;
     const int NB = Ops::nb();
     const int64_t npan = n >= 3 ? (n - 2 + NB - 1) / NB : 0;
-    const bool wantz = Z_out != nullptr;
-    StageClock clock;
-    EIGSOL_TRY(clock.start(4));
-    DevBuf dH, dZ, dV, dT, dw, drot;
+    DevBuf &dH = out.T, &dZ = out.Z, &dw = out.w, &drot = out.rot;
+    DevBuf dV, dT;
     EIGSOL_TRY(dH.alloc((size_t)n * n * sizeof(S)));
     EIGSOL_TRY(dw.alloc((size_t)n * sizeof(cplx)));
     if (wantz) EIGSOL_TRY(dZ.alloc((size_t)n * n * sizeof(S)));
@@ -311,12 +306,40 @@ int schur_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int max_iter, voi
     }
     if (escale != 0)
         hipLaunchKernelGGL(dev::schur_scale_pow2, dim3(1024), dim3(256), 0, st, dH.as<double>(), (kReal ? 1 : 2) * n * n, -escale);
-    std::vector<cplx> w(n);
     if constexpr (kReal)
         hipLaunchKernelGGL(dev::schur_eigs_real, dim3(grow), dim3(256), 0, st, dH.as<double>(), n, dw.as<double>());
     else
         hipLaunchKernelGGL(dev::schur_eigs_cplx, dim3(grow), dim3(256), 0, st, dH.as<cplx>(), n, dw.as<cplx>());
     EIGSOL_HIP(hipGetLastError());
+    out.sweeps = sweeps;
+    out.failed = failed;
+    return EIGSOL_OK;
+}
+
+template int schur_device<double>(eigsol_ctx*, int64_t, const void*, int, bool, SchurDevice&, StageClock&);
+template int schur_device<cplx>(eigsol_ctx*, int64_t, const void*, int, bool, SchurDevice&, StageClock&);
+
+namespace {
+
+template <class S>
+int schur_host(eigsol_ctx* ctx, int64_t n, const void* A_host, int max_iter, void* T_out, void* Z_out, void* eig_re_or_c,
+               double* eig_im, int32_t* iterations, int32_t* converged) {
+    constexpr bool kReal = std::is_same_v<S, double>;
+    {
+        const double* a = static_cast<const double*>(A_host);
+        const int64_t cnt = (kReal ? 1 : 2) * n * n;
+        for (int64_t i = 0; i < cnt; ++i)
+            if (!std::isfinite(a[i])) return fail(EIGSOL_E_SOLVER, "eigsol_schur_dense: the matrix holds a non-finite entry");
+    }
+    hipStream_t st = ctx->stream;
+    const bool wantz = Z_out != nullptr;
+    StageClock clock;
+    EIGSOL_TRY(clock.start(4));
+    SchurDevice sd;
+    EIGSOL_TRY(schur_device<S>(ctx, n, A_host, max_iter, wantz, sd, clock));
+    DevBuf &dH = sd.T, &dZ = sd.Z, &dw = sd.w;
+    const int32_t sweeps = sd.sweeps, failed = sd.failed;
+    std::vector<cplx> w(n);
     EIGSOL_HIP(hipMemcpyAsync(w.data(), dw.p, (size_t)n * sizeof(cplx), hipMemcpyDeviceToHost, st));
     EIGSOL_HIP(hipMemcpyAsync(T_out, dH.p, (size_t)n * n * sizeof(S), hipMemcpyDeviceToHost, st));
     if (wantz) EIGSOL_HIP(hipMemcpyAsync(Z_out, dZ.p, (size_t)n * n * sizeof(S), hipMemcpyDeviceToHost, st));
