@@ -602,10 +602,19 @@ struct EigResult {
 };
 
 // Schur form A = Z T Z^H (schur, solvers.hpp; no counterpart in the reference): the multishift sweeps of
-// qr_eigenvalues with T and Z kept (eigsol_schur_dense).
+// qr_eigenvalues with T and Z kept (eigsol_schur_dense).  sort: the eigenvalues to lead T (scipy.linalg.schur's
+// sort=; eigsol_schur_sorted_dense reorders on the device before anything is copied back).
+enum class SchurSort {
+    None = 0,
+    LeftHalfPlane = 1,        // Re < 0
+    RightHalfPlane = 2,       // Re >= 0
+    InsideUnitCircle = 3,     // |lambda| <= 1
+    OutsideUnitCircle = 4,    // |lambda| > 1
+};
 struct SchurOptions {
     int maxIterations = 1000;            // the sweeps' limit per deflation (SolverOptions::maxIterations)
     bool vectors = true;                 // false: T and the eigenvalues alone (the same bits)
+    SchurSort sort = SchurSort::None;
 };
 
 template <typename S>
@@ -615,6 +624,8 @@ struct SchurResult {
     std::vector<std::complex<double>> eigenvalues;       // in the order of T's diagonal; a pair: Im > 0 first, then its conjugate
     int iterations = 0;                                  // the sweeps', as QRResult reports them
     bool converged = false;                              // false: T is upper Hessenberg only, A = Z T Z^H still holds
+    std::int64_t sdim = 0;                               // with a sort or after ordschur: the selected eigenvalues, which lead T
+    bool ordered = false;                                // ... and whether every swap was accepted (false: partly reordered)
 };
 
 // Sylvester and Lyapunov equations (solve_sylvester / solve_lyapunov, solvers.hpp; no counterpart in the

@@ -13,6 +13,8 @@
 //                                  eigsol_svds_dense)
 //   krylovSchur<S> / _dense        new: nev eigenpairs, dominant or nearest a shift (eigsol_krylov_csr /
 //                                  eigsol_krylov_dense)
+//   schur<S> / ordschur<S>         new: the Schur form of a DenseMatrix<S>, optionally sorted, and its reordering
+//                                  (eigsol_schur_dense / eigsol_schur_sorted_dense / eigsol_ordschur_dense)
 //   solve_sylvester<S> / solve_lyapunov<S>  new: A X + X B = C and A X + X A^H = Q on DenseMatrix<S>
 //                                  (eigsol_sylvester_dense / eigsol_lyapunov_dense)
 //
@@ -670,6 +672,8 @@ SchurResult<S> schur(const DenseMatrix<S>& A, const SchurOptions& opts = {}) {
         rs.eigenvalues = std::move(rd.eigenvalues);
         rs.iterations = rd.iterations;
         rs.converged = rd.converged;
+        rs.sdim = rd.sdim;
+        rs.ordered = rd.ordered;
         return rs;
     } else if constexpr (!DeviceScalar<S>) {
         throw std::runtime_error("schur: scalar type not supported by the device path (double, std::complex<double>)");
@@ -682,16 +686,77 @@ SchurResult<S> schur(const DenseMatrix<S>& A, const SchurOptions& opts = {}) {
         res.eigenvalues.assign(static_cast<std::size_t>(n), std::complex<double>(0.0, 0.0));
         std::vector<double> wr(static_cast<std::size_t>(n), 0.0), wi(static_cast<std::size_t>(n), 0.0);
         constexpr bool real = std::is_floating_point_v<S>;
-        std::int32_t it = 0, conv = 0;
-        detail::check(eigsol_schur_dense(detail::ctx(), detail::dtype_of<S>(), n, A.data(), &o, res.T.data(),
-                                         opts.vectors ? static_cast<void*>(res.Z.data()) : nullptr,
-                                         real ? static_cast<void*>(wr.data()) : static_cast<void*>(res.eigenvalues.data()),
-                                         wi.data(), &it, &conv),
-                      "schur");
+        std::int32_t it = 0, conv = 0, ord = 0;
+        std::int64_t sdim = 0;
+        void* const zp = opts.vectors ? static_cast<void*>(res.Z.data()) : nullptr;
+        void* const wp = real ? static_cast<void*>(wr.data()) : static_cast<void*>(res.eigenvalues.data());
+        if (opts.sort == SchurSort::None)
+            detail::check(eigsol_schur_dense(detail::ctx(), detail::dtype_of<S>(), n, A.data(), &o, res.T.data(), zp, wp, wi.data(),
+                                             &it, &conv),
+                          "schur");
+        else
+            detail::check(eigsol_schur_sorted_dense(detail::ctx(), detail::dtype_of<S>(), n, A.data(), &o,
+                                                    static_cast<int>(opts.sort), res.T.data(), zp, wp, wi.data(), &sdim, &it, &conv,
+                                                    &ord),
+                          "schur");
+        res.sdim = sdim;
+        res.ordered = ord != 0;
         if constexpr (real)
             for (std::size_t i = 0; i < wr.size(); ++i) res.eigenvalues[i] = std::complex<double>(wr[i], wi[i]);
         res.iterations = it;
         res.converged = conv != 0;
+        return res;
+    }
+}
+
+// ---------------------------------------------------------------------------------------- ordschur
+// Reorders a Schur form so that the selected eigenvalues lead T (eigsol_ordschur_dense; LAPACK xTRSEN without its
+// condition estimates): select holds one flag per row of T; for a real T a flag on either row of a 2 x 2 block
+// selects the pair.  Z is updated where the input has one.  iterations / converged are carried over; sdim and
+// ordered are the reordering's.  float and std::complex<float> run on their fp64 promotion, as in schur.
+template <ScalarConcept S>
+SchurResult<S> ordschur(const SchurResult<S>& in, const std::vector<bool>& select) {
+    const std::int64_t n = in.T.rows();
+    if (n != in.T.cols()) throw std::runtime_error("ordschur: T must be square");
+    if (static_cast<std::int64_t>(select.size()) != n) throw std::runtime_error("ordschur: select needs one flag per row of T");
+    const bool vectors = in.Z.rows() == n && in.Z.cols() == n && n > 0;
+    if constexpr (PromotedScalar<S>) {
+        using D = device_scalar_t<S>;
+        SchurResult<D> id;
+        id.T = detail::convert_dense<D>(in.T);
+        if (vectors) id.Z = detail::convert_dense<D>(in.Z);
+        id.iterations = in.iterations;
+        id.converged = in.converged;
+        SchurResult<D> rd = ordschur<D>(id, select);
+        SchurResult<S> rs;
+        rs.T = detail::convert_dense<S>(rd.T);
+        if (vectors) rs.Z = detail::convert_dense<S>(rd.Z);
+        rs.eigenvalues = std::move(rd.eigenvalues);
+        rs.iterations = rd.iterations;
+        rs.converged = rd.converged;
+        rs.sdim = rd.sdim;
+        rs.ordered = rd.ordered;
+        return rs;
+    } else if constexpr (!DeviceScalar<S>) {
+        throw std::runtime_error("ordschur: scalar type not supported by the device path (double, std::complex<double>)");
+    } else {
+        SchurResult<S> res = in;
+        std::vector<std::uint8_t> sel(static_cast<std::size_t>(n), 0);
+        for (std::size_t i = 0; i < sel.size(); ++i) sel[i] = select[i] ? 1 : 0;
+        res.eigenvalues.assign(static_cast<std::size_t>(n), std::complex<double>(0.0, 0.0));
+        std::vector<double> wr(static_cast<std::size_t>(n), 0.0), wi(static_cast<std::size_t>(n), 0.0);
+        constexpr bool real = std::is_floating_point_v<S>;
+        std::int32_t ord = 0;
+        std::int64_t sdim = 0;
+        detail::check(eigsol_ordschur_dense(detail::ctx(), detail::dtype_of<S>(), n, res.T.data(),
+                                            vectors ? static_cast<void*>(res.Z.data()) : nullptr, sel.data(),
+                                            real ? static_cast<void*>(wr.data()) : static_cast<void*>(res.eigenvalues.data()),
+                                            wi.data(), &sdim, &ord),
+                      "ordschur");
+        if constexpr (real)
+            for (std::size_t i = 0; i < wr.size(); ++i) res.eigenvalues[i] = std::complex<double>(wr[i], wi[i]);
+        res.sdim = sdim;
+        res.ordered = ord != 0;
         return res;
     }
 }

@@ -654,9 +654,9 @@ int eigsol_eig_stage_times(eigsol_ctx* ctx, double* ms4);
  * EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD; n above the order the blocked reduction accepts, which is
  * eigsol_eigh_dense's: 16384 real, 8192 complex).  n == 0: EIGSOL_OK with *converged = 1.  A non-finite
  * entry of A fails with EIGSOL_E_SOLVER (found on the host, before the upload).
- * Out of scope: reordering the diagonal blocks (ordschur) and the complex Schur form of a real matrix
- * (rsf2csf); eigenvectors from T (xTREVC) and any change to eigsol_eig_dense; balancing; single precision
- * and double-double; any tuning of the deflation window or the chase.
+ * Out of scope: the complex Schur form of a real matrix (rsf2csf; reordering the diagonal blocks is
+ * eigsol_ordschur_dense below); eigenvectors from T (xTREVC) and any change to eigsol_eig_dense; balancing;
+ * single precision and double-double; any tuning of the deflation window or the chase.
  * eigsol_schur_stage_times: the context's last eigsol_schur_dense call by stream events, 4 doubles in ms:
  * reduction (guard, Hessenberg), forming Q, the sweeps with their updates, finish (standardisation,
  * scaling back, eigenvalues, the copies to the host). */
@@ -664,6 +664,56 @@ int eigsol_schur_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colm
                        const eigsol_solver_options* opts, void* T_out, void* Z_out, void* eig_re_or_c,
                        double* eig_im, int32_t* iterations, int32_t* converged);
 int eigsol_schur_stage_times(eigsol_ctx* ctx, double* ms4);
+
+/* ---------------------------------------------------------------- reordering a Schur form (dense)
+ * eigsol_ordschur_dense (LAPACK xTRSEN without its condition estimates; scipy.linalg.schur's sort=): reorders
+ * a Schur form A = Z T Z^H in place so that the selected eigenvalues lead T (csrc/ordschur.hip).  T_inout
+ * (host, n x n, column-major) is upper triangular (C128) or real quasi-triangular in eigsol_schur_dense's
+ * standard form (F64); Z_inout (NULL: none) is n x n likewise and receives Z U.  select holds one byte per
+ * row of T, non-zero: selected; for a real T a flag on either row of a 2 x 2 block selects the pair (LAPACK's
+ * rule).  The final order is the stable partition of T's diagonal blocks: the selected ones in their order,
+ * then the others in theirs, which is xTRSEN's.
+ * Algorithm: the power-of-two range guard of eigsol_schur_dense, undone exactly at the end; one flag byte
+ * per row on the device, which moves with its row; rounds of disjoint windows of two half-windows (47 rows
+ * real, 32 complex), even rounds on [2 k h, (2 k + 2) h), odd rounds on [(2 k + 1) h, (2 k + 3) h), a real
+ * window taking the 2 x 2 block that straddles its lower end and leaving the one that straddles its upper
+ * end to the window above.  One wave per window moves the window's selected blocks to its top in LDS by
+ * swaps of adjacent blocks (LAPACK dlaexc with its stability test, the small Sylvester equation solved by
+ * complete pivoting, every new 2 x 2 block standardised and possibly split; ztrexc's rotation for C128) and
+ * keeps the window's factor U; three launches on the fp64 matrix cores then apply U to T's columns right of
+ * the window, T's rows above it and Z's columns.  The host reads three words per round and stops after an
+ * even and an odd round without work.  No atomics: two calls give the same bits, and T and the eigenvalues
+ * have the same bits with and without Z; a selection that is already leading returns its input bit for bit.
+ * Out: the eigenvalues of the reordered T as eigsol_schur_dense writes them (eig_im is required for F64);
+ * *sdim (optional) the number of selected rows after the pair rule; *ordered (optional) 1, or 0 where a swap
+ * was rejected by dlaexc's test (the blocks are too close to exchange): the reordering stops after that
+ * round, T is a valid Schur form, A = Z T Z^H holds and the flags' count is still reported.
+ * Status: EIGSOL_E_INVALID (n < 0; null ctx; with n > 0 a null T_inout, select or eig_re_or_c, or a null
+ * eig_im with F64; unknown dtype; T with a non-zero below the sub-diagonal, a non-zero complex sub-diagonal
+ * entry, two consecutive non-zero real sub-diagonal entries or a real 2 x 2 block that is not in standard
+ * form), EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD; n above eigsol_schur_dense's order), EIGSOL_E_SOLVER (a
+ * non-finite entry of T or Z, found on the host).  n == 0: EIGSOL_OK with *sdim = 0, *ordered = 1.
+ *
+ * eigsol_schur_sorted_dense: eigsol_schur_dense followed by the reordering for sort = EIGSOL_SORT_LHP
+ * (Re < 0), _RHP (Re >= 0), _IUC (|lambda| <= 1) or _OUC (|lambda| > 1), scipy.linalg.schur's definitions, the
+ * modulus tested as re re + im im against 1;
+ * T and Z stay on the device in between and the flags are built there from the eigenvalues.  The result has
+ * the bits of eigsol_schur_dense followed by eigsol_ordschur_dense with the same selection.  Arguments and
+ * status as eigsol_schur_dense, and EIGSOL_E_INVALID for an unknown sort code.  A factorisation that did not
+ * converge is not reordered: *converged = 0, *ordered = 0, *sdim = 0.  eigsol_schur_stage_times then
+ * counts the reordering in its last stage.
+ * eigsol_ordschur_stats: the context's last reordering (either entry): its time in ms by stream events, the
+ * rounds that did work, the windows that did work and the swaps; null outputs are skipped.
+ * Out of scope: xTRSEN's condition estimates s and sep, use of U's block-triangular structure, pipelined
+ * swap chains, rsf2csf, generalised (QZ) reordering, single precision and double-double. */
+enum { EIGSOL_SORT_LHP = 1, EIGSOL_SORT_RHP = 2, EIGSOL_SORT_IUC = 3, EIGSOL_SORT_OUC = 4 };
+int eigsol_ordschur_dense(eigsol_ctx* ctx, int dtype, int64_t n, void* T_inout, void* Z_inout, const uint8_t* select,
+                          void* eig_re_or_c, double* eig_im, int64_t* sdim, int32_t* ordered);
+int eigsol_schur_sorted_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor,
+                              const eigsol_solver_options* opts, int sort, void* T_out, void* Z_out,
+                              void* eig_re_or_c, double* eig_im, int64_t* sdim, int32_t* iterations,
+                              int32_t* converged, int32_t* ordered);
+int eigsol_ordschur_stats(eigsol_ctx* ctx, double* ms, int32_t* rounds, int32_t* windows, int32_t* swaps);
 
 /* ---------------------------------------------------------------- Sylvester and Lyapunov equations (dense)
  * Bartels-Stewart on the device (csrc/sylvester.hip).  The reference has no such solver; the routines below

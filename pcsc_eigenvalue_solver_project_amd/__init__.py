@@ -29,6 +29,7 @@ __all__ = [
     "KrylovOptions", "KrylovResult", "krylov_schur", "krylov_orth", "krylov_rotate",
     "EighResult", "eigh", "eigvalsh", "eigh_stage_times", "tridiag_plan", "eigh_dc_stage_times", "dc_deflate",
     "cholesky", "geigh_stage_times", "EigResult", "eig", "eig_stage_times", "SchurResult", "schur", "schur_stage_times",
+    "OrdSchurResult", "ordschur", "ordschur_stats",
     "SylvesterResult", "solve_sylvester", "solve_continuous_lyapunov", "trsyl", "sylvester_stage_times",
     "SvdResult", "svd", "svdvals", "svd_stage_times",
     "SvdsOptions", "SvdsResult", "svds", "svds_stage_times", "dense_mv_h",
@@ -962,21 +963,40 @@ class SchurResult:
     opposite sign; complex input: upper triangular), ``Z`` n x n orthogonal / unitary or ``None``,
     ``eigenvalues`` complex128 in the order of T's diagonal (a conjugate pair is adjacent, bitwise conjugate,
     the member with the positive imaginary part first), ``iterations`` / ``converged`` the sweeps' as
-    :class:`QRResult` reports them.  Not converged: T is upper Hessenberg only; the product still holds."""
+    :class:`QRResult` reports them.  Not converged: T is upper Hessenberg only; the product still holds.
+    With ``sort``: ``sdim`` the number of leading eigenvalues that satisfy it and ``ordered`` whether every swap
+    was accepted (see :class:`OrdSchurResult`); ``None`` without."""
 
     T: np.ndarray
     Z: Optional[np.ndarray]
     eigenvalues: np.ndarray
     iterations: int
     converged: bool
+    sdim: Optional[int] = None
+    ordered: Optional[bool] = None
 
 
-def schur(ctx: Context, A, vectors: bool = True, opts: SolverOptions = SolverOptions()) -> SchurResult:
+_SORT_CODES = {"lhp": 1, "rhp": 2, "iuc": 3, "ouc": 4}   # EIGSOL_SORT_*
+
+
+def schur(ctx: Context, A, vectors: bool = True, opts: SolverOptions = SolverOptions(), sort=None) -> SchurResult:
     """Schur form of a general dense matrix on the device (``eigsol_schur_dense``): float64 input gives the real
     Schur form, complex128 input the complex one.  Blocked Hessenberg reduction, Q formed on the matrix cores,
     the multishift sweeps of :func:`qr_eigenvalues` with every update applied to the whole of T and to Z, the
     2 x 2 blocks of a real T standardised on the device.  ``vectors=False`` skips Z; T and the eigenvalues
-    are the same bits either way.  ``opts.maxIterations`` limits the sweeps per deflation."""
+    are the same bits either way.  ``opts.maxIterations`` limits the sweeps per deflation.
+
+    ``sort`` (SciPy's ``schur(sort=)``): ``"lhp"``, ``"rhp"``, ``"iuc"`` or ``"ouc"`` reorders the form on the
+    device before anything is copied back (``eigsol_schur_sorted_dense``); a boolean mask or a callable runs
+    :func:`ordschur` on the result.  Either way the bits are those of ``schur`` followed by :func:`ordschur`."""
+    if sort is not None and not isinstance(sort, str):
+        r = schur(ctx, A, vectors, opts)
+        if not r.converged:
+            return SchurResult(r.T, r.Z, r.eigenvalues, r.iterations, False, 0, False)
+        o = ordschur(ctx, r.T, r.Z, sort)
+        return SchurResult(o.T, o.Z, o.eigenvalues, r.iterations, r.converged, o.sdim, o.ordered)
+    if sort is not None and sort not in _SORT_CODES:
+        raise EigSolError(EIGSOL_E_INVALID, f"schur: sort is one of {sorted(_SORT_CODES)}, a mask or a callable, got {sort!r}")
     A = _square_dense(A, "schur")
     code = _dtype_code(A.dtype)
     n = A.shape[0]
@@ -988,10 +1008,102 @@ def schur(ctx: Context, A, vectors: bool = True, opts: SolverOptions = SolverOpt
     wr = np.zeros(max(n, 1), dtype=np.float64 if real else np.complex128)
     wi = np.zeros(max(n, 1), dtype=np.float64)
     it, conv = C.c_int32(0), C.c_int32(0)
-    call("eigsol_schur_dense", ctx.handle, code, n, _ptr(Af), C.byref(o), _ptr(T), _ptr(Z) if vectors and n else None,
-         _ptr(wr), wi.ctypes.data_as(C.POINTER(C.c_double)), C.byref(it), C.byref(conv))
+    sdim, ordered = None, None
+    if sort is None:
+        call("eigsol_schur_dense", ctx.handle, code, n, _ptr(Af), C.byref(o), _ptr(T), _ptr(Z) if vectors and n else None,
+             _ptr(wr), wi.ctypes.data_as(C.POINTER(C.c_double)), C.byref(it), C.byref(conv))
+    else:
+        sd, od = C.c_int64(0), C.c_int32(0)
+        call("eigsol_schur_sorted_dense", ctx.handle, code, n, _ptr(Af), C.byref(o), _SORT_CODES[sort], _ptr(T),
+             _ptr(Z) if vectors and n else None, _ptr(wr), wi.ctypes.data_as(C.POINTER(C.c_double)), C.byref(sd), C.byref(it),
+             C.byref(conv), C.byref(od))
+        sdim, ordered = int(sd.value), bool(od.value)
     w = (wr[:n] + 1j * wi[:n]) if real else wr[:n].copy()
-    return SchurResult(T, Z, np.asarray(w, dtype=np.complex128), int(it.value), bool(conv.value))
+    return SchurResult(T, Z, np.asarray(w, dtype=np.complex128), int(it.value), bool(conv.value), sdim, ordered)
+
+
+@dataclass
+class OrdSchurResult:
+    """Result of :func:`ordschur`: the reordered ``T`` and ``Z`` (``None`` if none was given), Fortran order, in
+    T's dtype; ``eigenvalues`` under :class:`SchurResult`'s contract; ``sdim`` the number of selected rows (a
+    selected conjugate pair counts two), which now lead; ``ordered`` false where a swap was rejected because two
+    blocks were too close to exchange: T is then a valid Schur form of the same matrix, partly reordered."""
+
+    T: np.ndarray
+    Z: Optional[np.ndarray]
+    eigenvalues: np.ndarray
+    sdim: int
+    ordered: bool
+
+
+def _block_eigenvalues(T: np.ndarray) -> np.ndarray:
+    """Eigenvalues of a (quasi-)triangular T in standard form, by :class:`SchurResult`'s contract."""
+    n = T.shape[0]
+    w = np.array(np.diagonal(T), dtype=np.complex128)
+    if not np.iscomplexobj(T) and n > 1:
+        lo, up = np.diagonal(T, -1), np.diagonal(T, 1)
+        for k in np.nonzero(lo)[0]:
+            im = np.sqrt(abs(up[k])) * np.sqrt(abs(lo[k]))
+            w[k] = complex(T[k, k], im)
+            w[k + 1] = complex(T[k + 1, k + 1], -im)
+    return w
+
+
+def ordschur(ctx: Context, T, Z, select) -> OrdSchurResult:
+    """Reorders a Schur form ``A = Z T Z^H`` on the device so that the selected eigenvalues lead T
+    (``eigsol_ordschur_dense``; LAPACK ``xTRSEN`` without its condition estimates).  ``T`` float64
+    (quasi-triangular, :func:`schur`'s standard 2 x 2 blocks) or complex128 (triangular); ``Z`` of the same
+    order, or ``None``.  ``select``: a boolean array with one flag per row of T (real T: a flag on either row of
+    a 2 x 2 block selects the pair); ``"lhp"`` (Re < 0), ``"rhp"`` (Re >= 0), ``"iuc"`` (|lambda| <= 1) or
+    ``"ouc"`` (|lambda| > 1); or a callable that maps the complex eigenvalue array to a boolean array, evaluated
+    on the host.  The selected blocks keep their order, and so do the others."""
+    T = np.asarray(T)
+    if T.ndim != 2 or T.shape[0] != T.shape[1]:
+        raise EigSolError(EIGSOL_E_NOT_SQUARE, f"ordschur: T must be square, got shape {T.shape}")
+    n = T.shape[0]
+    dt = np.complex128 if np.iscomplexobj(T) or (Z is not None and np.iscomplexobj(Z)) else np.float64
+    To = np.array(T, dtype=dt, order="F", copy=True)
+    Zo = None
+    if Z is not None:
+        Zo = np.array(Z, dtype=dt, order="F", copy=True)
+        if Zo.shape != (n, n):
+            raise EigSolError(EIGSOL_E_SIZE_MISMATCH, f"ordschur: Z {Zo.shape} does not fit T {T.shape}")
+    if isinstance(select, str) or callable(select):
+        w = _block_eigenvalues(To)
+        if callable(select):
+            mask = select(w)
+        elif select == "lhp":
+            mask = w.real < 0
+        elif select == "rhp":
+            mask = w.real >= 0
+        elif select == "iuc":
+            mask = w.real * w.real + w.imag * w.imag <= 1.0   # the device's expression, rounding for rounding
+        elif select == "ouc":
+            mask = w.real * w.real + w.imag * w.imag > 1.0
+        else:
+            raise EigSolError(EIGSOL_E_INVALID, f"ordschur: select is one of {sorted(_SORT_CODES)}, a mask or a callable")
+    else:
+        mask = select
+    mask = np.ascontiguousarray(np.asarray(mask).astype(bool).astype(np.uint8))
+    if mask.shape != (n,):
+        raise EigSolError(EIGSOL_E_SIZE_MISMATCH, f"ordschur: select needs one flag per row of T ({n}), got shape {mask.shape}")
+    real = dt == np.float64
+    wr = np.zeros(max(n, 1), dtype=np.float64 if real else np.complex128)
+    wi = np.zeros(max(n, 1), dtype=np.float64)
+    sd, od = C.c_int64(0), C.c_int32(0)
+    call("eigsol_ordschur_dense", ctx.handle, _dtype_code(dt), n, _ptr(To), _ptr(Zo) if Zo is not None and n else None,
+         _ptr(mask) if n else None, _ptr(wr), wi.ctypes.data_as(C.POINTER(C.c_double)), C.byref(sd), C.byref(od))
+    w = (wr[:n] + 1j * wi[:n]) if real else wr[:n].copy()
+    return OrdSchurResult(To, Zo, np.asarray(w, dtype=np.complex128), int(sd.value), bool(od.value))
+
+
+def ordschur_stats(ctx: Context) -> dict:
+    """The context's last reordering (:func:`ordschur` or ``schur(sort=...)``): ``seconds`` by stream events,
+    ``rounds`` and ``windows`` that did work, and ``swaps`` of adjacent blocks."""
+    ms = C.c_double(0.0)
+    r, wn, sw = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    call("eigsol_ordschur_stats", ctx.handle, C.byref(ms), C.byref(r), C.byref(wn), C.byref(sw))
+    return {"seconds": ms.value * 1e-3, "rounds": int(r.value), "windows": int(wn.value), "swaps": int(sw.value)}
 
 
 def schur_stage_times(ctx: Context) -> dict:

@@ -183,6 +183,10 @@ SIGNATURES = {
     "eigsol_eig_stage_times": [_vp, _pd],
     "eigsol_schur_dense": [_vp, C.c_int, _i64, _vp, C.POINTER(SolverOptionsC), _vp, _vp, _vp, _pd, _pi32, _pi32],
     "eigsol_schur_stage_times": [_vp, _pd],
+    "eigsol_ordschur_dense": [_vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _pd, _pi64, _pi32],
+    "eigsol_schur_sorted_dense": [_vp, C.c_int, _i64, _vp, C.POINTER(SolverOptionsC), C.c_int, _vp, _vp, _vp, _pd, _pi64,
+                                  _pi32, _pi32, _pi32],
+    "eigsol_ordschur_stats": [_vp, _pd, _pi32, _pi32, _pi32],
     "eigsol_trsyl_dense": [_vp, C.c_int, _i64, _i64, _vp, _vp, C.c_int, _vp, _pi32],
     "eigsol_sylvester_dense": [_vp, C.c_int, _i64, _i64, _vp, _vp, _vp, C.POINTER(SolverOptionsC), _vp, _pi32, _pi32],
     "eigsol_lyapunov_dense": [_vp, C.c_int, _i64, _vp, _vp, C.POINTER(SolverOptionsC), _vp, _pi32, _pi32],

@@ -1,5 +1,5 @@
 // The Schur pipeline of schur.hip between its upload and its download, for drivers that go on working with
-// T and Z on the device (sylvester.hip).
+// T and Z on the device (sylvester.hip, ordschur.hip).
 #pragma once
 
 #include "scratch.hpp"
