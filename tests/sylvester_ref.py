@@ -3,7 +3,14 @@
 
 Figure of a solution X of A X + X op(B) = C (A m x m, B n x n; ``Bop`` below is op(B) itself):
     r = ||A X + X op(B) - C||_F / (max(m, n) eps ((||A||_F + ||B||_F) ||X||_F + ||C||_F))
-No case here lies outside the range in which these norms can be formed, so nothing is rescaled.
+``figure`` forms the norms as they stand; ``figure_scaled`` first takes an exact power of two out of each of
+A, B, X and C (as schur_ref.figures does), for the scaled cases below whose norms would overflow or underflow.
+
+Componentwise figure of the triangular stage R Y + Y op(S) = F (``figure_cw``), not divided by the order:
+    w = max_ij |R Y + Y op(S) - F|_ij / (eps (|R| |Y| + |Y| |op(S)| + |F|)_ij)
+with the residual and the denominator formed in numpy.longdouble.  It sees an error in an entry of Y that is
+small against ||Y||_F, which r cannot.  Its bound (``bound_cw``) is max(3 x xTRSYL's w on the case, the floor of
+the scalar type), the floor being 3 x the largest w of xTRSYL over all constructed cases of that type.
 
 Named cases (``NAMES``; ``case(name)`` gives A, B, C): A = _gen(m, m), B = _gen(n, n + 1000),
 C = _gen(max(m, n), 7)[:m, :n] from tests/eig_ref.py, real ("r63x65") and complex ("c63x65": the imaginary
@@ -18,7 +25,28 @@ that the figure stays sensitive to every block; the diagonal is uniform in [1, 2
 [a b; -c a] with b, c in [0.5, 1.5].  Every eigenvalue has its real part in [1, 2], so lambda_i + mu_j is at
 least 2 in modulus and no pivot is perturbed.  The block positions are chosen by name to reach every path of
 the partition rule with NB = 64 (real) / 32 (complex).
+
+Hard constructed cases (``TRI_HARD``, seeds of their own so that TRI's bits stay; ``TRI_ALL`` is both lists):
+  close<d> (real, order 130, pairs at _straddle(130); d = 1e-04, 1e-08, 1e-12): eigenvalue pairs of R and op(S)
+    with lambda_i + mu_j = d.  R(5, 5) is set to R(10, 10), the real part of R's pair at row 10, and S is
+    overwritten at the hits: 1 x 1 with 1 x 1 at (i, j) = (5, 7) and (100, 65); 2 x 2 with 2 x 2 at (10, 30),
+    (63, 63), (126, 10), S's block becoming [-a + d, 2 g; -g / 2, -a + d] for R's [a b; -c a], g = sqrt(b c) (standard
+    form, the same imaginary part); which makes (5, 30) a 1 x 2 and (10, 7) a 2 x 1 system whose real parts sum
+    to d (their imaginary part keeps them regular: K has a diagonal of d and off-diagonal entries of order 1, so
+    complete pivoting must exchange).  Row 65 and not 64 for the second 1 x 1 hit: S's rows 63, 64 are a pair.
+  cclose<d> / cclose<d>h (complex, order 65): S(j, j) = -R(i, i) + d (its conjugate for the "h" names, so that
+    S^H has the hit) at (3, 4), (31, 32), (40, 31), (64, 0).  Both names run with both trans_b.
+  nonnormal65, nonnormal130 and nonnormal65p, nonnormal130p (pairs at _straddle(n)): the strict triangle is
+    N(0, 1), undamped; Y spans many orders of magnitude.
+  gradedF130x66: r130x66 with F(i, j) 2^-(i + j).
+  mixed_up / mixed_down: r130x66 as (2^200 R, 2^-200 S, F) / (2^-200 R, 2^200 S, 2^200 F).
+
+Scaled named cases (``SCALED``; "r65x63*A+B-" is (2^400 A, 2^-400 B, C) of r65x63, "*C+" is (A, B, 2^600 C)), on
+r65x63, c33x65, and lyap65 with "*A+" / "*A-".
 """
+import json
+import os
+
 import numpy as np
 import scipy.linalg as sla
 from scipy.linalg import lapack
@@ -27,6 +55,20 @@ import eig_ref as R
 
 EPS = R.EPS
 NB_REAL, NB_CPLX = 64, 32
+ACCURACY_JSON = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sylvester_accuracy.json")
+_figures = {}
+
+
+def record(key, **kw):
+    """One case's measured figures into profiles/sylvester_accuracy.json (the GPU tests of both files)."""
+    if not _figures and os.path.exists(ACCURACY_JSON):   # a partial run keeps the other cases' figures
+        with open(ACCURACY_JSON) as f:
+            _figures.update(json.load(f))
+    _figures[key] = {k: float(v) for k, v in kw.items()}
+    os.makedirs(os.path.dirname(ACCURACY_JSON), exist_ok=True)
+    with open(ACCURACY_JSON, "w") as f:
+        json.dump(_figures, f, indent=1, sort_keys=True)
+        f.write("\n")
 
 
 def nb_of(T):
@@ -39,6 +81,51 @@ def figure(A, Bop, C, X):
     if den == 0.0:
         den = 1.0
     return float(np.linalg.norm(A @ X + X @ Bop - C)) / (max(m, n) * EPS * den)
+
+
+def _pow2(M):
+    """(e, 2^-e M) with max |M| in [0.5, 1): the scaling is exact"""
+    M = np.asarray(M)
+    big = float(np.max(np.abs(M.real) + np.abs(M.imag))) if M.size else 0.0
+    e = int(np.frexp(big)[1]) if big > 0.0 else 0
+    return e, np.ldexp(M.real, -e) + (1j * np.ldexp(M.imag, -e) if np.iscomplexobj(M) else 0.0)
+
+
+def figure_scaled(A, Bop, C, X):
+    """``figure`` after an exact power-of-two rescaling of each operand, so that the norms of A = 2^ea A' etc.
+    can be formed at any scale: with E = max(ea + ex, eb + ex, ec) the residual is 2^E (2^(ea+ex-E) A' X' +
+    2^(eb+ex-E) X' B' - 2^(ec-E) C') and the denominator scales alike; 2^E cancels."""
+    m, n = C.shape
+    (ea, As), (eb, Bs), (ec, Cs), (ex, Xs) = (_pow2(M) for M in (A, Bop, C, X))
+    E = max(ea + ex, eb + ex, ec)
+    fa, fb, fc = (float(np.ldexp(1.0, max(k - E, -1074))) for k in (ea + ex, eb + ex, ec))
+    den = (fa * np.linalg.norm(As) + fb * np.linalg.norm(Bs)) * np.linalg.norm(Xs) + fc * np.linalg.norm(Cs)
+    if den == 0.0:
+        den = 1.0
+    return float(np.linalg.norm(fa * (As @ Xs) + fb * (Xs @ Bs) - fc * Cs)) / (max(m, n) * EPS * den)
+
+
+def figure_cw(Rm, Sop, F, Yv):
+    """The componentwise backward error w of Y in R Y + Y op(S) = F (``Sop`` is op(S) itself), formed in
+    long double; inf where an entry's denominator is 0 and its residual is not."""
+    cplx = any(np.iscomplexobj(M) for M in (Rm, Sop, F, Yv))
+    lt = np.clongdouble if cplx else np.longdouble
+    Rl, Sl, Fl, Yl = (np.asarray(M).astype(lt) for M in (Rm, Sop, F, Yv))
+    res = np.abs(Rl @ Yl + Yl @ Sl - Fl)
+    aR, aS, aF, aY = (np.abs(M) for M in (Rl, Sl, Fl, Yl))
+    den = aR @ aY + aY @ aS + aF
+    if not (np.all(np.isfinite(res)) and np.all(np.isfinite(den))):
+        return float("inf")
+    zero = den == 0
+    if np.any(res[zero] != 0):
+        return float("inf")
+    if np.all(zero):
+        return 0.0
+    return float(np.max(res[~zero] / den[~zero]) / np.longdouble(EPS))
+
+
+def bound_cw(lapack_w, dtype_floor):
+    return max(3.0 * lapack_w, dtype_floor)
 
 
 # ------------------------------------------------------------------ named cases
@@ -74,7 +161,7 @@ def _named(name):
     return A, R._gen(33, 33), _rect(A.shape[0], 33, 7)
 
 
-SHAPES = [(1, 1), (2, 2), (1, 5), (3, 2), (63, 65), (64, 64), (65, 63), (66, 130), (130, 66), (97, 33), (200, 7), (450, 450)]
+SHAPES = [(1, 1), (2, 2), (1, 5), (3, 2), (63, 65), (64, 64), (65, 63), (33, 65), (66, 130), (130, 66), (97, 33), (200, 7), (450, 450)]
 EIG_NAMED = ["jordan40", "graded60", "blk40", "kron30", "sym65", "tri30", "diag50"]
 _BUILDERS = {}
 for _m, _n in SHAPES:
@@ -87,6 +174,26 @@ for _k in EIG_NAMED:
     _BUILDERS[_k] = (lambda k=_k: _named(k))
 LYAPUNOV = ["lyap65", "lyap130"]
 NAMES = [k for k in _BUILDERS if k not in LYAPUNOV]
+_SCALES = {"A+B+": (400, 400, 0), "A-B-": (-400, -400, 0), "A+B-": (400, -400, 0), "A-B+": (-400, 400, 0),
+           "C+": (0, 0, 600), "C-": (0, 0, -600)}
+
+
+def _scaled_case(base, ea, eb, ec):
+    A, B, C = case(base)
+    return np.ldexp(A.real, ea) + (1j * np.ldexp(A.imag, ea) if np.iscomplexobj(A) else 0.0), \
+        np.ldexp(B.real, eb) + (1j * np.ldexp(B.imag, eb) if np.iscomplexobj(B) else 0.0), \
+        np.ldexp(C.real, ec) + (1j * np.ldexp(C.imag, ec) if np.iscomplexobj(C) else 0.0)
+
+
+SCALED = []
+for _b in ("r65x63", "c33x65"):
+    for _t, _e in _SCALES.items():
+        _BUILDERS[f"{_b}*{_t}"] = (lambda b=_b, e=_e: _scaled_case(b, *e))
+        SCALED.append(f"{_b}*{_t}")
+SCALED_LYAPUNOV = []
+for _t, _e in (("A+", 400), ("A-", -400)):
+    _BUILDERS[f"lyap65*{_t}"] = (lambda e=_e: _scaled_case("lyap65", e, e, 0))
+    SCALED_LYAPUNOV.append(f"lyap65*{_t}")
 _cache = {}
 
 
@@ -145,8 +252,82 @@ TRI = list(_TRI_SPECS)
 _tri_cache = {}
 
 
+def _rhs(m, n, seed, cplx):
+    F = np.random.default_rng(seed + 2).standard_normal((m, n))
+    return F + 1j * np.random.default_rng(seed + 3).standard_normal((m, n)) if cplx else F
+
+
+def _close(delta, seed):
+    n, pr = 130, _straddle(130)
+    Rm, Sm = tri(n, pr, seed), tri(n, pr, seed + 1)
+    Rm[5, 5] = Rm[10, 10]
+    for i, j in ((5, 7), (100, 65)):
+        assert i not in pr and i - 1 not in pr and j not in pr and j - 1 not in pr
+        Sm[j, j] = -Rm[i, i] + delta
+    for i, j in ((10, 30), (63, 63), (126, 10)):
+        assert i in pr and j in pr
+        g = np.sqrt(-Rm[i, i + 1] * Rm[i + 1, i])
+        Sm[j, j] = Sm[j + 1, j + 1] = -Rm[i, i] + delta
+        Sm[j, j + 1], Sm[j + 1, j] = 2.0 * g, -g / 2.0
+    return Rm, Sm, _rhs(n, n, seed, False)
+
+
+def _cclose(delta, seed, trans_b):
+    n = 65
+    Rm, Sm = tri(n, [], seed, True), tri(n, [], seed + 1, True)
+    for i, j in ((3, 4), (31, 32), (40, 31), (64, 0)):
+        v = -Rm[i, i] + delta
+        Sm[j, j] = np.conj(v) if trans_b else v
+    return Rm, Sm, _rhs(n, n, seed, True)
+
+
+def _nonnormal(n, pairs, seed):
+    def one(sd):
+        rng = np.random.default_rng(sd)
+        T = np.triu(rng.standard_normal((n, n)), 1) + np.diag(rng.uniform(1.0, 2.0, n))
+        for k in pairs:
+            T[k + 1, k + 1] = T[k, k]
+            T[k, k + 1] = rng.uniform(0.5, 1.5)
+            T[k + 1, k] = -rng.uniform(0.5, 1.5)
+        return T
+    return one(seed), one(seed + 1), _rhs(n, n, seed, False)
+
+
+def _graded():
+    Rm, Sm, F = tri_case("r130x66")
+    i, j = np.indices(F.shape)
+    return Rm, Sm, np.ldexp(F, -(i + j))
+
+
+def _mixed(up):
+    Rm, Sm, F = tri_case("r130x66")
+    e = 200 if up else -200
+    return np.ldexp(Rm, e), np.ldexp(Sm, -e), F if up else np.ldexp(F, 200)
+
+
+_HARD = {}   # name: builder taking the case's seed
+for _d in (1e-4, 1e-8, 1e-12):
+    _HARD[f"close{_d:.0e}"] = (lambda seed, d=_d: _close(d, seed))
+    _HARD[f"cclose{_d:.0e}"] = (lambda seed, d=_d: _cclose(d, seed, False))
+    _HARD[f"cclose{_d:.0e}h"] = (lambda seed, d=_d: _cclose(d, seed, True))
+for _n in (65, 130):
+    _HARD[f"nonnormal{_n}"] = (lambda seed, n=_n: _nonnormal(n, [], seed))
+    _HARD[f"nonnormal{_n}p"] = (lambda seed, n=_n: _nonnormal(n, _straddle(n), seed))
+_HARD["gradedF130x66"] = (lambda seed: _graded())
+_HARD["mixed_up"] = (lambda seed: _mixed(True))
+_HARD["mixed_down"] = (lambda seed: _mixed(False))
+TRI_HARD = list(_HARD)
+TRI_ALL = TRI + TRI_HARD
+
+
+def is_complex_case(name):
+    return np.iscomplexobj(tri_case(name)[0])
+
+
 def tri_case(name):
     """(R, S, F) of a constructed case, built once and read-only."""
+    if name not in _tri_cache and name in _HARD:
+        _tri_cache[name] = _frozen(*_HARD[name](9000 + TRI_HARD.index(name) * 4))
     if name not in _tri_cache:
         m, pr, n, ps, cplx = _TRI_SPECS[name]
         seed = 5000 + TRI.index(name) * 3
@@ -155,6 +336,12 @@ def tri_case(name):
             F = F + 1j * np.random.default_rng(seed + 3).standard_normal((m, n))
         _tri_cache[name] = _frozen(tri(m, pr, seed, cplx), tri(n, ps, seed + 1, cplx), F)
     return _tri_cache[name]
+
+
+def ldexp(M, e):
+    """2^e M, exactly (away from overflow and underflow)"""
+    M = np.asarray(M)
+    return np.ldexp(M.real, e) + 1j * np.ldexp(M.imag, e) if np.iscomplexobj(M) else np.ldexp(M, e)
 
 
 def op(S, trans_b):

@@ -5,7 +5,14 @@ Conditions, for every case (r = ||A X + X op(B) - C||_F / (max(m, n) eps ((||A||
 LAPACK's figure is the one tests/test_sylvester_cpu.py recorded in tests/golden/sylvester_ref_figures.json):
     converged, finite, shape, dtype (real in, real out), Fortran order, perturbed == 0;
     r <= max(2, 3 r_LAPACK).
-Every measured figure is written to profiles/sylvester_accuracy.json."""
+Every measured figure is written to profiles/sylvester_accuracy.json.
+
+Off the O(1) path: the scaled cases of sylvester_ref (A, B at 2^+-400, together and against each other, C at
+2^+-600; Lyapunov with A at 2^+-400) meet the same conditions with r formed by ``figure_scaled``.  Diagonal
+operands pass through the whole pipeline exactly (schur returns them bitwise with Z = I, which is asserted
+first), so X is C / (a_i + b_j) entry for entry over 3 x 2 blocks.  A complex Lyapunov solution over several
+blocks is Hermitian within what the residual bound allows.  No call modifies its inputs, and C-order,
+Fortran-order and strided views of the same values give the same bits."""
 import ctypes as C
 import json
 import os
@@ -23,21 +30,9 @@ import sylvester_ref as Y
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ACCURACY_JSON = os.path.join(ROOT, "profiles", "sylvester_accuracy.json")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "sylvester_ref_figures.json")
-_figures = {}
 _runs = {}
-
-
-def _record(key, **kw):
-    if not _figures and os.path.exists(ACCURACY_JSON):   # a partial run keeps the other cases' figures
-        with open(ACCURACY_JSON) as f:
-            _figures.update(json.load(f))
-    _figures[key] = {k: float(v) for k, v in kw.items()}
-    os.makedirs(os.path.dirname(ACCURACY_JSON), exist_ok=True)
-    with open(ACCURACY_JSON, "w") as f:
-        json.dump(_figures, f, indent=1, sort_keys=True)
-        f.write("\n")
+_record = Y.record   # shared with tests/test_gpu_trsyl.py: one table, one file
 
 
 def lapack():
@@ -73,6 +68,121 @@ def test_conditions(ctx, name):
     assert res.converged
     assert res.perturbed == 0
     assert r <= Y.bound(ref)
+
+
+@pytest.mark.parametrize("name", Y.SCALED + Y.SCALED_LYAPUNOV)
+def test_conditions_on_the_scaled_cases(ctx, name):
+    A, B, Cm = Y.case(name)
+    ref = lapack()[name]
+    res = E.solve_continuous_lyapunov(ctx, A, Cm) if name in Y.SCALED_LYAPUNOV else E.solve_sylvester(ctx, A, B, Cm)
+    X = res.X
+    assert X.shape == Cm.shape and X.dtype == np.result_type(A, B, Cm) and X.flags.f_contiguous
+    assert np.all(np.isfinite(X))
+    r = Y.figure_scaled(A, B, Cm, X)
+    _record(name, r=r, r_lapack=ref, perturbed=res.perturbed)
+    print(f"{name}: r={r:.3g} (LAPACK {ref:.3g}) perturbed={res.perturbed}")
+    assert res.converged
+    assert res.perturbed == 0
+    assert r <= Y.bound(ref)
+
+
+def _diag_operands():
+    rng = np.random.default_rng(130)
+    return rng.uniform(1.0, 2.0, 130), rng.uniform(1.0, 2.0, 66), Y._rect(130, 66, 7)
+
+
+def test_schur_returns_a_diagonal_matrix_unchanged_at_order_130(ctx):
+    """the precondition of the two tests below"""
+    a, b, _ = _diag_operands()
+    for d in (np.zeros(130), np.ones(130), np.full(130, 0.5), np.ones(66), a, b):
+        s = E.schur(ctx, np.diag(d))
+        assert np.array_equal(bits(s.T), bits(np.diag(d)))
+        assert np.array_equal(bits(s.Z), bits(np.eye(d.size)))
+
+
+def test_diagonal_operands_divide_entry_by_entry(ctx):
+    """Z = I and T diagonal: every transform product is a sum of exact zeros and one value, every group is
+    1 x 1, so each entry of F is read, divided and written exactly once across the 3 x 2 blocks"""
+    a, b, Cm = _diag_operands()
+    res = E.solve_sylvester(ctx, np.zeros((130, 130)), np.eye(66), Cm)
+    assert res.perturbed == 0 and np.array_equal(res.X, Cm)
+    res = E.solve_sylvester(ctx, np.eye(130), np.eye(66), Cm)
+    assert res.perturbed == 0 and np.array_equal(res.X, Cm / 2.0)
+    res = E.solve_sylvester(ctx, np.diag(a), np.diag(b), Cm)
+    want = Cm / (a[:, None] + b[None, :])
+    assert res.perturbed == 0 and np.all(np.abs(res.X - want) <= 2 * Y.EPS * np.abs(want))
+
+
+def test_diagonal_operands_through_lyapunov(ctx):
+    """as above with A on both sides; A = 0 is singular here, so A = I / 2 stands for it (a_i + a_j = 1, X == Q)"""
+    a, _, _ = _diag_operands()
+    Q = Y._rect(130, 130, 7)
+    Q = Q + Q.T
+    res = E.solve_continuous_lyapunov(ctx, np.eye(130) / 2.0, Q)
+    assert res.perturbed == 0 and np.array_equal(res.X, Q)
+    res = E.solve_continuous_lyapunov(ctx, np.eye(130), Q)
+    assert res.perturbed == 0 and np.array_equal(res.X, Q / 2.0)
+    res = E.solve_continuous_lyapunov(ctx, np.diag(a), Q)
+    want = Q / (a[:, None] + a[None, :])
+    assert res.perturbed == 0 and np.all(np.abs(res.X - want) <= 2 * Y.EPS * np.abs(want))
+    assert np.array_equal(res.X, res.X.T)
+
+
+def test_lyapunov_complex_across_blocks_is_hermitian(ctx):
+    """A of order 65 (three blocks of 32, 32, 1), Q Hermitian: X^H solves the same equation, so by the argument
+    of test_lyapunov_equals_sylvester_with_the_adjoint X and X^H differ by at most the sum of the two permitted
+    residual norms over sigma_min(I (x) A + conj(A) (x) I)"""
+    A, _, Cm = Y.case("c65x63")
+    m = 65
+    Cq = Y._rect(m, m, 7) + 1j * Y._rect(m, m, 8)
+    Q = Cq + Cq.conj().T
+    A = A[:m, :m] + 12.0 * np.eye(m)
+    res = E.solve_continuous_lyapunov(ctx, A, Q)
+    X = res.X
+    rl = Y.figure(A, A.conj().T, Q, sla.solve_continuous_lyapunov(A, Q))
+    r = Y.figure(A, A.conj().T, Q, X)
+    fro = np.linalg.norm
+    smin = float(sla.svdvals(np.kron(np.eye(m), A) + np.kron(A.conj(), np.eye(m)))[-1])
+    allowed = 2 * Y.bound(rl) * m * Y.EPS * (2 * fro(A) * fro(X) + fro(Q))
+    d = float(fro(X - X.conj().T))
+    print(f"r={r:.3g} LAPACK {rl:.3g} |X - X^H|={d:.3g} allowed {allowed / smin:.3g} (sigma_min {smin:.3g})")
+    assert X.dtype == np.complex128 and res.perturbed == 0 and np.all(np.isfinite(X))
+    assert r <= Y.bound(rl)
+    assert d <= allowed / smin
+
+
+def _layouts(M):
+    """the same values as a writable Fortran array, a writable C array and a strided view of a larger array"""
+    big = np.zeros((2 * M.shape[0] + 1, 3 * M.shape[1] + 2), dtype=M.dtype)
+    view = big[1::2, 2::3]
+    view[...] = M
+    return np.array(M, order="F"), np.array(M, order="C"), view
+
+
+@pytest.mark.parametrize("name", ["r65x63", "c33x65"])
+def test_inputs_are_not_modified(ctx, name):
+    A, B, Cm = Y.case(name)
+    want = run(ctx, name).X
+    for k in range(3):
+        args = [_layouts(M)[k] for M in (A, B, Cm)]
+        assert all(x.flags.writeable for x in args)
+        keep = [x.copy() for x in args]
+        got = E.solve_sylvester(ctx, *args).X
+        assert all(np.array_equal(bits(x), bits(y)) for x, y in zip(args, keep))
+        assert np.array_equal(bits(got), bits(want))
+
+
+@pytest.mark.parametrize("name", ["r130x66", "c65"])
+@pytest.mark.parametrize("trans_b", [False, True])
+def test_trsyl_does_not_modify_its_inputs(ctx, name, trans_b):
+    Rm, Sm, F = Y.tri_case(name)
+    want = E.trsyl(ctx, Rm, Sm, F, trans_b=trans_b)[0]
+    for k in range(3):
+        args = [_layouts(M)[k] for M in (Rm, Sm, F)]
+        keep = [x.copy() for x in args]
+        got = E.trsyl(ctx, *args, trans_b=trans_b)[0]
+        assert all(np.array_equal(bits(x), bits(y)) for x, y in zip(args, keep))
+        assert np.array_equal(bits(got), bits(want))
 
 
 def test_lyapunov_equals_sylvester_with_the_adjoint(ctx):

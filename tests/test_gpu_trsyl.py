@@ -4,6 +4,15 @@ Conditions on every constructed case of tests/sylvester_ref.py, with op(S) = S a
     finite, shape, dtype, Fortran order, perturbed == 0;
     r = ||R Y + Y op(S) - F||_F / (max(m, n) eps ((||R||_F + ||S||_F) ||Y||_F + ||F||_F)) <= max(2, 3 r_LAPACK),
     r_LAPACK being xTRSYL's figure recorded by tests/test_sylvester_cpu.py in tests/golden/sylvester_ref_figures.json.
+    w = max_ij |R Y + Y op(S) - F|_ij / (eps (|R| |Y| + |Y| |op(S)| + |F|)_ij), formed in long double and not divided by
+    the order, <= max(3 w_LAPACK, the scalar type's floor) (sylvester_ref.bound_cw; both recorded likewise).
+The constructed cases include the hard ones (TRI_HARD: nearly common eigenvalues, non-normal triangles, a graded
+right-hand side, R and S at scales 2^200 apart), on which r is blind to all but the largest entries of Y.
+Scaling R, S and F, or F alone, by 2^-300 or 2^300 changes no bit of Y but its exponent: every operation of the
+stage commutes with a power of two away from overflow and underflow (products, sums, the pivot choice, the
+quotients, Smith's division, smin = eps max above its floor); a comparison with an absolute constant would not.
+The smin rule as eigsol_hip.h documents it: per diagonal block pair, smin = max(eps max(max|R_ii|, max|S_jj|),
+2^-1022 / eps); a pivot below it is replaced, one at it or above is not; ``perturbed`` counts block pairs, not pivots.
 Diagonal R and S: one division per entry, so Y(i, j) = F(i, j) / (r_i + s_j) within 2 eps (the sum and the
 quotient round once each).  A singular pair is perturbed and reported; two runs give the same bits; a matrix
 that is not (quasi-)triangular is refused; the T and Z that schur itself leaves solve a general equation."""
@@ -48,17 +57,88 @@ def bits(a):
 
 
 @pytest.mark.parametrize("trans_b", [False, True])
-@pytest.mark.parametrize("name", Y.TRI)
+@pytest.mark.parametrize("name", Y.TRI_ALL)
 def test_conditions(ctx, name, trans_b):
     Rm, Sm, F = Y.tri_case(name)
     X, pert = run(ctx, name, trans_b)
-    ref = lapack()["tri"][f"{name}/{'H' if trans_b else 'N'}"]
+    key = f"{name}/{'H' if trans_b else 'N'}"
+    rec = lapack()
+    ref, wref = rec["tri"][key], rec["tri_cw"][key]
+    floor = rec["cw_floor"]["complex" if np.iscomplexobj(Rm) else "real"]
     assert X.shape == F.shape and X.dtype == F.dtype and X.flags.f_contiguous
     assert np.all(np.isfinite(X))
     r = Y.figure(Rm, Y.op(Sm, trans_b), F, X)
-    print(f"{name} trans_b={trans_b}: r={r:.3g} (LAPACK {ref:.3g}) perturbed={pert}")
+    w = Y.figure_cw(Rm, Y.op(Sm, trans_b), F, X)
+    Y.record("tri:" + key, r=r, r_lapack=ref, w=w, w_lapack=wref, perturbed=pert)
+    print(f"{name} trans_b={trans_b}: r={r:.3g} (LAPACK {ref:.3g}) w={w:.3g} (LAPACK {wref:.3g}, floor {floor:.3g}) "
+          f"perturbed={pert}")
     assert pert == 0
     assert r <= Y.bound(ref)
+    assert w <= Y.bound_cw(wref, floor)
+
+
+@pytest.mark.parametrize("trans_b", [False, True])
+@pytest.mark.parametrize("name", ["r130x66", "odd129", "c65"])
+def test_powers_of_two_change_only_the_exponent(ctx, name, trans_b):
+    Rm, Sm, F = Y.tri_case(name)
+    X = run(ctx, name, trans_b)[0]
+    for e in (-300, 300):
+        Xa, pa = E.trsyl(ctx, Y.ldexp(Rm, e), Y.ldexp(Sm, e), Y.ldexp(F, e), trans_b=trans_b)
+        Xf, pf = E.trsyl(ctx, Rm, Sm, Y.ldexp(F, e), trans_b=trans_b)
+        assert pa == 0 and pf == 0
+        assert np.array_equal(bits(Xa), bits(X)), f"2^{e} (R, S, F)"
+        assert np.array_equal(bits(Xf), bits(Y.ldexp(X, e))), f"2^{e} F"
+
+
+def _within(got, want, ulps=2):
+    return np.all(np.abs(got - want) <= ulps * Y.EPS * np.abs(want))
+
+
+@pytest.mark.parametrize("cplx", [False, True])
+def test_smin_at_its_edge_in_one_block(ctx, cplx):
+    """R = diag(1, 4), S = [-1 + d]: the block's largest entry is 4, so smin = 4 eps; the pivot 1 + (-1 + d) = d is
+    formed exactly.  d = 8 eps stays, d = 2 eps is replaced by 4 eps.  Complex: d is purely imaginary."""
+    eps = Y.EPS
+    unit = 1j if cplx else 1.0
+    Rm, F = np.diag([1.0, 4.0]) * (1.0 + 0j if cplx else 1.0), np.ones((2, 1)) * (1.0 + 0j if cplx else 1.0)
+    X, pert = E.trsyl(ctx, Rm, np.array([[-1.0 + 8 * eps * unit]]), F)
+    assert pert == 0
+    assert _within(X[0, 0], 1.0 / (8 * eps * unit)) and _within(X[1, 0], 1.0 / (3.0 + 8 * eps * unit))
+    X, pert = E.trsyl(ctx, Rm, np.array([[-1.0 + 2 * eps * unit]]), F)
+    assert pert == 1
+    assert _within(X[0, 0], 1.0 / (4 * eps)) and _within(X[1, 0], 1.0 / (3.0 + 2 * eps * unit))
+
+
+def test_smin_is_per_block_not_global(ctx):
+    """R = diag(1, .., 1, 4) of order 65: the 4 is alone in the second block (rows 64 ..), so smin is 4 eps there and
+    eps in the first block, whose pivots 1 + (-1 + 2 eps) = 2 eps therefore stay.  LAPACK's dtrsyl takes one smin =
+    eps max(||R||, ||S||) = 4 eps for the whole equation and reports info = 1 on this input
+    (tests/test_sylvester_cpu.py::test_dtrsyl_smin_is_global); eigsol_hip.h documents the rule per block pair,
+    and this test pins it."""
+    d = np.ones(65)
+    d[64] = 4.0
+    X, pert = E.trsyl(ctx, np.diag(d), np.array([[-1.0 + 2 * Y.EPS]]), np.ones((65, 1)))
+    assert pert == 0
+    assert _within(X[:64, 0], 1.0 / (2 * Y.EPS)) and _within(X[64, 0], 1.0 / (3.0 + 2 * Y.EPS))
+
+
+def test_smin_has_a_floor(ctx):
+    """eps max is below 2^-1022 / eps = 2^-970 here, which then is smin; the pivot 2^-999 is below it"""
+    t = np.array([[2.0 ** -1000]])
+    X, pert = E.trsyl(ctx, t, t, np.array([[1.5]]))
+    assert pert == 1 and np.all(np.isfinite(X))
+    assert _within(X[0, 0], 1.5 / (2.0 ** -1022 / Y.EPS))
+
+
+def test_perturbed_counts_block_pairs(ctx):
+    X, pert = E.trsyl(ctx, np.eye(2), np.array([[-1.0]]), np.ones((2, 1)))        # two pivots, one block
+    assert pert == 1 and np.all(np.isfinite(X))
+    X, pert = E.trsyl(ctx, np.eye(65), np.array([[-1.0]]), np.ones((65, 1)))      # 64 pivots and 1, two blocks
+    assert pert == 2 and np.all(np.isfinite(X))
+    X, pert = E.trsyl(ctx, np.eye(33) * (1.0 + 1j), np.array([[-1.0 - 1j]]), np.ones((33, 1)) + 0j)   # 32 and 1
+    assert pert == 2 and np.all(np.isfinite(X))
+    X, pert = E.trsyl(ctx, np.eye(2), np.diag([-1.0, 3.0]), np.ones((2, 2)))      # only one pair of the two is singular
+    assert pert == 1 and _within(X[:, 1], 0.25)
 
 
 @pytest.mark.parametrize("cplx", [False, True])
