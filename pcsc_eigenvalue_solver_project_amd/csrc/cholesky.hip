@@ -25,8 +25,6 @@
 namespace eigsol {
 namespace dev {
 
-__device__ __forceinline__ double conj_c(double a) { return a; }
-__device__ __forceinline__ cplx conj_c(cplx a) { return cplx{a.re, -a.im}; }
 __device__ __forceinline__ bool finite_c(double a) { return isfinite(a); }
 __device__ __forceinline__ bool finite_c(cplx a) { return isfinite(a.re) && isfinite(a.im); }
 __device__ __forceinline__ double real_c(double a) { return a; }
@@ -164,23 +162,6 @@ __global__ __launch_bounds__(64) void trsm_diag(const S* T, int64_t ldt, int nb,
     for (int idx = lane; idx < nb * nc; idx += 64) {
         const int i = idx % nb, c = idx / nb;
         X[i + (int64_t)(c0 + c) * ldx] = xs[i][c];
-    }
-}
-
-// Out (cols x rows) = In^H (In: rows x cols), 32 x 32 tiles through padded LDS
-template <class S>
-__global__ __launch_bounds__(256) void conj_transpose(int rows, int cols, const S* In, int64_t ldi, S* Out, int64_t ldo) {
-    __shared__ S tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int i0 = blockIdx.x * 32, j0 = blockIdx.y * 32;
-    for (int q = ty; q < 32; q += 8) {
-        const int i = i0 + tx, j = j0 + q;
-        if (i < rows && j < cols) tile[q][tx] = In[i + (int64_t)j * ldi];
-    }
-    __syncthreads();
-    for (int q = ty; q < 32; q += 8) {
-        const int j = j0 + tx, i = i0 + q;
-        if (i < rows && j < cols) Out[j + (int64_t)i * ldo] = conj_c(tile[tx][q]);
     }
 }
 

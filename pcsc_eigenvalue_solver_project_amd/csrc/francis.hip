@@ -10,7 +10,8 @@
 //
 // Locality: the chain is chased inside an LDS window [s, e) of at most kWin rows/columns with
 // the window's orthogonal factor U accumulated alongside; the parts of the reflectors' updates
-// outside the window are applied afterwards as small GEMMs on the fp64 matrix cores,
+// outside the window are applied afterwards as small GEMMs on the fp64 matrix cores
+// (window_update_tile of mfma_window.hpp, shared with zfrancis.hip and ordschur.hip),
 //     H(s:e, e:ihi]   <- U^T H(s:e, e:ihi]        H[l, s) x [s, e) <- H[l, s) x [s, e) U,
 // so every HBM element of the active block is touched O(1) times per window instead of once per
 // reflector.  Concurrency: the chain is split into C groups of 4+ bulges spaced kWin + 3 nbg
@@ -31,6 +32,7 @@
 #include <vector>
 
 #include "kernels_common.hpp"
+#include "mfma_window.hpp"
 #include "scratch.hpp"
 
 namespace eigsol {
@@ -44,7 +46,6 @@ constexpr int kMaxBulges = 48;   // shifts per sweep / 2 (at most 16 per window:
 // compiler-only ordering of LDS accesses (one wave's LDS operations execute in issue order)
 #define EIGSOL_LDS_ORDER() asm volatile("" ::: "memory")
 
-typedef double dbl4 __attribute__((ext_vector_type(4)));
 constexpr int kMaxGroups = 8;   // bulge groups chased concurrently, one window (workgroup) each
 
 // One window of a chase round: group g's bulges j = 0..nb-1 sit at rows k = l + t - 3 j for the
@@ -62,30 +63,6 @@ struct ChaseArgs {
     int l, ihi;       // active block
     ChaseWin w[kMaxGroups];   // window of workgroup blockIdx.x
 };
-
-// Reciprocal without the IEEE division sequence: v_rcp_f64 and two Newton steps (within an ulp
-// or two; a Householder reflector built from it is orthogonal to the same order).  x != 0, finite.
-// sqrt of a in [2^-4, 2^4] (no range reduction): hardware reciprocal square root, then Goldschmidt /
-// Newton corrections to full double precision (v_sqrt_f64 alone is far from it)
-__device__ __forceinline__ double sqrt_nr(double a) {
-    const double y = __builtin_amdgcn_rsq(a);
-    double s = a * y, h = 0.5 * y;
-    const double r = __builtin_fma(-h, s, 0.5);
-    s = __builtin_fma(s, r, s);
-    h = __builtin_fma(h, r, h);
-    double d = __builtin_fma(-s, s, a);
-    s = __builtin_fma(d, h, s);
-    d = __builtin_fma(-s, s, a);
-    return __builtin_fma(d, h, s);
-}
-
-__device__ __forceinline__ double rcp_nr(double x) {
-    double r = __builtin_amdgcn_rcp(x);
-    double e = __builtin_fma(-x, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-x, r, 1.0);
-    return __builtin_fma(r, e, r);
-}
 
 // The same chase with two barriers per step and no serial section.  Wave b owns bulge b for the
 // whole window: every lane computes the bulge's reflector redundantly from the same LDS words
@@ -280,143 +257,18 @@ __global__ __launch_bounds__(1024) void chase_wave_kernel(ChaseArgs ca) {
     }
 }
 
-// The delayed updates of up to kMaxGroups windows on the fp64 matrix cores
-// (v_mfma_f64_16x16x4_f64).  One launch applies one side for every window:
-//   left : H(s:s+W, lo:hi) <- U^T H(s:s+W, lo:hi)      64 columns per workgroup
-//   right: H(lo:hi, s:s+W) <- H(lo:hi, s:s+W) U        64 rows per workgroup
-// Left regions of different windows own disjoint rows and right regions disjoint columns, so a
-// launch is race-free; a left region of a window meets the right region of a window further down
-// the chain, hence lefts and rights are two launches (U_g^T X U_h = (U_g^T X) U_h).
-// U is staged in LDS (odd pitch, zero-padded to kWin), the left panel too; each wave computes a
-// kWin x 16 strip as six 16 x 16 tiles.  D layout of the f64 MFMA: lane L, register r holds
-// D[(L >> 4) + 4 r][L & 15] (cdna_hip_programming.md); D's column index is put on the output's
-// row, so 16 lanes store 128 contiguous bytes of one column.
-struct WinGemm {
-    int s, W;          // window rows/columns [s, s + W)
-    int64_t lo, hi;    // left: columns [lo, hi); right: rows [lo, hi)
-    int blk0;          // first workgroup of this window
-    const double* U;   // W x W, column-major
-};
-struct WinGemmBatch {
-    double* H;
-    int64_t n;
-    int nw;
-    WinGemm w[kMaxGroups + 1];
-};
-constexpr int kUP = kWin + 2;   // LDS pitch of U and of the left panel: (k + 2 i) mod 32 distinct for 32 lanes
-
-// kTile columns (left) / rows (right) of the off-window region per workgroup.  64: each wave owns
-// 16 of them and all six 16-row tiles of U; 32: waves (w & 1) own 16 of them and (w >> 1) three of
-// the six U tiles, so twice as many workgroups share a launch's MFMA work (a launch covers only a
-// few thousand columns, fewer workgroups than CUs at 64).  The k order of every output element is
-// the same for both tilings (bitwise the same updates).
+// The delayed updates of up to kMaxGroups windows on the fp64 matrix cores, one launch per side for
+// every window (mfma_window.hpp: the tile, the batch descriptor and why lefts and rights are two
+// launches):
+//   left : H(s:s+W, lo:hi) <- U^T H(s:s+W, lo:hi)      kTile columns per workgroup
+//   right: H(lo:hi, s:s+W) <- H(lo:hi, s:s+W) U        kTile rows per workgroup
+// kTile = 32 lets twice as many workgroups share a launch's MFMA work (a launch covers only a few
+// thousand columns, fewer workgroups than CUs at 64), with bitwise the same updates.
+using WinGemm = WindowRegion<double>;
+using WinGemmBatch = WindowBatch<double, kMaxGroups + 1>;
 template <bool kLeft, int kTile = 64>
 __global__ __launch_bounds__(256) void win_gemm_mfma(WinGemmBatch b) {
-    constexpr int kT = kTile == 64 ? 6 : 3;                // U row tiles per wave
-    __shared__ double us[kWin * kUP];                    // us[k + rho * kUP] = U(k, rho)
-    __shared__ double xs[kLeft ? kTile * kUP : 1];       // left: xs[k + c * kUP] = H(s + k, c0 + c)
-    int g = 0;
-#pragma unroll
-    for (int q = 1; q < kMaxGroups + 1; ++q)
-        if (q < b.nw && (int)blockIdx.x >= b.w[q].blk0) g = q;
-    const WinGemm w = b.w[g];
-    const int W = w.W;
-    const int64_t base = w.lo + (int64_t)((int)blockIdx.x - w.blk0) * kTile;
-    const int cnt = (int)min<int64_t>(kTile, w.hi - base);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 15, lk = lane >> 4;
-    const int ct = kTile == 64 ? wave : (wave & 1);      // this wave's 16 columns / rows of the tile
-    const int t0 = kTile == 64 ? 0 : 3 * (wave >> 1);    // ... and its first U row tile
-    // right: this lane's X(r_j, k) for k = lk, lk + 4, ... (issued first, consumed last)
-    constexpr int kKs = kWin / 4;
-    double xv[kLeft ? 1 : kKs];
-    const int rj = 16 * ct + li;
-    const bool rv = rj < cnt;
-    if constexpr (!kLeft) {
-        const double* xr = b.H + (base + min(rj, max(cnt - 1, 0))) + (int64_t)w.s * b.n;
-#pragma unroll
-        for (int q = 0; q < kKs; ++q) {
-            const int k = 4 * q + lk;
-            xv[q] = xr[(int64_t)min(k, W - 1) * b.n];
-        }
-    }
-    {
-        // U (and the left panel) into LDS: every global load of the thread issued before any store
-        constexpr int kPU = kWin * kWin / 256;
-        double tu[kPU];
-#pragma unroll
-        for (int q = 0; q < kPU; ++q) {
-            const int idx = threadIdx.x + 256 * q;
-            const int k = idx % kWin, rho = idx / kWin;
-            tu[q] = w.U[min(k, W - 1) + min(rho, W - 1) * W];
-        }
-        if constexpr (kLeft) {
-            constexpr int kPX = kWin * kTile / 256;
-            double tx[kPX];
-#pragma unroll
-            for (int q = 0; q < kPX; ++q) {
-                const int idx = threadIdx.x + 256 * q;
-                const int k = idx % kWin, c = idx / kWin;
-                tx[q] = b.H[(w.s + min(k, W - 1)) + (base + min(c, max(cnt - 1, 0))) * b.n];
-            }
-#pragma unroll
-            for (int q = 0; q < kPX; ++q) {
-                const int idx = threadIdx.x + 256 * q;
-                const int k = idx % kWin, c = idx / kWin;
-                xs[k + c * kUP] = (k < W && c < cnt) ? tx[q] : 0.0;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < kPU; ++q) {
-            const int idx = threadIdx.x + 256 * q;
-            const int k = idx % kWin, rho = idx / kWin;
-            us[k + rho * kUP] = (k < W && rho < W) ? tu[q] : 0.0;
-        }
-    }
-    __syncthreads();
-    dbl4 acc[kT];
-#pragma unroll
-    for (int t = 0; t < kT; ++t) acc[t] = dbl4{0.0, 0.0, 0.0, 0.0};
-    if constexpr (kLeft) {
-        // D[i][j] = sum_k X(k, c_i) U(k, rho_j): i = column 16 ct + i, j = row 16 (t0 + t) + j
-        const double* xc = xs + (16 * ct + li) * kUP;
-#pragma unroll
-        for (int q = 0; q < kKs; ++q) {     // rows k >= W of both LDS images are zero
-            const int k = 4 * q + lk;
-            const double av = xc[k];
-            double bv[kT];
-#pragma unroll
-            for (int t = 0; t < kT; ++t) bv[t] = us[k + (16 * (t0 + t) + li) * kUP];
-#pragma unroll
-            for (int t = 0; t < kT; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv[t], acc[t], 0, 0, 0);
-        }
-#pragma unroll
-        for (int t = 0; t < kT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int c = 16 * ct + lk + 4 * r, rho = 16 * (t0 + t) + li;
-                if (c < cnt && rho < W) b.H[(w.s + rho) + (base + c) * b.n] = acc[t][r];
-            }
-    } else {
-        // D[i][j] = sum_k U(k, rho_i) X(r_j, k): i = output column rho, j = row 16 ct + j
-#pragma unroll
-        for (int q = 0; q < kKs; ++q) {
-            const int k = 4 * q + lk;
-            const double bv = (rv && k < W) ? xv[q] : 0.0;
-            double av[kT];
-#pragma unroll
-            for (int t = 0; t < kT; ++t) av[t] = us[k + (16 * (t0 + t) + li) * kUP];
-#pragma unroll
-            for (int t = 0; t < kT; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[t], bv, acc[t], 0, 0, 0);
-        }
-#pragma unroll
-        for (int t = 0; t < kT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int rho = 16 * (t0 + t) + lk + 4 * r;
-                if (rv && rho < W) b.H[(base + rj) + (int64_t)(w.s + rho) * b.n] = acc[t][r];
-            }
-    }
+    window_update_batch<double, kWin, kLeft, kTile>(b);
 }
 
 // ------------------------------------------------------------ one-wave Francis double shift
@@ -915,16 +767,6 @@ __global__ __launch_bounds__(kAedThreads) void aed_kernel(double* H, int64_t n, 
     }
 }
 
-// diagonal and subdiagonal of the block [0, ihi]: out[0..n) = h(i,i), out[n..2n) = h(i,i-1)
-__global__ void diag_sub_kernel(const double* H, int64_t n, int ihi, double* out) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i > ihi) return;
-    out[i] = H[i + (int64_t)i * n];
-    out[n + i] = i > 0 ? H[i + (int64_t)(i - 1) * n] : 0.0;
-}
-
-__global__ void zero_entry_kernel(double* H, int64_t n, int i, int j) { H[i + (int64_t)j * n] = 0.0; }
-
 // Schur mode: the diagonal block H[l:l+m, l:l+m] (m <= kAedMax: T and V of the block fill the LDS, as the
 // AED's do) finished in one piece: real Schur form T = V^T H V by the one-wave factorisation with V kept.
 // T goes back in place (exact zeros below the sub-diagonal), V to Vout (m x m, column-major); the caller
@@ -1100,7 +942,7 @@ static int francis_impl(eigsol_ctx* ctx, double* H, int64_t n, int maxits, doubl
     // deflation scan of [0, ihi]: diagonal and subdiagonal into pinned host memory (only the
     // ihi + 1 leading entries of each half travel)
     auto scan = [&]() -> int {
-        hipLaunchKernelGGL(dev::diag_sub_kernel, dim3((ihi + 256) / 256), dim3(256), 0, st, H, n, ihi, dds);
+        hipLaunchKernelGGL(dev::diag_sub_kernel<double>, dim3((ihi + 256) / 256), dim3(256), 0, st, H, n, ihi, dds);
         if (hipMemcpyAsync(ds, dds, (ihi + 1) * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipMemcpyAsync(ds + n, dds + n, (ihi + 1) * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
             stream_wait(st) != hipSuccess)
@@ -1119,7 +961,7 @@ static int francis_impl(eigsol_ctx* ctx, double* H, int64_t n, int maxits, doubl
         }
         const int N = ihi - l + 1;
         if constexpr (kSchur) {   // the accepted sub-diagonal entry becomes an exact zero
-            if (l > 0 && ds[n + l] != 0.0) hipLaunchKernelGGL(dev::zero_entry_kernel, dim3(1), dim3(1), 0, st, H, n, l, l - 1);
+            if (l > 0 && ds[n + l] != 0.0) hipLaunchKernelGGL(dev::zero_entry_kernel<double>, dim3(1), dim3(1), 0, st, H, n, l, l - 1);
         }
         if (N <= (kSchur ? dev::kAedMax : kSmall)) {
             ++st_small;

@@ -1224,7 +1224,6 @@ __global__ __launch_bounds__(256) void gemm_valu(int m, int nn, int kk, double a
 // B^T fragment, B operand = A^T fragment) so that the f64 C/D layout (col = lane & 15,
 // row = (lane >> 4) + 4 reg, cdna_hip_programming.md) puts C's ROW on the lane: 16 lanes store
 // 128 contiguous bytes of one column.
-typedef double dbl4 __attribute__((ext_vector_type(4)));
 
 template <bool TA, bool TB>
 __global__ __launch_bounds__(256) void gemm_mfma_f64(int m, int nn, int kk, double alpha, const double* A,
@@ -1239,11 +1238,11 @@ __global__ __launch_bounds__(256) void gemm_mfma_f64(int m, int nn, int kk, doub
     const int kb = blockIdx.z * kc;
     const int ke = min(kk, kb + kc);
     C += blockIdx.z * zstride;
-    dbl4 acc[2][2];
+    mfma_d4 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = dbl4{0.0, 0.0, 0.0, 0.0};
+        for (int b = 0; b < 2; ++b) acc[a][b] = mfma_d4{0.0, 0.0, 0.0, 0.0};
     for (int k0 = kb; k0 < ke; k0 += KT) {
         for (int e = threadIdx.x; e < KT * TM; e += 256) {
             int r, q;
@@ -1311,11 +1310,11 @@ __global__ __launch_bounds__(256) void gemm_mfma_c128(int m, int nn, int kk, dou
     const int kb = blockIdx.z * kc;
     const int ke = min(kk, kb + kc);
     C += blockIdx.z * zstride;
-    dbl4 accR[2][2], accI[2][2];
+    mfma_d4 accR[2][2], accI[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) accR[a][b] = accI[a][b] = dbl4{0.0, 0.0, 0.0, 0.0};
+        for (int b = 0; b < 2; ++b) accR[a][b] = accI[a][b] = mfma_d4{0.0, 0.0, 0.0, 0.0};
     for (int k0 = kb; k0 < ke; k0 += KT) {
         for (int e = threadIdx.x; e < KT * TM; e += 256) {
             int r, q;

@@ -107,6 +107,8 @@ int hess_max_order_c128();
 // qr.hip: the power-of-two range guard of the Francis paths on a device matrix read as cnt doubles
 // (A <- 2^escale A where its largest entry lies outside [smlnum, 1 / smlnum]; else *escale = 0)
 int qr_range_guard(hipStream_t st, double* A, int64_t cnt, int* escale);
+// A <- 2^e A, exactly, stream-ordered: the guard's scaling and the callers' scaling back of a matrix
+void qr_scale_pow2(hipStream_t st, double* A, int64_t cnt, int e);
 
 inline bool dtype_complex(int dtype) { return dtype == EIGSOL_C128 || dtype == EIGSOL_C64 || dtype == EIGSOL_CDD; }
 inline bool dtype_single(int dtype) { return dtype == EIGSOL_F32 || dtype == EIGSOL_C64; }

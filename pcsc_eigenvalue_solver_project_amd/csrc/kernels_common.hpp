@@ -740,5 +740,62 @@ __device__ __forceinline__ void shift_multi_prologue(PowerCtl* ctl, const part4*
     __syncthreads();
 }
 
+// ------------------------------------------------------------------ dense drivers' small pieces
+// Reciprocal without the IEEE division sequence: v_rcp_f64 and two Newton steps (within an ulp
+// or two; a Householder reflector built from it is orthogonal to the same order).  x != 0, finite.
+__device__ __forceinline__ double rcp_nr(double x) {
+    double r = __builtin_amdgcn_rcp(x);
+    double e = __builtin_fma(-x, r, 1.0);
+    r = __builtin_fma(r, e, r);
+    e = __builtin_fma(-x, r, 1.0);
+    return __builtin_fma(r, e, r);
+}
+
+// sqrt of a in [2^-4, 2^4] (no range reduction): hardware reciprocal square root, then Goldschmidt /
+// Newton corrections to full double precision (v_sqrt_f64 alone is far from it)
+__device__ __forceinline__ double sqrt_nr(double a) {
+    const double y = __builtin_amdgcn_rsq(a);
+    double s = a * y, h = 0.5 * y;
+    const double r = __builtin_fma(-h, s, 0.5);
+    s = __builtin_fma(s, r, s);
+    h = __builtin_fma(h, r, h);
+    double d = __builtin_fma(-s, s, a);
+    s = __builtin_fma(d, h, s);
+    d = __builtin_fma(-s, s, a);
+    return __builtin_fma(d, h, s);
+}
+
+__device__ __forceinline__ double conj_c(double a) { return a; }
+__device__ __forceinline__ cplx conj_c(cplx a) { return cplx{a.re, -a.im}; }
+
+// Out (cols x rows) = In^H (In: rows x cols), 32 x 32 tiles through padded LDS
+template <class S>
+__global__ __launch_bounds__(256) void conj_transpose(int rows, int cols, const S* In, int64_t ldi, S* Out, int64_t ldo) {
+    __shared__ S tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int i0 = blockIdx.x * 32, j0 = blockIdx.y * 32;
+    for (int q = ty; q < 32; q += 8) {
+        const int i = i0 + tx, j = j0 + q;
+        if (i < rows && j < cols) tile[q][tx] = In[i + (int64_t)j * ldi];
+    }
+    __syncthreads();
+    for (int q = ty; q < 32; q += 8) {
+        const int j = j0 + tx, i = i0 + q;
+        if (i < rows && j < cols) Out[j + (int64_t)i * ldo] = conj_c(tile[tx][q]);
+    }
+}
+
+// diagonal and subdiagonal of the block [0, ihi]: out[0..n) = h(i,i), out[n..2n) = h(i,i-1)
+template <class S>
+__global__ void diag_sub_kernel(const S* H, int64_t n, int ihi, S* out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i > ihi) return;
+    out[i] = H[i + (int64_t)i * n];
+    out[n + i] = i > 0 ? H[i + (int64_t)(i - 1) * n] : s_zero<S>();
+}
+
+template <class S>
+__global__ void zero_entry_kernel(S* H, int64_t n, int i, int j) { H[i + (int64_t)j * n] = s_zero<S>(); }
+
 }  // namespace dev
 }  // namespace eigsol

@@ -19,7 +19,7 @@
 //      work and is reported in its descriptor by a plain store.
 //        ord_update<left>, ord_update<right>, ord_update<Z>: T(s:e, e:n) <- U^H T(s:e, e:n), then
 //      T(0:s, s:e) <- T(0:s, s:e) U, then Z(:, s:e) <- Z(:, s:e) U for every window that worked, on the
-//      fp64 matrix cores (the tiling of francis.hip's win_gemm_mfma / zfrancis.hip's zwin_gemm_mfma), the
+//      fp64 matrix cores (window_update_tile of mfma_window.hpp, shared with the QR sweeps), the
 //      window descriptors read from device memory; the tiles of an idle window leave at once.  All lefts
 //      before all rights; Z is a launch T never reads;
 //        the host reads three words per round (windows that worked, rejected swaps, swaps) and stops after
@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "kernels_common.hpp"
+#include "mfma_window.hpp"
 #include "ordschur.hpp"
 #include "scratch.hpp"
 
@@ -170,255 +171,29 @@ __global__ __launch_bounds__(64) void ord_window_kernel(S* T, int64_t n, unsigne
     if (lane == 0) wins[g] = me;
 }
 
-typedef double odbl4 __attribute__((ext_vector_type(4)));
-
 // The delayed updates of one round's windows, window blockIdx.y, 64 columns (left) or rows (right) per
-// workgroup: kKind 0: M = T, T(s:e, e:n) <- U^T T(s:e, e:n); 1: M = T, T(0:s, s:e) <- T(0:s, s:e) U;
-// 2: M = Z, Z(:, s:e) <- Z(:, s:e) U.  U (and the left panel) in LDS at pitch 98, zero-padded to 96; each
-// wave a 96 x 16 strip as six 16 x 16 tiles of v_mfma_f64_16x16x4_f64 (lane L, register r holds
-// D[(L >> 4) + 4 r][L & 15]); D's column index is put on the output's row.
-template <int kKind>
-__global__ __launch_bounds__(256) void ord_update_f64(double* M, int64_t n, const OrdWin* wins, const double* Us) {
-    constexpr bool kLeft = kKind == 0;
-    constexpr int kWin = OrdDims<double>::wmax, kUP = kWin + 2, kTile = 64, kT = kWin / 16, kKs = kWin / 4;
-    __shared__ double us[kWin * kUP];
-    __shared__ double xs[kLeft ? kTile * kUP : 1];
+// workgroup, on the fp64 matrix cores (mfma_window.hpp): kKind 0: M = T, T(s:e, e:n) <- U^H T(s:e, e:n);
+// 1: M = T, T(0:s, s:e) <- T(0:s, s:e) U; 2: M = Z, Z(:, s:e) <- Z(:, s:e) U.  The tiles of an idle window
+// and the tiles past a region's end leave at once.
+template <class S, int kKind>
+__global__ __launch_bounds__(256) void ord_update(S* M, int64_t n, const OrdWin* wins, const S* Us) {
+    constexpr int kWin = OrdDims<S>::wmax;
     const OrdWin w = wins[blockIdx.y];
     if (!w.active) return;
-    const int W = w.W;
-    const int64_t lo = kKind == 0 ? (int64_t)w.s + W : 0, hi = kKind == 1 ? (int64_t)w.s : n;
-    const int64_t base = lo + (int64_t)blockIdx.x * kTile;
+    const int64_t lo = kKind == 0 ? (int64_t)w.s + w.W : 0, hi = kKind == 1 ? (int64_t)w.s : n;
+    const int64_t base = lo + (int64_t)blockIdx.x * 64;
     if (base >= hi) return;
-    const double* const U = Us + (size_t)blockIdx.y * kWin * kWin;
-    const int cnt = (int)min<int64_t>(kTile, hi - base);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 15, lk = lane >> 4;
-    const int ct = wave;
-    double xv[kLeft ? 1 : kKs];
-    const int rj = 16 * ct + li;
-    const bool rv = rj < cnt;
-    if constexpr (!kLeft) {
-        const double* xr = M + (base + min(rj, cnt - 1)) + (int64_t)w.s * n;
-#pragma unroll
-        for (int q = 0; q < kKs; ++q) {
-            const int k = 4 * q + lk;
-            xv[q] = xr[(int64_t)min(k, W - 1) * n];
-        }
-    }
-    {
-        constexpr int kPU = kWin * kWin / 256;
-        double tu[kPU];
-#pragma unroll
-        for (int q = 0; q < kPU; ++q) {
-            const int idx = threadIdx.x + 256 * q;
-            const int k = idx % kWin, rho = idx / kWin;
-            tu[q] = U[min(k, W - 1) + min(rho, W - 1) * kWin];
-        }
-        if constexpr (kLeft) {
-            constexpr int kPX = kWin * kTile / 256;
-            double tx[kPX];
-#pragma unroll
-            for (int q = 0; q < kPX; ++q) {
-                const int idx = threadIdx.x + 256 * q;
-                const int k = idx % kWin, c = idx / kWin;
-                tx[q] = M[(w.s + min(k, W - 1)) + (base + min(c, cnt - 1)) * n];
-            }
-#pragma unroll
-            for (int q = 0; q < kPX; ++q) {
-                const int idx = threadIdx.x + 256 * q;
-                const int k = idx % kWin, c = idx / kWin;
-                xs[k + c * kUP] = (k < W && c < cnt) ? tx[q] : 0.0;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < kPU; ++q) {
-            const int idx = threadIdx.x + 256 * q;
-            const int k = idx % kWin, rho = idx / kWin;
-            us[k + rho * kUP] = (k < W && rho < W) ? tu[q] : 0.0;
-        }
-    }
-    __syncthreads();
-    odbl4 acc[kT];
-#pragma unroll
-    for (int t = 0; t < kT; ++t) acc[t] = odbl4{0.0, 0.0, 0.0, 0.0};
-    if constexpr (kLeft) {
-        // D[i][j] = sum_k X(k, c_i) U(k, rho_j)
-        const double* xc = xs + (16 * ct + li) * kUP;
-#pragma unroll
-        for (int q = 0; q < kKs; ++q) {
-            const int k = 4 * q + lk;
-            const double av = xc[k];
-            double bv[kT];
-#pragma unroll
-            for (int t = 0; t < kT; ++t) bv[t] = us[k + (16 * t + li) * kUP];
-#pragma unroll
-            for (int t = 0; t < kT; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv[t], acc[t], 0, 0, 0);
-        }
-#pragma unroll
-        for (int t = 0; t < kT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int c = 16 * ct + lk + 4 * r, rho = 16 * t + li;
-                if (c < cnt && rho < W) M[(w.s + rho) + (base + c) * n] = acc[t][r];
-            }
-    } else {
-        // D[i][j] = sum_k U(k, rho_i) X(r_j, k)
-#pragma unroll
-        for (int q = 0; q < kKs; ++q) {
-            const int k = 4 * q + lk;
-            const double bv = (rv && k < W) ? xv[q] : 0.0;
-            double av[kT];
-#pragma unroll
-            for (int t = 0; t < kT; ++t) av[t] = us[k + (16 * t + li) * kUP];
-#pragma unroll
-            for (int t = 0; t < kT; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[t], bv, acc[t], 0, 0, 0);
-        }
-#pragma unroll
-        for (int t = 0; t < kT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int rho = 16 * t + lk + 4 * r;
-                if (rv && rho < W) M[(base + rj) + (int64_t)(w.s + rho) * n] = acc[t][r];
-            }
-    }
-}
-
-// The same for complex windows of at most 64 rows: a complex tile product is four real ones on split re / im
-// planes; left applies U^H.
-template <int kKind>
-__global__ __launch_bounds__(256) void ord_update_c128(cplx* M, int64_t n, const OrdWin* wins, const cplx* Us) {
-    constexpr bool kLeft = kKind == 0;
-    constexpr int kWin = OrdDims<cplx>::wmax, kUP = kWin + 2, kTile = 64, kT = kWin / 16, kKs = kWin / 4;
-    __shared__ double ur[kWin * kUP], ui[kWin * kUP];
-    __shared__ double xr_s[kLeft ? kTile * kUP : 1], xi_s[kLeft ? kTile * kUP : 1];
-    const OrdWin w = wins[blockIdx.y];
-    if (!w.active) return;
-    const int W = w.W;
-    const int64_t lo = kKind == 0 ? (int64_t)w.s + W : 0, hi = kKind == 1 ? (int64_t)w.s : n;
-    const int64_t base = lo + (int64_t)blockIdx.x * kTile;
-    if (base >= hi) return;
-    const cplx* const U = Us + (size_t)blockIdx.y * kWin * kWin;
-    const int cnt = (int)min<int64_t>(kTile, hi - base);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 15, lk = lane >> 4;
-    cplx xv[kLeft ? 1 : kKs];
-    const int rj = 16 * wave + li;
-    const bool rv = rj < cnt;
-    if constexpr (!kLeft) {
-        const cplx* xrow = M + (base + min(rj, cnt - 1)) + (int64_t)w.s * n;
-#pragma unroll
-        for (int q = 0; q < kKs; ++q) xv[q] = xrow[(int64_t)min(4 * q + lk, W - 1) * n];
-    }
-    {
-        constexpr int kPU = kWin * kWin / 256;
-        cplx tu[kPU];
-#pragma unroll
-        for (int q = 0; q < kPU; ++q) {
-            const int idx = threadIdx.x + 256 * q;
-            const int k = idx % kWin, rho = idx / kWin;
-            tu[q] = U[min(k, W - 1) + min(rho, W - 1) * kWin];
-        }
-        if constexpr (kLeft) {
-            constexpr int kPX = kWin * kTile / 256;
-            cplx tx[kPX];
-#pragma unroll
-            for (int q = 0; q < kPX; ++q) {
-                const int idx = threadIdx.x + 256 * q;
-                const int k = idx % kWin, c = idx / kWin;
-                tx[q] = M[(w.s + min(k, W - 1)) + (base + min(c, cnt - 1)) * n];
-            }
-#pragma unroll
-            for (int q = 0; q < kPX; ++q) {
-                const int idx = threadIdx.x + 256 * q;
-                const int k = idx % kWin, c = idx / kWin;
-                const bool ok = k < W && c < cnt;
-                xr_s[k + c * kUP] = ok ? tx[q].re : 0.0;
-                xi_s[k + c * kUP] = ok ? tx[q].im : 0.0;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < kPU; ++q) {
-            const int idx = threadIdx.x + 256 * q;
-            const int k = idx % kWin, rho = idx / kWin;
-            const bool ok = k < W && rho < W;
-            ur[k + rho * kUP] = ok ? tu[q].re : 0.0;
-            ui[k + rho * kUP] = ok ? tu[q].im : 0.0;
-        }
-    }
-    __syncthreads();
-    odbl4 aR[kT], aI[kT];
-#pragma unroll
-    for (int t = 0; t < kT; ++t) aR[t] = aI[t] = odbl4{0.0, 0.0, 0.0, 0.0};
-    if constexpr (kLeft) {
-        // D[i][j] = sum_k X(k, c_i) conj(U(k, rho_j)): re = Xr Ur + Xi Ui, im = Xi Ur - Xr Ui
-        const int co = (16 * wave + li) * kUP;
-#pragma unroll
-        for (int q = 0; q < kKs; ++q) {
-            const int k = 4 * q + lk;
-            const double xr = xr_s[co + k], xi = xi_s[co + k];
-            double br[kT], bi[kT];
-#pragma unroll
-            for (int t = 0; t < kT; ++t) {
-                br[t] = ur[k + (16 * t + li) * kUP];
-                bi[t] = ui[k + (16 * t + li) * kUP];
-            }
-#pragma unroll
-            for (int t = 0; t < kT; ++t) {
-                aR[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(xr, br[t], aR[t], 0, 0, 0);
-                aR[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(xi, bi[t], aR[t], 0, 0, 0);
-                aI[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(xi, br[t], aI[t], 0, 0, 0);
-                aI[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(-xr, bi[t], aI[t], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < kT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int c = 16 * wave + lk + 4 * r, rho = 16 * t + li;
-                if (c < cnt && rho < W) M[(w.s + rho) + (base + c) * n] = cplx{aR[t][r], aI[t][r]};
-            }
-    } else {
-        // D[i][j] = sum_k U(k, rho_i) X(r_j, k): re = Ur Xr - Ui Xi, im = Ur Xi + Ui Xr
-#pragma unroll
-        for (int q = 0; q < kKs; ++q) {
-            const int k = 4 * q + lk;
-            const bool ok = rv && k < W;
-            const double xr = ok ? xv[q].re : 0.0, xi = ok ? xv[q].im : 0.0;
-            double ar[kT], ai[kT];
-#pragma unroll
-            for (int t = 0; t < kT; ++t) {
-                ar[t] = ur[k + (16 * t + li) * kUP];
-                ai[t] = ui[k + (16 * t + li) * kUP];
-            }
-#pragma unroll
-            for (int t = 0; t < kT; ++t) {
-                aR[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[t], xr, aR[t], 0, 0, 0);
-                aR[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(-ai[t], xi, aR[t], 0, 0, 0);
-                aI[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[t], xi, aI[t], 0, 0, 0);
-                aI[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai[t], xr, aI[t], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < kT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int rho = 16 * t + lk + 4 * r;
-                if (rv && rho < W) M[(base + rj) + (int64_t)(w.s + rho) * n] = cplx{aR[t][r], aI[t][r]};
-            }
-    }
+    window_update_tile<S, kWin, kKind == 0>(M, n, w.s, w.W, base, (int)min<int64_t>(64, hi - base),
+                                            Us + (size_t)blockIdx.y * kWin * kWin, kWin);
 }
 
 }  // namespace dev
 
 namespace {
 
-template <int kKind>
-void ord_launch_update(hipStream_t st, dim3 grid, double* M, int64_t n, const dev::OrdWin* wins, const double* Us) {
-    hipLaunchKernelGGL(dev::ord_update_f64<kKind>, grid, dim3(256), 0, st, M, n, wins, Us);
-}
-template <int kKind>
-void ord_launch_update(hipStream_t st, dim3 grid, cplx* M, int64_t n, const dev::OrdWin* wins, const cplx* Us) {
-    hipLaunchKernelGGL(dev::ord_update_c128<kKind>, grid, dim3(256), 0, st, M, n, wins, Us);
+template <int kKind, class S>
+void ord_launch_update(hipStream_t st, dim3 grid, S* M, int64_t n, const dev::OrdWin* wins, const S* Us) {
+    hipLaunchKernelGGL((dev::ord_update<S, kKind>), grid, dim3(256), 0, st, M, n, wins, Us);
 }
 
 }  // namespace
@@ -490,7 +265,7 @@ int ordschur_device(eigsol_ctx* ctx, int64_t n, SchurDevice& sd, bool wantz, con
         if (word[1] > 0) failed = true;
     }
     if (escale != 0)
-        hipLaunchKernelGGL(dev::schur_scale_pow2, dim3(1024), dim3(256), 0, st, sd.T.as<double>(), (kReal ? 1 : 2) * n * n, -escale);
+        qr_scale_pow2(st, sd.T.as<double>(), (kReal ? 1 : 2) * n * n, -escale);
     if constexpr (kReal)
         hipLaunchKernelGGL(dev::schur_eigs_real, dim3(grow), dim3(256), 0, st, sd.T.as<double>(), n, sd.w.as<double>());
     else

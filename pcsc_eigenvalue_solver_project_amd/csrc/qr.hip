@@ -411,6 +411,11 @@ static int qr_unshifted_host(eigsol_ctx* ctx, int64_t n, const void* A, int max_
     return rc;
 }
 
+// A <- 2^e A (exact): the range guard's scaling, and the scaling back of schur.hip and ordschur.hip
+void qr_scale_pow2(hipStream_t st, double* A, int64_t cnt, int e) {
+    hipLaunchKernelGGL(dev::scale_pow2_kernel, dim3(1024), dim3(256), 0, st, A, cnt, e);
+}
+
 // LAPACK xGEEV's range guard, shared by the Francis paths and eig (eig.hip): a matrix whose largest
 // entry (max |Re|, |Im| for a complex one: A is read as cnt doubles) lies outside [smlnum, bignum]
 // (smlnum = sqrt(safe min) / eps) is scaled into range first, here by an exact power of two, and the
@@ -432,7 +437,7 @@ int qr_range_guard(hipStream_t st, double* A, int64_t cnt, int* escale) {
     const double smlnum = std::sqrt(std::numeric_limits<double>::min()) / std::numeric_limits<double>::epsilon();
     if (std::isfinite(amax) && amax > 0.0 && (amax < smlnum || amax > 1.0 / smlnum)) {
         *escale = -std::ilogb(amax);
-        hipLaunchKernelGGL(dev::scale_pow2_kernel, dim3(1024), dim3(256), 0, st, A, cnt, *escale);
+        qr_scale_pow2(st, A, cnt, *escale);
     }
     return EIGSOL_OK;
 }

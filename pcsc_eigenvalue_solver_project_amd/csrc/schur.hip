@@ -205,7 +205,7 @@ int schur_device(eigsol_ctx* ctx, int64_t n, const void* A_host, int max_iter, b
         }
     }
     if (escale != 0)
-        hipLaunchKernelGGL(dev::schur_scale_pow2, dim3(1024), dim3(256), 0, st, dH.as<double>(), (kReal ? 1 : 2) * n * n, -escale);
+        qr_scale_pow2(st, dH.as<double>(), (kReal ? 1 : 2) * n * n, -escale);
     if constexpr (kReal)
         hipLaunchKernelGGL(dev::schur_eigs_real, dim3(grow), dim3(256), 0, st, dH.as<double>(), n, dw.as<double>());
     else

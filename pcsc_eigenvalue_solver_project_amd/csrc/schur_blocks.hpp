@@ -1,5 +1,5 @@
 // Pieces of schur.hip that the drivers working on a Schur form on the device share (ordschur.hip): the
-// standardisation of one 2 x 2 block, the exact scaling by a power of two and the eigenvalues of T's blocks.
+// standardisation of one 2 x 2 block and the eigenvalues of T's blocks.
 #pragma once
 
 #include <cmath>
@@ -8,10 +8,6 @@
 
 namespace eigsol {
 namespace dev {
-
-static __global__ __launch_bounds__(256) void schur_scale_pow2(double* A, int64_t cnt, int e) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * 256) A[i] = ldexp(A[i], e);
-}
 
 // One 2 x 2 block [a b; c d] to its standard form by the rotation [cs sn; -sn cs] (LAPACK dlanv2 without
 // its rescaling loop: the range guard has put the matrix inside [smlnum, 1 / smlnum]).

@@ -47,9 +47,6 @@
 namespace eigsol {
 namespace dev {
 
-__device__ __forceinline__ double syl_conj(double a) { return a; }
-__device__ __forceinline__ cplx syl_conj(cplx a) { return cplx{a.re, -a.im}; }
-
 // a / b by Smith's method (no overflow in |b|^2)
 __device__ inline cplx syl_cdiv(cplx a, cplx b) {
     if (fabs(b.re) >= fabs(b.im)) {
@@ -58,23 +55,6 @@ __device__ inline cplx syl_cdiv(cplx a, cplx b) {
     }
     const double r = b.re / b.im, den = b.re * r + b.im;
     return cplx{(a.re * r + a.im) / den, (a.im * r - a.re) / den};
-}
-
-// Out (cols x rows) = In^H (In: rows x cols), 32 x 32 tiles through padded LDS (as cholesky.hip's)
-template <class S>
-__global__ __launch_bounds__(256) void syl_conj_transpose(int rows, int cols, const S* In, int64_t ldi, S* Out, int64_t ldo) {
-    __shared__ S tile[32][33];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int i0 = blockIdx.x * 32, j0 = blockIdx.y * 32;
-    for (int q = ty; q < 32; q += 8) {
-        const int i = i0 + tx, j = j0 + q;
-        if (i < rows && j < cols) tile[q][tx] = In[i + (int64_t)j * ldi];
-    }
-    __syncthreads();
-    for (int q = ty; q < 32; q += 8) {
-        const int j = j0 + tx, i = i0 + q;
-        if (i < rows && j < cols) Out[j + (int64_t)i * ldo] = syl_conj(tile[tx][q]);
-    }
 }
 
 // sub[k] = T(k + 1, k) != 0, k < n - 1
@@ -187,7 +167,7 @@ __global__ __launch_bounds__(kSylThreads) void syl_block_kernel(const S* R, int6
                 if (!trans)
                     for (int k = 0; k < b0; ++k) acc = sub(acc, mul(sF[a + k * LD], sS[k + b * LD]));
                 else
-                    for (int k = b0 + sb; k < nb; ++k) acc = sub(acc, mul(sF[a + k * LD], syl_conj(sS[b + k * LD])));
+                    for (int k = b0 + sb; k < nb; ++k) acc = sub(acc, mul(sF[a + k * LD], conj_c(sS[b + k * LD])));
                 srhs[tid] = acc;
             }
         }
@@ -223,7 +203,7 @@ __global__ __launch_bounds__(kSylThreads) void syl_block_kernel(const S* R, int6
                 for (int u = 0; u < 4; ++u)
                     if (u < N) sF[(a0 + u % sa) + (b0 + u / sa) * LD] = x[u];
             } else {
-                const cplx sbb = trans ? syl_conj(sS[b0 + b0 * LD]) : sS[b0 + b0 * LD];
+                const cplx sbb = trans ? conj_c(sS[b0 + b0 * LD]) : sS[b0 + b0 * LD];
                 cplx den = add(sR[a0 + a0 * LD], sbb);
                 if (mod_abs(den) < smin) {
                     den = cplx{smin, 0.0};
@@ -477,7 +457,7 @@ int sylvester_host(eigsol_ctx* ctx, const char* who, int64_t m, int64_t n, const
     EIGSOL_TRY(dUt.alloc((size_t)m * m * sizeof(S)));
     EIGSOL_TRY(dpert.alloc(sizeof(int)));
     EIGSOL_HIP(hipMemcpyAsync(dC.p, C_host, (size_t)m * n * sizeof(S), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(dev::syl_conj_transpose<S>, dim3((unsigned)((m + 31) / 32), (unsigned)((m + 31) / 32)), dim3(256), 0, st,
+    hipLaunchKernelGGL(dev::conj_transpose<S>, dim3((unsigned)((m + 31) / 32), (unsigned)((m + 31) / 32)), dim3(256), 0, st,
                        (int)m, (int)m, U, m, dUt.as<S>(), m);
     EIGSOL_TRY(syl_product<S>(st, false, m, n, m, dUt.as<S>(), m, dC.as<S>(), m, dW.as<S>()));   // W = U^H C
     EIGSOL_TRY(syl_product<S>(st, false, m, n, n, dW.as<S>(), m, V, n, dC.as<S>()));             // F = W V

@@ -14,7 +14,8 @@
 //   * the chain is chased inside an LDS window [s, e) of at most 64 rows/columns (complex: H and
 //     its accumulated unitary U take 2 x 64 KiB of LDS), one wave per bulge; the window's updates
 //     outside it are applied afterwards as complex GEMMs over the columns right of the window
-//     (U^H X) and the rows above it (X U);
+//     (U^H X) and the rows above it (X U), on the fp64 matrix cores (window_update_tile of
+//     mfma_window.hpp, the tile francis.hip and ordschur.hip use too);
 //   * shifts: eigenvalues of the trailing 2 nb x 2 nb block; every 6th sweep without a deflation
 //     uses exceptional shifts; active blocks of at most 64 rows are finished in LDS by a one-wave
 //     single-shift QR (the ZLAHQR iteration: Wilkinson shift, exceptional shifts at iterations 10
@@ -29,6 +30,7 @@
 #include <vector>
 
 #include "kernels_common.hpp"
+#include "mfma_window.hpp"
 #include "scratch.hpp"
 
 namespace eigsol {
@@ -61,14 +63,6 @@ __device__ __forceinline__ cplx cdiv_s(cplx a, cplx b) {
     return cplx{(a.re * r + a.im) / d, (a.im * r - a.re) / d};
 }
 
-__device__ __forceinline__ double rcp_nr(double x) {   // x != 0, finite, normal reciprocal
-    double r = __builtin_amdgcn_rcp(x);
-    double e = __builtin_fma(-x, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-x, r, 1.0);
-    return __builtin_fma(r, e, r);
-}
-
 // ZLARFG on (alpha, x1, x2) (x2 ignored when !three): Q = I - tau v v^H, v = (1, v1, v2),
 // Q^H (alpha, x1, x2) = (beta, 0, 0).  tau = 0 (Q = I) when x = 0 and alpha is real.  The caller
 // scales the input to O(1).
@@ -97,20 +91,6 @@ __device__ __forceinline__ void zhouse(cplx a, cplx x1, cplx x2, bool three, dou
     };
     v1 = qt(x1);
     v2 = three ? qt(x2) : cplx{0.0, 0.0};
-}
-
-// sqrt of a in [2^-4, 2^4] (no range reduction): hardware reciprocal square root, then Goldschmidt /
-// Newton corrections to full double precision (francis.hip's, restated for this translation unit)
-__device__ __forceinline__ double sqrt_nr(double a) {
-    const double y = __builtin_amdgcn_rsq(a);
-    double s = a * y, h = 0.5 * y;
-    const double r = __builtin_fma(-h, s, 0.5);
-    s = __builtin_fma(s, r, s);
-    h = __builtin_fma(h, r, h);
-    double d = __builtin_fma(-s, s, a);
-    s = __builtin_fma(d, h, s);
-    d = __builtin_fma(-s, s, a);
-    return __builtin_fma(d, h, s);
 }
 
 // zhouse for the 2 x 2 reflectors of the one-wave QR, on any scale: (alpha, x1) is scaled by a power
@@ -619,163 +599,18 @@ __global__ __launch_bounds__(1024) void zchase_kernel(ZChaseBatch b) {
     }
 }
 
-// Delayed window updates.  left: H(s:s+W, cols) <- U^H H(s:s+W, cols) for the columns [lo, hi);
-// right: H(rows, s:s+W) <- H(rows, s:s+W) U for the rows [lo, hi).
-struct ZWinGemm {
-    int s, W;          // window rows/columns [s, s + W)
-    int64_t lo, hi;    // left: columns [lo, hi); right: rows [lo, hi)
-    int blk0;          // first workgroup of this window
-    const cplx* U;
-};
-struct ZWinGemmBatch {   // left regions of different windows own disjoint rows, right regions disjoint columns
-    cplx* H;
-    int64_t n;
-    int nw;
-    ZWinGemm w[kZMaxGroups];
-};
-// On the fp64 matrix cores (v_mfma_f64_16x16x4_f64; the VALU kernel that preceded this one, 8 output
-// columns per 128-thread workgroup, was removed): a complex tile
-// product is four real ones on split re/im planes.  64 output columns (left) / rows (right) per
-// workgroup of 4 waves, each wave a 16-wide strip against the window's 4 row tiles; U (and the
-// left panel) staged in LDS as re/im planes at a pitch of kZWin + 2 (the real kernel's
-// conflict-free pitch).  D layout: lane L, register r holds D[(L >> 4) + 4 r][L & 15].
-typedef double zdbl4 __attribute__((ext_vector_type(4)));
-constexpr int kZUP = kZWin + 2;
+// Delayed window updates on the fp64 matrix cores (mfma_window.hpp; the VALU kernel that preceded it,
+// 8 output columns per 128-thread workgroup, was removed).  left: H(s:s+W, cols) <- U^H H(s:s+W, cols)
+// for the columns [lo, hi); right: H(rows, s:s+W) <- H(rows, s:s+W) U for the rows [lo, hi); 64
+// columns / rows per workgroup of 4 waves.
+using ZWinGemm = WindowRegion<cplx>;
+using ZWinGemmBatch = WindowBatch<cplx, kZMaxGroups>;
 constexpr int kZMG = 64;   // outputs per workgroup
 constexpr int kZMT = 4 * kZMG;   // threads: one wave per 16 outputs
 template <bool kLeft>
 __global__ __launch_bounds__(kZMT) void zwin_gemm_mfma(ZWinGemmBatch bt) {
-    __shared__ double ur[kZWin * kZUP], ui[kZWin * kZUP];
-    __shared__ double xr_s[kLeft ? kZMG * kZUP : 1], xi_s[kLeft ? kZMG * kZUP : 1];
-    int g = 0;
-#pragma unroll
-    for (int q = 1; q < kZMaxGroups; ++q)
-        if (q < bt.nw && (int)blockIdx.x >= bt.w[q].blk0) g = q;
-    const ZWinGemm w = bt.w[g];
-    const int W = w.W;
-    const int64_t n = bt.n;
-    const int64_t base = w.lo + (int64_t)((int)blockIdx.x - w.blk0) * kZMG;
-    const int cnt = (int)min<int64_t>(kZMG, w.hi - base);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int li = lane & 15, lk = lane >> 4;
-    constexpr int kKs = kZWin / 4;
-    // right: this lane's X(r_j, k), k = lk, lk + 4, ... (issued first, consumed last)
-    cplx xv[kLeft ? 1 : kKs];
-    const int rj = 16 * wave + li;
-    const bool rv = rj < cnt;
-    if constexpr (!kLeft) {
-        const cplx* xrow = bt.H + (base + min(rj, max(cnt - 1, 0))) + (int64_t)w.s * n;
-#pragma unroll
-        for (int q = 0; q < kKs; ++q) xv[q] = xrow[(int64_t)min(4 * q + lk, W - 1) * n];
-    }
-    {
-        constexpr int kPU = kZWin * kZWin / kZMT;
-        cplx tu[kPU];
-#pragma unroll
-        for (int q = 0; q < kPU; ++q) {
-            const int idx = threadIdx.x + kZMT * q;
-            const int k = idx % kZWin, rho = idx / kZWin;
-            tu[q] = w.U[min(k, W - 1) + min(rho, W - 1) * W];
-        }
-        if constexpr (kLeft) {
-            constexpr int kPX = kZWin * kZMG / kZMT;
-            cplx tx[kPX];
-#pragma unroll
-            for (int q = 0; q < kPX; ++q) {
-                const int idx = threadIdx.x + kZMT * q;
-                const int k = idx % kZWin, c = idx / kZWin;
-                tx[q] = bt.H[(w.s + min(k, W - 1)) + (base + min(c, max(cnt - 1, 0))) * n];
-            }
-#pragma unroll
-            for (int q = 0; q < kPX; ++q) {
-                const int idx = threadIdx.x + kZMT * q;
-                const int k = idx % kZWin, c = idx / kZWin;
-                const bool ok = k < W && c < cnt;
-                xr_s[k + c * kZUP] = ok ? tx[q].re : 0.0;
-                xi_s[k + c * kZUP] = ok ? tx[q].im : 0.0;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < kPU; ++q) {
-            const int idx = threadIdx.x + kZMT * q;
-            const int k = idx % kZWin, rho = idx / kZWin;
-            const bool ok = k < W && rho < W;
-            ur[k + rho * kZUP] = ok ? tu[q].re : 0.0;
-            ui[k + rho * kZUP] = ok ? tu[q].im : 0.0;
-        }
-    }
-    __syncthreads();
-    constexpr int kT = kZWin / 16;
-    zdbl4 aR[kT], aI[kT];
-#pragma unroll
-    for (int t = 0; t < kT; ++t) aR[t] = aI[t] = zdbl4{0.0, 0.0, 0.0, 0.0};
-    if constexpr (kLeft) {
-        // D[i][j] = sum_k X(k, c_i) conj(U(k, rho_j)): re = Xr Ur + Xi Ui, im = Xi Ur - Xr Ui
-        const int co = (16 * wave + li) * kZUP;
-#pragma unroll
-        for (int q = 0; q < kKs; ++q) {   // rows k >= W of both LDS images are zero
-            const int k = 4 * q + lk;
-            const double xr = xr_s[co + k], xi = xi_s[co + k];
-            double br[kT], bi[kT];
-#pragma unroll
-            for (int t = 0; t < kT; ++t) {
-                br[t] = ur[k + (16 * t + li) * kZUP];
-                bi[t] = ui[k + (16 * t + li) * kZUP];
-            }
-#pragma unroll
-            for (int t = 0; t < kT; ++t) {
-                aR[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(xr, br[t], aR[t], 0, 0, 0);
-                aR[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(xi, bi[t], aR[t], 0, 0, 0);
-                aI[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(xi, br[t], aI[t], 0, 0, 0);
-                aI[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(-xr, bi[t], aI[t], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < kT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int c = 16 * wave + lk + 4 * r, rho = 16 * t + li;
-                if (c < cnt && rho < W) bt.H[(w.s + rho) + (base + c) * n] = cplx{aR[t][r], aI[t][r]};
-            }
-    } else {
-        // D[i][j] = sum_k U(k, rho_i) X(r_j, k): re = Ur Xr - Ui Xi, im = Ur Xi + Ui Xr
-#pragma unroll
-        for (int q = 0; q < kKs; ++q) {
-            const int k = 4 * q + lk;
-            const bool ok = rv && k < W;
-            const double xr = ok ? xv[q].re : 0.0, xi = ok ? xv[q].im : 0.0;
-            double ar[kT], ai[kT];
-#pragma unroll
-            for (int t = 0; t < kT; ++t) {
-                ar[t] = ur[k + (16 * t + li) * kZUP];
-                ai[t] = ui[k + (16 * t + li) * kZUP];
-            }
-#pragma unroll
-            for (int t = 0; t < kT; ++t) {
-                aR[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[t], xr, aR[t], 0, 0, 0);
-                aR[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(-ai[t], xi, aR[t], 0, 0, 0);
-                aI[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[t], xi, aI[t], 0, 0, 0);
-                aI[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai[t], xr, aI[t], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < kT; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int rho = 16 * t + lk + 4 * r;
-                if (rv && rho < W) bt.H[(base + rj) + (int64_t)(w.s + rho) * n] = cplx{aR[t][r], aI[t][r]};
-            }
-    }
+    window_update_batch<cplx, kZWin, kLeft, kZMG>(bt);
 }
-
-__global__ void zdiag_sub_kernel(const cplx* H, int64_t n, int ihi, cplx* out) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i > ihi) return;
-    out[i] = H[i + (int64_t)i * n];
-    out[n + i] = i > 0 ? H[i + (int64_t)(i - 1) * n] : cplx{0.0, 0.0};
-}
-
-__global__ void zzero_entry_kernel(cplx* H, int64_t n, int i, int j) { H[i + (int64_t)j * n] = cplx{0.0, 0.0}; }
 
 // Schur mode: the diagonal block H[l:l+m, l:l+m] (m <= kZSmall) finished in one piece: complex Schur form
 // T = V^H H V by the one-wave factorisation with V kept.  T goes back in place (exact zeros below the
@@ -874,7 +709,7 @@ static int zfrancis_impl(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* 
         return EIGSOL_OK;
     };
     auto scan = [&]() -> int {   // only the ihi + 1 leading entries of each half travel
-        hipLaunchKernelGGL(dev::zdiag_sub_kernel, dim3((ihi + 256) / 256), dim3(256), 0, st, H, (int64_t)n, ihi, dds);
+        hipLaunchKernelGGL(dev::diag_sub_kernel<cplx>, dim3((ihi + 256) / 256), dim3(256), 0, st, H, (int64_t)n, ihi, dds);
         EIGSOL_HIP(hipMemcpyAsync(ds, dds, (ihi + 1) * sizeof(cplx), hipMemcpyDeviceToHost, st));
         EIGSOL_HIP(hipMemcpyAsync(ds + n, dds + n, (ihi + 1) * sizeof(cplx), hipMemcpyDeviceToHost, st));
         EIGSOL_HIP(stream_wait(st));
@@ -913,7 +748,7 @@ static int zfrancis_impl(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* 
         const int N = ihi - l + 1;
         if constexpr (kSchur) {   // the accepted sub-diagonal entry becomes an exact zero
             if (l > 0 && (ds[n + l].re != 0.0 || ds[n + l].im != 0.0))
-                hipLaunchKernelGGL(dev::zzero_entry_kernel, dim3(1), dim3(1), 0, st, H, (int64_t)n, l, l - 1);
+                hipLaunchKernelGGL(dev::zero_entry_kernel<cplx>, dim3(1), dim3(1), 0, st, H, (int64_t)n, l, l - 1);
         }
         if (N <= dev::kZSmall) {
             int info[2] = {0, 0};
