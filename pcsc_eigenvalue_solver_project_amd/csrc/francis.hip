@@ -25,15 +25,11 @@
 // 128 rows are finished entirely in LDS.  Deflation: |h(k,k-1)| <= eps (|h(k,k)| + |h(k-1,k-1)|).
 #include <algorithm>
 #include <cmath>
-#include <complex>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
-#include "kernels_common.hpp"
-#include "mfma_window.hpp"
-#include "scratch.hpp"
+#include "sweep_driver.hpp"
 
 namespace eigsol {
 
@@ -47,22 +43,6 @@ constexpr int kMaxBulges = 48;   // shifts per sweep / 2 (at most 16 per window:
 #define EIGSOL_LDS_ORDER() asm volatile("" ::: "memory")
 
 constexpr int kMaxGroups = 8;   // bulge groups chased concurrently, one window (workgroup) each
-
-// One window of a chase round: group g's bulges j = 0..nb-1 sit at rows k = l + t - 3 j for the
-// group-local steps t in [t0, t1); the window [s, e) holds them for the whole round.
-struct ChaseWin {
-    int s, e;         // window [s, e)
-    int t0, t1;       // group-local chase steps of this round
-    int nb;           // bulges of the group
-    const double* shifts;   // per bulge: xs (= ys) and ws of the shift pair
-    double* U;        // out: (e - s)^2 accumulated factor, column-major
-};
-struct ChaseArgs {
-    double* H;
-    int64_t n;        // leading dimension
-    int l, ihi;       // active block
-    ChaseWin w[kMaxGroups];   // window of workgroup blockIdx.x
-};
 
 // The same chase with two barriers per step and no serial section.  Wave b owns bulge b for the
 // whole window: every lane computes the bulge's reflector redundantly from the same LDS words
@@ -79,8 +59,8 @@ struct ChaseArgs {
 // steps before bulge b+1 takes them over, so wave b keeps its three columns in registers: per
 // step it loads the new column k+2 (stored by bulge b-1 at the end of its previous phase A) and
 // stores the column it drops, instead of reading and writing all three.
-__global__ __launch_bounds__(1024) void chase_wave_kernel(ChaseArgs ca) {
-    const ChaseWin a = ca.w[blockIdx.x];
+__global__ __launch_bounds__(1024) void chase_wave_kernel(ChaseBatch<double, kMaxGroups> ca) {
+    const ChaseWin<double> a = ca.w[blockIdx.x];
     __shared__ double h[kWin * (kWin + 1)];
     __shared__ double u[kWin * kWin];
     __shared__ double trash[4];   // target of the stores of lanes past a row / column range (branch-free)
@@ -264,7 +244,6 @@ __global__ __launch_bounds__(1024) void chase_wave_kernel(ChaseArgs ca) {
 //   right: H(lo:hi, s:s+W) <- H(lo:hi, s:s+W) U        kTile rows per workgroup
 // kTile = 32 lets twice as many workgroups share a launch's MFMA work (a launch covers only a few
 // thousand columns, fewer workgroups than CUs at 64), with bitwise the same updates.
-using WinGemm = WindowRegion<double>;
 using WinGemmBatch = WindowBatch<double, kMaxGroups + 1>;
 template <bool kLeft, int kTile = 64>
 __global__ __launch_bounds__(256) void win_gemm_mfma(WinGemmBatch b) {
@@ -820,36 +799,47 @@ static constexpr int kSmall = 128;   // blocks of at most this many rows are fin
 // (one chain of 16 bulges: 40 was best); the window's one-wave Schur factorisation costs O(nw^3) latency-bound steps
 static constexpr int kAedWin = 64;
 
-// kSchur = false: the eigenvalue-only iteration (francis_large_f64).  kSchur = true (schur_sweeps_f64): the
-// same sweeps, shifts and launches of the chase, with every delayed update widened to the whole matrix
-// (left regions to column n - 1, right regions from row 0), the window factors also applied to Z (n x n,
-// leading dimension n; null: none), accepted sub-diagonal entries stored as zeros and blocks of at most
-// kAedMax rows finished by schur_block_kernel; wr / wi are not written.
+// the real sweeps' side of sweep_driver.hpp
+struct RealSweep {
+    using S = double;
+    static constexpr int kWin = dev::kWin, kMaxGroups = dev::kMaxGroups, kMaxRegions = dev::kMaxGroups + 1;
+    static constexpr const char* kName = "francis";
+    static void chase(hipStream_t st, int nwin, const dev::ChaseBatch<double, dev::kMaxGroups>& b) {
+        hipLaunchKernelGGL(dev::chase_wave_kernel, dim3(nwin), dim3(1024), 0, st, b);
+    }
+    template <bool kLeft>
+    static void update(hipStream_t st, int tile, int grid, const dev::WinGemmBatch& b) {
+        if (tile == 32) hipLaunchKernelGGL((dev::win_gemm_mfma<kLeft, 32>), dim3(grid), dim3(256), 0, st, b);
+        else hipLaunchKernelGGL((dev::win_gemm_mfma<kLeft, 64>), dim3(grid), dim3(256), 0, st, b);
+    }
+    // 32 when 64-wide tiles would leave CUs idle
+    static int update_tile(int span, int num_cus) { return span / 64 < num_cus ? 32 : 64; }
+};
+
+// kSchur = false: the eigenvalue-only iteration (francis_large_f64).  kSchur = true (schur_sweeps_f64): Schur mode
+// (sweep_driver.hpp), blocks of at most kAedMax rows finished by schur_block_kernel; wr / wi are not written.
 template <bool kSchur>
 static int francis_impl(eigsol_ctx* ctx, double* H, int64_t n, int maxits, double* wr, double* wi,
                         int32_t* sweeps_out, int32_t* fail_out, double* Z) {
     hipStream_t st = ctx->stream;
-    const double eps = 2.220446049250313e-16;
-    DevBuf bsw, bsinfo, bflag, bwr, bwi, bds, bU, bsh, binfo;
+    SweepDriver<RealSweep, kSchur> sd{st, H, Z, n, ctx->num_cus};
+    EIGSOL_TRY(sd.alloc());
+    DevBuf bsw, bsinfo, bflag, bwr, bwi, bsh, binfo;
     EIGSOL_TRY(bsw.alloc(2 * dev::kAedMax * sizeof(double)));   // concurrent shifts (ShiftJob): re, im
     EIGSOL_TRY(bsinfo.alloc(64));
     EIGSOL_TRY(bflag.alloc(64));
     EIGSOL_HIP(hipMemsetAsync(bflag.p, 0, 64, st));
     EIGSOL_TRY(bwr.alloc(n * sizeof(double)));
     EIGSOL_TRY(bwi.alloc(n * sizeof(double)));
-    EIGSOL_TRY(bds.alloc(2 * n * sizeof(double)));
-    EIGSOL_TRY(bU.alloc(dev::kMaxGroups * dev::kWin * dev::kWin * sizeof(double)));
     EIGSOL_TRY(bsh.alloc(4 * dev::kMaxBulges * sizeof(double)));
     EIGSOL_TRY(binfo.alloc(64));
     double *const dsw = bsw.as<double>(), *const dwr = bwr.as<double>(), *const dwi = bwi.as<double>();
-    double *const dds = bds.as<double>(), *const dU = bU.as<double>(), *const dsh = bsh.as<double>();
+    double *const dU = sd.dU, *const dsh = bsh.as<double>();
     int *const dsinfo = bsinfo.as<int>(), *const dinfo = binfo.as<int>();
     unsigned* const dflag = bflag.as<unsigned>();
     unsigned flag_epoch = 0;
     int rc = EIGSOL_OK;
-    // every per-sweep transfer goes through pinned host memory: a pageable hipMemcpyAsync is staged
-    // by the runtime and waited for with a sleeping wait, ~1 ms per copy (round-4 kernel trace,
-    // tools/gap_analysis.py), more than a sweep's kernels at the end of the iteration
+    // the per-sweep transfers' pinned staging (sweep_driver.hpp: why pinned)
     struct Staging {
         int info[8];
         int cinfo[4];
@@ -857,21 +847,16 @@ static int francis_impl(eigsol_ctx* ctx, double* H, int64_t n, int maxits, doubl
         double cwr[2 * dev::kAedMax];   // concurrent shifts: re [0, kAedMax), im [kAedMax, 2 kAedMax)
         double swr[2 * dev::kMaxBulges], swi[2 * dev::kMaxBulges], sh[2 * dev::kMaxBulges];
     };
-    PinBuf bhp, bhs;
+    PinBuf bhp;
     EIGSOL_TRY(bhp.alloc(sizeof(Staging)));
-    EIGSOL_TRY(bhs.alloc(2 * n * sizeof(double)));
     Staging* const hp = bhp.as<Staging>();
-    double* const ds = bhs.as<double>();   // deflation scans: diagonal [0, n), subdiagonal [n, 2n)
+    const double* const ds = sd.ds;   // the latest deflation scan: diagonal [0, n), subdiagonal [n, 2n)
     double* const swr = hp->swr;
     double* const swi = hp->swi;
-    int sweeps = 0, failed = 0;
+    int &sweeps = sd.sweeps, &failed = sd.failed, &stall = sd.stall;
     int ihi = (int)n - 1;
-    int stall = 0;               // sweeps on the current bottom block without a deflation
-    // `sweeps` tracks the largest number of sweeps any single deflation needed
     const int max_stall = std::max(1, maxits);
     static const bool stats = std::getenv("EIGSOL_QR_STATS") != nullptr;
-    constexpr int max_groups = dev::kMaxGroups;   // bulge groups chased concurrently
-    constexpr int max_bulges = 32;                // bulges per chain
     constexpr int aed_win = kAedWin;
     // The AED stops at the first undeflatable block.  (Until round 3 it formed the whole window's
     // Schur form, whose undeflated eigenvalues were the shifts; removed.)  4096^2: 1.33 -> 1.23 s:
@@ -895,43 +880,19 @@ static int francis_impl(eigsol_ctx* ctx, double* H, int64_t n, int maxits, doubl
     // small-deflation case 141 sweeps run instead of 115 but skip their 0.79 ms shift QRs, whose
     // eigenvalue QR of the window hides under the AED (~1.1 ms): 0.946 -> 0.928 s and 0.948 ->
     // 0.930 s (seed 7), one-to-one with LAPACK (3.3e-12).  The two narrower modes were removed.
-    long long st_steps = 0, st_aed_steps = 0, st_aed_ph[3] = {0, 0, 0};
-    int st_sweeps = 0, st_windows = 0, st_small = 0, st_small_rows = 0, st_aed = 0, st_aed_defl = 0, st_conc = 0;
-    // Schur mode: the factor U (W x W) of the rows / columns [s, s + W) applied outside them: U^T to the
-    // columns [e, n), U to the rows [0, rhi) and to Z's columns
-    auto apply_outside = [&](int s, int W, int64_t rhi, const double* U) {
-        const int e = s + W;
-        dev::WinGemmBatch gb{H, n, 1, {}};
-        if (e < n) {
-            gb.w[0] = dev::WinGemm{s, W, (int64_t)e, n, 0, U};
-            hipLaunchKernelGGL(dev::win_gemm_mfma<true>, dim3((unsigned)((n - e + 63) / 64)), dim3(256), 0, st, gb);
-        }
-        if (rhi > 0) {
-            gb.w[0] = dev::WinGemm{s, W, 0, rhi, 0, U};
-            hipLaunchKernelGGL(dev::win_gemm_mfma<false>, dim3((unsigned)((rhi + 63) / 64)), dim3(256), 0, st, gb);
-        }
-        if (Z) {
-            dev::WinGemmBatch zb{Z, n, 1, {}};
-            zb.w[0] = dev::WinGemm{s, W, 0, n, 0, U};
-            hipLaunchKernelGGL(dev::win_gemm_mfma<false>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, zb);
-        }
-    };
+    long long st_aed_steps = 0, st_aed_ph[3] = {0, 0, 0};
+    int st_sweeps = 0, st_small = 0, st_small_rows = 0, st_aed = 0, st_aed_defl = 0, st_conc = 0;
     auto finish_small = [&](int l, int hi) -> int {
         const int m = hi - l + 1;
         if constexpr (kSchur) {
             if (m == 1) return EIGSOL_OK;   // a 1 x 1 block is its own Schur form
             hipLaunchKernelGGL(dev::schur_block_kernel, dim3(1), dim3(dev::kAedThreads), 0, st, H, n, l, m,
                                std::max(1, maxits), dU, dinfo);
-            apply_outside(l, m, l, dU);
+            sd.apply_outside(l, m, l, dU);
             EIGSOL_HIP(hipGetLastError());
-            int* info = hp->info;
-            EIGSOL_HIP(hipMemcpyAsync(info, dinfo, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
-            EIGSOL_HIP(stream_wait(st));
-            if (info[0]) failed = 1;
-            sweeps = std::max(sweeps, info[1]);
-            return EIGSOL_OK;
+        } else {
+            EIGSOL_TRY(hqr_small(st, H + l + (int64_t)l * n, n, m, std::max(1, maxits), dwr + l, dwi + l, dinfo));
         }
-        EIGSOL_TRY(hqr_small(st, H + l + (int64_t)l * n, n, m, std::max(1, maxits), dwr + l, dwi + l, dinfo));
         int* info = hp->info;
         EIGSOL_HIP(hipMemcpyAsync(info, dinfo, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
         EIGSOL_HIP(stream_wait(st));
@@ -939,43 +900,22 @@ static int francis_impl(eigsol_ctx* ctx, double* H, int64_t n, int maxits, doubl
         sweeps = std::max(sweeps, info[1]);
         return EIGSOL_OK;
     };
-    // deflation scan of [0, ihi]: diagonal and subdiagonal into pinned host memory (only the
-    // ihi + 1 leading entries of each half travel)
-    auto scan = [&]() -> int {
-        hipLaunchKernelGGL(dev::diag_sub_kernel<double>, dim3((ihi + 256) / 256), dim3(256), 0, st, H, n, ihi, dds);
-        if (hipMemcpyAsync(ds, dds, (ihi + 1) * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipMemcpyAsync(ds + n, dds + n, (ihi + 1) * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            stream_wait(st) != hipSuccess)
-            return fail(EIGSOL_E_HIP, "francis: deflation scan");
-        return EIGSOL_OK;
-    };
-    bool scanned = false;   // the previous sweep's closing scan is still current (nothing ran since)
     while (rc == EIGSOL_OK && ihi >= 0) {
-        if (!scanned && (rc = scan()) != EIGSOL_OK) break;
-        scanned = false;
-        int l = ihi;
-        while (l > 0) {
-            const double s0 = std::fabs(ds[l - 1]) + std::fabs(ds[l]);
-            if (std::fabs(ds[n + l]) <= eps * s0 || ds[n + l] == 0.0) break;
-            --l;
-        }
+        int l;
+        if ((rc = sd.next_block(ihi, &l)) != EIGSOL_OK) break;
         const int N = ihi - l + 1;
-        if constexpr (kSchur) {   // the accepted sub-diagonal entry becomes an exact zero
-            if (l > 0 && ds[n + l] != 0.0) hipLaunchKernelGGL(dev::zero_entry_kernel<double>, dim3(1), dim3(1), 0, st, H, n, l, l - 1);
-        }
         if (N <= (kSchur ? dev::kAedMax : kSmall)) {
             ++st_small;
             st_small_rows += N;
             rc = finish_small(l, ihi);
             if (kSchur && failed) break;   // the block stays unreduced: T is upper Hessenberg there
             ihi = l - 1;
-            sweeps = std::max(sweeps, stall);
-            stall = 0;
+            sd.deflated();
             continue;
         }
         if (++stall > max_stall) { failed = 1; sweeps = std::max(sweeps, stall); break; }
         // aggressive early deflation on the trailing window; its undeflated eigenvalues are the shifts
-        int nb = std::min(max_bulges, std::max(1, N / 8));
+        int nb = chase_bulges_f64(N);
         int ns = 2 * nb;
         bool have_shifts = false;
         {
@@ -1010,16 +950,9 @@ static int francis_impl(eigsol_ctx* ctx, double* H, int64_t n, int maxits, doubl
                 const int nd = info[1], m = info[3];
                 if (nd > 0) {
                     st_aed_defl += nd;
-                    if constexpr (kSchur) {   // V on the columns right of the window, the rows above it and Z
-                        apply_outside(kw, nw, kw, dU);
-                    } else if (kw > l) {   // rows above the window: H[l, kw) x [kw, kw + nw) V
-                        dev::WinGemmBatch gb{H, n, 1, {}};
-                        gb.w[0] = dev::WinGemm{kw, nw, (int64_t)l, (int64_t)kw, 0, dU};
-                        hipLaunchKernelGGL(dev::win_gemm_mfma<false>, dim3((kw - l + 63) / 64), dim3(256), 0, st, gb);
-                    }
+                    sd.apply_aed(l, kw, nw, dU);
                     ihi = kw + m - 1;
-                    sweeps = std::max(sweeps, stall);
-                    stall = 0;
+                    sd.deflated();
                     if (100 * nd >= kNibble * nw || m < 4) continue;   // enough deflated: look again first
                 }
                 if (conc_ok && nd == 0) {   // the block the shift QR below would solve, already solved
@@ -1052,7 +985,7 @@ static int francis_impl(eigsol_ctx* ctx, double* H, int64_t n, int maxits, doubl
                             ++k;
                         }
                     const int N2 = ihi - l + 1;
-                    nb = std::min({max_bulges, std::max(1, N2 / 8), std::max(1, k / 2)});
+                    nb = std::min(chase_bulges_f64(N2), std::max(1, k / 2));
                     ns = 2 * nb;
                     for (int i = 0; i < ns; ++i) {   // the bottom ns of the undeflated ones
                         swr[i] = swr[k - ns + i];
@@ -1071,7 +1004,7 @@ static int francis_impl(eigsol_ctx* ctx, double* H, int64_t n, int maxits, doubl
         // on ad hoc shifts and its shift QR went unused: a bug, fixed in round 4.)
         const bool exceptional = stall > 0 && stall % 6 == 0;
         if (!have_shifts && !exceptional) {
-            nb = std::min(max_bulges, std::max(1, (ihi - l + 1) / 8));
+            nb = chase_bulges_f64(ihi - l + 1);
             ns = 2 * nb;
             // shifts: eigenvalues of the trailing 2nb x 2nb block
             rc = hqr_small(st, H + (ihi - ns + 1) + (int64_t)(ihi - ns + 1) * n, n, ns, 60, dwr + ihi - ns + 1,
@@ -1088,7 +1021,7 @@ static int francis_impl(eigsol_ctx* ctx, double* H, int64_t n, int maxits, doubl
         // every 6th stalled sweep uses exceptional shifts from the bottom subdiagonal
         double* const sh = hp->sh;   // 2 nb values; the chase reads them from dsh
         if (exceptional) {
-            nb = std::min(max_bulges, std::max(1, (ihi - l + 1) / 8));
+            nb = chase_bulges_f64(ihi - l + 1);
             for (int b = 0; b < nb; ++b) {
                 const double sc = std::fabs(ds[n + ihi - b]) + std::fabs(ds[ihi - b]) + 1e-300;
                 sh[2 * b] = ds[ihi - b] + 0.75 * sc;
@@ -1124,101 +1057,9 @@ static int francis_impl(eigsol_ctx* ctx, double* H, int64_t n, int maxits, doubl
             break;
         }
         ++st_sweeps;
-        // chase: C groups of nbg bulges, group g starting G steps after group g-1, each group in its
-        // own LDS window; a round advances every group's window by the same number of steps
-        // groups of >= 4 bulges; the spacing costs (C - 1) G extra steps, kept below N / 4
-        const int Nact = ihi - l + 1;   // after the AED's deflations
-        const int C = std::max(1, std::min({max_groups, nb / 4, 1 + Nact / (4 * (dev::kWin + 12))}));
-        const int nbg = std::min(nb / C, 16);   // one wave per bulge: at most 16 per window
-        const int G = dev::kWin + 3 * nbg;   // group spacing: windows stay disjoint
-        const int Tg = (ihi - 1 - l) + 3 * (nbg - 1) + 1;     // steps of one group
-        const int T = (C - 1) * G + Tg;
-        int t0 = 0;
-        while (t0 < T && rc == EIGSOL_OK) {
-            dev::ChaseArgs ca{H, n, l, ihi, {}};
-            int t1 = T, nwin = 0;
-            int g_act[dev::kMaxGroups];
-            for (int g = 0; g < C; ++g) {
-                const int tl = t0 - g * G;
-                if (tl < 0) { t1 = std::min(t1, g * G); break; }    // later groups start at a round boundary
-                if (tl >= Tg) continue;                              // group done
-                int s;
-                if (tl <= 3 * (nbg - 1)) s = std::max(0, l - 1);
-                else s = std::max(0, l + tl - 3 * (nbg - 1) - 1);
-                const int e = std::min(s + dev::kWin, ihi + 1);
-                const int kmax = (e == ihi + 1) ? ihi - 1 : e - 4;
-                int tl1 = tl;
-                while (tl1 < Tg) {
-                    const int blead = std::max(0, (l + tl1 - (ihi - 1) + 2) / 3);   // first bulge not past ihi-1
-                    if (blead >= nbg) { tl1 = Tg; break; }
-                    if (l + tl1 - 3 * blead > kmax) break;
-                    ++tl1;
-                }
-                t1 = std::min(t1, tl1 + g * G);
-                ca.w[nwin] = dev::ChaseWin{s, e, tl, 0, nbg, dsh + 2 * g * nbg, dU + (size_t)nwin * dev::kWin * dev::kWin};
-                g_act[nwin++] = g;
-            }
-            if (nwin == 0 && t1 > t0) { t0 = t1; continue; }   // every started group done, the next not yet due
-            if (t1 <= t0 || nwin == 0) { rc = fail(EIGSOL_E_SOLVER, "francis: window did not advance (internal error)"); break; }
-            for (int q = 0; q < nwin; ++q) {
-                ca.w[q].t1 = t1 - g_act[q] * G;
-                if (q > 0 && ca.w[q].e > ca.w[q - 1].s) { rc = fail(EIGSOL_E_SOLVER, "francis: windows overlap (internal error)"); break; }
-            }
-            if (rc != EIGSOL_OK) break;
-            st_windows += nwin;
-            st_steps += t1 - t0;
-            hipLaunchKernelGGL(dev::chase_wave_kernel, dim3(nwin), dim3(1024), 0, st, ca);
-            // delayed updates: every left region, then every right region; tiles of 64 columns /
-            // rows per workgroup (32 when 64-wide tiles would leave CUs idle)
-            // Schur mode: left regions to column n - 1, right regions from row 0 (the window's own rows
-            // from max(l, s) on were updated by the chase), and Z's columns [s, e) as one more right batch
-            dev::WinGemmBatch lb{H, n, 0, {}}, rb{H, n, 0, {}}, zb{Z, n, 0, {}};
-            const int lend = kSchur ? (int)n : ihi + 1;   // left regions: columns [e, lend)
-            auto rlo = [&](const dev::ChaseWin&) { return kSchur ? 0 : l; };                       // right regions: rows
-            auto rhi = [&](const dev::ChaseWin& w) { return kSchur ? std::max(l, w.s) : w.s; };   // [rlo, rhi)
-            int nlb = 0, nrb = 0, nzb = 0, span = 0;
-            for (int q = 0; q < nwin; ++q) {
-                const dev::ChaseWin& w = ca.w[q];
-                if (w.e < lend) span += lend - w.e;
-                if (rhi(w) > rlo(w)) span += rhi(w) - rlo(w);
-            }
-            const int tile = span / 64 < ctx->num_cus ? 32 : 64;
-            for (int q = 0; q < nwin; ++q) {
-                const dev::ChaseWin& w = ca.w[q];
-                const int W = w.e - w.s;
-                if (w.e < lend) {
-                    lb.w[lb.nw++] = dev::WinGemm{w.s, W, (int64_t)w.e, (int64_t)lend, nlb, w.U};
-                    nlb += (lend - w.e + tile - 1) / tile;
-                }
-                if (rhi(w) > rlo(w)) {
-                    rb.w[rb.nw++] = dev::WinGemm{w.s, W, (int64_t)rlo(w), (int64_t)rhi(w), nrb, w.U};
-                    nrb += (rhi(w) - rlo(w) + tile - 1) / tile;
-                }
-                if (kSchur && Z) {
-                    zb.w[zb.nw++] = dev::WinGemm{w.s, W, 0, n, nzb, w.U};
-                    nzb += (int)((n + 63) / 64);
-                }
-            }
-            if (tile == 32) {
-                if (nlb > 0) hipLaunchKernelGGL((dev::win_gemm_mfma<true, 32>), dim3(nlb), dim3(256), 0, st, lb);
-                if (nrb > 0) hipLaunchKernelGGL((dev::win_gemm_mfma<false, 32>), dim3(nrb), dim3(256), 0, st, rb);
-            } else {
-                if (nlb > 0) hipLaunchKernelGGL(dev::win_gemm_mfma<true>, dim3(nlb), dim3(256), 0, st, lb);
-                if (nrb > 0) hipLaunchKernelGGL(dev::win_gemm_mfma<false>, dim3(nrb), dim3(256), 0, st, rb);
-            }
-            if (nzb > 0) hipLaunchKernelGGL(dev::win_gemm_mfma<false>, dim3(nzb), dim3(256), 0, st, zb);
-            t0 = t1;
-        }
-        if (hipGetLastError() != hipSuccess) { rc = fail(EIGSOL_E_HIP, "francis: launch"); break; }
-        // a deflation anywhere below resets the stall counter; the scan also serves the next pass
-        if ((rc = scan()) != EIGSOL_OK) break;
-        scanned = true;
-        for (int k = ihi; k > l; --k)
-            if (std::fabs(ds[n + k]) <= eps * (std::fabs(ds[k - 1]) + std::fabs(ds[k]))) {
-                sweeps = std::max(sweeps, stall);
-                stall = 0;
-                break;
-            }
+        // chase (sweep_driver.hpp), on the block as the AED's deflations left it
+        if ((rc = sd.run_chase(l, ihi, chase_plan_f64(nb, ihi - l + 1), dsh)) != EIGSOL_OK) break;
+        if ((rc = sd.close_sweep(l, ihi)) != EIGSOL_OK) break;
     }
     if (rc == EIGSOL_OK && !kSchur) {
         if (hipMemcpyAsync(wr, dwr, n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -1229,12 +1070,9 @@ static int francis_impl(eigsol_ctx* ctx, double* H, int64_t n, int maxits, doubl
     if (stats)
         std::fprintf(stderr, "francis: n=%lld sweeps=%d windows=%d steps=%lld small_blocks=%d small_rows=%d kSmall=%d "
                      "aed=%d aed_deflated=%d aed_win=%d aed_steps=%lld aed_phase_ms=%.1f/%.1f/%.1f conc_shifts=%d\n",
-                     (long long)n, st_sweeps, st_windows, st_steps, st_small, st_small_rows, kSmall, st_aed, st_aed_defl,
+                     (long long)n, st_sweeps, sd.st_windows, sd.st_steps, st_small, st_small_rows, kSmall, st_aed, st_aed_defl,
                      aed_win, st_aed_steps, st_aed_ph[0] * 1e-5, st_aed_ph[1] * 1e-5, st_aed_ph[2] * 1e-5, st_conc);
-    // iterations reported: sweeps spent on the slowest deflation (>= 1, the final check), so that
-    // iterations <= maxIterations exactly when the iteration converged
-    *sweeps_out = std::max(1, sweeps);
-    *fail_out = failed;
+    sd.report(sweeps_out, fail_out);
     return rc;
 }
 

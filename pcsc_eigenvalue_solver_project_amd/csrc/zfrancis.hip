@@ -22,16 +22,10 @@
 //     and 20, Ahues-Tisseur deflation test).
 // Deflation: |h(k,k-1)| <= eps (|h(k,k)| + |h(k-1,k-1)|) with |z| = |Re z| + |Im z| (ZLAHQR's cabs1).
 #include <algorithm>
-#include <cmath>
-#include <complex>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <vector>
 
-#include "kernels_common.hpp"
-#include "mfma_window.hpp"
-#include "scratch.hpp"
+#include "sweep_driver.hpp"
 
 namespace eigsol {
 namespace dev {
@@ -469,31 +463,8 @@ __global__ __launch_bounds__(kZAedThreads) void zaed_kernel(cplx* Hg, int64_t n,
 }
 
 // ---------------------------------------------------------------- windowed multishift chase
-struct ZChaseWin {
-    int s, e;          // window [s, e)
-    int t0, t1;        // chase steps of this launch (chain-relative)
-    int nb;            // bulges of the chain
-    const cplx* shifts;   // 2 per bulge
-    cplx* U;           // out: (e - s)^2, column-major
-};
-struct ZChaseBatch {   // one workgroup per window; the windows are disjoint
-    cplx* H;
-    int64_t n;
-    int l, ihi;
-    ZChaseWin w[kZMaxGroups];
-};
-struct ZChaseArgs {
-    cplx* H;
-    int64_t n;
-    int l, ihi;
-    int s, e, t0, t1, nb;
-    const cplx* shifts;
-    cplx* U;
-};
-
-__global__ __launch_bounds__(1024) void zchase_kernel(ZChaseBatch b) {
-    const ZChaseWin wd = b.w[blockIdx.x];
-    const ZChaseArgs a{b.H, b.n, b.l, b.ihi, wd.s, wd.e, wd.t0, wd.t1, wd.nb, wd.shifts, wd.U};
+__global__ __launch_bounds__(1024) void zchase_kernel(ChaseBatch<cplx, kZMaxGroups> b) {
+    const ChaseWin<cplx> a = b.w[blockIdx.x];
     __shared__ cplx h[kZWin * (kZWin + 1)];
     __shared__ cplx u[kZWin * kZWin];
     constexpr int lh = kZWin + 1, lu = kZWin;
@@ -502,11 +473,11 @@ __global__ __launch_bounds__(1024) void zchase_kernel(ZChaseBatch b) {
     auto Hw = [&](int i, int j) -> cplx& { return h[(i - a.s) + (j - a.s) * lh]; };
     for (int idx = tid; idx < W * W; idx += 1024) {
         const int i = idx % W, j = idx / W;
-        h[i + j * lh] = a.H[(a.s + i) + (int64_t)(a.s + j) * a.n];
+        h[i + j * lh] = b.H[(a.s + i) + (int64_t)(a.s + j) * b.n];
         u[i + j * lu] = (i == j) ? cplx{1.0, 0.0} : cplx{0.0, 0.0};
     }
     __syncthreads();
-    const int l = a.l, ihi = a.ihi;
+    const int l = b.l, ihi = b.ihi;
     const int wv = tid >> 6, ln = tid & 63;
     const int rlo = max(l, a.s);
     for (int t = a.t0; t < a.t1; ++t) {
@@ -594,7 +565,7 @@ __global__ __launch_bounds__(1024) void zchase_kernel(ZChaseBatch b) {
     }
     for (int idx = tid; idx < W * W; idx += 1024) {
         const int i = idx % W, j = idx / W;
-        a.H[(a.s + i) + (int64_t)(a.s + j) * a.n] = h[i + j * lh];
+        b.H[(a.s + i) + (int64_t)(a.s + j) * b.n] = h[i + j * lh];
         a.U[idx] = u[i + j * lu];
     }
 }
@@ -603,7 +574,6 @@ __global__ __launch_bounds__(1024) void zchase_kernel(ZChaseBatch b) {
 // 8 output columns per 128-thread workgroup, was removed).  left: H(s:s+W, cols) <- U^H H(s:s+W, cols)
 // for the columns [lo, hi); right: H(rows, s:s+W) <- H(rows, s:s+W) U for the rows [lo, hi); 64
 // columns / rows per workgroup of 4 waves.
-using ZWinGemm = WindowRegion<cplx>;
 using ZWinGemmBatch = WindowBatch<cplx, kZMaxGroups>;
 constexpr int kZMG = 64;   // outputs per workgroup
 constexpr int kZMT = 4 * kZMG;   // threads: one wave per 16 outputs
@@ -650,48 +620,53 @@ __global__ __launch_bounds__(kZAedThreads) void zschur_block_kernel(cplx* Hg, in
 
 }  // namespace dev
 
-static double cabs1_h(const cplx& a) { return std::fabs(a.re) + std::fabs(a.im); }
-
 // AED window.  Early-stop AED, 32 bulges in 4 chains: window
 // 32 / 48 / 64 at 1024^2 0.292 / 0.287 / 0.320 s; 48 vs 64 at 4096^2 2.65 / 2.75 s.  Without the
 // AED: 1024^2 0.37-0.42 s, 4096^2 4.4 s; an AED over the window's whole Schur form (LAPACK's, the
 // undeflated eigenvalues becoming the shifts) 0.54 / 4.4 s.  Both were removed.
 static constexpr int kZAedWin = 48;
 
-// eigenvalues of the complex Hessenberg matrix H (device, n x n, leading dimension n; destroyed).
-// kSchur = true (schur_sweeps_c128): the same sweeps, shifts and launches of the chase, with every delayed
-// update widened to the whole matrix (left regions to column n - 1, right regions from row 0), the window
-// factors also applied to Z (n x n, leading dimension n; null: none), accepted sub-diagonal entries stored
-// as zeros and blocks of at most kZSmall rows finished by zschur_block_kernel; w_host is not written.
+// the complex sweeps' side of sweep_driver.hpp
+struct ComplexSweep {
+    using S = cplx;
+    static constexpr int kWin = dev::kZWin, kMaxGroups = dev::kZMaxGroups, kMaxRegions = dev::kZMaxGroups;
+    static constexpr const char* kName = "complex QR";
+    static void chase(hipStream_t st, int nwin, const dev::ChaseBatch<cplx, dev::kZMaxGroups>& b) {
+        hipLaunchKernelGGL(dev::zchase_kernel, dim3(nwin), dim3(1024), 0, st, b);
+    }
+    template <bool kLeft>
+    static void update(hipStream_t st, int, int grid, const dev::ZWinGemmBatch& b) {
+        hipLaunchKernelGGL(dev::zwin_gemm_mfma<kLeft>, dim3(grid), dim3(dev::kZMT), 0, st, b);
+    }
+    static int update_tile(int, int) { return dev::kZMG; }
+};
+
+// eigenvalues of the complex Hessenberg matrix H (device, n x n, leading dimension n; destroyed).  kSchur = true
+// (schur_sweeps_c128): Schur mode (sweep_driver.hpp), blocks <= kZSmall finished by zschur_block_kernel; no w_host.
 template <bool kSchur>
 static int zfrancis_impl(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* w_host, int32_t* sweeps_out,
                          int32_t* fail_out, cplx* Z) {
     hipStream_t st = ctx->stream;
-    const double eps = 2.220446049250313e-16;
-    DevBuf bw, bds, bU, bsh, binfo, bV;
+    SweepDriver<ComplexSweep, kSchur> sd{st, H, Z, n, ctx->num_cus};
+    EIGSOL_TRY(sd.alloc());
+    DevBuf bw, bsh, binfo, bV;
     EIGSOL_TRY(bw.alloc(n * sizeof(cplx)));
-    EIGSOL_TRY(bds.alloc(2 * n * sizeof(cplx)));
-    EIGSOL_TRY(bU.alloc((size_t)dev::kZMaxGroups * dev::kZWin * dev::kZWin * sizeof(cplx)));
     EIGSOL_TRY(bsh.alloc(2 * dev::kZMaxBulges * sizeof(cplx)));
     EIGSOL_TRY(binfo.alloc(64));
     EIGSOL_TRY(bV.alloc((size_t)dev::kZSmall * dev::kZSmall * sizeof(cplx)));   // the AED window's unitary factor
-    cplx *const dw = bw.as<cplx>(), *const dds = bds.as<cplx>(), *const dU = bU.as<cplx>(), *const dsh = bsh.as<cplx>();
-    cplx* const dV = bV.as<cplx>();
+    cplx *const dw = bw.as<cplx>(), *const dsh = bsh.as<cplx>(), *const dV = bV.as<cplx>();
     int* const dinfo = binfo.as<int>();
     int rc = EIGSOL_OK;
-    // every per-sweep transfer goes through pinned host memory: a pageable hipMemcpyAsync is staged
-    // by the runtime and waited for with a sleeping wait, ~1 ms per copy (round-4 kernel trace of
-    // 4096^2: 1.12 s of 2.8 s idle after such copies, tools/gap_analysis.py)
+    // the per-sweep transfers' pinned staging (sweep_driver.hpp: why pinned)
     struct Staging {
         int info[8];
         cplx sh[2 * dev::kZMaxBulges];
     };
-    PinBuf bhp, bhs;
+    PinBuf bhp;
     EIGSOL_TRY(bhp.alloc(sizeof(Staging)));
-    EIGSOL_TRY(bhs.alloc(2 * n * sizeof(cplx)));
     Staging* const hp = bhp.as<Staging>();
-    cplx* const ds = bhs.as<cplx>();   // deflation scans: diagonal [0, n), subdiagonal [n, 2n)
-    int sweeps = 0, failed = 0, stall = 0;
+    const cplx* const ds = sd.ds;   // the latest deflation scan: diagonal [0, n), subdiagonal [n, 2n)
+    int &sweeps = sd.sweeps, &failed = sd.failed, &stall = sd.stall;
     int st_sweeps = 0, st_aed = 0, st_aed_defl = 0, st_small = 0;
     static const bool stats = std::getenv("EIGSOL_QR_STATS") != nullptr;
     int ihi = (int)n - 1;
@@ -708,48 +683,10 @@ static int zfrancis_impl(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* 
         info[1] = hp->info[1];
         return EIGSOL_OK;
     };
-    auto scan = [&]() -> int {   // only the ihi + 1 leading entries of each half travel
-        hipLaunchKernelGGL(dev::diag_sub_kernel<cplx>, dim3((ihi + 256) / 256), dim3(256), 0, st, H, (int64_t)n, ihi, dds);
-        EIGSOL_HIP(hipMemcpyAsync(ds, dds, (ihi + 1) * sizeof(cplx), hipMemcpyDeviceToHost, st));
-        EIGSOL_HIP(hipMemcpyAsync(ds + n, dds + n, (ihi + 1) * sizeof(cplx), hipMemcpyDeviceToHost, st));
-        EIGSOL_HIP(stream_wait(st));
-        return EIGSOL_OK;
-    };
-    // Schur mode: the factor U (W x W) of the rows / columns [s, s + W) applied outside them: U^H to the
-    // columns [e, n), U to the rows [0, rhi) and to Z's columns
-    auto apply_outside = [&](int s, int W, int64_t rhi, const cplx* U) {
-        const int e = s + W;
-        constexpr int per = dev::kZMG;
-        dev::ZWinGemmBatch gb{H, (int64_t)n, 1, {}};
-        if (e < n) {
-            gb.w[0] = dev::ZWinGemm{s, W, (int64_t)e, (int64_t)n, 0, U};
-            hipLaunchKernelGGL(dev::zwin_gemm_mfma<true>, dim3((unsigned)((n - e + per - 1) / per)), dim3(dev::kZMT), 0, st, gb);
-        }
-        if (rhi > 0) {
-            gb.w[0] = dev::ZWinGemm{s, W, 0, rhi, 0, U};
-            hipLaunchKernelGGL(dev::zwin_gemm_mfma<false>, dim3((unsigned)((rhi + per - 1) / per)), dim3(dev::kZMT), 0, st, gb);
-        }
-        if (Z) {
-            dev::ZWinGemmBatch zb{Z, (int64_t)n, 1, {}};
-            zb.w[0] = dev::ZWinGemm{s, W, 0, (int64_t)n, 0, U};
-            hipLaunchKernelGGL(dev::zwin_gemm_mfma<false>, dim3((unsigned)((n + per - 1) / per)), dim3(dev::kZMT), 0, st, zb);
-        }
-    };
-    bool scanned = false;   // the previous sweep's closing scan is still current (nothing ran since)
     while (rc == EIGSOL_OK && ihi >= 0) {
-        if (!scanned && (rc = scan()) != EIGSOL_OK) break;
-        scanned = false;
-        int l = ihi;
-        while (l > 0) {
-            const cplx sd = ds[n + l];
-            if (cabs1_h(sd) <= eps * (cabs1_h(ds[l - 1]) + cabs1_h(ds[l])) || (sd.re == 0.0 && sd.im == 0.0)) break;
-            --l;
-        }
+        int l;
+        if ((rc = sd.next_block(ihi, &l)) != EIGSOL_OK) break;
         const int N = ihi - l + 1;
-        if constexpr (kSchur) {   // the accepted sub-diagonal entry becomes an exact zero
-            if (l > 0 && (ds[n + l].re != 0.0 || ds[n + l].im != 0.0))
-                hipLaunchKernelGGL(dev::zero_entry_kernel<cplx>, dim3(1), dim3(1), 0, st, H, (int64_t)n, l, l - 1);
-        }
         if (N <= dev::kZSmall) {
             int info[2] = {0, 0};
             ++st_small;
@@ -757,7 +694,7 @@ static int zfrancis_impl(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* 
                 if (N > 1) {   // a 1 x 1 block is its own Schur form
                     hipLaunchKernelGGL(dev::zschur_block_kernel, dim3(1), dim3(dev::kZAedThreads), 0, st, H, (int64_t)n, l, N,
                                        dw + l, dV, dinfo);
-                    apply_outside(l, N, l, dV);
+                    sd.apply_outside(l, N, l, dV);
                     if (hipGetLastError() != hipSuccess ||
                         hipMemcpyAsync(hp->info, dinfo, 2 * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
                         stream_wait(st) != hipSuccess) {
@@ -776,22 +713,10 @@ static int zfrancis_impl(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* 
             continue;
         }
         if (++stall > max_stall) { failed = 1; sweeps = std::max(sweeps, stall); break; }
-        // up to 32 bulges per sweep (64 shifts) in C chains of at most 8 (a chain's 3 nb rows must
-        // leave its 64-row window room to advance), the chains chased concurrently in disjoint
-        // windows.  With the AED (round 3) 32 bulges in 4 chains beat 16 in 2: 1024^2 0.31 -> 0.29 s,
-        // 2048^2 0.93 -> 0.77 s, 4096^2 3.28 -> 2.65 s
-        constexpr int max_nb = 32, max_groups = 4;
         // aggressive early deflation on the trailing window, stopped at the first undeflatable
         // eigenvalue; the shifts come from the trailing block afterwards
         constexpr int aed_win = kZAedWin;
         constexpr int nibble = 14;   // % of the window deflated that skips the sweep (LAPACK's NIBBLE)
-        // bulges of a sweep on an active block of Nact rows (C chains of nbg): the shift count 2 nb
-        auto plan = [&](int Nact, int& C, int& nbg) {
-            const int nb = std::min(max_nb, std::max(1, Nact / 16));
-            C = std::max(1, std::min({max_groups, (nb + 7) / 8, 1 + Nact / (4 * (dev::kZWin + 12))}));
-            nbg = std::max(1, std::min(8, nb / C));
-            return nbg * C;
-        };
         {
             const int nw = std::min(aed_win, N);
             const int kw = ihi - nw + 1;
@@ -808,25 +733,17 @@ static int zfrancis_impl(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* 
                 const int nd = info[1];
                 if (nd > 0) {
                     st_aed_defl += nd;
-                    if constexpr (kSchur) {   // V on the columns right of the window, the rows above it and Z
-                        apply_outside(kw, nw, kw, dV);
-                    } else if (kw > l) {   // rows of the block above the window: H[l, kw) x [kw, kw + nw) V
-                        dev::ZWinGemmBatch rb{H, (int64_t)n, 1, {}};
-                        rb.w[0] = dev::ZWinGemm{kw, nw, (int64_t)l, (int64_t)kw, 0, dV};
-                        hipLaunchKernelGGL(dev::zwin_gemm_mfma<false>, dim3((kw - l + dev::kZMG - 1) / dev::kZMG),
-                                           dim3(dev::kZMT), 0, st, rb);
-                    }
+                    sd.apply_aed(l, kw, nw, dV);
                     const int m = info[3];
                     ihi = kw + m - 1;
-                    sweeps = std::max(sweeps, stall);
-                    stall = 0;
+                    sd.deflated();
                     if (100 * nd >= nibble * nw || m < 2 || ihi - l + 1 <= dev::kZSmall) continue;
                 }
             }
         }
-        const int Nact = ihi - l + 1;   // after the AED's deflations
-        int C, nbg;
-        const int nb = plan(Nact, C, nbg);
+        // bulges of the sweep on the block as the AED's deflations left it (C chains of nbg): the shift count 2 nb
+        const ChasePlan plan = chase_plan_c128(ihi - l + 1);
+        const int nb = plan.C * plan.nbg;
         const int ns = 2 * nb;
         cplx* const sh = hp->sh;   // ns values; the chase reads them from dsh
         // every 6th sweep without a deflation: exceptional shifts (LAPACK's KEXSH; stall is 0 right
@@ -841,7 +758,7 @@ static int zfrancis_impl(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* 
         if (exceptional) {
             for (int b = 0; b < nb; ++b) {
                 const cplx d = ds[ihi - b];
-                const double sc = cabs1_h(ds[n + ihi - b]) + cabs1_h(d) * 1e-3 + 1e-300;
+                const double sc = abs1(ds[n + ihi - b]) + abs1(d) * 1e-3 + 1e-300;
                 sh[2 * b] = cplx{d.re + 0.75 * sc, d.im};
                 sh[2 * b + 1] = cplx{d.re - 0.75 * sc, d.im};
             }
@@ -851,81 +768,8 @@ static int zfrancis_impl(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* 
             }
         }
         ++st_sweeps;
-        // chase: chain g starts G steps after chain g-1 (windows stay disjoint); a round advances
-        // every started chain's window by the same number of steps
-        const int G = dev::kZWin + 3 * nbg;
-        const int Tg = (ihi - 1 - l) + 3 * (nbg - 1) + 1;   // steps of one chain
-        const int T = (C - 1) * G + Tg;
-        int t0 = 0;
-        while (t0 < T && rc == EIGSOL_OK) {
-            dev::ZChaseBatch cb{H, (int64_t)n, l, ihi, {}};
-            int t1 = T, nwin = 0;
-            int g_act[dev::kZMaxGroups];
-            for (int g = 0; g < C; ++g) {
-                const int tl = t0 - g * G;
-                if (tl < 0) { t1 = std::min(t1, g * G); break; }    // later chains start at a round boundary
-                if (tl >= Tg) continue;                              // chain done
-                const int s = tl <= 3 * (nbg - 1) ? std::max(0, l - 1) : std::max(0, l + tl - 3 * (nbg - 1) - 1);
-                const int e = std::min(s + dev::kZWin, ihi + 1);
-                const int kmax = (e == ihi + 1) ? ihi - 1 : e - 4;
-                int tl1 = tl;
-                while (tl1 < Tg) {
-                    const int blead = std::max(0, (l + tl1 - (ihi - 1) + 2) / 3);   // first bulge not past ihi-1
-                    if (blead >= nbg) { tl1 = Tg; break; }
-                    if (l + tl1 - 3 * blead > kmax) break;
-                    ++tl1;
-                }
-                t1 = std::min(t1, tl1 + g * G);
-                cb.w[nwin] = dev::ZChaseWin{s, e, tl, 0, nbg, dsh + 2 * g * nbg, dU + (size_t)nwin * dev::kZWin * dev::kZWin};
-                g_act[nwin++] = g;
-            }
-            if (nwin == 0 && t1 > t0) { t0 = t1; continue; }   // every started chain done, the next not yet due
-            if (t1 <= t0 || nwin == 0) { rc = fail(EIGSOL_E_SOLVER, "complex QR: window did not advance (internal error)"); break; }
-            for (int q = 0; q < nwin; ++q) {
-                cb.w[q].t1 = t1 - g_act[q] * G;
-                if (q > 0 && cb.w[q].e > cb.w[q - 1].s) { rc = fail(EIGSOL_E_SOLVER, "complex QR: windows overlap (internal error)"); break; }
-            }
-            if (rc != EIGSOL_OK) break;
-            hipLaunchKernelGGL(dev::zchase_kernel, dim3(nwin), dim3(1024), 0, st, cb);
-            // delayed updates: every left region, then every right region (U_a^H X U_b = (U_a^H X) U_b)
-            // on the matrix cores
-            constexpr int per = dev::kZMG;
-            // Schur mode: left regions to column n - 1, right regions from row 0 (the window's own rows
-            // from max(l, s) on were updated by the chase), and Z's columns [s, e) as one more right batch
-            dev::ZWinGemmBatch lb{H, (int64_t)n, 0, {}}, rb{H, (int64_t)n, 0, {}}, zb{Z, (int64_t)n, 0, {}};
-            const int lend = kSchur ? (int)n : ihi + 1;   // left regions: columns [e, lend)
-            int nlb = 0, nrb = 0, nzb = 0;
-            for (int q = 0; q < nwin; ++q) {
-                const dev::ZChaseWin& w = cb.w[q];
-                const int W = w.e - w.s;
-                const int rlo = kSchur ? 0 : l, rhi = kSchur ? std::max(l, w.s) : w.s;   // right regions: rows [rlo, rhi)
-                if (w.e < lend) {
-                    lb.w[lb.nw++] = dev::ZWinGemm{w.s, W, (int64_t)w.e, (int64_t)lend, nlb, w.U};
-                    nlb += (lend - w.e + per - 1) / per;
-                }
-                if (rhi > rlo) {
-                    rb.w[rb.nw++] = dev::ZWinGemm{w.s, W, (int64_t)rlo, (int64_t)rhi, nrb, w.U};
-                    nrb += (rhi - rlo + per - 1) / per;
-                }
-                if (kSchur && Z) {
-                    zb.w[zb.nw++] = dev::ZWinGemm{w.s, W, 0, (int64_t)n, nzb, w.U};
-                    nzb += (int)((n + per - 1) / per);
-                }
-            }
-            if (nlb > 0) hipLaunchKernelGGL(dev::zwin_gemm_mfma<true>, dim3(nlb), dim3(dev::kZMT), 0, st, lb);
-            if (nrb > 0) hipLaunchKernelGGL(dev::zwin_gemm_mfma<false>, dim3(nrb), dim3(dev::kZMT), 0, st, rb);
-            if (nzb > 0) hipLaunchKernelGGL(dev::zwin_gemm_mfma<false>, dim3(nzb), dim3(dev::kZMT), 0, st, zb);
-            t0 = t1;
-        }
-        if (hipGetLastError() != hipSuccess) { rc = fail(EIGSOL_E_HIP, "complex QR: launch"); break; }
-        if ((rc = scan()) != EIGSOL_OK) break;
-        scanned = true;
-        for (int k = ihi; k > l; --k)
-            if (cabs1_h(ds[n + k]) <= eps * (cabs1_h(ds[k - 1]) + cabs1_h(ds[k]))) {
-                sweeps = std::max(sweeps, stall);
-                stall = 0;
-                break;
-            }
+        if ((rc = sd.run_chase(l, ihi, plan, dsh)) != EIGSOL_OK) break;
+        if ((rc = sd.close_sweep(l, ihi)) != EIGSOL_OK) break;
     }
     if (rc == EIGSOL_OK && !kSchur) {
         if (hipMemcpyAsync(w_host, dw, n * sizeof(cplx), hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -935,8 +779,7 @@ static int zfrancis_impl(eigsol_ctx* ctx, cplx* H, int64_t n, int maxits, cplx* 
     if (stats)
         std::fprintf(stderr, "complex francis: n=%lld sweeps=%d small_blocks=%d aed=%d aed_deflated=%d\n",
                      (long long)n, st_sweeps, st_small, st_aed, st_aed_defl);
-    *sweeps_out = std::max(1, sweeps);
-    *fail_out = failed;
+    sd.report(sweeps_out, fail_out);
     return rc;
 }
 
