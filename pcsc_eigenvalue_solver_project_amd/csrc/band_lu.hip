@@ -680,8 +680,8 @@ int band_create(eigsol_ctx* ctx, int dtype, int64_t n, const int32_t* rp, const 
 }
 
 template <class S>
-static int band_launch_t(BandFactor* f, bool iter, const void* b, void* y, void* buf0, void* buf1, PowerCtl* ctl,
-                         const void* rank_part, void* my_part, void* trace, int parity) {
+static int band_launch_t(BandFactor* f, bool iter, const void* b, void* y, const ShiftIter& it) {
+    const int parity = it.parity;
     dev::BandSolveArgs<S> a{};
     a.ab0 = static_cast<const S*>(f->ab) + f->top;
     a.ld = f->ldab - 1;
@@ -697,12 +697,12 @@ static int band_launch_t(BandFactor* f, bool iter, const void* b, void* y, void*
     a.zf = static_cast<S*>(f->zf);
     a.b_plain = static_cast<const S*>(b);
     a.y_plain = static_cast<S*>(y);
-    a.buf0 = static_cast<S*>(buf0);
-    a.buf1 = static_cast<S*>(buf1);
-    a.ctl = ctl;
-    a.rank_part = static_cast<const dev::part4*>(rank_part);
-    a.my_part = static_cast<dev::part4*>(my_part);
-    a.trace = static_cast<S*>(trace);
+    a.buf0 = static_cast<S*>(it.buf0);
+    a.buf1 = static_cast<S*>(it.buf1);
+    a.ctl = it.ctl;
+    a.rank_part = static_cast<const dev::part4*>(it.rank_part);
+    a.my_part = static_cast<dev::part4*>(it.my_part);
+    a.trace = static_cast<S*>(it.trace);
     a.sig_re = f->sig_re;
     a.sig_im = f->sig_im;
     const size_t lds = (size_t)f->ring * sizeof(S);
@@ -716,15 +716,11 @@ static int band_launch_t(BandFactor* f, bool iter, const void* b, void* y, void*
     return EIGSOL_OK;
 }
 
-int band_launch(BandFactor* f, bool iter, const void* b, void* y, void* buf0, void* buf1, PowerCtl* ctl,
-                const void* rank_part, void* my_part, void* trace, int parity) {
-    if (f->dtype == EIGSOL_C128)
-        return band_launch_t<cplx>(f, iter, b, y, buf0, buf1, ctl, rank_part, my_part, trace, parity);
-    if (f->dtype == EIGSOL_F32)
-        return band_launch_t<float>(f, iter, b, y, buf0, buf1, ctl, rank_part, my_part, trace, parity);
-    if (f->dtype == EIGSOL_C64)
-        return band_launch_t<cplxf>(f, iter, b, y, buf0, buf1, ctl, rank_part, my_part, trace, parity);
-    return band_launch_t<double>(f, iter, b, y, buf0, buf1, ctl, rank_part, my_part, trace, parity);
+int band_launch(BandFactor* f, bool iter, const void* b, void* y, const ShiftIter& it) {
+    if (f->dtype == EIGSOL_C128) return band_launch_t<cplx>(f, iter, b, y, it);
+    if (f->dtype == EIGSOL_F32) return band_launch_t<float>(f, iter, b, y, it);
+    if (f->dtype == EIGSOL_C64) return band_launch_t<cplxf>(f, iter, b, y, it);
+    return band_launch_t<double>(f, iter, b, y, it);
 }
 
 // algorithmic bytes of one solve: the stored band of L and U (kl + 1 + kl + ku entries a column)

@@ -3,7 +3,7 @@
 
 #include <vector>
 
-#include "internal.hpp"
+#include "shifted.hpp"
 
 namespace eigsol {
 
@@ -22,8 +22,7 @@ void band_plan(int dtype, int64_t n, const int32_t* rp, const int32_t* ci, BandP
 int band_create(eigsol_ctx* ctx, int dtype, int64_t n, const int32_t* rp, const int32_t* ci, const void* v,
                 double sre, double sim, BandPlan& plan, BandFactor** out);
 void band_free(BandFactor* f);
-int band_launch(BandFactor* f, bool iter, const void* b, void* y, void* buf0, void* buf1, PowerCtl* ctl,
-                const void* rank_part, void* my_part, void* trace, int parity);
+int band_launch(BandFactor* f, bool iter, const void* b, void* y, const ShiftIter& it);
 void band_info(const BandFactor* f, double* bytes, int32_t* tiles);
 
 }  // namespace eigsol

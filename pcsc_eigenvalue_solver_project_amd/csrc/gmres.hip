@@ -15,7 +15,7 @@
 //     otherwise M's own pattern (ILU(0)).  Over the exact LU a solve is x = U^-1 L^-1 b and its
 //     true residual; GMRES cycles run only if that misses the tolerance (refinement);
 //   * the factors L (unit lower) and U are solved with the sync-free level-ordered triangular
-//     solve of the config-5 path (shifted.hip), i.e. K^-1 v = U^-1 (L^-1 v);
+//     solve of the config-5 path (sptrsv.hip), i.e. K^-1 v = U^-1 (L^-1 v);
 //   * GMRES(m) with right preconditioning, x0 = 0, classical Gram-Schmidt with one
 //     re-orthogonalisation pass (CGS2: two multi-column dot launches and two updates per step,
 //     deterministic fixed-order reductions), Givens rotations and the small least-squares solve on

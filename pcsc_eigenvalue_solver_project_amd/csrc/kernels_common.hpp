@@ -625,7 +625,7 @@ __device__ __forceinline__ void shift_prologue(PowerCtl* ctl, const part4* rank_
     __syncthreads();
 }
 
-// Multi-solve launches (triangular factors; shifted.hip, sptrsv_chunk_role_kernel): launch 0 is an
+// Multi-solve launches (triangular factors; sptrsv.hip, sptrsv_chunk_role_kernel): launch 0 is an
 // ordinary single solve (reference iteration 0), launch t >= 1 runs reference iterations
 // k_j = 1 + K (t - 1) + j, j = 0..K-1, together.  Solve 0 is w_0 = (A - sigma I)^{-1} x
 // with x = v / ||v|| (v the previous launch's last solution), exactly as a single launch does;

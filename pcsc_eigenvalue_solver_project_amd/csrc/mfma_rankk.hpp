@@ -1,5 +1,5 @@
 // Rank-K update on the fp64 matrix cores (gfx950, v_mfma_f64_16x16x4_f64), shared by the blocked
-// Hessenberg reduction (hessenberg.hip) and the blocked LU of the shifted solve (shifted.hip).
+// Hessenberg reduction (hessenberg.hip) and the blocked LU of the shifted solve (dense_lu.hip).
 //
 //   C(m x nn) += alpha * L(m x K) * R^T          R stored nn x K      (kRT = false)
 //   C(m x nn) += alpha * L(m x K) * Rt           Rt stored K x nn     (kRT = true)

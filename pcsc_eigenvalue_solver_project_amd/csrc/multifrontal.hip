@@ -853,7 +853,7 @@ __global__ __launch_bounds__(256) void mf_bwd_flow_kernel(const MfFront* fr, con
 }
 
 // ---- large fronts: one workgroup per 64-row block, sync-free (the dense path's blocked TRSV,
-// shifted.hip dense_trsv_kernel, on a front).  Pivot block k of a front publishes its solved 64
+// dense_lu.hip dense_trsv_kernel, on a front).  Pivot block k of a front publishes its solved 64
 // values with write-through stores and raises flag[flag0 + k] to the solve's epoch; a row block
 // waits for the flags of the blocks it multiplies.  Blocks a row block waits for have lower
 // workgroup indices (forward: ascending pivot blocks, then the struct rows; backward: descending),

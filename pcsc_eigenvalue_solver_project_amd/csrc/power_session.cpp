@@ -192,8 +192,8 @@ static int launch_iteration(eigsol_power* s) {
         return csr_power_launch(s->csr, s->nbuf, s->buf[0], s->buf[1], s->ctl, s->rank_part, s->ctx->nranks,
                                 s->my_part, s->blk_part, s->trace, s->parity, s->grid, &s->peer->args);
     if (s->shift)
-        return shift_iter_launch(s->shift, s->buf[0], s->buf[1], s->ctl, s->rank_part, s->my_part,
-                                 s->trace, s->parity, s->launches == 0);
+        return shift_iter_launch(s->shift, ShiftIter{s->buf[0], s->buf[1], s->ctl, s->rank_part, s->my_part, s->trace, s->parity},
+                                 s->launches == 0);
     if (s->csr && s->dist && s->split) {
         // launch t writes y_t into buf[t & 1]: the first half's rows go out while the second half computes
         for (int part = 0; part < 2; ++part) {

@@ -1,8 +1,11 @@
-// The shifted-solve factor (ShiftFactor) and what its two translation units share: shifted.hip (solve
-// kernels, launch paths, dense LU, general-sparse dispatch) and tri_factor.hip (analysis and layout of
-// the level-ordered triangular factor).  Private to those two files; other modules see shifted.hpp.
+// The shifted-solve factor (ShiftFactor): one sub-struct per factor kind, each owning its buffers and its launch
+// state, and what the family's translation units share.  sptrsv.hip: the level-ordered triangular solve (TriFactor);
+// tri_factor.hip: that factor's analysis and layout; dense_lu.hip: the dense partial-pivot LU (DenseFactor);
+// shifted.hip: the factor's lifetime, the general-sparse dispatch and the GMRES family's iteration (GmresState).
+// Private to those files; other modules see shifted.hpp.
 #pragma once
 
+#include <type_traits>
 #include <vector>
 
 #include "band_lu.hpp"
@@ -18,24 +21,17 @@ constexpr int kMaxMulti = 4;      // solves per multi-solve launch (one head wav
 
 constexpr size_t kPinBytes = 256;   // ShiftFactor::hpin
 
-struct ShiftFactor {
-    eigsol_ctx* ctx = nullptr;
-    int dtype = EIGSOL_F64;
-    int64_t n = 0;
-    int kind = 0;                 // 0 triangular CSR, 1 dense LU, 2 ILU(0)-preconditioned GMRES, 3 band LU
-    GmresSolver* gm = nullptr;    // kind 2 (gmres.hip)
-    bool lag_prev = false;        // kind 2 iteration: the previous launch's solve check is still to be read
-    double lag_bdiv = 0.0;        // ... and that solve's divisor (||y_{t-1}||)
-    void* promo = nullptr;        // kind 2 in single precision: [2][n] double-precision right-hand side and
-                                  // solution of the GMRES family's solve (its factors are built in double)
-    BandFactor* band = nullptr;   // kind 3 (band_lu.hip)
-    void* hpin = nullptr;         // pinned host scratch for per-solve readbacks (pageable copies sleep ~1 ms)
-    eigsol_csr* src = nullptr;    // kind 2: A, retained for the densified-LU fallback
-    int fell_back = 0;            // kind 1 reached through the GMRES fallback
-    double sig_re = 0.0, sig_im = 0.0;
-    // triangular: everything indexed by solve position (rows sorted by level, levels padded)
+enum class FactorKind { Tri, Dense, Gmres, Band };
+
+template <class T>
+static void free_null(T*& p) {
+    if (p) hipFree(p);
+    p = nullptr;
+}
+
+// level-ordered triangular CSR: everything indexed by solve position (rows sorted by level, levels padded)
+struct TriFactor {
     int upper = 1;
-    int64_t nnz_total = 0;        // nonzeros of A (diagonal included), for roofline accounting
     int64_t nnz_off = 0;
     int32_t* order = nullptr;     // head position -> row (-1: level padding)
     void* z[2] = {nullptr, nullptr};   // solve values polled by readers; sentinel = not yet solved
@@ -88,22 +84,99 @@ struct ShiftFactor {
     int32_t* err = nullptr;
     void* wave_part = nullptr;    // part4 per wave
     int32_t epoch = 0;
-    int grid = 0;
-    // dense
+    int grid = 0;                 // tail grid: one residency round (cooperative launch)
+
+    void release() {
+        free_null(order), free_null(z[0]), free_null(z[1]);
+        free_null(hval), free_null(hcol), free_null(hpiv), free_null(passes);
+        free_null(wval), free_null(wcol), free_null(wrp), free_null(wdst);
+        free_null(smeta), free_null(trow), free_null(tpiv), free_null(tcol), free_null(tval);
+        free_null(porder), free_null(pptr), free_null(pcol), free_null(pval), free_null(ppiv);
+        for (void*& p : aux) free_null(p);
+        for (auto& zj : zm) free_null(zj[0]), free_null(zj[1]);
+        free_null(kpart), free_null(kblk), free_null(work), free_null(err), free_null(wave_part);
+    }
+};
+
+// dense partial-pivot LU (Matrix::Dense, densified sparse matrices, the GMRES family's fallback)
+struct DenseFactor {
     void* lu = nullptr;           // column-major n x n, L (unit) below, U on and above the diagonal
     int32_t* perm = nullptr;      // P b: b_perm[i] = b[perm[i]]
     int32_t* zero_pivot = nullptr;
     size_t lds_bytes = 0;
-    // dense, multi-CU substitution (large n): epoch flags per block row, forward results
-    int dense_multi = 0;
+    // multi-CU substitution (large n): epoch flags per block row, forward results
+    int multi = 0;
+    int nblk = 0;                 // block rows of 64
     int32_t* flag_f = nullptr;
     int32_t* flag_b = nullptr;
     void* zf = nullptr;
     void* tinv = nullptr;         // [nblk][2] inverted diagonal blocks inv(L_kk), inv(U_kk), 64 x 64 column-major
     void* tmul = nullptr;         // [nblk][2] premultiplied next-to-diagonal tiles (dense_tmul_kernel)
-    int dense_v = 2;              // substitution kernel: 2 = dense_trsv2_kernel, 1 = dense_trsv_kernel (ill-conditioned
+    int version = 2;              // substitution kernel: 2 = dense_trsv2_kernel, 1 = dense_trsv_kernel (ill-conditioned
                                   // diagonal blocks, or EIGSOL_DENSE_TRSV=1; see dense_lu_factor)
+    int32_t epoch = 0;
+    int grid = 0;                 // persistent block-row workgroups, all resident (cooperative launch)
+    uint32_t* work = nullptr;
+    int32_t* err = nullptr;
+    void* wave_part = nullptr;    // part4 per workgroup
+
+    void release() {
+        free_null(lu), free_null(perm), free_null(zero_pivot), free_null(flag_f), free_null(flag_b);
+        free_null(zf), free_null(tinv), free_null(tmul), free_null(work), free_null(err), free_null(wave_part);
+    }
 };
+
+// the GMRES family (exact / multifrontal LU, ILU(0) + GMRES; gmres.hip) and its host-driven iteration
+struct GmresState {
+    GmresSolver* gm = nullptr;
+    bool lag_prev = false;        // the previous launch's solve check is still to be read
+    double lag_bdiv = 0.0;        // ... and that solve's divisor (||y_{t-1}||)
+    void* promo = nullptr;        // single precision: [2][n] double-precision right-hand side and solution of
+                                  // the family's solve (its factors are built in double)
+    eigsol_csr* src = nullptr;    // A, retained for the densified-LU fallback
+    int red_grid = 0;             // blocks of the partials reduction
+    uint32_t* work = nullptr;
+    void* wave_part = nullptr;
+
+    void release() {
+        if (gm) gmres_free(gm);
+        if (src) csr_release(src);
+        gm = nullptr, src = nullptr;
+        free_null(promo), free_null(work), free_null(wave_part);
+    }
+};
+
+struct ShiftFactor {
+    eigsol_ctx* ctx = nullptr;
+    int dtype = EIGSOL_F64;
+    int64_t n = 0;
+    double sig_re = 0.0, sig_im = 0.0;
+    int64_t nnz_total = 0;        // nonzeros of A (diagonal included), for roofline accounting
+    FactorKind kind = FactorKind::Tri;
+    int fell_back = 0;            // Dense reached through the GMRES fallback
+    void* hpin = nullptr;         // pinned host scratch for per-solve readbacks (pageable copies sleep ~1 ms)
+    TriFactor tri;
+    DenseFactor dense;
+    GmresState gmres;
+    BandFactor* band = nullptr;   // band_lu.hip
+};
+
+// the launch fields every solve kernel's argument struct shares (TriArgs, DenseSolveArgs, DenseTriArgs)
+template <class Args>
+static void fill_iter(Args& a, const ShiftFactor* f, const void* b, void* y, const ShiftIter& it) {
+    using S = std::remove_pointer_t<decltype(a.buf0)>;
+    a.n = f->n;
+    a.b_plain = static_cast<const S*>(b);
+    a.y_plain = static_cast<S*>(y);
+    a.buf0 = static_cast<S*>(it.buf0);
+    a.buf1 = static_cast<S*>(it.buf1);
+    a.ctl = it.ctl;
+    a.rank_part = static_cast<const dev::part4*>(it.rank_part);
+    a.my_part = static_cast<dev::part4*>(it.my_part);
+    a.trace = static_cast<S*>(it.trace);
+    a.sig_re = f->sig_re;
+    a.sig_im = f->sig_im;
+}
 
 namespace dev {
 
@@ -156,7 +229,21 @@ template <class S> static bool h_zero(S a) {
 
 // shifted.hip
 ShiftFactor* shift_factor_new(eigsol_ctx* ctx, int dtype, int64_t n, double sre, double sim, int64_t nnz);
+
+// sptrsv.hip.  Each __global__ template of the family is defined, and its address taken, in one file only
+// (cooperative launches, attributes and occupancy queries must name the instantiation that is launched).
 int tri_launch_setup(ShiftFactor* f);
+int tri_launch(ShiftFactor* f, bool iter, const void* b, void* y, const ShiftIter& it, bool first);
+// the GMRES family's iteration: the stop decision of launch it.parity, and the norm / Rayleigh partials of y
+int iter_decide_launch(ShiftFactor* f, const ShiftIter& it);
+int iter_part_launch(ShiftFactor* f, const ShiftIter& it);
+
+// dense_lu.hip
+int dense_limits(int dtype, int64_t n, const char* who);
+// factor a copy of the column-major device matrix a, or the densified A, shifted by f's sigma, into d
+int dense_from_matrix(const ShiftFactor* f, const void* a, DenseFactor& d);
+int dense_from_csr(const ShiftFactor* f, const eigsol_csr* A, DenseFactor& d);
+int dense_launch(ShiftFactor* f, bool iter, const void* b, void* y, const ShiftIter& it);
 
 // tri_factor.hip
 // a CSR matrix held in three device arrays that stay their owner's

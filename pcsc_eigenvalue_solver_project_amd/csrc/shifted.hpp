@@ -1,4 +1,4 @@
-// Shifted solves (shifted.hip, tri_factor.hip): the interface the other modules use.
+// Shifted solves (shifted.hip, sptrsv.hip, tri_factor.hip, dense_lu.hip): the interface the other modules use.
 #pragma once
 
 #include <vector>
@@ -8,6 +8,15 @@
 namespace eigsol {
 
 struct ShiftFactor;   // shift_factor.hpp
+
+// one launch of the iteration: the power loop's buffers and control block (same parity convention)
+struct ShiftIter {
+    void *buf0, *buf1;
+    PowerCtl* ctl;
+    const void* rank_part;
+    void *my_part, *trace;
+    int parity;
+};
 
 // factor of A - sigma I (sigma: one scalar of the matrix's dtype)
 int shift_factor_csr(eigsol_csr* A, const void* sigma, ShiftFactor** out);
@@ -24,8 +33,7 @@ int shift_grid(const ShiftFactor* f);
 void* shift_aux(const ShiftFactor* f, int j);
 int shift_error(ShiftFactor* f);
 void shift_lag_reset(ShiftFactor* f);
-int shift_iter_launch(ShiftFactor* f, void* buf0, void* buf1, PowerCtl* ctl, const void* rank_part,
-                      void* my_part, void* trace, int parity, int first);
+int shift_iter_launch(ShiftFactor* f, const ShiftIter& it, int first);
 int shift_solve_launch(ShiftFactor* f, const void* b_dev, void* y_dev);
 void shift_info(const ShiftFactor* f, double* bytes, int32_t* variant, int32_t* tiles);
 

@@ -3,7 +3,7 @@
 // A triangular A (config 5), the L and U of the general-sparse family (gmres.hip) and the shift-invert
 // mode of the Krylov-Schur solver all solve with the same factor: pivots d_i - sigma, rows ordered by
 // dependency level, a head of narrow levels solved from LDS and a tail spread over the GPU (the solve
-// kernels and their launch paths: shifted.hip).  The factor is built on the device (factor_tri_device)
+// kernels and their launch paths: sptrsv.hip).  The factor is built on the device (factor_tri_device)
 // or on the host (factor_tri_host); both take every head / tail decision and every layout knob from
 // one plan (tri_plan), so the device build gives the host build's layout bit for bit.  tri_build is
 // the one way in.
@@ -309,15 +309,15 @@ template <class S>
 static TriPlan tri_plan(ShiftFactor* f, const std::vector<int64_t>& lstart, const std::vector<int64_t>& lcount,
                         const std::vector<int32_t>& lmaxlen, const std::vector<int32_t>* plen) {
     TriPlan pl;
-    if (const char* e = std::getenv("EIGSOL_TRSV_HEAD")) f->wave_head = std::strcmp(e, "block") ? 1 : 0;
-    f->hlevels = head_levels<S>(lstart, lcount, lmaxlen, f->nlevels, f->wave_head != 0);
+    if (const char* e = std::getenv("EIGSOL_TRSV_HEAD")) f->tri.wave_head = std::strcmp(e, "block") ? 1 : 0;
+    f->tri.hlevels = head_levels<S>(lstart, lcount, lmaxlen, f->tri.nlevels, f->tri.wave_head != 0);
     if (const char* e = std::getenv("EIGSOL_TRSV_POLL_FAST"))
-        f->poll_fast = (f->poll_fast & ~0xffff) | std::min(0xffff, std::max(0, std::atoi(e)));
+        f->tri.poll_fast = (f->tri.poll_fast & ~0xffff) | std::min(0xffff, std::max(0, std::atoi(e)));
     if (const char* e = std::getenv("EIGSOL_TRSV_POLL_SLOW"))
-        f->poll_fast = (f->poll_fast & 0xffff) | (std::min(7, std::max(0, std::atoi(e))) << 16);
-    if (const char* e = std::getenv("EIGSOL_TRSV_POLL_MODE")) f->poll_mode = std::atoi(e);
-    f->hpos = (int32_t)lstart[f->hlevels];
-    for (int32_t l = 0; l < f->hlevels; ++l) {
+        f->tri.poll_fast = (f->tri.poll_fast & 0xffff) | (std::min(7, std::max(0, std::atoi(e))) << 16);
+    if (const char* e = std::getenv("EIGSOL_TRSV_POLL_MODE")) f->tri.poll_mode = std::atoi(e);
+    f->tri.hpos = (int32_t)lstart[f->tri.hlevels];
+    for (int32_t l = 0; l < f->tri.hlevels; ++l) {
         const int32_t p0 = (int32_t)lstart[l], p1 = (int32_t)(lstart[l] + lcount[l]);
         for (int32_t p = p0; p < p1; p += dev::kHeadRows) {
             const int32_t e = std::min(p1, p + dev::kHeadRows);
@@ -329,34 +329,34 @@ static TriPlan tri_plan(ShiftFactor* f, const std::vector<int64_t>& lstart, cons
     while (!pl.passes.empty() && pl.passes.size() % dev::kHeadDepth) pl.passes.push_back(make_int2(0, 0));   // empty
     pl.nwreal = (int32_t)pl.wpass.size();
     while (pl.wpass.size() % dev::kWHeadDepth) pl.wpass.push_back(make_int2(0, 0));
-    f->nwpass = (int32_t)pl.wpass.size();
+    f->tri.nwpass = (int32_t)pl.wpass.size();
     // tail variant: slices (row per lane) for few, very wide levels; chunks (16 lanes per row)
     // otherwise.  EIGSOL_TRSV_TAIL=slice|chunk overrides.
     {
         // slices when most tail rows sit in levels of >= 64k rows (a wave's 64 rows then rarely
         // wait); measured: one 1M-row level 74 vs 195 us, config 5 (widest level 21k) 1.3 vs 0.86 ms
         int64_t trows = 0, wide = 0;
-        for (int32_t l = f->hlevels; l < f->nlevels; ++l) {
+        for (int32_t l = f->tri.hlevels; l < f->tri.nlevels; ++l) {
             trows += lcount[l];
             if (lcount[l] >= 65536) wide += lcount[l];
         }
-        f->tail_chunks = (trows > 0 && 2 * wide < trows) ? 1 : 0;
-        if (const char* e = std::getenv("EIGSOL_TRSV_TAIL")) f->tail_chunks = std::strcmp(e, "slice") ? 1 : 0;
+        f->tri.tail_chunks = (trows > 0 && 2 * wide < trows) ? 1 : 0;
+        if (const char* e = std::getenv("EIGSOL_TRSV_TAIL")) f->tri.tail_chunks = std::strcmp(e, "slice") ? 1 : 0;
     }
-    if (f->tail_chunks) {
-        f->chunk0 = f->hpos / dev::kWaveRows;
-        f->nchunks = f->npos / dev::kWaveRows;
+    if (f->tri.tail_chunks) {
+        f->tri.chunk0 = f->tri.hpos / dev::kWaveRows;
+        f->tri.nchunks = f->tri.npos / dev::kWaveRows;
         int32_t longest = 0;
-        for (int32_t l = f->hlevels; l < f->nlevels; ++l) longest = std::max(longest, lmaxlen[l]);
+        for (int32_t l = f->tri.hlevels; l < f->tri.nlevels; ++l) longest = std::max(longest, lmaxlen[l]);
         // rows past 16 entries: the second entry of every lane is polled with the first
         // (EIGSOL_TRSV_TWO=0|1 overrides; round 4, the exact LU's U of config 5 made general)
-        f->chunk_two = longest > dev::kRowLanes ? 1 : 0;
-        if (const char* e = std::getenv("EIGSOL_TRSV_TWO")) f->chunk_two = std::atoi(e) != 0;
+        f->tri.chunk_two = longest > dev::kRowLanes ? 1 : 0;
+        if (const char* e = std::getenv("EIGSOL_TRSV_TWO")) f->tri.chunk_two = std::atoi(e) != 0;
     }
     // tail slices (see sptrsv_slice_kernel): 64 rows of one level each; B = the smallest of
     // 4 / 8 / 16 that holds the entries of at least 95 % of the slices (longer slices loop)
     if (plen)
-        for (int32_t l = f->tail_chunks ? f->nlevels : f->hlevels; l < f->nlevels; ++l)
+        for (int32_t l = f->tri.tail_chunks ? f->tri.nlevels : f->tri.hlevels; l < f->tri.nlevels; ++l)
             for (int64_t p = lstart[l]; p < lstart[l] + lcount[l]; p += 64) {
                 const int32_t c = (int32_t)std::min<int64_t>(64, lstart[l] + lcount[l] - p);
                 int32_t K = 0;
@@ -365,14 +365,14 @@ static TriPlan tri_plan(ShiftFactor* f, const std::vector<int64_t>& lstart, cons
                 pl.scount.push_back(c);
                 pl.slen.push_back(K);
             }
-    f->nslices = (int32_t)pl.slen.size();
+    f->tri.nslices = (int32_t)pl.slen.size();
     {
         std::vector<int32_t> sorted(pl.slen);
         std::sort(sorted.begin(), sorted.end());
         const int32_t q95 = sorted.empty() ? 0 : sorted[(size_t)(0.95 * (double)(sorted.size() - 1))];
-        f->slice_b = q95 <= 4 ? 4 : (q95 <= 8 ? 8 : 16);
+        f->tri.slice_b = q95 <= 4 ? 4 : (q95 <= 8 ? 8 : 16);
     }
-    pl.device_buildable = f->tail_chunks && (f->hpos == 0 || f->wave_head);
+    pl.device_buildable = f->tri.tail_chunks && (f->tri.hpos == 0 || f->tri.wave_head);
     return pl;
 }
 
@@ -388,18 +388,18 @@ template <class S>
 static int tri_state_alloc(ShiftFactor* f) {
     hipStream_t st = f->ctx->stream;
     const int64_t n = f->n;
-    EIGSOL_TRY(dev_upload(st, &f->z[0], nullptr, (n + 1) * sizeof(S)));
-    EIGSOL_TRY(dev_upload(st, &f->z[1], nullptr, (n + 1) * sizeof(S)));
-    EIGSOL_TRY(dev_upload(st, (void**)&f->work, nullptr, 64));
-    EIGSOL_TRY(dev_upload(st, (void**)&f->err, nullptr, 64));
-    EIGSOL_TRY(dev_upload(st, &f->wave_part, nullptr, (size_t)f->grid * dev::kWaves * sizeof(dev::part4)));
+    EIGSOL_TRY(dev_upload(st, &f->tri.z[0], nullptr, (n + 1) * sizeof(S)));
+    EIGSOL_TRY(dev_upload(st, &f->tri.z[1], nullptr, (n + 1) * sizeof(S)));
+    EIGSOL_TRY(dev_upload(st, (void**)&f->tri.work, nullptr, 64));
+    EIGSOL_TRY(dev_upload(st, (void**)&f->tri.err, nullptr, 64));
+    EIGSOL_TRY(dev_upload(st, &f->tri.wave_part, nullptr, (size_t)f->tri.grid * dev::kWaves * sizeof(dev::part4)));
     const uint32_t sent = (uint32_t)(dev::kSent & 0xffffffffu);
-    for (void* zb : f->z) {
+    for (void* zb : f->tri.z) {
         hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(zb), (int)sent, n * sizeof(S) / 4, st);
         hipMemsetAsync(static_cast<char*>(zb) + n * sizeof(S), 0, sizeof(S), st);
     }
-    hipMemsetAsync(f->work, 0, 64, st);
-    hipMemsetAsync(f->err, 0, 64, st);
+    hipMemsetAsync(f->tri.work, 0, 64, st);
+    hipMemsetAsync(f->tri.err, 0, 64, st);
     if (hipStreamSynchronize(st) != hipSuccess) return fail(EIGSOL_E_HIP, "factor upload");
     return EIGSOL_OK;
 }
@@ -409,15 +409,15 @@ static int tri_state_alloc(ShiftFactor* f) {
 template <class S>
 static int tri_empty_slice0(ShiftFactor* f) {
     hipStream_t st = f->ctx->stream;
-    const int32_t Bs = f->slice_b;
+    const int32_t Bs = f->tri.slice_b;
     const std::vector<int2> smeta(1, make_int2(0, Bs));
     const std::vector<int32_t> trow(64, -1), tcol((size_t)64 * Bs, (int32_t)f->n);   // padding: the zero slot z[n]
     const std::vector<S> tpiv(64, make_sigma<S>(1.0, 0.0)), tval((size_t)64 * Bs, s_zero<S>());
-    EIGSOL_TRY(dev_upload(st, (void**)&f->smeta, smeta.data(), smeta.size() * sizeof(int2)));
-    EIGSOL_TRY(dev_upload(st, (void**)&f->trow, trow.data(), trow.size() * 4));
-    EIGSOL_TRY(dev_upload(st, &f->tpiv, tpiv.data(), tpiv.size() * sizeof(S)));
-    EIGSOL_TRY(dev_upload(st, (void**)&f->tcol, tcol.data(), tcol.size() * 4));
-    EIGSOL_TRY(dev_upload(st, &f->tval, tval.data(), tval.size() * sizeof(S)));
+    EIGSOL_TRY(dev_upload(st, (void**)&f->tri.smeta, smeta.data(), smeta.size() * sizeof(int2)));
+    EIGSOL_TRY(dev_upload(st, (void**)&f->tri.trow, trow.data(), trow.size() * 4));
+    EIGSOL_TRY(dev_upload(st, &f->tri.tpiv, tpiv.data(), tpiv.size() * sizeof(S)));
+    EIGSOL_TRY(dev_upload(st, (void**)&f->tri.tcol, tcol.data(), tcol.size() * 4));
+    EIGSOL_TRY(dev_upload(st, &f->tri.tval, tval.data(), tval.size() * sizeof(S)));
     EIGSOL_HIP(hipStreamSynchronize(st));   // the small host vectors above go out of scope
     return EIGSOL_OK;
 }
@@ -427,7 +427,7 @@ static int tri_empty_slice0(ShiftFactor* f) {
 template <class S>
 static void tri_dump(const ShiftFactor* f) {
     const char* pre = std::getenv("EIGSOL_TRSV_DUMP");
-    if (!pre || f->kind != 0) return;
+    if (!pre || f->kind != FactorKind::Tri) return;
     hipStreamSynchronize(f->ctx->stream);
     auto put = [&](const char* name, const void* d, size_t bytes) {
         std::vector<unsigned char> h(bytes);
@@ -438,43 +438,43 @@ static void tri_dump(const ShiftFactor* f) {
             std::fclose(fp);
         }
     };
-    const int32_t meta[21] = {f->nlevels, f->npos, f->hpos, f->hlevels, f->nwpass, f->chunk0, f->nchunks, f->chunk_two,
-                              f->tail_chunks, f->grid, f->multi, (int32_t)f->nnz_off,
-                              f->npass, f->nslices, f->slice_b, f->wave_head, f->poll_fast, f->poll_mode, f->grid_multi,
-                              f->hconc, f->red_grid};
+    const int32_t meta[21] = {f->tri.nlevels, f->tri.npos, f->tri.hpos, f->tri.hlevels, f->tri.nwpass, f->tri.chunk0, f->tri.nchunks, f->tri.chunk_two,
+                              f->tri.tail_chunks, f->tri.grid, f->tri.multi, (int32_t)f->tri.nnz_off,
+                              f->tri.npass, f->tri.nslices, f->tri.slice_b, f->tri.wave_head, f->tri.poll_fast, f->tri.poll_mode, f->tri.grid_multi,
+                              f->tri.hconc, f->tri.red_grid};
     if (FILE* fp = std::fopen((std::string(pre) + "_meta.bin").c_str(), "wb")) {
         std::fwrite(meta, sizeof(meta), 1, fp);
         std::fclose(fp);
     }
     // the position-indexed chunk arrays exist with the chunk tail only
-    const size_t cpos = f->tail_chunks ? (size_t)f->npos : 0, cnnz = f->tail_chunks ? (size_t)f->nnz_off : 0;
-    put("porder", f->porder, cpos * 4);
-    put("pptr", f->pptr, f->tail_chunks ? (cpos + 1) * 4 : 0);
-    put("pcol", f->pcol, cnnz * 4);
-    put("pval", f->pval, cnnz * sizeof(S));
-    put("ppiv", f->ppiv, cpos * sizeof(S));
-    put("order", f->order, (size_t)f->hpos * 4);
-    put("wval", f->wval, (size_t)f->nwpass * 256 * sizeof(S));
-    put("wcol", f->wcol, (size_t)f->nwpass * 256 * 4);
-    put("wrp", f->wrp, (size_t)f->nwpass * 16 * sizeof(S));
-    put("wdst", f->wdst, (size_t)f->nwpass * 16 * 4);
+    const size_t cpos = f->tri.tail_chunks ? (size_t)f->tri.npos : 0, cnnz = f->tri.tail_chunks ? (size_t)f->tri.nnz_off : 0;
+    put("porder", f->tri.porder, cpos * 4);
+    put("pptr", f->tri.pptr, f->tri.tail_chunks ? (cpos + 1) * 4 : 0);
+    put("pcol", f->tri.pcol, cnnz * 4);
+    put("pval", f->tri.pval, cnnz * sizeof(S));
+    put("ppiv", f->tri.ppiv, cpos * sizeof(S));
+    put("order", f->tri.order, (size_t)f->tri.hpos * 4);
+    put("wval", f->tri.wval, (size_t)f->tri.nwpass * 256 * sizeof(S));
+    put("wcol", f->tri.wcol, (size_t)f->tri.nwpass * 256 * 4);
+    put("wrp", f->tri.wrp, (size_t)f->tri.nwpass * 16 * sizeof(S));
+    put("wdst", f->tri.wdst, (size_t)f->tri.nwpass * 16 * 4);
     // slice tail (slice 0 always exists; the entry streams end with one more slice_b-deep slice, the
     // prefetch past the last slice) and one-workgroup head
-    const size_t ns = (size_t)std::max(1, f->nslices);
+    const size_t ns = (size_t)std::max(1, f->tri.nslices);
     int2 last = make_int2(0, 0);
-    if (f->nslices > 0 &&
-        hipMemcpy(&last, f->smeta + (f->nslices - 1), sizeof(int2), hipMemcpyDeviceToHost) != hipSuccess)
+    if (f->tri.nslices > 0 &&
+        hipMemcpy(&last, f->tri.smeta + (f->tri.nslices - 1), sizeof(int2), hipMemcpyDeviceToHost) != hipSuccess)
         return;
-    const size_t tent = (f->nslices > 0 ? (size_t)last.x + 64 * (size_t)last.y : 0) + 64 * (size_t)f->slice_b;
-    put("smeta", f->smeta, ns * sizeof(int2));
-    put("trow", f->trow, ns * 64 * 4);
-    put("tpiv", f->tpiv, ns * 64 * sizeof(S));
-    put("tcol", f->tcol, tent * 4);
-    put("tval", f->tval, tent * sizeof(S));
-    put("hcol", f->hcol, (size_t)f->npass * dev::kHeadThreads * 4);
-    put("hval", f->hval, (size_t)f->npass * dev::kHeadThreads * sizeof(S));
-    put("hpiv", f->hpiv, (size_t)f->npass * dev::kHeadRows * sizeof(S));
-    put("passes", f->passes, (size_t)f->npass * sizeof(int2));
+    const size_t tent = (f->tri.nslices > 0 ? (size_t)last.x + 64 * (size_t)last.y : 0) + 64 * (size_t)f->tri.slice_b;
+    put("smeta", f->tri.smeta, ns * sizeof(int2));
+    put("trow", f->tri.trow, ns * 64 * 4);
+    put("tpiv", f->tri.tpiv, ns * 64 * sizeof(S));
+    put("tcol", f->tri.tcol, tent * 4);
+    put("tval", f->tri.tval, tent * sizeof(S));
+    put("hcol", f->tri.hcol, (size_t)f->tri.npass * dev::kHeadThreads * 4);
+    put("hval", f->tri.hval, (size_t)f->tri.npass * dev::kHeadThreads * sizeof(S));
+    put("hpiv", f->tri.hpiv, (size_t)f->tri.npass * dev::kHeadRows * sizeof(S));
+    put("passes", f->tri.passes, (size_t)f->tri.npass * sizeof(int2));
 }
 
 // Triangular CSR (host arrays, columns ascending per row) -> level-ordered factor of A - sigma I.
@@ -485,7 +485,7 @@ static int factor_tri_host(eigsol_ctx* ctx, int dtype, int64_t n, const int32_t*
     const int64_t nnz = rp[n];
     ShiftFactor* f = shift_factor_new(ctx, dtype, n, sre, sim, nnz);
     int rc = EIGSOL_OK;
-    f->upper = up ? 1 : 0;
+    f->tri.upper = up ? 1 : 0;
     // split diagonal / off-diagonal; pivots d_i - sigma (missing diagonal: 0 - sigma)
     const S sig = make_sigma<S>(sre, sim);
     std::vector<int32_t> orp(n + 1, 0), oci;
@@ -509,32 +509,32 @@ static int factor_tri_host(eigsol_ctx* ctx, int dtype, int64_t n, const int32_t*
         }
         orp[i + 1] = (int32_t)oci.size();
     }
-    f->nnz_off = (int64_t)oci.size();
+    f->tri.nnz_off = (int64_t)oci.size();
     std::vector<int32_t> order;
     std::vector<int64_t> lstart, lcount;
-    level_order(orp, oci, n, up, order, f->nlevels, lstart, lcount);
-    f->npos = (int32_t)order.size();
-    std::vector<int32_t> plen(f->npos, 0);         // off-diagonal entries per position
-    std::vector<int32_t> lmaxlen(f->nlevels, 0);   // longest row (off-diagonal entries) per level
-    for (int32_t l = 0; l < f->nlevels; ++l)
+    level_order(orp, oci, n, up, order, f->tri.nlevels, lstart, lcount);
+    f->tri.npos = (int32_t)order.size();
+    std::vector<int32_t> plen(f->tri.npos, 0);         // off-diagonal entries per position
+    std::vector<int32_t> lmaxlen(f->tri.nlevels, 0);   // longest row (off-diagonal entries) per level
+    for (int32_t l = 0; l < f->tri.nlevels; ++l)
         for (int64_t p = lstart[l]; p < lstart[l] + lcount[l]; ++p) {
             plen[p] = orp[order[p] + 1] - orp[order[p]];
             lmaxlen[l] = std::max(lmaxlen[l], plen[p]);
         }
     const TriPlan pl = tri_plan<S>(f, lstart, lcount, lmaxlen, &plen);
     const std::vector<int2>& passes = pl.passes;
-    f->npass = (int32_t)passes.size();
+    f->tri.npass = (int32_t)passes.size();
     std::vector<int32_t> rowpos;
-    if (f->hpos > 0) {
+    if (f->tri.hpos > 0) {
         rowpos.assign(n, -1);
-        for (int32_t p = 0; p < f->hpos; ++p)
+        for (int32_t p = 0; p < f->tri.hpos; ++p)
             if (order[p] >= 0) rowpos[order[p]] = p;
     }
     // head, pass-major (see sptrsv_head_kernel): columns are LDS positions of earlier head rows
-    const size_t hslots = (size_t)f->npass * dev::kHeadThreads;
-    std::vector<int32_t> hcol(hslots, f->hpos);   // padding: the zero slot
-    std::vector<S> hval(hslots, s_zero<S>()), hpiv((size_t)f->npass * dev::kHeadRows, make_sigma<S>(1.0, 0.0));
-    for (int32_t q = 0; q < f->npass; ++q) {
+    const size_t hslots = (size_t)f->tri.npass * dev::kHeadThreads;
+    std::vector<int32_t> hcol(hslots, f->tri.hpos);   // padding: the zero slot
+    std::vector<S> hval(hslots, s_zero<S>()), hpiv((size_t)f->tri.npass * dev::kHeadRows, make_sigma<S>(1.0, 0.0));
+    for (int32_t q = 0; q < f->tri.npass; ++q) {
         const int32_t p0 = passes[q].x, p1 = passes[q].y & ~dev::kPassBarrier;
         for (int32_t p = p0; p < p1; ++p) {
             const size_t g = (size_t)q * dev::kHeadRows + (p - p0);
@@ -562,10 +562,10 @@ static int factor_tri_host(eigsol_ctx* ctx, int dtype, int64_t n, const int32_t*
                 return r;
             }
         };
-        wval.assign((size_t)f->nwpass * 256, s_zero<S>());
-        wcol.assign((size_t)f->nwpass * 256, f->hpos);
-        wrp.assign((size_t)f->nwpass * dev::kWHeadRows, make_sigma<S>(1.0, 0.0));
-        wdst.assign((size_t)f->nwpass * dev::kWHeadRows, -1);
+        wval.assign((size_t)f->tri.nwpass * 256, s_zero<S>());
+        wcol.assign((size_t)f->tri.nwpass * 256, f->tri.hpos);
+        wrp.assign((size_t)f->tri.nwpass * dev::kWHeadRows, make_sigma<S>(1.0, 0.0));
+        wdst.assign((size_t)f->tri.nwpass * dev::kWHeadRows, -1);
         for (int32_t q = 0; q < pl.nwreal; ++q) {
             const int32_t p = pl.wpass[q].x;
             for (int32_t u = 0; u < pl.wpass[q].y; ++u) {
@@ -583,13 +583,13 @@ static int factor_tri_host(eigsol_ctx* ctx, int dtype, int64_t n, const int32_t*
     }
     std::vector<int32_t> porder, pptr, pcol;
     std::vector<S> pval, ppiv;
-    if (f->tail_chunks) {   // position-indexed copies: no dependent metadata loads in the kernel
+    if (f->tri.tail_chunks) {   // position-indexed copies: no dependent metadata loads in the kernel
         porder = order;
-        pptr.assign((size_t)f->npos + 1, 0);
-        ppiv.assign((size_t)f->npos, make_sigma<S>(1.0, 0.0));
+        pptr.assign((size_t)f->tri.npos + 1, 0);
+        ppiv.assign((size_t)f->tri.npos, make_sigma<S>(1.0, 0.0));
         pcol.reserve(oci.size());
         pval.reserve(oci.size());
-        for (int32_t p = 0; p < f->npos; ++p) {
+        for (int32_t p = 0; p < f->tri.npos; ++p) {
             const int32_t i = order[p];
             if (i >= 0) {
                 for (int32_t e = orp[i]; e < orp[i + 1]; ++e) {
@@ -604,13 +604,13 @@ static int factor_tri_host(eigsol_ctx* ctx, int dtype, int64_t n, const int32_t*
     // the tail slices of the plan (none: nothing here, tri_empty_slice0 below)
     const std::vector<int32_t>&slen = pl.slen, &scount = pl.scount;
     const std::vector<int64_t>& sfirst = pl.sfirst;
-    const int32_t Bs = f->slice_b;
-    std::vector<int2> smeta(f->nslices, make_int2(0, Bs));
-    std::vector<int32_t> trow((size_t)f->nslices * 64, -1);
-    std::vector<S> tpiv((size_t)f->nslices * 64, make_sigma<S>(1.0, 0.0));
+    const int32_t Bs = f->tri.slice_b;
+    std::vector<int2> smeta(f->tri.nslices, make_int2(0, Bs));
+    std::vector<int32_t> trow((size_t)f->tri.nslices * 64, -1);
+    std::vector<S> tpiv((size_t)f->tri.nslices * 64, make_sigma<S>(1.0, 0.0));
     int64_t tent = 0;
-    for (int32_t sl = 0; sl < f->nslices; ++sl) tent += 64 * (int64_t)std::max(slen[sl], Bs);
-    if (f->nslices > 0) tent += 64 * (int64_t)Bs;   // the prefetch of "slice ns" reads slice 0's range: keep it in bounds
+    for (int32_t sl = 0; sl < f->tri.nslices; ++sl) tent += 64 * (int64_t)std::max(slen[sl], Bs);
+    if (f->tri.nslices > 0) tent += 64 * (int64_t)Bs;   // the prefetch of "slice ns" reads slice 0's range: keep it in bounds
     if (tent * (int64_t)sizeof(S) >= (int64_t)1 << 32) {
         shift_factor_free(f);
         return fail(EIGSOL_E_UNSUPPORTED, "triangular solve: factor streams exceed 4 GiB");
@@ -619,7 +619,7 @@ static int factor_tri_host(eigsol_ctx* ctx, int dtype, int64_t n, const int32_t*
     std::vector<S> tval((size_t)tent, s_zero<S>());
     {
         int64_t off = 0;
-        for (int32_t sl = 0; sl < f->nslices; ++sl) {
+        for (int32_t sl = 0; sl < f->tri.nslices; ++sl) {
             const int32_t Kp = std::max(slen[sl], Bs);
             smeta[sl] = make_int2((int32_t)off, Kp);
             for (int32_t u = 0; u < scount[sl]; ++u) {
@@ -638,31 +638,31 @@ static int factor_tri_host(eigsol_ctx* ctx, int dtype, int64_t n, const int32_t*
     std::vector<S>().swap(ov);
     auto up_ = [&](void** dst, const void* src, size_t bytes) -> int { return dev_upload(st, dst, src, bytes); };
     if (rc == EIGSOL_OK) rc = tri_launch_setup(f);
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->order, order.data(), (size_t)f->hpos * 4);
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->hcol, hcol.data(), hcol.size() * 4);
-    if (rc == EIGSOL_OK) rc = up_(&f->hval, hval.data(), hval.size() * sizeof(S));
-    if (rc == EIGSOL_OK) rc = up_(&f->hpiv, hpiv.data(), hpiv.size() * sizeof(S));
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->passes, passes.data(), passes.size() * sizeof(int2));
-    if (rc == EIGSOL_OK) rc = up_(&f->wval, wval.data(), wval.size() * sizeof(S));
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->wcol, wcol.data(), wcol.size() * 4);
-    if (rc == EIGSOL_OK) rc = up_(&f->wrp, wrp.data(), wrp.size() * sizeof(S));
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->wdst, wdst.data(), wdst.size() * 4);
-    if (rc == EIGSOL_OK && f->nslices == 0) rc = tri_empty_slice0<S>(f);
-    if (f->nslices > 0) {
-        if (rc == EIGSOL_OK) rc = up_((void**)&f->smeta, smeta.data(), smeta.size() * sizeof(int2));
-        if (rc == EIGSOL_OK) rc = up_((void**)&f->trow, trow.data(), trow.size() * 4);
-        if (rc == EIGSOL_OK) rc = up_(&f->tpiv, tpiv.data(), tpiv.size() * sizeof(S));
-        if (rc == EIGSOL_OK) rc = up_((void**)&f->tcol, tcol.data(), tcol.size() * 4);
-        if (rc == EIGSOL_OK) rc = up_(&f->tval, tval.data(), tval.size() * sizeof(S));
+    if (rc == EIGSOL_OK) rc = up_((void**)&f->tri.order, order.data(), (size_t)f->tri.hpos * 4);
+    if (rc == EIGSOL_OK) rc = up_((void**)&f->tri.hcol, hcol.data(), hcol.size() * 4);
+    if (rc == EIGSOL_OK) rc = up_(&f->tri.hval, hval.data(), hval.size() * sizeof(S));
+    if (rc == EIGSOL_OK) rc = up_(&f->tri.hpiv, hpiv.data(), hpiv.size() * sizeof(S));
+    if (rc == EIGSOL_OK) rc = up_((void**)&f->tri.passes, passes.data(), passes.size() * sizeof(int2));
+    if (rc == EIGSOL_OK) rc = up_(&f->tri.wval, wval.data(), wval.size() * sizeof(S));
+    if (rc == EIGSOL_OK) rc = up_((void**)&f->tri.wcol, wcol.data(), wcol.size() * 4);
+    if (rc == EIGSOL_OK) rc = up_(&f->tri.wrp, wrp.data(), wrp.size() * sizeof(S));
+    if (rc == EIGSOL_OK) rc = up_((void**)&f->tri.wdst, wdst.data(), wdst.size() * 4);
+    if (rc == EIGSOL_OK && f->tri.nslices == 0) rc = tri_empty_slice0<S>(f);
+    if (f->tri.nslices > 0) {
+        if (rc == EIGSOL_OK) rc = up_((void**)&f->tri.smeta, smeta.data(), smeta.size() * sizeof(int2));
+        if (rc == EIGSOL_OK) rc = up_((void**)&f->tri.trow, trow.data(), trow.size() * 4);
+        if (rc == EIGSOL_OK) rc = up_(&f->tri.tpiv, tpiv.data(), tpiv.size() * sizeof(S));
+        if (rc == EIGSOL_OK) rc = up_((void**)&f->tri.tcol, tcol.data(), tcol.size() * 4);
+        if (rc == EIGSOL_OK) rc = up_(&f->tri.tval, tval.data(), tval.size() * sizeof(S));
     }
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->porder, porder.data(), porder.size() * 4);
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->pptr, pptr.data(), pptr.size() * 4);
-    if (rc == EIGSOL_OK) rc = up_((void**)&f->pcol, pcol.data(), pcol.size() * 4);
-    if (rc == EIGSOL_OK) rc = up_(&f->pval, pval.data(), pval.size() * sizeof(S));
-    if (rc == EIGSOL_OK) rc = up_(&f->ppiv, ppiv.data(), ppiv.size() * sizeof(S));
+    if (rc == EIGSOL_OK) rc = up_((void**)&f->tri.porder, porder.data(), porder.size() * 4);
+    if (rc == EIGSOL_OK) rc = up_((void**)&f->tri.pptr, pptr.data(), pptr.size() * 4);
+    if (rc == EIGSOL_OK) rc = up_((void**)&f->tri.pcol, pcol.data(), pcol.size() * 4);
+    if (rc == EIGSOL_OK) rc = up_(&f->tri.pval, pval.data(), pval.size() * sizeof(S));
+    if (rc == EIGSOL_OK) rc = up_(&f->tri.ppiv, ppiv.data(), ppiv.size() * sizeof(S));
     if (rc == EIGSOL_OK) rc = tri_state_alloc<S>(f);
     if (rc != EIGSOL_OK) { shift_factor_free(f); return rc; }
-    f->kind = 0;
+    f->kind = FactorKind::Tri;
     tri_dump<S>(f);
     *out = f;
     return EIGSOL_OK;
@@ -759,9 +759,9 @@ static int factor_tri_device(const TriCsrView& A, double sre, double sim, ShiftF
     std::vector<int64_t> lstart(nlevels + 1, 0), lcount(hcnt.begin(), hcnt.end());
     for (int32_t l = 0; l < nlevels; ++l) lstart[l + 1] = lstart[l] + ((lcount[l] + W - 1) / W) * W;
     f = shift_factor_new(ctx, A.dtype, n, sre, sim, nnz);
-    f->upper = up ? 1 : 0;
-    f->nlevels = nlevels;
-    f->npos = (int32_t)lstart[nlevels];
+    f->tri.upper = up ? 1 : 0;
+    f->tri.nlevels = nlevels;
+    f->tri.npos = (int32_t)lstart[nlevels];
     const TriPlan pl = tri_plan<S>(f, lstart, lcount, hmax, nullptr);
     if (!pl.device_buildable) {
         declined = true;
@@ -773,7 +773,7 @@ static int factor_tri_device(const TriCsrView& A, double sre, double sim, ShiftF
     int32_t *lev_s = nullptr, *rows_s = nullptr, *ustart = nullptr, *pstart = nullptr, *plen = nullptr;
     if ((rc = dalloc((void**)&lev_s, n * 4)) || (rc = dalloc((void**)&rows_s, n * 4)) ||
         (rc = dalloc((void**)&ustart, (size_t)nlevels * 4)) || (rc = dalloc((void**)&pstart, (size_t)nlevels * 4)) ||
-        (rc = dalloc((void**)&plen, ((size_t)f->npos + 1) * 4)))
+        (rc = dalloc((void**)&plen, ((size_t)f->tri.npos + 1) * 4)))
         return rc;
     if (tri_sort_rows_by_level(st, lev, lev_s, rows_s, n, bits) != hipSuccess)
         return fail(EIGSOL_E_HIP, "triangular analysis: level sort");
@@ -788,64 +788,64 @@ static int factor_tri_device(const TriCsrView& A, double sre, double sim, ShiftF
     }
     EIGSOL_HIP(hipMemcpyAsync(ustart, hu.data(), (size_t)nlevels * 4, hipMemcpyHostToDevice, st));
     EIGSOL_HIP(hipMemcpyAsync(pstart, hp.data(), (size_t)nlevels * 4, hipMemcpyHostToDevice, st));
-    const int64_t npos = f->npos;
-    EIGSOL_TRY(dev_upload(st, (void**)&f->porder, nullptr, (size_t)npos * 4));
-    EIGSOL_HIP(hipMemsetAsync(f->porder, 0xFF, (size_t)npos * 4, st));
-    hipLaunchKernelGGL(dev::tri_order_kernel, dim3(gb), dim3(256), 0, st, lev_s, rows_s, n, ustart, pstart, f->porder);
-    EIGSOL_TRY(dev_upload(st, (void**)&f->order, nullptr, (size_t)f->hpos * 4));
-    if (f->hpos > 0)
-        EIGSOL_HIP(hipMemcpyAsync(f->order, f->porder, (size_t)f->hpos * 4, hipMemcpyDeviceToDevice, st));
+    const int64_t npos = f->tri.npos;
+    EIGSOL_TRY(dev_upload(st, (void**)&f->tri.porder, nullptr, (size_t)npos * 4));
+    EIGSOL_HIP(hipMemsetAsync(f->tri.porder, 0xFF, (size_t)npos * 4, st));
+    hipLaunchKernelGGL(dev::tri_order_kernel, dim3(gb), dim3(256), 0, st, lev_s, rows_s, n, ustart, pstart, f->tri.porder);
+    EIGSOL_TRY(dev_upload(st, (void**)&f->tri.order, nullptr, (size_t)f->tri.hpos * 4));
+    if (f->tri.hpos > 0)
+        EIGSOL_HIP(hipMemcpyAsync(f->tri.order, f->tri.porder, (size_t)f->tri.hpos * 4, hipMemcpyDeviceToDevice, st));
     // position-indexed chunk CSR: pivots, row pointers (scan of the off-diagonal counts), entries
     const S one = make_sigma<S>(1.0, 0.0);
-    EIGSOL_TRY(dev_upload(st, &f->ppiv, nullptr, (size_t)npos * sizeof(S)));
-    EIGSOL_TRY(dev_upload(st, (void**)&f->pptr, nullptr, ((size_t)npos + 1) * 4));
-    hipLaunchKernelGGL((dev::tri_poslen_kernel<S>), dim3((unsigned)((npos + 256) / 256)), dim3(256), 0, st, f->porder,
-                       npos, offlen, pv, one, plen, static_cast<S*>(f->ppiv));
-    if (tri_exclusive_scan(st, plen, f->pptr, npos) != hipSuccess)
+    EIGSOL_TRY(dev_upload(st, &f->tri.ppiv, nullptr, (size_t)npos * sizeof(S)));
+    EIGSOL_TRY(dev_upload(st, (void**)&f->tri.pptr, nullptr, ((size_t)npos + 1) * 4));
+    hipLaunchKernelGGL((dev::tri_poslen_kernel<S>), dim3((unsigned)((npos + 256) / 256)), dim3(256), 0, st, f->tri.porder,
+                       npos, offlen, pv, one, plen, static_cast<S*>(f->tri.ppiv));
+    if (tri_exclusive_scan(st, plen, f->tri.pptr, npos) != hipSuccess)
         return fail(EIGSOL_E_HIP, "triangular analysis: row pointer scan");
-    EIGSOL_HIP(hipMemcpyAsync(hostw + 5, f->pptr + npos, 4, hipMemcpyDeviceToHost, st));
+    EIGSOL_HIP(hipMemcpyAsync(hostw + 5, f->tri.pptr + npos, 4, hipMemcpyDeviceToHost, st));
     EIGSOL_HIP(hipStreamSynchronize(st));
-    f->nnz_off = hostw[5];
-    EIGSOL_TRY(dev_upload(st, (void**)&f->pcol, nullptr, (size_t)f->nnz_off * 4));
-    EIGSOL_TRY(dev_upload(st, &f->pval, nullptr, (size_t)f->nnz_off * sizeof(S)));
+    f->tri.nnz_off = hostw[5];
+    EIGSOL_TRY(dev_upload(st, (void**)&f->tri.pcol, nullptr, (size_t)f->tri.nnz_off * 4));
+    EIGSOL_TRY(dev_upload(st, &f->tri.pval, nullptr, (size_t)f->tri.nnz_off * sizeof(S)));
     hipLaunchKernelGGL((dev::tri_gather_kernel<S>), dim3((unsigned)((npos * dev::kRowLanes + 255) / 256)), dim3(256), 0,
-                       st, f->porder, npos, f->pptr, A.rowptr, A.col, val, offlen, f->pcol, static_cast<S*>(f->pval));
+                       st, f->tri.porder, npos, f->tri.pptr, A.rowptr, A.col, val, offlen, f->tri.pcol, static_cast<S*>(f->tri.pval));
     // one-wave head: the plan's passes (the padding passes keep the arrays' pre-fill)
     const std::vector<int2>& ptab = pl.wpass;
     const int32_t nreal = pl.nwreal;
-    const size_t wslots = (size_t)f->nwpass * 256, wrows = (size_t)f->nwpass * dev::kWHeadRows;
-    EIGSOL_TRY(dev_upload(st, &f->wval, nullptr, wslots * sizeof(S)));
-    EIGSOL_TRY(dev_upload(st, (void**)&f->wcol, nullptr, wslots * 4));
-    EIGSOL_TRY(dev_upload(st, &f->wrp, nullptr, wrows * sizeof(S)));
-    EIGSOL_TRY(dev_upload(st, (void**)&f->wdst, nullptr, wrows * 4));
-    if (f->nwpass > 0) {
+    const size_t wslots = (size_t)f->tri.nwpass * 256, wrows = (size_t)f->tri.nwpass * dev::kWHeadRows;
+    EIGSOL_TRY(dev_upload(st, &f->tri.wval, nullptr, wslots * sizeof(S)));
+    EIGSOL_TRY(dev_upload(st, (void**)&f->tri.wcol, nullptr, wslots * 4));
+    EIGSOL_TRY(dev_upload(st, &f->tri.wrp, nullptr, wrows * sizeof(S)));
+    EIGSOL_TRY(dev_upload(st, (void**)&f->tri.wdst, nullptr, wrows * 4));
+    if (f->tri.nwpass > 0) {
         int32_t* rowpos = nullptr;
         int2* dtab = nullptr;
         if ((rc = dalloc((void**)&rowpos, n * 4)) || (rc = dalloc((void**)&dtab, (size_t)nreal * sizeof(int2))))
             return rc;
         EIGSOL_HIP(hipMemcpyAsync(dtab, ptab.data(), (size_t)nreal * sizeof(int2), hipMemcpyHostToDevice, st));
         EIGSOL_HIP(hipMemsetAsync(rowpos, 0xFF, n * 4, st));
-        EIGSOL_HIP(hipMemsetAsync(f->wval, 0, wslots * sizeof(S), st));
-        EIGSOL_HIP(hipMemsetAsync(f->wdst, 0xFF, wrows * 4, st));
-        hipLaunchKernelGGL((dev::fill_kernel<int32_t>), dim3(256), dim3(256), 0, st, f->wcol, (int64_t)wslots, f->hpos);
-        hipLaunchKernelGGL((dev::fill_kernel<S>), dim3(64), dim3(256), 0, st, static_cast<S*>(f->wrp), (int64_t)wrows, one);
-        hipLaunchKernelGGL(dev::tri_rowpos_kernel, dim3((unsigned)((f->hpos + 255) / 256)), dim3(256), 0, st, f->porder,
-                           f->hpos, rowpos);
+        EIGSOL_HIP(hipMemsetAsync(f->tri.wval, 0, wslots * sizeof(S), st));
+        EIGSOL_HIP(hipMemsetAsync(f->tri.wdst, 0xFF, wrows * 4, st));
+        hipLaunchKernelGGL((dev::fill_kernel<int32_t>), dim3(256), dim3(256), 0, st, f->tri.wcol, (int64_t)wslots, f->tri.hpos);
+        hipLaunchKernelGGL((dev::fill_kernel<S>), dim3(64), dim3(256), 0, st, static_cast<S*>(f->tri.wrp), (int64_t)wrows, one);
+        hipLaunchKernelGGL(dev::tri_rowpos_kernel, dim3((unsigned)((f->tri.hpos + 255) / 256)), dim3(256), 0, st, f->tri.porder,
+                           f->tri.hpos, rowpos);
         hipLaunchKernelGGL((dev::tri_whead_kernel<S>), dim3((unsigned)((nreal * dev::kWHeadRows + 255) / 256)), dim3(256),
-                           0, st, dtab, nreal, f->porder, A.rowptr, A.col, val, pv, rowpos, static_cast<S*>(f->wval),
-                           f->wcol, static_cast<S*>(f->wrp), f->wdst);
+                           0, st, dtab, nreal, f->tri.porder, A.rowptr, A.col, val, pv, rowpos, static_cast<S*>(f->tri.wval),
+                           f->tri.wcol, static_cast<S*>(f->tri.wrp), f->tri.wdst);
     }
     // the one-workgroup head's tables stay empty (npass = 0: that head is not built here)
-    EIGSOL_TRY(dev_upload(st, (void**)&f->hcol, nullptr, 0));
-    EIGSOL_TRY(dev_upload(st, &f->hval, nullptr, 0));
-    EIGSOL_TRY(dev_upload(st, &f->hpiv, nullptr, 0));
-    EIGSOL_TRY(dev_upload(st, (void**)&f->passes, nullptr, 0));
+    EIGSOL_TRY(dev_upload(st, (void**)&f->tri.hcol, nullptr, 0));
+    EIGSOL_TRY(dev_upload(st, &f->tri.hval, nullptr, 0));
+    EIGSOL_TRY(dev_upload(st, &f->tri.hpiv, nullptr, 0));
+    EIGSOL_TRY(dev_upload(st, (void**)&f->tri.passes, nullptr, 0));
     // slice tail: none (nslices = 0)
     EIGSOL_TRY(tri_empty_slice0<S>(f));
     if (hipGetLastError() != hipSuccess) return fail(EIGSOL_E_HIP, "triangular analysis: launch");
     if ((rc = tri_launch_setup(f)) != EIGSOL_OK) return rc;
     if ((rc = tri_state_alloc<S>(f)) != EIGSOL_OK) return rc;
-    f->kind = 0;
+    f->kind = FactorKind::Tri;
     tri_dump<S>(f);
     *out = own.release();
     return EIGSOL_OK;

@@ -1,4 +1,4 @@
-// Device primitives of the triangular factor's on-device analysis (shifted.hip, factor_tri_device):
+// Device primitives of the triangular factor's on-device analysis (tri_factor.hip, factor_tri_device):
 // a stable sort of the rows by dependency level and an exclusive scan of the per-position entry
 // counts.  rocPRIM's device-wide radix sort and decoupled-lookback scan, kept in their own
 // translation unit (heavy templates).

@@ -1,7 +1,7 @@
 """GPU: the dense partial-pivot LU and its substitutions at the orders the kernels branch on, with exact
 interchange bookkeeping, and on factors whose diagonal blocks are ill conditioned.
 
-Code under test (csrc/shifted.hip): lu_pivot_kernel, lu_update_kernel, lu_laswp_kernel, lu_trsm_kernel,
+Code under test (csrc/dense_lu.hip): lu_pivot_kernel, lu_update_kernel, lu_laswp_kernel, lu_trsm_kernel,
 rankk_update (panels of RankKMax<S> = 64 real / 32 complex columns), dense_lu_solve_kernel (n <= 64),
 dense_tinv_kernel, dense_tcond_kernel, dense_tmul_kernel, dense_trsv2_kernel (n > 64, 64-row blocks
 applied as products with the blocks' explicit inverses) and dense_trsv_kernel (64-step triangles; the

@@ -191,8 +191,22 @@ def test_gmres_stagnation_falls_back_to_dense_lu(ctx, convdiff, env):
     n = fx["n"]
     A = E.CsrMatrix(ctx, rp, ci, v, (n, n))
     sigma = complex(*fx["sigma"])
-    r = E.shifted_inverse_power_method(A, E.ShiftedSolverOptions(fx["max_iter"], fx["tol"], sigma),
-                                       S.start_vector(n, np.complex128))
+    # the iteration of shifted_inverse_power_method, through a session whose factor can be asked what it is:
+    # ILU(0) + GMRES before the first step, the densified LU (moved into the same factor) after the run
+    sess = E.ShiftedSession(A, sigma)
+    assert sess.kernel_info()["variant"] == 7, sess.kernel_info()
+    sess.begin(E.ShiftedSolverOptions(fx["max_iter"], fx["tol"], sigma), S.start_vector(n, np.complex128))
+    issued, chunk, done = 0, 4, False
+    while not done:
+        assert issued < fx["max_iter"] + 6, "the iteration did not terminate"
+        k = min(chunk, max(1, fx["max_iter"] + 2 - issued))
+        sess.step(k)
+        issued += k
+        done = sess.query()[0]
+        chunk = min(2 * chunk, 64)
+    r = sess.finish()
+    assert sess.kernel_info()["variant"] in (4, 20), sess.kernel_info()
+    sess.close()
     _check_fixture(r, fx, xref)
     A.close()
 

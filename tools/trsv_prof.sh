@@ -1,6 +1,6 @@
 #!/bin/bash
 # Config-5 triangular solve: kernel trace + PMC passes (ordinary launches: EIGSOL_TRSV_NO_COOP=1,
-# see shifted.hip).  Run from the repo root on the GPU box.
+# see sptrsv.hip).  Run from the repo root on the GPU box.
 set -o pipefail
 R=$(pwd); OUT=$R/gpurun_out/trsv; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
