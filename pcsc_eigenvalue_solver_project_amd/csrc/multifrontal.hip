@@ -35,39 +35,27 @@
 // The pivoting is restricted to each front, so the factor is the exact LU of a row-permuted M
 // only when no pivot is tiny; gmres.hip therefore treats it like the no-pivot exact LU: the solve
 // is checked by its true residual and refined by GMRES cycles on the same factor when it misses.
+// This file is the device half: the kernels, the factor's device state and the solve's launches.
+// The host half (ordering, symbolic structure, launch and solve tables) is multifrontal_plan.cpp,
+// plain C++ behind multifrontal_plan.hpp.
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cmath>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <numeric>
-#include <thread>
+#include <string>
 #include <vector>
 
 #include "kernels_common.hpp"
 #include "mfma_rankk.hpp"
-#include "multifrontal.hpp"
+#include "multifrontal_plan.hpp"
 
 namespace eigsol {
 
-namespace dev {
+static_assert(kMfPanelF64 == dev::RankKMax<double>::value && kMfPanelC128 == dev::RankKMax<cplx>::value,
+              "multifrontal_plan.hpp: the plan's panel widths are the rank-k tile's");
 
-struct MfFront {
-    int64_t off;    // front at F + off: d x d, column-major, leading dimension d
-    int64_t uoff;   // forward contribution vector (ms entries) at u + uoff
-    int64_t sof;    // struct indices (new numbering) at sidx + sof; their positions in the parent's list at cmap + sof
-    int32_t d, ns, c0, ms;
-    int32_t ch0, ch1;   // children chl[ch0 .. ch1) (fixed order)
-    int32_t parent;
-    int32_t flag0;  // large fronts: first of the front's pivot-block flags; -1: solved by one workgroup
-    int64_t zoff;   // large fronts: assembled right-hand side (d entries) at z + zoff
-    int64_t goff;   // inverse form (ns <= 64, d <= 256; -1: none) at F + goff: [inv(L11); L21 inv(L11)]
-                    // (d x ns, ld d), then [inv(U11), -inv(U11) U12] (ns x d, ld ns)
-};
+namespace dev {
 
 __device__ __forceinline__ double mf_rl(double v, int src) {
     const long long b = __double_as_longlong(v);
@@ -428,21 +416,6 @@ __global__ __launch_bounds__(256) void mf_fwd_kernel(const MfFront* fr, const in
     mf_fwd_front<S>(fr[list[blockIdx.x]], lds_raw, fr, chl, F, cmap, pinv, w, u);
 }
 
-// a whole small subtree per workgroup: its fronts are the postorder range [lo, hi], children
-// before parents, so the forward pass walks it upward without any other workgroup (the children's
-// contributions were written by this workgroup, visible after its barrier)
-template <class S>
-__global__ __launch_bounds__(256) void mf_fwd_sub_kernel(const MfFront* fr, const int32_t* ranges, const int32_t* chl,
-                                                         const S* F, const int32_t* cmap, const int32_t* pinv, S* w,
-                                                         S* u) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int32_t lo = ranges[2 * blockIdx.x], hi = ranges[2 * blockIdx.x + 1];
-    for (int32_t s = lo; s <= hi; ++s) {
-        mf_fwd_front<S>(fr[s], lds_raw, fr, chl, F, cmap, pinv, w, u);
-        __syncthreads();
-    }
-}
-
 // backward: fronts list[0 .. gridDim.x) of one height (their ancestors solved).  LDS: t (ns), xs (ms).
 template <class S>
 __device__ __forceinline__ void mf_bwd_front(const MfFront f, unsigned char* lds_raw, const S* F,
@@ -536,320 +509,6 @@ __global__ __launch_bounds__(256) void mf_bwd_kernel(const MfFront* fr, const in
                                                      const int32_t* sidx, const S* w, S* x) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     mf_bwd_front<S>(fr[list[blockIdx.x]], lds_raw, F, sidx, w, x);
-}
-
-// the backward pass over a small subtree: parents before children (the subtree root's ancestors
-// were solved by earlier launches)
-template <class S>
-__global__ __launch_bounds__(256) void mf_bwd_sub_kernel(const MfFront* fr, const int32_t* ranges, const S* F,
-                                                         const int32_t* sidx, const S* w, S* x) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int32_t lo = ranges[2 * blockIdx.x], hi = ranges[2 * blockIdx.x + 1];
-    for (int32_t s = hi; s >= lo; --s) {
-        mf_bwd_front<S>(fr[s], lds_raw, F, sidx, w, x);
-        __syncthreads();
-    }
-}
-
-// ---- small fronts (ns <= 64 pivots, ms <= 192 struct rows): one wave per front, four fronts per
-// workgroup, no workgroup barrier (each wave's LDS slice is its own), so a CU keeps up to 32
-// fronts in flight.  Same arithmetic order as mf_fwd_kernel / mf_bwd_kernel's single block.
-constexpr int kWaveNs = 64, kWaveMs = 192;
-
-__device__ __forceinline__ void mf_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-template <class S>
-__global__ __launch_bounds__(256) void mf_fwd_wave_kernel(const MfFront* fr, const int32_t* list, int32_t cnt,
-                                                          const int32_t* chl, const S* F, const int32_t* cmap,
-                                                          const int32_t* pinv, S* w, S* u) {
-    __shared__ S sh[4][2 * kWaveNs + kWaveMs];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int t = blockIdx.x * 4 + wv;
-    if (t >= cnt) return;
-    const MfFront f = fr[list[t]];
-    const int d = f.d, ns = f.ns, ms = f.ms;
-    S* r = sh[wv];
-    S* y = r + kWaveNs;
-    S* acc = y + kWaveNs;
-    if (lane < ns) r[lane] = w[f.c0 + lane];
-    for (int k = lane; k < ms; k += 64) acc[k] = s_zero<S>();
-    mf_wave_sync();
-    for (int k = f.ch0; k < f.ch1; ++k) {
-        const MfFront c = fr[chl[k]];
-        const int32_t* map = cmap + c.sof;
-        const S* uc = u + c.uoff;
-        for (int q = lane; q < c.ms; q += 64) {
-            const int pos = map[q];
-            const S v = uc[q];
-            if (pos < ns) r[pos] = sub(r[pos], v);
-            else acc[pos - ns] = add(acc[pos - ns], v);
-        }
-        mf_wave_sync();
-    }
-    const S* A = F + f.off;
-    S v = lane < ns ? r[pinv[f.c0 + lane]] : s_zero<S>();
-    const int row = min(lane, ns - 1);
-    for (int j0 = 0; j0 < ns; j0 += 16) {
-        S lv[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) lv[q] = A[row + (int64_t)min(j0 + q, ns - 1) * d];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int j = j0 + q;
-            if (j < ns) {
-                const S yj = mf_rl(v, j);
-                if (lane > j) v = sub(v, mul(lv[q], yj));
-            }
-        }
-    }
-    if (lane < ns) {
-        y[lane] = v;
-        w[f.c0 + lane] = v;
-    }
-    mf_wave_sync();
-    for (int i = ns + lane; i < d; i += 64) {
-        S sacc = s_zero<S>();
-        const S* Ai = A + i;
-        for (int j0 = 0; j0 < ns; j0 += 16) {
-            S lv[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) lv[q] = Ai[(int64_t)min(j0 + q, ns - 1) * d];
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-                if (j0 + q < ns) sacc = add(sacc, mul(lv[q], y[j0 + q]));
-        }
-        u[f.uoff + (i - ns)] = add(acc[i - ns], sacc);
-    }
-}
-
-template <class S>
-__global__ __launch_bounds__(256) void mf_bwd_wave_kernel(const MfFront* fr, const int32_t* list, int32_t cnt,
-                                                          const S* F, const int32_t* sidx, const S* w, S* x) {
-    __shared__ S sh[4][kWaveMs];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int t = blockIdx.x * 4 + wv;
-    if (t >= cnt) return;
-    const MfFront f = fr[list[t]];
-    const int d = f.d, ns = f.ns, ms = f.ms;
-    S* xs = sh[wv];
-    for (int q = lane; q < ms; q += 64) xs[q] = x[sidx[f.sof + q]];
-    mf_wave_sync();
-    const S* A = F + f.off;
-    const int row = min(lane, ns - 1);
-    S s = s_zero<S>();
-    {
-        const S* Ak = A + row + (int64_t)ns * d;
-        for (int q0 = 0; q0 < ms; q0 += 16) {
-            S uv[16];
-#pragma unroll
-            for (int e = 0; e < 16; ++e) uv[e] = Ak[(int64_t)min(q0 + e, ms - 1) * d];
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-                if (q0 + e < ms) s = add(s, mul(uv[e], xs[q0 + e]));
-        }
-    }
-    S v = lane < ns ? sub(w[f.c0 + lane], s) : s_zero<S>();
-    for (int j1 = ns; j1 > 0; j1 -= 16) {
-        S uv[16];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) uv[e] = A[row + (int64_t)max(j1 - 1 - e, 0) * d];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int j = j1 - 1 - e;
-            if (j >= 0) {
-                if (lane == j) v = sdiv(v, uv[e]);
-                const S xj = mf_rl(v, j);
-                if (lane < j) v = sub(v, mul(uv[e], xj));
-            }
-        }
-    }
-    if (lane < ns) x[f.c0 + lane] = v;
-}
-
-// ---- the lower heights in one launch each way (dataflow, opt-in EIGSOL_MF_FLOW=1): one workgroup
-// per front in height order (forward ascending, backward descending), waiting for the fronts it
-// reads - the children's contributions (forward) or the parent's solution (backward) - through
-// per-front epoch flags; a front only waits for fronts of lower workgroup index (in-order
-// dispatch), values are handed over write-through and loaded at agent scope.  Same arithmetic, in
-// the same order, as mf_fwd_kernel / mf_bwd_kernel.  Measured and rejected as the default: 2.01 ->
-// 4.5 ms per 1M iteration (waiting workgroups hold the CU slots the producers need, and the
-// acquire polls invalidate L2).  A ticket-ordered persistent variant hung in a way that device
-// printf made disappear; not kept.
-__device__ __forceinline__ void mf_wait_flag(const int32_t* f, int32_t epoch, int32_t* err, int who = -1) {
-    (void)who;
-    int spins = 0;
-    while (__hip_atomic_load(const_cast<int32_t*>(f), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != epoch) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > (1 << 22)) {
-            atomicOr(err, 2);
-            break;
-        }
-    }
-}
-
-template <class S>
-__global__ __launch_bounds__(256) void mf_fwd_flow_kernel(const MfFront* fr, const int32_t* order, int32_t cnt,
-                                                          int32_t* done, int32_t epoch, const int32_t* chl,
-                                                          const S* F, const int32_t* cmap, const int32_t* pinv, S* w,
-                                                          S* u, int32_t* err) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    {
-        const int32_t t = (int32_t)blockIdx.x;
-        if (t >= cnt) return;
-        const int32_t sidx_f = order[t];
-        const MfFront f = fr[sidx_f];
-        const int d = f.d, ns = f.ns, ms = f.ms;
-        S* r = reinterpret_cast<S*>(lds_raw);
-        S* y = r + ns;
-        S* acc = y + ns;
-        for (int k = f.ch0 + tid; k < f.ch1; k += 256) mf_wait_flag(done + chl[k], epoch, err, sidx_f);
-        for (int q = tid; q < ns; q += 256) r[q] = w[f.c0 + q];
-        for (int q = tid; q < ms; q += 256) acc[q] = s_zero<S>();
-        __syncthreads();
-        for (int k = f.ch0; k < f.ch1; ++k) {
-            const MfFront c = fr[chl[k]];
-            const int32_t* map = cmap + c.sof;
-            const S* uc = u + c.uoff;
-            for (int q = tid; q < c.ms; q += 256) {
-                const int pos = map[q];
-                const S v = mf_ld(uc + q);
-                if (pos < ns) r[pos] = sub(r[pos], v);
-                else acc[pos - ns] = add(acc[pos - ns], v);
-            }
-            __syncthreads();
-        }
-        for (int q = tid; q < ns; q += 256) y[q] = r[pinv[f.c0 + q]];
-        __syncthreads();
-        const S* A = F + f.off;
-        for (int jb = 0; jb < ns; jb += 64) {
-            const int bw = min(64, ns - jb);
-            if (wv == 0) {
-                S v = lane < bw ? y[jb + lane] : s_zero<S>();
-                const int row = jb + min(lane, bw - 1);
-                for (int j0 = 0; j0 < bw; j0 += 16) {
-                    S lv[16];
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) lv[q] = A[row + (int64_t)(jb + min(j0 + q, bw - 1)) * d];
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) {
-                        const int j = j0 + q;
-                        if (j < bw) {
-                            const S yj = mf_rl(v, j);
-                            if (lane > j) v = sub(v, mul(lv[q], yj));
-                        }
-                    }
-                }
-                if (lane < bw) y[jb + lane] = v;
-            }
-            __syncthreads();
-            for (int i = jb + bw + tid; i < d; i += 256) {
-                S sacc = s_zero<S>();
-                const S* Ai = A + i + (int64_t)jb * d;
-                for (int j0 = 0; j0 < bw; j0 += 16) {
-                    S lv[16];
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) lv[q] = Ai[(int64_t)min(j0 + q, bw - 1) * d];
-#pragma unroll
-                    for (int q = 0; q < 16; ++q)
-                        if (j0 + q < bw) sacc = add(sacc, mul(lv[q], y[jb + j0 + q]));
-                }
-                if (i < ns) y[i] = sub(y[i], sacc);
-                else acc[i - ns] = add(acc[i - ns], sacc);
-            }
-            __syncthreads();
-        }
-        for (int q = tid; q < ns; q += 256) w[f.c0 + q] = y[q];
-        for (int q = tid; q < ms; q += 256) mf_st(u + f.uoff + q, acc[q]);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        // release: writes the XCD's L2 back, so pollers on other XCDs see the flag and the values
-        // (a relaxed agent-scope store was measured never to reach them)
-        if (tid == 0) __hip_atomic_store(done + sidx_f, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-template <class S>
-__global__ __launch_bounds__(256) void mf_bwd_flow_kernel(const MfFront* fr, const int32_t* order, int32_t cnt,
-                                                          int32_t* done, int32_t epoch, int32_t hflow,
-                                                          const int32_t* height, const S* F, const int32_t* sidx,
-                                                          const S* w, S* x, int32_t* err) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    {
-        const int32_t t = (int32_t)blockIdx.x;
-        if (t >= cnt) return;
-        const int32_t sf = order[t];
-        const MfFront f = fr[sf];
-        const int d = f.d, ns = f.ns, ms = f.ms;
-        S* tv_ = reinterpret_cast<S*>(lds_raw);
-        S* xs = tv_ + ns;
-        if (tid == 0 && f.parent >= 0 && height[f.parent] < hflow) mf_wait_flag(done + f.parent, epoch, err, sf);
-        __syncthreads();
-        for (int q = tid; q < ms; q += 256) xs[q] = mf_ld(x + sidx[f.sof + q]);
-        __syncthreads();
-        const S* A = F + f.off;
-        for (int k = tid; k < ns; k += 256) {
-            S sacc = s_zero<S>();
-            const S* Ak = A + k + (int64_t)ns * d;
-            int q0 = 0;
-            for (; q0 + 8 <= ms; q0 += 8) {
-                S uv[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) uv[e] = Ak[(int64_t)(q0 + e) * d];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) sacc = add(sacc, mul(uv[e], xs[q0 + e]));
-            }
-            for (; q0 < ms; ++q0) sacc = add(sacc, mul(Ak[(int64_t)q0 * d], xs[q0]));
-            tv_[k] = sub(w[f.c0 + k], sacc);
-        }
-        __syncthreads();
-        for (int jb = ((ns - 1) / 64) * 64; jb >= 0; jb -= 64) {
-            const int bw = min(64, ns - jb);
-            if (wv == 0) {
-                S v = lane < bw ? tv_[jb + lane] : s_zero<S>();
-                const int row = jb + min(lane, bw - 1);
-                for (int j1 = bw; j1 > 0; j1 -= 16) {
-                    S uv[16];
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) uv[e] = A[row + (int64_t)(jb + max(j1 - 1 - e, 0)) * d];
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        const int j = j1 - 1 - e;
-                        if (j >= 0) {
-                            if (lane == j) v = sdiv(v, uv[e]);
-                            const S xj = mf_rl(v, j);
-                            if (lane < j) v = sub(v, mul(uv[e], xj));
-                        }
-                    }
-                }
-                if (lane < bw) tv_[jb + lane] = v;
-            }
-            __syncthreads();
-            for (int i = tid; i < jb; i += 256) {
-                S sacc = s_zero<S>();
-                const S* Ai = A + i + (int64_t)jb * d;
-                for (int j0 = 0; j0 < bw; j0 += 16) {
-                    S uv[16];
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) uv[e] = Ai[(int64_t)min(j0 + e, bw - 1) * d];
-#pragma unroll
-                    for (int e = 0; e < 16; ++e)
-                        if (j0 + e < bw) sacc = add(sacc, mul(uv[e], tv_[jb + j0 + e]));
-                }
-                tv_[i] = sub(tv_[i], sacc);
-            }
-            __syncthreads();
-        }
-        for (int k = tid; k < ns; k += 256) mf_st(x + f.c0 + k, tv_[k]);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(done + sf, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
 }
 
 // ---- large fronts: one workgroup per 64-row block, sync-free (the dense path's blocked TRSV,
@@ -1015,72 +674,11 @@ __global__ __launch_bounds__(256) void mf_inv_kernel(const MfFront* fr, const in
 // over the pivot columns on one wave followed by the struct rows (the diagonal blocks of the large
 // fronts are inverted the same way, mf_inv_kernel).
 template <class S>
-__global__ __launch_bounds__(256) void mf_invform_kernel(const MfFront* fr, const int32_t* list, S* F) {
-    __shared__ S T[64 * 65];
-    __shared__ S X[64 * 65];
-    const MfFront f = fr[list[blockIdx.x]];
-    const int tid = threadIdx.x, d = f.d, ns = f.ns;
-    const S* A = F + f.off;
-    S* Gf = F + f.goff;
-    S* Gb = Gf + (int64_t)d * ns;
-    S one;
-    set_re_im(one, 1.0, 0.0);
-    for (int e = tid; e < 64 * 64; e += 256) {
-        const int i = e & 63, j = e >> 6;
-        T[i + j * 65] = (i < ns && j < ns) ? A[i + (int64_t)j * d] : (i == j ? one : s_zero<S>());
-    }
-    __syncthreads();
-    if (tid < 64) {   // inv(L11), column t (unit lower)
-        const int t = tid;
-        for (int i = 0; i < 64; ++i) {
-            S v = i == t ? one : s_zero<S>();
-            for (int j = t; j < i; ++j) v = sub(v, mul(T[i + j * 65], X[j + t * 65]));
-            X[i + t * 65] = i < t ? s_zero<S>() : v;
-        }
-    }
-    __syncthreads();
-    // rows < ns: inv(L11); rows ns .. d: W = L21 inv(L11), W(i, j) = sum_{k >= j} L21(i, k) inv(L11)(k, j)
-    for (int e = tid; e < d * ns; e += 256) {
-        const int i = e % d, j = e / d;
-        S v;
-        if (i < ns) {
-            v = X[i + j * 65];
-        } else {
-            v = s_zero<S>();
-            for (int k = j; k < ns; ++k) v = add(v, mul(A[i + (int64_t)k * d], X[k + j * 65]));
-        }
-        Gf[i + (int64_t)j * d] = v;
-    }
-    __syncthreads();
-    if (tid < 64) {   // inv(U11), column t
-        const int t = tid;
-        for (int i = 63; i >= 0; --i) {
-            S v = i == t ? one : s_zero<S>();
-            for (int j = i + 1; j <= t; ++j) v = sub(v, mul(T[i + j * 65], X[j + t * 65]));
-            X[i + t * 65] = i > t ? s_zero<S>() : sdiv(v, T[i + i * 65]);
-        }
-    }
-    __syncthreads();
-    // columns < ns: inv(U11); columns ns + q: -inv(U11) U12(:, q), U12(k, q) = A(k, ns + q)
-    for (int e = tid; e < ns * d; e += 256) {
-        const int i = e % ns, c = e / ns;
-        S v;
-        if (c < ns) {
-            v = X[i + c * 65];
-        } else {
-            v = s_zero<S>();
-            for (int k = i; k < ns; ++k) v = sub(v, mul(X[i + k * 65], A[k + (int64_t)c * d]));
-        }
-        Gb[i + (int64_t)c * ns] = v;
-    }
-}
-template <class S>
 __global__ __launch_bounds__(256) void mf_invform2_kernel(const MfFront* fr, const int32_t* list, S* F) {
-    // mf_invform_kernel's forms with the same operations in the same order, restructured for latency:
+    // Built for latency (the first kernel, one HBM load per multiply-add, gave bitwise the same forms):
     // inv(L11) (wave 0) and inv(U11) (wave 1) concurrently into one LDS array X (strictly below the
     // diagonal inv(L11), whose unit diagonal is implicit; on and above it inv(U11)), and L21 / U12 read
-    // from HBM once, 64-row / 64-column tiles staged in T (free after the inversions), instead of one
-    // HBM load per multiply-add.
+    // from HBM once, 64-row / 64-column tiles staged in T (free after the inversions).
     __shared__ S T[64 * 65];
     __shared__ S X[64 * 65];
     const MfFront f = fr[list[blockIdx.x]];
@@ -1095,7 +693,7 @@ __global__ __launch_bounds__(256) void mf_invform2_kernel(const MfFront* fr, con
         T[i + j * 65] = (i < ns && j < ns) ? A[i + (int64_t)j * d] : (i == j ? one : s_zero<S>());
     }
     __syncthreads();
-    // XL(k, j) / XU(i, k) as the old kernel's X held them
+    // XL(k, j): inv(L11) with its implicit unit diagonal and the zeros above it
     auto xl = [&](int k, int j) { return k == j ? one : (k < j ? s_zero<S>() : X[k + j * 65]); };
     if (wv == 0) {   // inv(L11), column t (unit lower)
         const int t = lane;
@@ -1503,240 +1101,6 @@ __global__ __launch_bounds__(256) void mf_bwd_big_small_kernel(const MfFront* fr
     }
 }
 
-// ---- large fronts, two pivot blocks per workgroup (EIGSOL_MF_PAIR=1, value flags only; off by
-// default: measured slower, see MfFactor::pair).  A chain of
-// 64-row blocks pays one cross-CU hand-off per block (the producer's write-through store, the
-// consumer's poll: ~2-3 us with the chip busy).  Here a workgroup owns pivot blocks 2u and 2u + 1:
-// it awaits the dependencies the two share once, solves block 2u, and hands its values to block
-// 2u + 1 in LDS, so a front's chain crosses CUs once per pair.  Every row's sum keeps
-// mf_big_fwd_kernel's / mf_big_bwd_kernel's order (the column blocks in the same sequence, the
-// handed-over block last), so the solution is bitwise the same.
-// Reduction of the four waves' partial row sums, then the inverted diagonal block: returns the
-// block's solution in wave 0 (lane = row); part / vsh are the caller's LDS, synchronised here.
-template <class S>
-__device__ __forceinline__ S mf_pair_finish(S acc, S rhs, int rn, const S (&iv)[16], S (&part)[4][64], S* vsh) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    part[wv][lane] = acc;
-    __syncthreads();
-    if (wv == 0) {
-        const S sum = add(add(part[0][lane], part[1][lane]), add(part[2][lane], part[3][lane]));
-        vsh[lane] = lane < rn ? sub(rhs, sum) : s_zero<S>();
-    }
-    __syncthreads();
-    S p = s_zero<S>();
-#pragma unroll
-    for (int t = 0; t < 16; ++t) p = add(p, mul(iv[t], vsh[16 * wv + t]));
-    part[wv][lane] = p;
-    __syncthreads();
-    return add(add(part[0][lane], part[1][lane]), add(part[2][lane], part[3][lane]));
-}
-
-// forward: tab = (front, unit); unit < npair = ceil(nblk / 2) covers pivot blocks 2 unit and
-// 2 unit + 1, the others are struct row blocks (nblk + unit - npair, as mf_big_fwd_kernel)
-template <class S>
-__global__ __launch_bounds__(256) void mf_big_fwd2_kernel(const MfFront* fr, const int32_t* tab, const S* F,
-                                                          const S* Tinv, const S* z, S* w, S* u, int32_t* err, int bo,
-                                                          S* x) {
-    __shared__ S part[4][64];
-    __shared__ S ysh[4][16];
-    __shared__ S vsh[64];
-    __shared__ S ya[64];
-    const int s = tab[2 * blockIdx.x], un = tab[2 * blockIdx.x + 1];
-    const MfFront f = fr[s];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int d = f.d, ns = f.ns;
-    const int nblk = (ns + 63) / 64, npair = (nblk + 1) / 2;
-    const bool piv = un < npair;
-    const int ba = piv ? 2 * un : nblk + (un - npair);   // the (first) row block
-    const bool hasb = piv && ba + 1 < nblk;
-    const int ra0 = piv ? 64 * ba : ns + 64 * (ba - nblk);
-    const int rna = min(64, (piv ? ns : d) - ra0);
-    const int rnb = hasb ? min(64, ns - (ra0 + 64)) : 0;
-    const S* A = F + f.off;
-    const int rowa = ra0 + min(lane, rna - 1);
-    const int rowb = hasb ? ra0 + 64 + min(lane, rnb - 1) : rowa;
-    S iva[16], ivb[16];
-    if (piv) {
-        const S* ti = Tinv + (int64_t)(f.flag0 + ba) * kMfTinv + lane + (16 * wv) * 64;
-#pragma unroll
-        for (int t = 0; t < 16; ++t) iva[t] = ti[t * 64];
-    }
-    if (hasb) {
-        const S* ti = Tinv + (int64_t)(f.flag0 + ba + 1) * kMfTinv + lane + (16 * wv) * 64;
-#pragma unroll
-        for (int t = 0; t < 16; ++t) ivb[t] = ti[t * 64];
-    }
-    const S zra = lane < rna ? z[f.zoff + ra0 + lane] : s_zero<S>();
-    const S zrb = (hasb && lane < rnb) ? z[f.zoff + ra0 + 64 + lane] : s_zero<S>();
-    // block 2u + 1's tile over block 2u's columns: loaded before the chain of waits
-    S th[16];
-    if (hasb) {
-        const int c0 = 64 * ba + 16 * wv;
-#pragma unroll
-        for (int t = 0; t < 16; ++t) th[t] = A[rowb + (int64_t)min(c0 + t, ns - 1) * d];
-    }
-    S acca = s_zero<S>(), accb = s_zero<S>();
-    const int cend = piv ? ba : nblk;
-    for (int c = 0; c < cend; ++c) {
-        const int c0 = 64 * c + 16 * wv;
-        S tva[16], tvb[16];
-#pragma unroll
-        for (int t = 0; t < 16; ++t) tva[t] = A[rowa + (int64_t)min(c0 + t, ns - 1) * d];
-        if (hasb) {
-#pragma unroll
-            for (int t = 0; t < 16; ++t) tvb[t] = A[rowb + (int64_t)min(c0 + t, ns - 1) * d];
-        }
-        if (lane < 16) ysh[wv][lane] = c0 + lane < ns ? mf_poll(w + f.c0 + c0 + lane, err, bo) : s_zero<S>();
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        mf_acc16(acca, tva, ysh[wv], c0, ns);
-        if (hasb) mf_acc16(accb, tvb, ysh[wv], c0, ns);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (!piv) {
-        part[wv][lane] = acca;
-        __syncthreads();
-        const S sum = add(add(part[0][lane], part[1][lane]), add(part[2][lane], part[3][lane]));
-        if (wv == 0 && lane < rna) u[f.uoff + (ra0 - ns) + lane] = add(zra, sum);
-        return;
-    }
-    const S y = mf_pair_finish(acca, zra, rna, iva, part, vsh);
-    if (wv == 0) {
-        // publish (the value is its own flag); x of these rows becomes "unsolved" for the backward pass
-        const S yc = mf_clean(y);
-        if (lane < rna) {
-            mf_st(w + f.c0 + ra0 + lane, yc);
-            mf_st(x + f.c0 + ra0 + lane, mf_sent(y));
-        }
-        ya[lane] = yc;   // what block 2u + 1 would have polled
-    }
-    if (!hasb) return;
-    __syncthreads();
-    mf_acc16(accb, th, ya + 16 * wv, 64 * ba + 16 * wv, ns);
-    const S yb = mf_pair_finish(accb, zrb, rnb, ivb, part, vsh);
-    if (wv == 0 && lane < rnb) {
-        mf_st(w + f.c0 + ra0 + 64 + lane, mf_clean(yb));
-        mf_st(x + f.c0 + ra0 + 64 + lane, mf_sent(yb));
-    }
-}
-
-// backward: tab = (front, unit), units descending; unit u covers pivot blocks 2u + 1 (when it
-// exists, solved first) and 2u
-template <class S>
-__global__ __launch_bounds__(256) void mf_big_bwd2_kernel(const MfFront* fr, const int32_t* tab, const S* F,
-                                                          const S* Tinv, const int32_t* sidx, const S* w, S* x,
-                                                          int32_t* err, int bo) {
-    __shared__ S part[4][64];
-    __shared__ S ysh[4][16];
-    __shared__ S vsh[64];
-    __shared__ S xa[64];
-    extern __shared__ __align__(16) unsigned char xs_raw[];
-    S* xsh = reinterpret_cast<S*>(xs_raw);   // x(struct), ms entries
-    const int s = tab[2 * blockIdx.x], un = tab[2 * blockIdx.x + 1];
-    const MfFront f = fr[s];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int d = f.d, ns = f.ns, ms = f.ms;
-    const int nblk = (ns + 63) / 64;
-    const int bl = 2 * un;                   // the lower block (always present)
-    const bool hash = bl + 1 < nblk;         // the higher block, solved first
-    const int rl0 = 64 * bl, rnl = min(64, ns - rl0);
-    const int rh0 = rl0 + 64, rnh = hash ? min(64, ns - rh0) : 0;
-    const S* A = F + f.off;
-    const int rowl = rl0 + min(lane, rnl - 1);
-    const int rowh = hash ? rh0 + min(lane, rnh - 1) : rowl;
-    S ivl[16], ivh[16];
-    {
-        const S* ti = Tinv + (int64_t)(f.flag0 + bl) * kMfTinv + 4096 + lane + (16 * wv) * 64;
-#pragma unroll
-        for (int t = 0; t < 16; ++t) ivl[t] = ti[t * 64];
-    }
-    if (hash) {
-        const S* ti = Tinv + (int64_t)(f.flag0 + bl + 1) * kMfTinv + 4096 + lane + (16 * wv) * 64;
-#pragma unroll
-        for (int t = 0; t < 16; ++t) ivh[t] = ti[t * 64];
-    }
-    const S wl = lane < rnl ? w[f.c0 + rl0 + lane] : s_zero<S>();
-    const S wh = (hash && lane < rnh) ? w[f.c0 + rh0 + lane] : s_zero<S>();
-    // the lower block's tile over the higher block's columns (used after the higher block is solved)
-    S tl[16];
-    if (hash) {
-        const int c0 = rh0 + 16 * wv;
-#pragma unroll
-        for (int t = 0; t < 16; ++t) tl[t] = A[rowl + (int64_t)min(c0 + t, ns - 1) * d];
-    }
-    S accl = s_zero<S>(), acch = s_zero<S>();
-    // U12 x(struct) for both blocks' rows (x(struct) gathered into LDS once)
-    for (int q = tid; q < ms; q += 256) xsh[q] = x[sidx[f.sof + q]];
-    __syncthreads();
-    {
-        const S* tile_l = A + rowl + (int64_t)ns * d;
-        const S* tile_h = A + rowh + (int64_t)ns * d;
-        int q0 = 16 * wv;
-        for (; q0 + 64 < ms; q0 += 128) {
-            S ta[16], tb[16];
-#pragma unroll
-            for (int t = 0; t < 16; ++t) ta[t] = tile_l[(int64_t)(q0 + t) * d];
-#pragma unroll
-            for (int t = 0; t < 16; ++t) tb[t] = tile_l[(int64_t)min(q0 + 64 + t, ms - 1) * d];
-            mf_acc16(accl, ta, xsh + q0, q0, ms);
-            mf_acc16(accl, tb, xsh + q0 + 64, q0 + 64, ms);
-            if (hash) {
-#pragma unroll
-                for (int t = 0; t < 16; ++t) ta[t] = tile_h[(int64_t)(q0 + t) * d];
-#pragma unroll
-                for (int t = 0; t < 16; ++t) tb[t] = tile_h[(int64_t)min(q0 + 64 + t, ms - 1) * d];
-                mf_acc16(acch, ta, xsh + q0, q0, ms);
-                mf_acc16(acch, tb, xsh + q0 + 64, q0 + 64, ms);
-            }
-        }
-        if (q0 < ms) {
-            S ta[16];
-#pragma unroll
-            for (int t = 0; t < 16; ++t) ta[t] = tile_l[(int64_t)min(q0 + t, ms - 1) * d];
-            mf_acc16(accl, ta, xsh + q0, q0, ms);
-            if (hash) {
-#pragma unroll
-                for (int t = 0; t < 16; ++t) ta[t] = tile_h[(int64_t)min(q0 + t, ms - 1) * d];
-                mf_acc16(acch, ta, xsh + q0, q0, ms);
-            }
-        }
-    }
-    // later pivot blocks (the last first) as their values arrive
-    const int clow = hash ? bl + 1 : bl;
-    for (int c = nblk - 1; c > clow; --c) {
-        const int c0 = 64 * c + 16 * wv;
-        S tvl[16], tvh[16];
-#pragma unroll
-        for (int t = 0; t < 16; ++t) tvl[t] = A[rowl + (int64_t)min(c0 + t, ns - 1) * d];
-        if (hash) {
-#pragma unroll
-            for (int t = 0; t < 16; ++t) tvh[t] = A[rowh + (int64_t)min(c0 + t, ns - 1) * d];
-        }
-        if (lane < 16) ysh[wv][lane] = c0 + lane < ns ? mf_poll(x + f.c0 + c0 + lane, err, bo) : s_zero<S>();
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        mf_acc16(accl, tvl, ysh[wv], c0, ns);
-        if (hash) mf_acc16(acch, tvh, ysh[wv], c0, ns);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (hash) {
-        const S xh = mf_pair_finish(acch, wh, rnh, ivh, part, vsh);
-        if (wv == 0) {
-            const S xc = mf_clean(xh);
-            if (lane < rnh) mf_st(x + f.c0 + rh0 + lane, xc);
-            xa[lane] = xc;
-        }
-        __syncthreads();
-        mf_acc16(accl, tl, xa + 16 * wv, rh0 + 16 * wv, ns);
-    }
-    const S xl = mf_pair_finish(accl, wl, rnl, ivl, part, vsh);
-    if (wv == 0 && lane < rnl) mf_st(x + f.c0 + rl0 + lane, mf_clean(xl));
-}
-
 }  // namespace dev
 
 // ================================================================== host side
@@ -1744,8 +1108,6 @@ struct MfFactor {
     eigsol_ctx* ctx = nullptr;
     int dtype = EIGSOL_F64;
     int64_t n = 0;
-    int nb = 32;
-    int64_t nfront = 0;
     dev::MfFront* fronts = nullptr;
     int32_t* chl = nullptr;
     int32_t* sidx = nullptr;
@@ -1757,43 +1119,19 @@ struct MfFactor {
     void* u = nullptr;
     void* w = nullptr;
     void* x = nullptr;
-    std::vector<int64_t> hstart;      // lists[hstart[h] .. hstart[h + 1])
-    std::vector<int32_t> lds_fwd, lds_bwd;   // dynamic LDS bytes per height (one-workgroup fronts)
-    std::vector<int32_t> lds_bbig;           // per height: x(struct) of the large fronts (mf_big_bwd_kernel)
-    // solve: per height the one-workgroup fronts (slists[sstart[h] .. + nsmall[h])), then the
-    // large fronts (the next nbig[h] entries: their assembly launch); the large fronts' row-block
-    // tables (front, block) for the forward / backward launches at tabf / tabb + off[h], cnt[h] pairs
+    MfSolveTables T;                  // per height: where its fronts and row blocks are in slists / tabf / tabb
     int32_t* slists = nullptr;
     int32_t* tabf = nullptr;
     int32_t* tabb = nullptr;
-    int32_t* tabf2 = nullptr;         // the same with two pivot blocks per entry (mf_big_fwd2 / bwd2_kernel)
-    int32_t* tabb2 = nullptr;
-    // EIGSOL_MF_PAIR=1 (value flags only; measured and left off, round 6, tools/r06_mf_pair_ab.sh):
-    // 1M convection-diffusion 1.495 / 1.509 -> 1.776 / 1.793 ms per iteration, bitwise the same
-    // solution - a workgroup holding two blocks' tiles (256 VGPRs + AGPRs, one wave per SIMD) loads
-    // them at half the rate, and that, not the hand-off count, is what the chain waits on
-    bool pair = false;
     int32_t* flags = nullptr;         // one per pivot block of the large fronts (epoch words)
     int32_t* err = nullptr;           // a flag wait that timed out
     void* z = nullptr;                // large fronts' assembled right-hand sides
     void* tinv = nullptr;             // inverted diagonal blocks of the large fronts and premultiplied tiles (kMfTinv scalars each)
     int32_t epoch = 0;
-    int32_t hflow = 0;
-    int32_t* flow_f = nullptr;
-    int32_t* flow_b = nullptr;
-    int32_t* fheight = nullptr;
-    int32_t* done = nullptr;
-    int32_t nflow = 0, lds_flow_f = 0, lds_flow_b = 0;
-    int flow_mode = 3;
-    int32_t* sub_ranges = nullptr;
-    int32_t nsub = 0, lds_sub_f = 0, lds_sub_b = 0;                // bit 0 forward, bit 1 backward (EIGSOL_MF_FLOW_MODE, debugging)
     int backoff = 2;                  // EIGSOL_MF_BACKOFF: 1 growing sleeps, 2 relaxed polls (flag stores: release)
     bool fuse_asm = true;             // EIGSOL_MF_FUSE_ASM=0: small fronts and large-front assembly as two launches
     bool fuse_big = true;             // EIGSOL_MF_FUSE_BIG=0: no mf_fwd_height_kernel
     uint8_t* bigm = nullptr;          // [n] 1 on the large fronts' pivot rows (mf_fwd_height_kernel's gather)
-    std::vector<int64_t> sstart, nwave, nsmall, nbig, foff, fcnt, boff, bcnt, foff2, fcnt2, boff2, bcnt2;
-    std::vector<int32_t> lds_asm;
-    std::vector<int32_t> lds_asm2;    // mf_fwd_height_kernel's assembly: d entries per large front
     MfStats st;
     int64_t nstatic = 0;   // static pivots of the factorization (0 unless the retry set them)
 };
@@ -1804,913 +1142,13 @@ void mf_free(MfFactor* f) {
     hipStreamSynchronize(f->ctx->stream);
     for (void* p : {(void*)f->fronts, (void*)f->chl, (void*)f->sidx, (void*)f->cmap, (void*)f->perm, (void*)f->pinv,
                     (void*)f->lists, f->F, f->u, f->w, f->x, (void*)f->slists, (void*)f->tabf, (void*)f->tabb,
-                    (void*)f->tabf2, (void*)f->tabb2, (void*)f->flags, (void*)f->err, f->z, f->tinv, (void*)f->flow_f, (void*)f->flow_b,
-                    (void*)f->fheight, (void*)f->done, (void*)f->sub_ranges, (void*)f->bigm})
+                    (void*)f->flags, (void*)f->err, f->z, f->tinv, (void*)f->bigm})
         if (p) hipFree(p);
     ctx_release(f->ctx);
     delete f;
 }
 
 const MfStats& mf_stats(const MfFactor* f) { return f->st; }
-
-namespace {
-
-struct SymGraph {
-    std::vector<int64_t> ptr;
-    std::vector<int32_t> adj;
-};
-
-// pattern of M + M^T without the diagonal, each list sorted and unique
-// fn(begin, end) over [0, n) in contiguous chunks on up to nth host threads
-template <class Fn>
-void par_for(int64_t n, int nth, Fn fn) {
-    if (nth <= 1 || n < 4096) { fn((int64_t)0, n); return; }
-    std::vector<std::thread> th;
-    const int64_t chunk = (n + nth - 1) / nth;
-    try {
-        for (int t = 1; t < nth; ++t) {
-            const int64_t b = t * chunk, e = std::min(n, b + chunk);
-            if (b < e) th.emplace_back(fn, b, e);
-        }
-    } catch (const std::exception&) {
-        for (auto& x : th) x.join();
-        fn(chunk, n);   // no more threads: the rest on this one
-        fn((int64_t)0, std::min(n, chunk));
-        return;
-    }
-    fn((int64_t)0, std::min(n, chunk));
-    for (auto& x : th) x.join();
-}
-
-int host_threads() {
-    int nth = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    if (const char* e = std::getenv("EIGSOL_MF_THREADS")) nth = std::max(1, std::atoi(e));
-    return nth;
-}
-
-// pattern of M + M^T without the diagonal, each list sorted and unique: M's rows merged with the
-// rows of its transpose (a counting-sort transpose keeps them sorted)
-bool sym_graph(int64_t n, const std::vector<int32_t>& rp, const std::vector<int32_t>& ci, SymGraph& g,
-               const std::atomic<bool>* stop = nullptr) {
-    const int nth = host_threads();
-    auto stopped = [&]() { return stop && stop->load(std::memory_order_relaxed); };
-    std::vector<int64_t> tp(n + 1, 0);
-    for (int64_t e = 0; e < (int64_t)rp[n]; ++e) ++tp[ci[e] + 1];
-    for (int64_t i = 0; i < n; ++i) tp[i + 1] += tp[i];
-    if (stopped()) return false;
-    std::vector<int32_t> tc(rp[n]);
-    {
-        std::vector<int64_t> fill(tp.begin(), tp.end() - 1);
-        for (int64_t i = 0; i < n; ++i) {
-            if ((i & 65535) == 0 && stopped()) return false;
-            for (int32_t e = rp[i]; e < rp[i + 1]; ++e) tc[fill[ci[e]]++] = (int32_t)i;
-        }
-    }
-    // merge row i of M and of M^T (both ascending), without i and repeats; count, then fill
-    auto merge = [&](int64_t i, int32_t* out) -> int64_t {
-        int64_t a = rp[i], ae = rp[i + 1], b = tp[i], be = tp[i + 1], k = 0;
-        int32_t last = -1;
-        while (a < ae || b < be) {
-            int32_t c;
-            if (b >= be || (a < ae && ci[a] <= tc[b])) c = ci[a++];
-            else c = tc[b++];
-            if (c == i || c == last) continue;
-            last = c;
-            if (out) out[k] = c;
-            ++k;
-        }
-        return k;
-    };
-    g.ptr.assign(n + 1, 0);
-    par_for(n, nth, [&](int64_t b, int64_t e) {
-        for (int64_t i = b; i < e; ++i) {
-            if ((i & 65535) == 0 && stopped()) return;
-            g.ptr[i + 1] = merge(i, nullptr);
-        }
-    });
-    if (stopped()) return false;
-    for (int64_t i = 0; i < n; ++i) g.ptr[i + 1] += g.ptr[i];
-    if (stopped()) return false;
-    g.adj.resize(g.ptr[n]);
-    par_for(n, nth, [&](int64_t b, int64_t e) {
-        for (int64_t i = b; i < e; ++i) {
-            if ((i & 65535) == 0 && stopped()) return;
-            merge(i, g.adj.data() + g.ptr[i]);
-        }
-    });
-    return !stopped();
-}
-
-struct NdNode {
-    std::vector<int32_t> members;
-    int32_t parent;
-    std::vector<int32_t> key;   // position in the dissection (independent of thread timing)
-};
-
-// Nested dissection of the vertices of g: tree nodes (leaves and separators) with parents, in a
-// canonical order (sorted by key: the path of choices from the whole graph to the node's piece).
-// Pieces are dissected by a pool of host threads (they touch disjoint vertex sets; a piece's BFS
-// reads its neighbours' set tags with relaxed atomics); the tree does not depend on the timing.
-bool nested_dissection(int64_t n, const SymGraph& g, int leaf, std::vector<NdNode>& tree,
-                       const std::atomic<bool>* stop) {
-    struct Task {
-        std::vector<int32_t> nodes;
-        int32_t parent;
-        std::vector<int32_t> key;
-    };
-    std::vector<Task> stack;
-    {
-        Task t;
-        t.nodes.resize(n);
-        std::iota(t.nodes.begin(), t.nodes.end(), 0);
-        t.parent = -1;
-        stack.push_back(std::move(t));
-    }
-    // per-vertex state in one record, so a neighbour test touches one cache line: the piece tag
-    // (written by the piece's owner, read by the neighbouring pieces' BFS), the BFS stamp and level
-    struct Vs {
-        int64_t tag, seen;
-        int32_t level;
-    };
-    std::vector<Vs> vs(n, Vs{-1, -1, 0});
-    // pseudo-peripheral restarts per piece.  1M convection-diffusion: 2 / 1 / 0
-    // rounds -> 1.374e8 / 1.368e8 / 1.47e8 factor entries, 1.13e11 / 1.12e11 / 1.83e11 flops; on the box
-    // the set-up is the same for 1 and 2 (0.63-0.67 s) and the solve 1.55 against 1.57 ms: 2 stays
-    constexpr int pp_rounds = 2;
-    std::atomic<int64_t> stamp{0}, bstamp{0};
-    std::mutex mu;
-    std::condition_variable cv;
-    int active = 0;
-    bool aborted = false;
-    auto tag_of = [&](int32_t v) { return __atomic_load_n(&vs[v].tag, __ATOMIC_RELAXED); };
-    auto add_node = [&](std::vector<int32_t>&& members, int32_t parent, std::vector<int32_t> key) -> int32_t {
-        std::lock_guard<std::mutex> lk(mu);
-        tree.push_back(NdNode{std::move(members), parent, std::move(key)});
-        return (int32_t)tree.size() - 1;
-    };
-    auto push_task = [&](Task&& t) {
-        std::lock_guard<std::mutex> lk(mu);
-        stack.push_back(std::move(t));
-        cv.notify_one();
-    };
-    auto work = [&]() {
-        std::vector<int32_t> q;
-        // raised inside a BFS once *stop is seen (checked every 64K visits: a whole-graph BFS of the
-        // top piece takes tens of ms), the task then abandons the dissection
-        bool cut = false;
-        // BFS inside the piece tagged `tag` from root: q holds the visit order, vs[].level the levels
-        auto bfs = [&](int32_t root, int64_t tag) -> int32_t {
-            const int64_t b = ++bstamp;
-            q.clear();
-            q.push_back(root);
-            vs[root].seen = b;
-            vs[root].level = 0;
-            int32_t depth = 0;
-            for (size_t h = 0; h < q.size(); ++h) {
-                const int32_t v = q[h];
-                if ((h & 65535) == 65535 && stop && stop->load(std::memory_order_relaxed)) {
-                    cut = true;
-                    return depth;
-                }
-                const int32_t lw = vs[v].level + 1;
-                for (int64_t e = g.ptr[v]; e < g.ptr[v + 1]; ++e) {
-                    const int32_t w = g.adj[e];
-                    if (tag_of(w) != tag || vs[w].seen == b) continue;
-                    vs[w].seen = b;
-                    vs[w].level = lw;
-                    depth = std::max(depth, lw);
-                    q.push_back(w);
-                }
-            }
-            return depth;
-        };
-        auto sub_degree = [&](int32_t v, int64_t tag) {
-            int32_t dgr = 0;
-            for (int64_t e = g.ptr[v]; e < g.ptr[v + 1]; ++e) dgr += tag_of(g.adj[e]) == tag;
-            return dgr;
-        };
-        for (;;) {
-            Task t;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return aborted || !stack.empty() || active == 0; });
-                if (aborted || stack.empty()) { cv.notify_all(); return; }
-                t = std::move(stack.back());
-                stack.pop_back();
-                ++active;
-            }
-            auto done = [&]() {
-                std::lock_guard<std::mutex> lk(mu);
-                --active;
-                if (active == 0 && stack.empty()) cv.notify_all();
-            };
-            auto abort_task = [&]() {
-                std::lock_guard<std::mutex> lk(mu);
-                aborted = true;
-                --active;
-                cv.notify_all();
-            };
-            if (cut || (stop && stop->load(std::memory_order_relaxed))) {
-                abort_task();
-                return;
-            }
-            const int64_t sz = (int64_t)t.nodes.size();
-            if (sz == 0) { done(); continue; }
-            if (sz <= leaf) {
-                add_node(std::move(t.nodes), t.parent, std::move(t.key));
-                done();
-                continue;
-            }
-            const int64_t tag = ++stamp;
-            for (int32_t v : t.nodes) __atomic_store_n(&vs[v].tag, tag, __ATOMIC_RELAXED);
-            // from the piece's first vertex: connectivity, and the first pseudo-peripheral level set
-            const int32_t depth0 = bfs(t.nodes[0], tag);
-            if (cut) {
-                abort_task();
-                return;
-            }
-            if ((int64_t)q.size() < sz) {
-                // disconnected: components (in the order of their first vertex in the piece); the
-                // small ones packed into leaves, the others new pieces
-                std::vector<std::vector<int32_t>> comps;
-                const int64_t b0 = vs[t.nodes[0]].seen;   // this piece's first BFS; later ones are larger
-                comps.push_back(q);
-                for (int32_t v : t.nodes) {
-                    if (vs[v].seen >= b0) continue;
-                    bfs(v, tag);
-                    if (cut) break;
-                    comps.push_back(q);
-                }
-                if (cut) {
-                    abort_task();
-                    return;
-                }
-                std::vector<int32_t> pack;
-                int32_t slot = 0;
-                auto key_at = [&](int32_t k) {
-                    std::vector<int32_t> kk = t.key;
-                    kk.push_back(k);
-                    return kk;
-                };
-                for (auto& c : comps) {
-                    if ((int64_t)c.size() > leaf) {
-                        push_task(Task{std::move(c), t.parent, key_at(slot++)});
-                        continue;
-                    }
-                    if ((int64_t)(pack.size() + c.size()) > leaf) {
-                        add_node(std::move(pack), t.parent, key_at(slot++));
-                        pack.clear();
-                    }
-                    pack.insert(pack.end(), c.begin(), c.end());
-                }
-                if (!pack.empty()) add_node(std::move(pack), t.parent, key_at(slot++));
-                done();
-                continue;
-            }
-            // pseudo-peripheral root (George-Liu): restart from a minimum-degree vertex of the last
-            // level while the eccentricity grows
-            int32_t root = t.nodes[0];
-            int32_t ecc = depth0;   // q and the levels are still those of the BFS from root
-            for (int round = 0; round < pp_rounds; ++round) {
-                int32_t best = -1, bd = INT32_MAX;
-                for (size_t h = q.size(); h-- > 0;) {
-                    const int32_t v = q[h];
-                    if (vs[v].level != ecc) break;
-                    const int32_t dv = sub_degree(v, tag);
-                    if (dv < bd || (dv == bd && v < best)) { bd = dv; best = v; }
-                }
-                const int32_t e2 = bfs(best, tag);
-                if (e2 <= ecc) {
-                    if (e2 < ecc) ecc = bfs(root, tag);   // restore the levels of the better root
-                    break;
-                }
-                root = best;
-                ecc = e2;
-            }
-            if (cut) {
-                abort_task();
-                return;
-            }
-            const int32_t nlev = ecc + 1;
-            if (nlev < 3) {   // no level structure to cut: one dense front
-                add_node(std::move(t.nodes), t.parent, std::move(t.key));
-                done();
-                continue;
-            }
-            std::vector<int64_t> cnt(nlev, 0);
-            for (int32_t v : t.nodes) ++cnt[vs[v].level];
-            int32_t m = 1;
-            {
-                int64_t cum = 0;
-                for (int32_t l = 0; l < nlev; ++l) {
-                    if (2 * (cum + cnt[l] / 2) >= sz) { m = l; break; }
-                    cum += cnt[l];
-                }
-                m = std::max(1, std::min(nlev - 2, m));
-            }
-            // separator: the vertices of level m that touch level m + 1; the rest of level m joins A
-            std::vector<int32_t> A, B, Sep;
-            for (int32_t v : t.nodes) {
-                const int32_t l = vs[v].level;
-                if (l < m) A.push_back(v);
-                else if (l > m) B.push_back(v);
-                else {
-                    bool touch = false;
-                    for (int64_t e = g.ptr[v]; e < g.ptr[v + 1] && !touch; ++e)
-                        touch = tag_of(g.adj[e]) == tag && vs[g.adj[e]].level == m + 1;
-                    (touch ? Sep : A).push_back(v);
-                }
-            }
-            std::vector<int32_t>().swap(t.nodes);
-            std::vector<int32_t> ka = t.key, kb = t.key;
-            ka.push_back(0);
-            kb.push_back(1);
-            const int32_t id = add_node(std::move(Sep), t.parent, std::move(t.key));
-            push_task(Task{std::move(A), id, std::move(ka)});
-            push_task(Task{std::move(B), id, std::move(kb)});
-            done();
-        }
-    };
-    int nth = host_threads();
-    if (n < 20000) nth = 1;
-    std::vector<std::thread> pool;
-    try {
-        for (int i = 1; i < nth; ++i) pool.emplace_back(work);
-    } catch (const std::exception&) {   // fewer threads: the others do the work
-    }
-    work();
-    for (auto& th : pool) th.join();
-    if (aborted) return false;
-    // canonical order: by key; parents renumbered
-    std::vector<int32_t> ord(tree.size());
-    std::iota(ord.begin(), ord.end(), 0);
-    std::sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) { return tree[x].key < tree[y].key; });
-    std::vector<int32_t> newid(tree.size());
-    for (size_t i = 0; i < ord.size(); ++i) newid[ord[i]] = (int32_t)i;
-    std::vector<NdNode> sorted;
-    sorted.reserve(tree.size());
-    for (int32_t o : ord) {
-        NdNode nd = std::move(tree[o]);
-        if (nd.parent >= 0) nd.parent = newid[nd.parent];
-        std::vector<int32_t>().swap(nd.key);
-        sorted.push_back(std::move(nd));
-    }
-    tree.swap(sorted);
-    return true;
-}
-
-}  // namespace
-
-// The ordering and symbolic structure (host only): fronts in postorder with their columns,
-// structs, children, parent maps; per-height lists; work and size figures.
-struct MfPlan {
-    int64_t nt = 0;
-    std::vector<int32_t> perm, iperm, snode, chl, sidx, cmap, height, lists;
-    std::vector<int64_t> sof, hstart;
-    std::vector<dev::MfFront> fr;
-    int32_t H = 0;
-    int64_t maxd = 0, maxns = 0, uo = 0;
-    double fe = 0.0, fac = 0.0, flops = 0.0;
-};
-
-// returns false on an internal inconsistency (a struct entry outside the ancestors)
-// max_front_entries: the plan is abandoned once the fronts' sum of d^2 passes it (a pattern
-// without small separators, e.g. a random graph); stop: abandoned when raised (another thread's
-// factor won)
-bool mf_plan(int64_t n, const std::vector<int32_t>& rp, const std::vector<int32_t>& ci, int leaf, bool cplx_flops,
-             MfPlan& P, double max_front_entries = 1e300, const std::atomic<bool>* stop = nullptr) {
-    static const bool dbg = std::getenv("EIGSOL_MF_DEBUG") != nullptr;
-    auto tp = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!dbg) return;
-        const auto t = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[mf] %s %.3f s\n", what, std::chrono::duration<double>(t - tp).count());
-        tp = t;
-    };
-    // the graph relabelled in breadth-first order (neighbours get nearby labels: the many BFS
-    // passes of the dissection then walk memory locally whatever the caller's numbering)
-    SymGraph g;
-    std::vector<int32_t> ord(n);   // label -> caller's index
-    auto stopped = [&]() { return stop && stop->load(std::memory_order_relaxed); };
-    {
-        SymGraph g0;
-        if (!sym_graph(n, rp, ci, g0, stop)) return false;
-        lap("graph: symmetric pattern");
-        std::vector<char> done(n, 0);
-        int64_t head = 0, tail = 0;
-        for (int64_t s0 = 0; s0 < n; ++s0) {
-            if (done[s0]) continue;
-            done[s0] = 1;
-            ord[tail++] = (int32_t)s0;
-            while (head < tail) {
-                if ((head & 65535) == 0 && stopped()) return false;
-                const int32_t v = ord[head++];
-                for (int64_t e = g0.ptr[v]; e < g0.ptr[v + 1]; ++e)
-                    if (!done[g0.adj[e]]) { done[g0.adj[e]] = 1; ord[tail++] = g0.adj[e]; }
-            }
-        }
-        if (stopped()) return false;
-        lap("graph: breadth-first labels");
-        std::vector<int32_t> lab(n);
-        for (int64_t k = 0; k < n; ++k) lab[ord[k]] = (int32_t)k;
-        g.ptr.assign(n + 1, 0);
-        for (int64_t k = 0; k < n; ++k) g.ptr[k + 1] = g.ptr[k] + (g0.ptr[ord[k] + 1] - g0.ptr[ord[k]]);
-        g.adj.resize(g0.adj.size());
-        par_for(n, host_threads(), [&](int64_t b, int64_t e) {
-            for (int64_t k = b; k < e; ++k) {
-                const int32_t v = ord[k];
-                int64_t o = g.ptr[k];
-                for (int64_t x = g0.ptr[v]; x < g0.ptr[v + 1]; ++x) g.adj[o++] = lab[g0.adj[x]];
-                std::sort(g.adj.begin() + g.ptr[k], g.adj.begin() + o);
-            }
-        });
-    }
-    lap("graph");
-    std::vector<NdNode> tree;
-    if (!nested_dissection(n, g, leaf, tree, stop)) return false;
-    lap("dissection");
-    // postorder numbering: children before parents, each tree node one contiguous column range
-    const int64_t nt = (int64_t)tree.size();
-    P.nt = nt;
-    std::vector<int32_t> post;   // tree node of each front (postorder)
-    post.reserve(nt);
-    {
-        std::vector<std::vector<int32_t>> kids(nt);
-        std::vector<int32_t> roots;
-        for (int64_t i = 0; i < nt; ++i) {
-            if (tree[i].parent < 0) roots.push_back((int32_t)i);
-            else kids[tree[i].parent].push_back((int32_t)i);
-        }
-        std::vector<std::pair<int32_t, size_t>> st;
-        for (int32_t r : roots) {
-            st.push_back({r, 0});
-            while (!st.empty()) {
-                auto& top = st.back();
-                if (top.second < kids[top.first].size()) {
-                    const int32_t c = kids[top.first][top.second++];
-                    st.push_back({c, 0});
-                } else {
-                    post.push_back(top.first);
-                    st.pop_back();
-                }
-            }
-        }
-    }
-    std::vector<int32_t> front_of_node(nt);
-    for (int64_t s = 0; s < nt; ++s) front_of_node[post[s]] = (int32_t)s;
-    P.perm.assign(n, 0);
-    P.iperm.assign(n, 0);
-    P.snode.assign(n, 0);
-    P.fr.assign(nt, dev::MfFront{});
-    auto& fr = P.fr;
-    {
-        int32_t c = 0;
-        for (int64_t s = 0; s < nt; ++s) {
-            const NdNode& nd = tree[post[s]];
-            fr[s].c0 = c;
-            fr[s].ns = (int32_t)nd.members.size();
-            fr[s].parent = nd.parent < 0 ? -1 : front_of_node[nd.parent];
-            for (int32_t v : nd.members) {
-                P.perm[c] = v;
-                P.iperm[v] = c;
-                P.snode[c] = (int32_t)s;
-                ++c;
-            }
-        }
-    }
-    std::vector<NdNode>().swap(tree);
-    // children lists (postorder, i.e. the fixed extend-add order)
-    auto& chl = P.chl;
-    {
-        std::vector<std::vector<int32_t>> ch(nt);
-        for (int64_t s = 0; s < nt; ++s)
-            if (fr[s].parent >= 0) ch[fr[s].parent].push_back((int32_t)s);
-        for (int64_t s = 0; s < nt; ++s) {
-            fr[s].ch0 = (int32_t)chl.size();
-            chl.insert(chl.end(), ch[s].begin(), ch[s].end());
-            fr[s].ch1 = (int32_t)chl.size();
-        }
-    }
-    // heights (a leaf 0, a parent one above its highest child) and the per-height front lists
-    // (descending ns: each panel's fronts are a prefix)
-    P.height.assign(nt, 0);
-    P.H = 0;
-    for (int64_t s = 0; s < nt; ++s) {
-        for (int32_t k = fr[s].ch0; k < fr[s].ch1; ++k) P.height[s] = std::max(P.height[s], P.height[chl[k]] + 1);
-        P.H = std::max(P.H, P.height[s]);
-    }
-    P.hstart.assign(P.H + 2, 0);
-    {
-        std::vector<std::vector<int32_t>> byh(P.H + 1);
-        for (int64_t s = 0; s < nt; ++s) byh[P.height[s]].push_back((int32_t)s);
-        for (int32_t h = 0; h <= P.H; ++h) {
-            std::stable_sort(byh[h].begin(), byh[h].end(), [&](int32_t a, int32_t b) { return fr[a].ns > fr[b].ns; });
-            P.lists.insert(P.lists.end(), byh[h].begin(), byh[h].end());
-            P.hstart[h + 1] = (int64_t)P.lists.size();
-        }
-    }
-    // symbolic: struct(s) = indices >= c1 reached from s's rows in M + M^T or through a child's
-    // struct (each list ascending).  A front needs only its children's lists, so the fronts of one
-    // height are independent: they run on the host threads (a mark array per thread), height after
-    // height, and the lists are concatenated in front order -- the same arrays as a serial pass.
-    auto& sidx = P.sidx;
-    auto& sof = P.sof;
-    sof.assign(nt + 1, 0);
-    {
-        std::vector<std::vector<int32_t>> lists(nt);
-        std::atomic<bool> over{false};
-        std::atomic<double> fe_run{0.0};
-        const int nth = host_threads();
-        std::vector<std::vector<int32_t>> marks(std::max(1, nth));
-        auto one = [&](int32_t s, std::vector<int32_t>& mark) {
-            const int32_t c0 = fr[s].c0, c1 = c0 + fr[s].ns;
-            std::vector<int32_t>& lst = lists[s];
-            for (int32_t i = c0; i < c1; ++i) {
-                const int32_t v = P.perm[i];
-                for (int64_t e = g.ptr[v]; e < g.ptr[v + 1]; ++e) {
-                    const int32_t j = P.iperm[g.adj[e]];
-                    if (j >= c1 && mark[j] != s) { mark[j] = s; lst.push_back(j); }
-                }
-            }
-            for (int32_t k = fr[s].ch0; k < fr[s].ch1; ++k)
-                for (int32_t j : lists[chl[k]])
-                    if (j >= c1 && mark[j] != s) { mark[j] = s; lst.push_back(j); }
-            std::sort(lst.begin(), lst.end());
-            const double d = (double)fr[s].ns + (double)lst.size();
-            double cur = fe_run.load(std::memory_order_relaxed);
-            while (!fe_run.compare_exchange_weak(cur, cur + d * d, std::memory_order_relaxed)) {}
-            if (cur + d * d > max_front_entries) over.store(true, std::memory_order_relaxed);
-        };
-        for (int32_t h = 0; h <= P.H; ++h) {
-            const int64_t b = P.hstart[h], m = P.hstart[h + 1] - b;
-            const int use = m < 8 ? 1 : (int)std::min<int64_t>(std::max(1, nth), m);
-            auto run = [&](int t) {
-                std::vector<int32_t>& mark = marks[t];
-                if (mark.empty()) mark.assign(n, -1);
-                for (int64_t k = t; k < m; k += use) {   // fronts dealt round-robin: sizes vary by position
-                    if (over.load(std::memory_order_relaxed) || stopped()) return;
-                    one(P.lists[b + k], mark);
-                }
-            };
-            if (use <= 1) {
-                run(0);
-            } else {
-                std::vector<std::thread> th;
-                try {
-                    for (int t = 1; t < use; ++t) th.emplace_back(run, t);
-                } catch (const std::exception&) {
-                    for (auto& x : th) x.join();
-                    th.clear();
-                    for (int t = 1; t < use; ++t) run(t);   // no more threads: this one does the rest
-                }
-                run(0);
-                for (auto& x : th) x.join();
-            }
-            if (over.load() || stopped()) return false;
-        }
-        int64_t tot = 0;
-        for (int64_t s = 0; s < nt; ++s) tot += (int64_t)lists[s].size();
-        sidx.reserve(tot);
-        for (int64_t s = 0; s < nt; ++s) {
-            sidx.insert(sidx.end(), lists[s].begin(), lists[s].end());
-            std::vector<int32_t>().swap(lists[s]);
-            sof[s + 1] = (int64_t)sidx.size();
-            fr[s].ms = (int32_t)(sof[s + 1] - sof[s]);
-            fr[s].sof = sof[s];
-            fr[s].d = fr[s].ns + fr[s].ms;
-        }
-    }
-    std::vector<int64_t>().swap(g.ptr);
-    std::vector<int32_t>().swap(g.adj);
-    // labels -> the caller's indices
-    for (int64_t c = 0; c < n; ++c) {
-        P.perm[c] = ord[P.perm[c]];
-        P.iperm[P.perm[c]] = (int32_t)c;
-    }
-    lap("symbolic");
-    // sizes and work
-    for (int64_t s = 0; s < nt; ++s) {
-        const double d = fr[s].d, ns = fr[s].ns;
-        fr[s].off = (int64_t)P.fe;
-        fr[s].uoff = P.uo;
-        P.uo += fr[s].ms;
-        P.fe += d * d;
-        P.fac += ns * (2.0 * d - ns);
-        // sum_{k < ns} 2 (d - k - 1)^2 multiply-adds ~ 2 (ns d^2 - ns^2 d + ns^3 / 3)
-        P.flops += 2.0 * (ns * d * d - ns * ns * d + ns * ns * ns / 3.0);
-        P.maxd = std::max<int64_t>(P.maxd, fr[s].d);
-        P.maxns = std::max<int64_t>(P.maxns, fr[s].ns);
-    }
-    if (cplx_flops) P.flops *= 4.0;
-    lap("sizes");
-    // parent positions of every child's struct entries
-    P.cmap.assign(sidx.size(), 0);
-    for (int64_t s = 0; s < nt; ++s) {
-        const int32_t p = fr[s].parent;
-        if (p < 0) {
-            if (fr[s].ms) return false;   // a root reaches nothing past itself
-            continue;
-        }
-        const int32_t pc0 = fr[p].c0, pc1 = pc0 + fr[p].ns;
-        const int32_t* ps = sidx.data() + sof[p];
-        const int32_t pm = fr[p].ms;
-        int32_t cur = 0;
-        for (int64_t e = sof[s]; e < sof[s + 1]; ++e) {
-            const int32_t j = sidx[e];
-            if (j < pc0) return false;   // struct(s) must lie in the ancestors
-            if (j < pc1) P.cmap[e] = j - pc0;
-            else {
-                while (cur < pm && ps[cur] < j) ++cur;   // both ascending
-                if (cur == pm || ps[cur] != j) return false;
-                P.cmap[e] = fr[p].ns + cur;
-            }
-        }
-    }
-    lap("parent maps");
-    return true;
-}
-
-struct MfLaunch {
-    int kind;   // 0 extend, 1 panel, 2 gemm
-    int32_t h, q;
-    int64_t off, cnt;
-};
-
-struct MfHost {
-    MfPlan P;
-    int64_t n = 0, nnz = 0;
-    int nb = 32;
-    int64_t sb = 16;
-    std::vector<int64_t> dst;              // M's entries -> front offsets
-    std::vector<MfLaunch> plan;            // factorization launches
-    std::vector<int32_t> tab, slists, tabf, tabb, tabf2, tabb2, lds_asm, lds_asm2;
-    std::vector<int64_t> sstart, nwave, nsmall, nbig, foff, fcnt, boff, bcnt, foff2, fcnt2, boff2, bcnt2;
-    int32_t nflag = 0;
-    int64_t zsz = 0;
-    int32_t hflow = 0;                     // heights below it: the dataflow launches (0: off)
-    std::vector<int32_t> flow_f, flow_b;   // their fronts, ascending / descending height
-    int32_t lds_flow_f = 0, lds_flow_b = 0;
-    std::vector<int32_t> sub_ranges;       // small subtrees solved by one workgroup each: (lo, hi) fronts
-    int32_t lds_sub_f = 0, lds_sub_b = 0;
-    std::vector<int32_t> inv_list;         // fronts with an inverse form (MfFront::goff)
-    int64_t gsz = 0;                       // its scalars, stored after the fronts in F
-    MfStats stt;
-};
-
-// The host half of the factor: plan, bounds, entry destinations, launch and solve tables.  Needs
-// no device (free_bytes: the device memory the fronts may take), so gmres.hip runs it on a second
-// host thread beside the natural-order fill attempt.
-int mf_prepare_host(int64_t n, const std::vector<int32_t>& rp, const std::vector<int32_t>& ci, bool cplx_s,
-                    double free_bytes, MfHost& X, const std::atomic<bool>* stop) {
-    using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
-    const int NB = cplx_s ? dev::RankKMax<cplx>::value : dev::RankKMax<double>::value;
-    const int64_t sb = cplx_s ? 16 : 8;
-    X.n = n;
-    X.nb = NB;
-    X.sb = sb;
-    int leaf = 64;
-    if (const char* e = std::getenv("EIGSOL_MF_LEAF")) leaf = std::max(4, std::atoi(e));
-    MfPlan& P = X.P;
-    double cap = 0.45 * free_bytes;
-    if (const char* e = std::getenv("EIGSOL_MF_MAX_GB")) cap = std::min(cap, std::atof(e) * 1073741824.0);
-    if (!mf_plan(n, rp, ci, leaf, cplx_s, P, cap / (double)sb, stop)) return EIGSOL_E_UNSUPPORTED;
-    const int64_t nt = P.nt;
-    auto& fr = P.fr;
-    const auto& chl = P.chl;
-    const auto& sidx = P.sidx;
-    const auto& sof = P.sof;
-    const auto& lists = P.lists;
-    const auto& hstart = P.hstart;
-    const int32_t H = P.H;
-    const double fe = P.fe, fac = P.fac;
-    MfStats& stt = X.stt;
-    stt.fronts = nt;
-    stt.heights = H + 1;
-    stt.max_front = P.maxd;
-    stt.max_pivots = P.maxns;
-    stt.front_entries = fe;
-    stt.factor_entries = fac;
-    stt.flops = P.flops;
-    // bounds: device memory for the fronts, the solve kernels' LDS, the work
-    const double lds_max = 120.0 * 1024.0;
-    if (fe * (double)sb > cap || (double)(P.maxns + P.maxd) * (double)sb > lds_max || P.flops > 4e13)
-        return EIGSOL_E_UNSUPPORTED;
-    // destinations of M's entries (the caller's numbering) in the fronts
-    const int64_t nnz = rp[n];
-    X.nnz = nnz;
-    auto& dst = X.dst;
-    dst.assign(nnz, 0);
-    auto pos_in = [&](int32_t s, int32_t j) -> int64_t {
-        const int32_t c0 = fr[s].c0;
-        if (j < c0 + fr[s].ns) return j - c0;
-        const int32_t* b = sidx.data() + sof[s];
-        const int64_t k = std::lower_bound(b, b + fr[s].ms, j) - b;
-        return (k < fr[s].ms && b[k] == j) ? fr[s].ns + k : -1;
-    };
-    std::atomic<bool> bad{false};
-    par_for(n, host_threads(), [&](int64_t rb, int64_t re) {
-        for (int64_t r = rb; r < re; ++r)
-            for (int32_t e = rp[r]; e < rp[r + 1]; ++e) {
-                const int32_t i = P.iperm[r], j = P.iperm[ci[e]];
-                const int32_t s = P.snode[std::min(i, j)];
-                const int64_t pi = pos_in(s, i), pj = pos_in(s, j);
-                if (pi < 0 || pj < 0) { bad.store(true); return; }   // not in the front: an inconsistent plan
-                dst[e] = fr[s].off + pi + pj * (int64_t)fr[s].d;
-            }
-    });
-    if (bad.load()) return EIGSOL_E_UNSUPPORTED;
-    // launch tables: extend-add (child, first column) per (height, child rank); trailing-update
-    // tiles (front, tile row, tile column) per (height, panel)
-    using Launch = MfLaunch;
-    auto& plan = X.plan;
-    auto& tab = X.tab;
-    for (int32_t h = 0; h <= H; ++h) {
-        const int32_t* L = lists.data() + hstart[h];
-        const int64_t cnt = hstart[h + 1] - hstart[h];
-        int32_t maxch = 0, maxq = 0;
-        for (int64_t t = 0; t < cnt; ++t) {
-            maxch = std::max(maxch, fr[L[t]].ch1 - fr[L[t]].ch0);
-            maxq = std::max(maxq, (fr[L[t]].ns + NB - 1) / NB);
-        }
-        for (int32_t j = 0; j < maxch; ++j) {
-            const int64_t o = (int64_t)tab.size();
-            for (int64_t t = 0; t < cnt; ++t) {
-                const dev::MfFront& p = fr[L[t]];
-                if (p.ch1 - p.ch0 <= j) continue;
-                const int32_t c = chl[p.ch0 + j];
-                for (int32_t c0 = 0; c0 < fr[c].ms; c0 += 64) { tab.push_back(c); tab.push_back(c0); }
-            }
-            const int64_t k = ((int64_t)tab.size() - o) / 2;
-            if (k) plan.push_back(Launch{0, h, j, o, k});
-        }
-        for (int32_t q = 0; q < maxq; ++q) {
-            int64_t np = 0;
-            while (np < cnt && fr[L[np]].ns > q * NB) ++np;
-            plan.push_back(Launch{1, h, q, hstart[h], np});
-            const int64_t o = (int64_t)tab.size();
-            for (int64_t t = 0; t < np; ++t) {
-                const dev::MfFront& f = fr[L[t]];
-                const int32_t c1 = std::min(f.ns, (q + 1) * NB), m = f.d - c1;
-                const int32_t nt64 = (m + 63) / 64;
-                for (int32_t a = 0; a < nt64; ++a)
-                    for (int32_t b = 0; b < nt64; ++b) { tab.push_back(L[t]); tab.push_back(a); tab.push_back(b); }
-            }
-            const int64_t k = ((int64_t)tab.size() - o) / 3;
-            if (k) plan.push_back(Launch{2, h, q, o, k});
-        }
-    }
-    // solve plan: fronts with many pivots or rows are solved by one workgroup per 64-row block
-    // (mf_big_*), the others by one workgroup each (mf_fwd / mf_bwd)
-    int big_ns = 96;
-    constexpr int big_d = 256;
-    if (const char* e = std::getenv("EIGSOL_MF_BIG_NS")) big_ns = std::atoi(e);
-    auto &slists = X.slists, &tabf = X.tabf, &tabb = X.tabb, &tabf2 = X.tabf2, &tabb2 = X.tabb2, &lds_asm = X.lds_asm;
-    auto& lds_asm2 = X.lds_asm2;
-    auto &sstart = X.sstart, &nwave = X.nwave, &nsmall = X.nsmall, &nbig = X.nbig, &foff = X.foff, &fcnt = X.fcnt,
-         &boff = X.boff, &bcnt = X.bcnt, &foff2 = X.foff2, &fcnt2 = X.fcnt2, &boff2 = X.boff2, &bcnt2 = X.bcnt2;
-    sstart.assign(H + 2, 0);
-    for (auto* v : {&nwave, &nsmall, &nbig, &foff, &fcnt, &boff, &bcnt, &foff2, &fcnt2, &boff2, &bcnt2}) v->assign(H + 1, 0);
-    // one wave per small front (EIGSOL_MF_WAVE=1): measured 2.21 against 2.01 ms per 1M iteration
-    // with one workgroup per front - the same loads in flight per CU, and the struct rows' GEMV on
-    // one wave instead of four
-    bool wave_ok = false;
-    if (const char* e = std::getenv("EIGSOL_MF_WAVE")) wave_ok = std::atoi(e) != 0;
-    // small subtrees (at most sub_cap pivots, EIGSOL_MF_SUB; 0: off) solved whole by one workgroup
-    // each: their fronts are a contiguous postorder range, so a workgroup walks it up (forward) and
-    // down (backward) with no hand-off between workgroups and no per-height launch.  Measured and
-    // left off (1M convection-diffusion, tools/mf_grid.sh): caps 256 / 512 / 1024 / 2048 pivots
-    // 2.21 / 2.33 / 2.63 / 2.70 ms per iteration against 2.00 - the per-height launches keep every
-    // front of a height in flight, a subtree's fronts run one after the other
-    int sub_cap = 0;
-    if (const char* e = std::getenv("EIGSOL_MF_SUB")) sub_cap = std::atoi(e);
-    if (const char* e = std::getenv("EIGSOL_MF_FLOW"))
-        if (std::atoi(e) != 0) sub_cap = 0;   // the dataflow experiment takes the lower heights itself
-    std::vector<char> insub(nt, 0);
-    X.sub_ranges.clear();
-    if (sub_cap > 0) {
-        std::vector<int64_t> subp(nt, 0);
-        std::vector<int32_t> lo(nt);
-        for (int64_t s2 = 0; s2 < nt; ++s2) {   // postorder: children first
-            subp[s2] += fr[s2].ns;
-            if (fr[s2].ch0 == fr[s2].ch1) lo[s2] = (int32_t)s2;
-            else {
-                int32_t m = (int32_t)s2;
-                for (int32_t k = fr[s2].ch0; k < fr[s2].ch1; ++k) m = std::min(m, lo[chl[k]]);
-                lo[s2] = m;
-            }
-            if (fr[s2].parent >= 0) subp[fr[s2].parent] += subp[s2];
-            insub[s2] = subp[s2] <= sub_cap;
-        }
-        for (int64_t s2 = 0; s2 < nt; ++s2)
-            if (insub[s2] && (fr[s2].parent < 0 || !insub[fr[s2].parent])) {
-                X.sub_ranges.push_back(lo[s2]);
-                X.sub_ranges.push_back((int32_t)s2);
-            }
-        for (int64_t s2 = 0; s2 < nt; ++s2)
-            if (insub[s2]) {
-                X.lds_sub_f = std::max<int32_t>(X.lds_sub_f, (int32_t)((2 * fr[s2].ns + fr[s2].ms) * sb));
-                X.lds_sub_b = std::max<int32_t>(X.lds_sub_b, (int32_t)((fr[s2].ns + fr[s2].ms) * sb));
-            }
-    }
-    lds_asm.assign(H + 1, 0);
-    lds_asm2.assign(H + 1, 0);
-    bool inv_on = true;
-    constexpr int inv_d = 256;   // 256 / 384 / 512: 1.71 / 1.72 / 1.72 ms per 1M iteration (tools/mf_grid.sh)
-    if (const char* e = std::getenv("EIGSOL_MF_INVFORM")) inv_on = std::atoi(e) != 0;
-    int32_t& nflag = X.nflag;
-    int64_t& zsz = X.zsz;
-    for (int32_t h = 0; h <= H; ++h) {
-        std::vector<int32_t> big, wg;
-        for (int64_t t = hstart[h]; t < hstart[h + 1]; ++t) {
-            dev::MfFront& q = fr[lists[t]];
-            q.flag0 = -1;
-            q.zoff = 0;
-            if (insub[lists[t]]) continue;
-            // fronts of at most 64 pivots and inv_d rows stay one-workgroup fronts (inverse form)
-            const bool inv_ok = inv_on && q.ns <= 64 && q.d <= inv_d;
-            const bool is_big = big_ns > 0 && (q.ns >= big_ns || (q.d >= big_d && !inv_ok));
-            if (is_big) big.push_back(lists[t]);
-            else if (wave_ok && q.ns <= dev::kWaveNs && q.ms <= dev::kWaveMs) slists.push_back(lists[t]);
-            else wg.push_back(lists[t]);
-        }
-        nwave[h] = (int64_t)slists.size() - sstart[h];
-        slists.insert(slists.end(), wg.begin(), wg.end());
-        nsmall[h] = (int64_t)wg.size();
-        nbig[h] = (int64_t)big.size();
-        slists.insert(slists.end(), big.begin(), big.end());
-        sstart[h + 1] = (int64_t)slists.size();
-        foff[h] = (int64_t)tabf.size() / 2;
-        boff[h] = (int64_t)tabb.size() / 2;
-        foff2[h] = (int64_t)tabf2.size() / 2;
-        boff2[h] = (int64_t)tabb2.size() / 2;
-        for (int32_t b : big) {
-            dev::MfFront& q = fr[b];
-            const int32_t nblk = (q.ns + 63) / 64, nsb = (q.ms + 63) / 64;
-            q.flag0 = nflag;
-            q.zoff = zsz;
-            nflag += nblk;
-            zsz += q.d;
-            for (int32_t k = 0; k < nblk + nsb; ++k) { tabf.push_back(b); tabf.push_back(k); }
-            for (int32_t k = nblk - 1; k >= 0; --k) { tabb.push_back(b); tabb.push_back(k); }
-            const int32_t npair = (nblk + 1) / 2;
-            for (int32_t k = 0; k < npair + nsb; ++k) { tabf2.push_back(b); tabf2.push_back(k); }
-            for (int32_t k = npair - 1; k >= 0; --k) { tabb2.push_back(b); tabb2.push_back(k); }
-            lds_asm[h] = std::max<int32_t>(lds_asm[h], (int32_t)(q.ns * sb));
-            lds_asm2[h] = std::max<int32_t>(lds_asm2[h], (int32_t)((q.ns + q.ms) * sb));   // d: mf_big_asm_front2
-        }
-        fcnt[h] = (int64_t)tabf.size() / 2 - foff[h];
-        bcnt[h] = (int64_t)tabb.size() / 2 - boff[h];
-        fcnt2[h] = (int64_t)tabf2.size() / 2 - foff2[h];
-        bcnt2[h] = (int64_t)tabb2.size() / 2 - boff2[h];
-    }
-    // inverse forms of the one-workgroup fronts with at most 64 pivots and inv_d rows
-    // (mf_invform_kernel), kept only while the fronts and the forms fit 0.6 of the device memory
-    X.inv_list.clear();
-    X.gsz = 0;
-    {
-        const bool on = inv_on;
-        for (int64_t s2 = 0; s2 < nt; ++s2) {
-            dev::MfFront& q = fr[s2];
-            q.goff = -1;
-            if (on && q.flag0 < 0 && q.ns <= 64 && q.d <= inv_d) {
-                q.goff = (int64_t)fe + X.gsz;
-                X.gsz += 2 * (int64_t)q.d * q.ns;
-                X.inv_list.push_back((int32_t)s2);
-            }
-        }
-        if (((double)fe + (double)X.gsz) * (double)sb > 0.6 * free_bytes) {
-            for (int32_t s2 : X.inv_list) fr[s2].goff = -1;
-            X.inv_list.clear();
-            X.gsz = 0;
-        }
-    }
-    // dataflow launches for the heights below the first one with a large front (EIGSOL_MF_FLOW=0: off)
-    {
-        bool flow = false;
-        if (const char* e = std::getenv("EIGSOL_MF_FLOW")) flow = std::atoi(e) != 0;
-        int32_t hf = H + 1;
-        for (int32_t h = 0; h <= H; ++h)
-            if (nbig[h]) { hf = h; break; }
-        X.hflow = flow ? hf : 0;
-        X.flow_f.clear();
-        X.flow_b.clear();
-        for (int32_t h = 0; h < X.hflow; ++h)
-            for (int64_t t = hstart[h]; t < hstart[h + 1]; ++t) {
-                const dev::MfFront& q = fr[lists[t]];
-                X.flow_f.push_back(lists[t]);
-                X.lds_flow_f = std::max<int32_t>(X.lds_flow_f, (int32_t)((2 * q.ns + q.ms) * sb));
-                X.lds_flow_b = std::max<int32_t>(X.lds_flow_b, (int32_t)((q.ns + q.ms) * sb));
-            }
-        for (int32_t h = X.hflow - 1; h >= 0; --h)
-            for (int64_t t = hstart[h]; t < hstart[h + 1]; ++t) X.flow_b.push_back(lists[t]);
-    }
-    stt.order_seconds = std::chrono::duration<double>(clk::now() - t0).count();
-    if (std::getenv("EIGSOL_MF_DEBUG"))
-        std::fprintf(stderr, "[mf] plan + maps + tables %.3f s; fronts %lld, heights %d, factor entries %.3g, flops %.3g\n",
-                     stt.order_seconds, (long long)nt, H + 1, fac, P.flops);
-    return EIGSOL_OK;
-}
 
 template <class S>
 int mf_create_t(eigsol_ctx* ctx, int dtype, MfHost& X, const S* vals, MfFactor** out, double tau, int64_t* nstatic) {
@@ -2726,50 +1164,25 @@ int mf_create_t(eigsol_ctx* ctx, int dtype, MfHost& X, const S* vals, MfFactor**
     const auto& chl = P.chl;
     const auto& sidx = P.sidx;
     const auto& lists = P.lists;
-    const auto& hstart = P.hstart;
     const int32_t H = P.H;
     const double fe = P.fe, fac = P.fac;
     const int64_t uo = P.uo;
     MfStats& stt = X.stt;
-    using Launch = MfLaunch;
     const auto& dst = X.dst;
-    const auto& plan = X.plan;
-    const auto& tab = X.tab;
-    const auto &slists = X.slists, &tabf = X.tabf, &tabb = X.tabb, &tabf2 = X.tabf2, &tabb2 = X.tabb2,
-               &lds_asm = X.lds_asm;
-    auto& lds_asm2 = X.lds_asm2;
-    const auto &sstart = X.sstart, &nwave = X.nwave, &nsmall = X.nsmall, &nbig = X.nbig, &foff = X.foff,
-               &fcnt = X.fcnt, &boff = X.boff, &bcnt = X.bcnt;
+    const auto &tab = X.tab, &slists = X.slists, &tabf = X.tabf, &tabb = X.tabb;
+    const MfSolveTables& T = X.T;
     const int32_t nflag = X.nflag;
     const int64_t zsz = X.zsz;
-    (void)plan;
     // ---- device
     auto* f = new MfFactor();
     f->ctx = ctx;
     ctx_retain(ctx);
     f->dtype = dtype;
     f->n = n;
-    f->nb = NB;
-    f->nfront = nt;
-    f->hstart = hstart;
-    f->sstart = sstart;
-    f->nwave = nwave;
-    f->nsmall = nsmall;
-    f->nbig = nbig;
-    f->foff = foff;
-    f->fcnt = fcnt;
-    f->boff = boff;
-    f->bcnt = bcnt;
-    f->foff2 = X.foff2;
-    f->fcnt2 = X.fcnt2;
-    f->boff2 = X.boff2;
-    f->bcnt2 = X.bcnt2;
-    f->lds_asm = lds_asm;
-    f->lds_asm2 = lds_asm2;
+    f->T = T;
     // the fused forward launch's assembly holds a whole front's right-hand side in LDS
-    for (int32_t b : lds_asm2)
+    for (int32_t b : T.lds_asm2)
         if (b > 120 * 1024) f->fuse_big = false;
-    if (const char* e = std::getenv("EIGSOL_MF_PAIR")) f->pair = std::atoi(e) != 0;
     if (const char* e = std::getenv("EIGSOL_MF_BACKOFF")) f->backoff = std::atoi(e) & 3;
     if (const char* e = std::getenv("EIGSOL_MF_FUSE_ASM")) f->fuse_asm = std::atoi(e) != 0;
     if (const char* e = std::getenv("EIGSOL_MF_FUSE_BIG"))
@@ -2785,16 +1198,6 @@ int mf_create_t(eigsol_ctx* ctx, int dtype, MfHost& X, const S* vals, MfFactor**
         const char* e = std::getenv("EIGSOL_MF_PREMUL");
         if (!(e && std::atoi(e) == 0)) f->backoff |= 8;
     }
-    f->lds_fwd.assign(H + 1, 0);
-    f->lds_bwd.assign(H + 1, 0);
-    // the inverse-form branch keeps 256 partial sums after the front's vectors
-    const int32_t inv_lds = X.gsz ? (int32_t)(256 * sb) : 0;
-    for (int32_t h = 0; h <= H; ++h)
-        for (int64_t t = sstart[h] + nwave[h]; t < sstart[h] + nwave[h] + nsmall[h]; ++t) {
-            const dev::MfFront& q = fr[slists[t]];
-            f->lds_fwd[h] = std::max<int32_t>(f->lds_fwd[h], (int32_t)((2 * q.ns + q.ms) * sb) + inv_lds);
-            f->lds_bwd[h] = std::max<int32_t>(f->lds_bwd[h], (int32_t)((q.ns + q.ms) * sb) + inv_lds);
-        }
     hipStream_t st = ctx->stream;
     int rc = EIGSOL_OK;
     int32_t *d_tab = nullptr, *d_piv = nullptr, *d_z = nullptr;
@@ -2820,30 +1223,11 @@ int mf_create_t(eigsol_ctx* ctx, int dtype, MfHost& X, const S* vals, MfFactor**
     dm((void**)&f->slists, slists.size() * 4);
     dm((void**)&f->tabf, tabf.size() * 4);
     dm((void**)&f->tabb, tabb.size() * 4);
-    dm((void**)&f->tabf2, tabf2.size() * 4);
-    dm((void**)&f->tabb2, tabb2.size() * 4);
     dm((void**)&f->flags, (size_t)nflag * 4);
     dm((void**)&f->err, 4);
     dm(&f->z, (size_t)zsz * sb);
     dm((void**)&f->bigm, (size_t)n);
     dm(&f->tinv, (size_t)nflag * dev::kMfTinv * sb);
-    f->hflow = X.hflow;
-    f->nflow = (int32_t)X.flow_f.size();
-    f->lds_flow_f = X.lds_flow_f;
-    f->lds_flow_b = X.lds_flow_b;
-    if (const char* e = std::getenv("EIGSOL_MF_FLOW_MODE")) f->flow_mode = std::atoi(e) & 3;
-    dm((void**)&f->flow_f, X.flow_f.size() * 4);
-    dm((void**)&f->flow_b, X.flow_b.size() * 4);
-    dm((void**)&f->fheight, nt * 4);
-    dm((void**)&f->done, nt * 4);
-    f->nsub = (int32_t)(X.sub_ranges.size() / 2);
-    f->lds_bbig.assign(H + 1, 0);
-    for (int32_t h = 0; h <= H; ++h)
-        for (int64_t t = sstart[h] + nwave[h] + nsmall[h]; t < sstart[h] + nwave[h] + nsmall[h] + nbig[h]; ++t)
-            f->lds_bbig[h] = std::max<int32_t>(f->lds_bbig[h], (int32_t)(fr[slists[t]].ms * sb));
-    f->lds_sub_f = X.lds_sub_f ? X.lds_sub_f + inv_lds : 0;
-    f->lds_sub_b = X.lds_sub_b ? X.lds_sub_b + inv_lds : 0;
-    dm((void**)&f->sub_ranges, X.sub_ranges.size() * 4);
     dm(&f->F, ((size_t)fe + (size_t)X.gsz) * sb);
     int32_t* d_inv = nullptr;
     if (!X.inv_list.empty()) dm((void**)&d_inv, X.inv_list.size() * 4);
@@ -2872,25 +1256,18 @@ int mf_create_t(eigsol_ctx* ctx, int dtype, MfHost& X, const S* vals, MfFactor**
         up(f->slists, slists.data(), slists.size() * 4);
         up(f->tabf, tabf.data(), tabf.size() * 4);
         up(f->tabb, tabb.data(), tabb.size() * 4);
-        up(f->tabf2, tabf2.data(), tabf2.size() * 4);
-        up(f->tabb2, tabb2.data(), tabb2.size() * 4);
         hipMemsetAsync(f->flags, 0, std::max<size_t>((size_t)nflag * 4, 4), st);
-        up(f->flow_f, X.flow_f.data(), X.flow_f.size() * 4);
-        up(f->flow_b, X.flow_b.data(), X.flow_b.size() * 4);
-        up(f->fheight, P.height.data(), nt * 4);
-        up(f->sub_ranges, X.sub_ranges.data(), X.sub_ranges.size() * 4);
         {
             // the large fronts' pivot rows (mf_fwd_height_kernel's gather) and an all-unsolved z
             std::vector<uint8_t> bm((size_t)n, 0);
             for (int32_t h = 0; h <= H; ++h)
-                for (int64_t t = sstart[h] + nwave[h] + nsmall[h]; t < sstart[h] + nwave[h] + nsmall[h] + nbig[h]; ++t) {
+                for (int64_t t = T.sstart[h] + T.nsmall[h]; t < T.sstart[h + 1]; ++t) {
                     const dev::MfFront& q = fr[slists[t]];
                     for (int32_t r = 0; r < q.ns; ++r) bm[(size_t)q.c0 + r] = 1;
                 }
             up(f->bigm, bm.data(), (size_t)n);
             hipMemsetD32Async(static_cast<hipDeviceptr_t>(f->z), 0x7FF4DEADu, std::max<size_t>((size_t)zsz * sb / 4, 1), st);
         }
-        hipMemsetAsync(f->done, 0, nt * 4, st);
         hipMemsetAsync(f->err, 0, 4, st);
         up(d_tab, tab.data(), tab.size() * 4);
         if (d_inv) up(d_inv, X.inv_list.data(), X.inv_list.size() * 4);
@@ -2901,7 +1278,7 @@ int mf_create_t(eigsol_ctx* ctx, int dtype, MfHost& X, const S* vals, MfFactor**
         S* F = static_cast<S*>(f->F);
         if (nnz)
             hipLaunchKernelGGL((dev::mf_scatter_kernel<S>), dim3((nnz + 255) / 256), dim3(256), 0, st, d_dst, d_v, nnz, F);
-        for (const Launch& l : plan) {
+        for (const MfLaunch& l : X.plan) {
             if (l.kind == 0)
                 hipLaunchKernelGGL((dev::mf_extend_kernel<S>), dim3(l.cnt), dim3(256), 0, st, f->fronts, d_tab + l.off,
                                    f->cmap, F);
@@ -2920,14 +1297,7 @@ int mf_create_t(eigsol_ctx* ctx, int dtype, MfHost& X, const S* vals, MfFactor**
                                    f->tabb, F, static_cast<S*>(f->tinv));
         }
         if (d_inv)
-        {
-            // EIGSOL_MF_INVFORM=1: round 5's kernel (one HBM load per multiply-add of L21 inv(L11) and inv(U11) U12)
-            const char* ie = std::getenv("EIGSOL_MF_INVFORM");
-            if (ie && std::atoi(ie) == 1)
-                hipLaunchKernelGGL((dev::mf_invform_kernel<S>), dim3(X.inv_list.size()), dim3(256), 0, st, f->fronts, d_inv, F);
-            else
-                hipLaunchKernelGGL((dev::mf_invform2_kernel<S>), dim3(X.inv_list.size()), dim3(256), 0, st, f->fronts, d_inv, F);
-        }
+            hipLaunchKernelGGL((dev::mf_invform2_kernel<S>), dim3(X.inv_list.size()), dim3(256), 0, st, f->fronts, d_inv, F);
         hipMemcpyAsync(hpiv.data(), d_piv, n * 4, hipMemcpyDeviceToHost, st);
         hipMemcpyAsync(hz2, d_z, 8, hipMemcpyDeviceToHost, st);
         if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess)
@@ -2955,40 +1325,22 @@ int mf_create_t(eigsol_ctx* ctx, int dtype, MfHost& X, const S* vals, MfFactor**
     }
     if (rc == EIGSOL_OK) {
         int32_t mx = 0;
-        for (int32_t b : f->lds_fwd) mx = std::max(mx, b);
-        for (int32_t b : f->lds_bwd) mx = std::max(mx, b);
-        for (int32_t b : f->lds_asm) mx = std::max(mx, b);
+        for (int32_t b : T.lds_fwd) mx = std::max(mx, b);
+        for (int32_t b : T.lds_bwd) mx = std::max(mx, b);
+        for (int32_t b : T.lds_asm) mx = std::max(mx, b);
         if (f->fuse_big)
-            for (int32_t b : f->lds_asm2) mx = std::max(mx, b);
-        mx = std::max(mx, std::max(f->lds_flow_f, f->lds_flow_b));
-        mx = std::max(mx, std::max(f->lds_sub_f, f->lds_sub_b));
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(dev::mf_fwd_kernel<S>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(dev::mf_bwd_kernel<S>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(dev::mf_big_asm_kernel<S>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(dev::mf_fwd_asm_kernel<S>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(dev::mf_fwd_height_kernel<S>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(dev::mf_fwd_flow_kernel<S>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(dev::mf_bwd_flow_kernel<S>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(dev::mf_fwd_sub_kernel<S>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(dev::mf_bwd_sub_kernel<S>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(dev::mf_big_bwd_kernel<S>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                *std::max_element(f->lds_bbig.begin(), f->lds_bbig.end())) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(dev::mf_big_bwd2_kernel<S>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                *std::max_element(f->lds_bbig.begin(), f->lds_bbig.end())) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(dev::mf_bwd_big_small_kernel<S>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                std::max(mx, *std::max_element(f->lds_bbig.begin(), f->lds_bbig.end()))) != hipSuccess)
+            for (int32_t b : T.lds_asm2) mx = std::max(mx, b);
+        const int32_t mxb = *std::max_element(T.lds_bbig.begin(), T.lds_bbig.end());
+        auto lds = [](const void* kernel, int32_t bytes) {
+            return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
+        };
+        if (!lds(reinterpret_cast<const void*>(dev::mf_fwd_kernel<S>), mx) ||
+            !lds(reinterpret_cast<const void*>(dev::mf_bwd_kernel<S>), mx) ||
+            !lds(reinterpret_cast<const void*>(dev::mf_big_asm_kernel<S>), mx) ||
+            !lds(reinterpret_cast<const void*>(dev::mf_fwd_asm_kernel<S>), mx) ||
+            !lds(reinterpret_cast<const void*>(dev::mf_fwd_height_kernel<S>), mx) ||
+            !lds(reinterpret_cast<const void*>(dev::mf_big_bwd_kernel<S>), mxb) ||
+            !lds(reinterpret_cast<const void*>(dev::mf_bwd_big_small_kernel<S>), std::max(mx, mxb)))
             rc = fail(EIGSOL_E_HIP, "solve_shifted: multifrontal solve LDS");
     }
     if (rc != EIGSOL_OK) {
@@ -3005,95 +1357,63 @@ int mf_create_t(eigsol_ctx* ctx, int dtype, MfHost& X, const S* vals, MfFactor**
 template <class S>
 static void mf_solve_enqueue(MfFactor* f, hipStream_t st, const S* b, S* out, int32_t ef, int32_t eb) {
     const int64_t n = f->n;
+    const MfSolveTables& T = f->T;
     S* w = static_cast<S*>(f->w);
     S* x = static_cast<S*>(f->x);
     const S* F = static_cast<const S*>(f->F);
-    // one forward launch per height with large fronts (mf_fwd_height_kernel; value flags, no pairs,
+    // one forward launch per height with large fronts (mf_fwd_height_kernel; value flags,
     // EIGSOL_MF_FUSE_BIG=0 off): the gather leaves those fronts' pivot rows of w unsolved
-    const bool hfuse = f->bigm && f->fuse_big && (f->backoff & 4) && !f->pair;
+    const bool hfuse = f->bigm && f->fuse_big && (f->backoff & 4);
     hipLaunchKernelGGL((dev::mf_gather_kernel<S>), dim3((n + 255) / 256), dim3(256), 0, st, f->perm, b, w, n,
                        hfuse ? f->bigm : (const uint8_t*)nullptr);
-    const int32_t H = (int32_t)f->hstart.size() - 2;
+    const int32_t H = (int32_t)T.nsmall.size() - 1;
     S* u = static_cast<S*>(f->u);
     S* z = static_cast<S*>(f->z);
-    const int flow_grid = (int)std::max<int64_t>(1, f->nflow);   // one workgroup per front, in order
-    const bool ff = f->nflow && (f->flow_mode & 1), fb = f->nflow && (f->flow_mode & 2);
-    // two pivot blocks per workgroup (mf_big_fwd2 / bwd2_kernel): value flags only
-    const bool pair = f->pair && (f->backoff & 4);
-    if (f->nsub)
-        hipLaunchKernelGGL((dev::mf_fwd_sub_kernel<S>), dim3(f->nsub), dim3(256), f->lds_sub_f, st, f->fronts,
-                           f->sub_ranges, f->chl, F, f->cmap, f->pinv, w, u);
-    if (ff) {
-        hipLaunchKernelGGL((dev::mf_fwd_flow_kernel<S>), dim3(flow_grid), dim3(256), f->lds_flow_f, st, f->fronts,
-                           f->flow_f, f->nflow, f->done, ef, f->chl, F, f->cmap, f->pinv, w, u, f->err);
-    }
-    for (int32_t h = ff ? f->hflow : 0; h <= H; ++h) {
-        const int32_t* L = f->slists + f->sstart[h];
-        const int64_t nw = f->nwave[h];
-        if (nw)
-            hipLaunchKernelGGL((dev::mf_fwd_wave_kernel<S>), dim3((nw + 3) / 4), dim3(256), 0, st, f->fronts, L,
-                               (int32_t)nw, f->chl, F, f->cmap, f->pinv, w, u);
-        if (hfuse && f->nbig[h]) {
-            hipLaunchKernelGGL((dev::mf_fwd_height_kernel<S>), dim3(f->nsmall[h] + f->nbig[h] + f->fcnt[h]), dim3(256),
-                               std::max(f->lds_fwd[h], f->lds_asm2[h]), st, f->fronts, L + nw, (int32_t)f->nsmall[h],
-                               (int32_t)f->nbig[h], f->tabf + 2 * f->foff[h], f->chl, F, (const S*)f->tinv, f->cmap,
+    for (int32_t h = 0; h <= H; ++h) {
+        const int32_t* L = f->slists + T.sstart[h];
+        if (hfuse && T.nbig[h]) {
+            hipLaunchKernelGGL((dev::mf_fwd_height_kernel<S>), dim3(T.nsmall[h] + T.nbig[h] + T.fcnt[h]), dim3(256),
+                               std::max(T.lds_fwd[h], T.lds_asm2[h]), st, f->fronts, L, (int32_t)T.nsmall[h],
+                               (int32_t)T.nbig[h], f->tabf + 2 * T.foff[h], f->chl, F, (const S*)f->tinv, f->cmap,
                                f->pinv, f->perm, b, w, u, z, f->err, f->backoff, x);
             continue;
         }
         // EIGSOL_MF_FUSE_ASM=0: the small fronts and the large fronts' assembly as two launches
-        const bool fuse = f->fuse_asm && f->nsmall[h] && f->nbig[h];
+        const bool fuse = f->fuse_asm && T.nsmall[h] && T.nbig[h];
         if (fuse)
-            hipLaunchKernelGGL((dev::mf_fwd_asm_kernel<S>), dim3(f->nsmall[h] + f->nbig[h]), dim3(256),
-                               std::max(f->lds_fwd[h], f->lds_asm[h]), st, f->fronts, L + nw, f->nsmall[h], f->chl, F,
+            hipLaunchKernelGGL((dev::mf_fwd_asm_kernel<S>), dim3(T.nsmall[h] + T.nbig[h]), dim3(256),
+                               std::max(T.lds_fwd[h], T.lds_asm[h]), st, f->fronts, L, T.nsmall[h], f->chl, F,
                                f->cmap, f->pinv, w, u, z, f->backoff);
-        else if (f->nsmall[h])
-            hipLaunchKernelGGL((dev::mf_fwd_kernel<S>), dim3(f->nsmall[h]), dim3(256), f->lds_fwd[h], st, f->fronts,
-                               L + nw, f->chl, F, f->cmap, f->pinv, w, u);
-        if (f->nbig[h]) {
+        else if (T.nsmall[h])
+            hipLaunchKernelGGL((dev::mf_fwd_kernel<S>), dim3(T.nsmall[h]), dim3(256), T.lds_fwd[h], st, f->fronts,
+                               L, f->chl, F, f->cmap, f->pinv, w, u);
+        if (T.nbig[h]) {
             if (!fuse)
-                hipLaunchKernelGGL((dev::mf_big_asm_kernel<S>), dim3(f->nbig[h]), dim3(256), f->lds_asm[h], st,
-                                   f->fronts, L + nw + f->nsmall[h], f->chl, f->cmap, f->pinv, w, (const S*)u, z,
+                hipLaunchKernelGGL((dev::mf_big_asm_kernel<S>), dim3(T.nbig[h]), dim3(256), T.lds_asm[h], st,
+                                   f->fronts, L + T.nsmall[h], f->chl, f->cmap, f->pinv, w, (const S*)u, z,
                                    f->backoff);
-            if (pair)
-                hipLaunchKernelGGL((dev::mf_big_fwd2_kernel<S>), dim3(f->fcnt2[h]), dim3(256), 0, st, f->fronts,
-                                   f->tabf2 + 2 * f->foff2[h], F, (const S*)f->tinv, (const S*)z, w, u, f->err,
-                                   f->backoff, x);
-            else
-                hipLaunchKernelGGL((dev::mf_big_fwd_kernel<S>), dim3(f->fcnt[h]), dim3(256), 0, st, f->fronts,
-                                   f->tabf + 2 * f->foff[h], F, (const S*)f->tinv, z, w, u, f->flags, ef,
-                                   f->err, f->backoff, x);
+            hipLaunchKernelGGL((dev::mf_big_fwd_kernel<S>), dim3(T.fcnt[h]), dim3(256), 0, st, f->fronts,
+                               f->tabf + 2 * T.foff[h], F, (const S*)f->tinv, z, w, u, f->flags, ef, f->err,
+                               f->backoff, x);
         }
     }
-    for (int32_t h = H; h >= (fb ? f->hflow : 0); --h) {
-        const int32_t* L = f->slists + f->sstart[h];
-        if (f->nbig[h] && pair)
-            hipLaunchKernelGGL((dev::mf_big_bwd2_kernel<S>), dim3(f->bcnt2[h]), dim3(256), f->lds_bbig[h], st,
-                               f->fronts, f->tabb2 + 2 * f->boff2[h], F, (const S*)f->tinv, f->sidx, (const S*)w, x,
+    for (int32_t h = H; h >= 0; --h) {
+        const int32_t* L = f->slists + T.sstart[h];
+        if (f->fuse_asm && T.nbig[h] && T.nsmall[h]) {
+            hipLaunchKernelGGL((dev::mf_bwd_big_small_kernel<S>), dim3(T.bcnt[h] + T.nsmall[h]), dim3(256),
+                               std::max(T.lds_bbig[h], T.lds_bwd[h]), st, f->fronts, f->tabb + 2 * T.boff[h],
+                               T.bcnt[h], L, F, (const S*)f->tinv, f->sidx, (const S*)w, x, f->flags, eb, f->err,
+                               f->backoff);
+            continue;
+        }
+        if (T.nbig[h])
+            hipLaunchKernelGGL((dev::mf_big_bwd_kernel<S>), dim3(T.bcnt[h]), dim3(256), T.lds_bbig[h], st, f->fronts,
+                               f->tabb + 2 * T.boff[h], F, (const S*)f->tinv, f->sidx, (const S*)w, x, f->flags, eb,
                                f->err, f->backoff);
-        const bool fuse = f->fuse_asm && !pair && f->nbig[h] && f->nsmall[h];
-        if (fuse)
-            hipLaunchKernelGGL((dev::mf_bwd_big_small_kernel<S>), dim3(f->bcnt[h] + f->nsmall[h]), dim3(256),
-                               std::max(f->lds_bbig[h], f->lds_bwd[h]), st, f->fronts, f->tabb + 2 * f->boff[h],
-                               f->bcnt[h], L + f->nwave[h], F, (const S*)f->tinv, f->sidx, (const S*)w, x, f->flags, eb,
-                               f->err, f->backoff);
-        else if (f->nbig[h] && !pair)
-            hipLaunchKernelGGL((dev::mf_big_bwd_kernel<S>), dim3(f->bcnt[h]), dim3(256), f->lds_bbig[h], st, f->fronts,
-                               f->tabb + 2 * f->boff[h], F, (const S*)f->tinv, f->sidx, (const S*)w, x, f->flags, eb,
-                               f->err, f->backoff);
-        const int64_t nw = f->nwave[h];
-        if (f->nsmall[h] && !fuse)
-            hipLaunchKernelGGL((dev::mf_bwd_kernel<S>), dim3(f->nsmall[h]), dim3(256), f->lds_bwd[h], st, f->fronts,
-                               L + nw, F, f->sidx, w, x);
-        if (nw)
-            hipLaunchKernelGGL((dev::mf_bwd_wave_kernel<S>), dim3((nw + 3) / 4), dim3(256), 0, st, f->fronts, L,
-                               (int32_t)nw, F, f->sidx, w, x);
+        if (T.nsmall[h])
+            hipLaunchKernelGGL((dev::mf_bwd_kernel<S>), dim3(T.nsmall[h]), dim3(256), T.lds_bwd[h], st, f->fronts,
+                               L, F, f->sidx, w, x);
     }
-    if (f->nsub)
-        hipLaunchKernelGGL((dev::mf_bwd_sub_kernel<S>), dim3(f->nsub), dim3(256), f->lds_sub_b, st, f->fronts,
-                           f->sub_ranges, F, f->sidx, (const S*)w, x);
-    if (fb)
-        hipLaunchKernelGGL((dev::mf_bwd_flow_kernel<S>), dim3(flow_grid), dim3(256), f->lds_flow_b, st, f->fronts,
-                           f->flow_b, f->nflow, f->done, eb, f->hflow, f->fheight, F, f->sidx, (const S*)w, x, f->err);
     hipLaunchKernelGGL((dev::mf_scatter_out_kernel<S>), dim3((n + 255) / 256), dim3(256), 0, st, f->perm, x, out, n);
 }
 
@@ -3114,26 +1434,12 @@ int mf_solve_t(MfFactor* f, const S* b, S* out) {
         int32_t e = 0;
         EIGSOL_HIP(hipMemcpyAsync(&e, f->err, 4, hipMemcpyDeviceToHost, st));
         EIGSOL_HIP(hipStreamSynchronize(st));
-        std::fprintf(stderr, "[mf] solve epoch %d err %d nflow %d hflow %d\n", f->epoch, e, f->nflow, f->hflow);
+        std::fprintf(stderr, "[mf] solve epoch %d err %d\n", f->epoch, e);
     }
     return EIGSOL_OK;
 }
 
 const int32_t* mf_err_word(const MfFactor* f) { return f->err; }
-
-MfHost* mf_host_new() { return new MfHost(); }
-const MfStats& mf_host_stats(const MfHost* X) { return X->stt; }
-void mf_host_free(MfHost* X) { delete X; }
-
-int mf_prepare(int64_t n, const std::vector<int32_t>& rp, const std::vector<int32_t>& ci, int dtype, double free_bytes,
-               MfHost* X, const std::atomic<bool>* stop) {
-    if (dtype != EIGSOL_C128 && dtype != EIGSOL_F64) return EIGSOL_E_UNSUPPORTED;
-    try {
-        return mf_prepare_host(n, rp, ci, dtype == EIGSOL_C128, free_bytes, *X, stop);
-    } catch (const std::exception&) {   // host allocation of the plan: decline
-        return EIGSOL_E_UNSUPPORTED;
-    }
-}
 
 int mf_create(eigsol_ctx* ctx, int dtype, MfHost* X, const void* v, MfFactor** out, double static_pivot,
               int64_t* nstatic) {

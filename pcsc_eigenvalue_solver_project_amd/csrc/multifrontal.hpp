@@ -1,12 +1,14 @@
-// Nested-dissection multifrontal LU of the general-sparse shifted solve (multifrontal.hip): host
-// interface.  Used by gmres.hip as the exact factor K of M = A - sigma I where the natural-order
-// symbolic LU passes its fill cap (round 5: the permuted 1M convection-diffusion matrix).
+// Nested-dissection multifrontal LU of the general-sparse shifted solve: host interface.  Used by
+// gmres.hip as the exact factor K of M = A - sigma I where the natural-order symbolic LU passes its
+// fill cap (round 5: the permuted 1M convection-diffusion matrix).  The host half (mf_host_*,
+// mf_prepare) is multifrontal_plan.cpp, the device half multifrontal.hip; this header is plain C++.
 #pragma once
 
 #include <atomic>
+#include <cstdint>
 #include <vector>
 
-#include "internal.hpp"
+#include "eigsol_hip.h"
 
 namespace eigsol {
 
