@@ -104,9 +104,7 @@ struct CsrArgs {
     int32_t cont;            // second part: read the first part's decision, add to its partial
     // pair path (csr_pair_kernel; pair_prologue in kernels_common.hpp)
     int32_t pair_mode;       // the session runs on the pair carry (single launches use pair_prologue too)
-    int32_t pair_ntiles;
-    const int4* pair_meta;   // per tile {first halo slice, end halo slice, first row read, end row read}
-    part4* pair_part;        // partials of a pair launch's second product
+    part4* pair_part;       // partials of a pair launch's second product
     part4* pair_blk;
 };
 
@@ -713,8 +711,9 @@ __device__ __forceinline__ uint32_t slice_entry(uint32_t off, int k, int lane) {
 
 // Every load of one slice's first KB entries, its window and the row lengths.  Loads are clamped
 // (to entry K-1, window entry wl-1): same cache lines, no extra bytes, no exec-masked loads.
-// kClamp (halo slices of a pair tile): only lanes [lane_lo, lane_hi] hold rows that are read, so
-// the value and offset loads of the other lanes repeat the nearest such lane's addresses.
+// kClamp (csr_pair_kernel): only lanes [lane_lo, lane_hi] hold rows that are read (all 64 of an own
+// slice, fewer of a halo slice at the end of a workgroup's range), so the value and offset loads
+// of the other lanes repeat the nearest such lane's addresses.
 template <class S, int KB, bool kG, bool kDist = false, bool kClamp = false>
 __device__ __forceinline__ void slice_issue(const CsrArgs<S>& a, const S* xin, int slice, int4 m,
                                             SliceRegs<S, KB, kG>& R, const S* gin = nullptr, int lane_lo = 0,
@@ -787,15 +786,16 @@ __device__ __forceinline__ S shfl_s(S v, int src) {
     else return S{__shfl(v.re, src, 64), __shfl(v.im, src, 64)};
 }
 
-// kPair (csr_pair_kernel, first product of a tile): 1: an own slice, whose rows also go, scaled
-// by s, to the tile's LDS array lw (entry 0 = row span_lo); 2: a halo slice, whose rows
-// [need_lo, need_hi) go to the LDS array only.
+// kPair (csr_pair_kernel, first product): 1: an own slice, whose rows go, scaled by s, to the
+// workgroup's LDS ring lw (row r at entry r mod kPairRing) and nowhere else; 2: a halo slice, whose
+// rows [need_lo, need_hi) go to the ring and which leaves no partials.
+constexpr int kPairRing = 16 * kSliceRows;   // rows of s w1 a workgroup keeps (see csr_pair_kernel)
 template <class S, bool kPower, int KB, bool kG, bool kDist = false, int kPair = 0>
 __device__ __forceinline__ void slice_compute(const CsrArgs<S>& a, const S* xin, S* yout, double nrm,
                                               const SliceRegs<S, KB, kG>& R, int4 mc, int sl, S* xw,
                                               double& n2, double& rr, double& ri, const S* gin = nullptr,
-                                              int parity = 0, S* lw = nullptr, int span_lo = 0, double s = 1.0,
-                                              int need_lo = 0, int need_hi = 0) {
+                                              int parity = 0, S* lw = nullptr, double s = 1.0, int need_lo = 0,
+                                              int need_hi = 0) {
     const int lane = threadIdx.x & 63;
     const int K = mc.z & 0xff;
     const S* sval = a.sval;
@@ -879,10 +879,10 @@ __device__ __forceinline__ void slice_compute(const CsrArgs<S>& a, const S* xin,
         if constexpr (kPower) xi = scale_in(xin[rowc + a.xoff], nrm);
     }
     if (valid) {
-        if constexpr (kPair != 2) yout[row] = sacc;   // a non-temporal store measured slower: the next launch reads y as x
-        if constexpr (kPair == 1) lw[row - span_lo] = s * sacc;   // s = 2^-e: exact
+        if constexpr (kPair == 0) yout[row] = sacc;   // a non-temporal store measured slower: the next launch reads y as x
+        if constexpr (kPair == 1) lw[row & (kPairRing - 1)] = s * sacc;   // s = 2^-e: exact
         if constexpr (kPair == 2)
-            if (row >= need_lo && row < need_hi) lw[row - span_lo] = s * sacc;
+            if (row >= need_lo && row < need_hi) lw[row & (kPairRing - 1)] = s * sacc;
         if constexpr (kPower && kPair != 2) {
             n2 += sq_abs(sacc);
             acc_dot(rr, ri, xi, sacc);
@@ -1030,33 +1030,35 @@ __global__ __launch_bounds__(kThreads) void csr_slice_kernel(CsrArgs<S> a, int p
 
 // ============================================================================ pair kernel
 // Two power iterations per pass over a matrix whose slices are all window slices (pair_prologue
-// in kernels_common.hpp has the algebra and the control plane).  A workgroup takes tiles of
-// kPairT consecutive slices, XCD-contiguous like the slice ranges above.  First product: the
-// tile's own slices and the halo slices their windows reach are multiplied exactly as
-// slice_compute does for a single launch (w1 is bitwise a single launch's y); own rows go to
-// global memory, and own and halo rows, scaled by s, to a block-level LDS array.  After one block
-// barrier the own slices, whose values and offsets are still in the owning wave's registers, are
-// multiplied again with s w1 read from the LDS array in place of the x window.  The LDS array is
-// double buffered, so one barrier per tile is enough: a wave can only write buffer b again after
-// the barrier of the tile in between, which every wave reaches after its reads of b.
-// Halo slices load only the lanes whose rows are read (slice_issue, kClamp).
-// own slices per tile.  band10m f64, us per iteration,
-// two workgroups per CU: 4: 175, 8: 142, 16: 120-125, 20: 123 (248 VGPRs); the halo slices of a
-// band of half-width 64 are read whole, so the tile size sets the extra matrix traffic (2 / T)
-constexpr int kPairT = 16;
-constexpr int kPairHalo = 4;              // halo slices a tile may have (both sides together)
-constexpr int kPairSpan = (kPairT + kPairHalo) * kSliceRows;
-constexpr int kPairBlocksPerCU = 2;        // T = 16: 1 / 2 / 3 per CU 148 / 120 / 130 us
-// the next tile's loads go out while this tile computes (two register sets of kPairT / kWaves
-// slices per wave); larger tiles hold too many registers for that and rely on the other resident blocks
-constexpr bool kPairPipe = kPairT <= 8;
-static_assert(kPairT % kWaves == 0 && kPairHalo <= kWaves, "pair tile: whole rounds of waves, one halo slice per wave");
+// in kernels_common.hpp has the algebra and the control plane).  A workgroup walks one contiguous
+// range of slices in order, in rounds of kWaves slices, one per wave; the ranges are XCD-contiguous
+// like the slice ranges above and equal to within one round.  First product: a round's slices are
+// multiplied exactly as slice_compute does for a single launch (w1 is bitwise a single launch's
+// y), and their rows, scaled by s, go to a block-level LDS ring of kPairRing rows indexed by
+// row mod kPairRing; w1 itself is not stored (eigsol_power_finish recomputes it when a stop
+// returns it).  After the round's block barrier a wave multiplies its slice of the round before
+// again, from the values and offsets it kept in registers, with s w1 read from the ring in place
+// of the x window.  A window is kSliceWin = 256 entries and holds the slice's own 64 rows, so it
+// reaches at most kPairReach = 3 slices to either side: after the barrier of round r the ring
+// holds every slice a window of round r-1 can reach above, and the slices written next (round
+// r+1) lie less than 16 slices above the lowest one such a window still reads.
+// Range ends: the slices below and above the range that its windows reach (at most three a side)
+// join the range's first and last rounds as halo slices (kPair == 2: only the lanes whose rows are
+// read are loaded, no partials); they are the only slices read twice.
+// The next round's loads go out before this round computes (three register sets, the loop is
+// unrolled by three so each has a static name).  band10m f64 (150 VGPRs, no scratch, 16.1 KiB of
+// LDS), us per iteration by workgroups per CU: 2: 120, 3: 116, 4 (held to 128 VGPRs, which
+// spills 56 bytes a lane): 121; without the prefetch, three per CU: 116, no different.
+constexpr int kPairReach = (kSliceWin - kSliceRows) / kSliceRows;
+constexpr int kPairBlocksPerCU = 3;
+static_assert(kPairRing >= (2 * kPairReach + 2 * kWaves + 1) * kSliceRows && (kPairRing & (kPairRing - 1)) == 0,
+              "pair ring: the reads of round r-1 and the writes of round r+1 never share an entry");
 
-// Second product of one own slice from its registers: x = s w1 from the tile's LDS array.
+// Second product of one own slice from its registers: x = s w1 from the workgroup's LDS ring.
 template <class S, int KB>
 __device__ __forceinline__ void slice_compute2(const CsrArgs<S>& a, S* yout, const SliceRegs<S, KB, false>& R,
-                                               int4 mc, int sl, const S* lw, int span_lo, double& n2,
-                                               double& rr, double& ri) {
+                                               int4 mc, int sl, const S* lw, double& n2, double& rr,
+                                               double& ri) {
     const int lane = threadIdx.x & 63;
     const int K = mc.z & 0xff;
     const S* sval = a.sval;
@@ -1069,11 +1071,11 @@ __device__ __forceinline__ void slice_compute2(const CsrArgs<S>& a, S* yout, con
     const int row = sl * kSliceRows + lane;
     const bool valid = row < a.nrows;
     const int rowc = valid ? row : a.nrows - 1;
-    const S* xw = lw + (mc.y - span_lo);   // the slice's window lies inside the tile's span
+    const uint32_t w0 = (uint32_t)mc.y;   // window entry e is row w0 + e
     S sacc = s_zero<S>();
 #pragma unroll
     for (int u = 0; u < KB; ++u) {
-        const S pr = mul(slice_val(R, u), xw[(R.c[u >> 2] >> (8 * (u & 3))) & 0xffu]);
+        const S pr = mul(slice_val(R, u), lw[(w0 + ((R.c[u >> 2] >> (8 * (u & 3))) & 0xffu)) & (kPairRing - 1)]);
         if (u < R.len) sacc = add(sacc, pr);
     }
     for (int k0 = KB & ~3; k0 < K; k0 += 4) {
@@ -1081,12 +1083,12 @@ __device__ __forceinline__ void slice_compute2(const CsrArgs<S>& a, S* yout, con
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const S pr = mul(ldg(sval, slice_entry<S>((uint32_t)mc.x, min(k0 + u, K - 1), lane)),
-                             xw[(cw >> (8 * u)) & 0xffu]);
+                             lw[(w0 + ((cw >> (8 * u)) & 0xffu)) & (kPairRing - 1)]);
             if (k0 + u >= KB && k0 + u < R.len) sacc = add(sacc, pr);
         }
     }
     if (valid) {
-        const S xi = lw[rowc - span_lo];
+        const S xi = lw[rowc & (kPairRing - 1)];
         yout[row] = sacc;
         n2 += sq_abs(sacc);
         acc_dot(rr, ri, xi, sacc);
@@ -1094,13 +1096,11 @@ __device__ __forceinline__ void slice_compute2(const CsrArgs<S>& a, S* yout, con
 }
 
 template <class S, int KB>
-__global__ __launch_bounds__(kThreads) void csr_pair_kernel(CsrArgs<S> a, int parity, const S* xin, S* out1,
-                                                            S* out2) {
+__global__ __launch_bounds__(kThreads) void csr_pair_kernel(CsrArgs<S> a, int parity, const S* xin, S* out2) {
     static_assert(is_real_v<S>, "pair kernel: real scalars");
-    constexpr int Q = kPairT / kWaves;   // own slices a wave holds across the barrier
     using Regs = SliceRegs<S, KB, false>;
     __shared__ __align__(16) S xw_all[kWaves][kSliceWin];
-    __shared__ __align__(16) S w1s[2][kPairSpan];
+    __shared__ __align__(16) S ring[kPairRing];
     __shared__ double sm[3 * kWaves];
     __shared__ Prologue pro;
     __shared__ int s_last;
@@ -1111,77 +1111,89 @@ __global__ __launch_bounds__(kThreads) void csr_pair_kernel(CsrArgs<S> a, int pa
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     double p[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 
-    // XCD-contiguous tile ranges; the tile loop and its barrier are block-uniform
-    const int tstep = gridDim.x >> 3;
-    const int chunk = (a.pair_ntiles + 7) >> 3;
-    const int tbeg = (blockIdx.x & 7) * chunk;
-    const int tend = min(a.pair_ntiles, tbeg + chunk);
-    auto issue = [&](Regs(&R)[Q], int4(&mc)[Q], int tl) {
+    // own range [rb, re): whole rounds of this XCD's eighth of the slices, split evenly over its
+    // workgroups (an empty range when the XCD has fewer rounds than workgroups)
+    const int nb = gridDim.x >> 3, bi = blockIdx.x >> 3;   // grid % 8 == 0
+    const int chunk = (a.nslices + 7) >> 3;
+    const int xb = min((int)(blockIdx.x & 7) * chunk, a.nslices), xe = min(a.nslices, xb + chunk);
+    const int nr = (xe - xb + kWaves - 1) / kWaves;
+    const int rb = xb + kWaves * (int)((int64_t)bi * nr / nb);
+    const int re = min(xe, xb + kWaves * (int)((int64_t)(bi + 1) * nr / nb));
+    // rows [lo, hi) the range's windows read: only its first and last kPairReach slices reach outside
+    int lo = rb * kSliceRows, hi = min(re * kSliceRows, a.nrows);
 #pragma unroll
-        for (int j = 0; j < Q; ++j) mc[j] = ld_uniform(a.slice_meta, min(tl * kPairT + j * kWaves + wave, a.nslices - 1));
-#pragma unroll
-        for (int j = 0; j < Q; ++j)   // past the last slice: reloads it, unused
-            slice_issue<S, KB, false>(a, xin, min(tl * kPairT + j * kWaves + wave, a.nslices - 1), mc[j], R[j]);
+    for (int j = 0; j < kPairReach; ++j) {
+        if (rb + j < re) lo = min(lo, ld_uniform(a.slice_meta, rb + j).y);
+        if (re - 1 - j >= rb) {
+            const int4 m = ld_uniform(a.slice_meta, re - 1 - j);
+            hi = max(hi, m.y + ((m.z >> 9) & 0x1ff));
+        }
+    }
+    // slices walked: the own range and its halo slices; every loop bound below is block-uniform
+    const int eb = lo / kSliceRows, ee = rb < re ? (hi + kSliceRows - 1) / kSliceRows : eb;
+
+    auto issue = [&](Regs& R, int4& mc, int sl) {
+        const int slc = min(sl, ee - 1);   // past the last slice: reloads it, unused
+        mc = ld_uniform(a.slice_meta, slc);
+        slice_issue<S, KB, false, false, true>(a, xin, slc, mc, R, nullptr, min(max(lo - slc * kSliceRows, 0), 63),
+                                               min(max(hi - 1 - slc * kSliceRows, 0), 63));
     };
-    // one tile from registers R; the next tile's loads go out into Rn behind the halo slice's
-    auto run = [&](const Regs(&R)[Q], const int4(&mc)[Q], int tl, int b, Regs(&Rn)[Q], int4(&mn)[Q]) {
-        const int4 tm = ld_uniform(a.pair_meta, tl);
-        const int s0 = tl * kPairT, s1 = min(s0 + kPairT, a.nslices);
-        const int hl = s0 - tm.x, nh = hl + (tm.y - s1);   // halo slices: below the tile, in all
-        const int span_lo = tm.x * kSliceRows;
-        S* lw = w1s[b];
-        Regs RH;
-        int4 mh = make_int4(0, 0, 0, 0);
-        const int hs = wave < hl ? tm.x + wave : s1 + (wave - hl);   // wave < nh: this wave's halo slice
-        if (wave < nh) {
-            mh = ld_uniform(a.slice_meta, hs);
-            slice_issue<S, KB, false, false, true>(a, xin, hs, mh, RH, nullptr, min(max(tm.z - hs * kSliceRows, 0), 63),
-                                                   min(max(tm.w - 1 - hs * kSliceRows, 0), 63));
-        }
-        if (kPairPipe && tl + tstep < tend) issue(Rn, mn, tl + tstep);
-#pragma unroll
-        for (int j = 0; j < Q; ++j) {
-            const int sl = s0 + j * kWaves + wave;
-            if (sl < s1)
-                slice_compute<S, true, KB, false, false, 1>(a, xin, out1, nrm, R[j], mc[j], sl, xw_all[wave], p[0], p[1],
-                                                            p[2], nullptr, 0, lw, span_lo, s);
-        }
-        if (wave < nh) {
-            double z0 = 0.0, z1 = 0.0, z2 = 0.0;
-            slice_compute<S, true, KB, false, false, 2>(a, xin, out1, nrm, RH, mh, hs, xw_all[wave], z0, z1, z2, nullptr,
-                                                        0, lw, span_lo, s, tm.z, tm.w);
+    // One round: the next round's loads into N, the first product of slice sl from C, the barrier,
+    // then the second product of the round before's slice from K.
+    auto round = [&](const Regs& K, const int4& mk, const Regs& C, const int4& mc, Regs& N, int4& mn, int sl) {
+        if (sl - wave + kWaves < ee) issue(N, mn, sl + kWaves);
+        if (sl < ee) {
+            if (sl >= rb && sl < re) {
+                slice_compute<S, true, KB, false, false, 1>(a, xin, nullptr, nrm, C, mc, sl, xw_all[wave], p[0], p[1],
+                                                            p[2], nullptr, 0, ring, s);
+            } else {
+                double z0 = 0.0, z1 = 0.0, z2 = 0.0;
+                slice_compute<S, true, KB, false, false, 2>(a, xin, nullptr, nrm, C, mc, sl, xw_all[wave], z0, z1, z2,
+                                                            nullptr, 0, ring, s, lo, hi);
+            }
         }
         __syncthreads();
-#pragma unroll
-        for (int j = 0; j < Q; ++j) {
-            const int sl = s0 + j * kWaves + wave;
-            if (sl < s1) slice_compute2<S, KB>(a, out2, R[j], mc[j], sl, lw, span_lo, p[3], p[4], p[5]);
-        }
+        const int sp = sl - kWaves;
+        if (sp >= rb && sp < re) slice_compute2<S, KB>(a, out2, K, mk, sp, ring, p[3], p[4], p[5]);
     };
     {
-        Regs RA[Q], RB[Q];
-        int4 ma[Q], mb[Q];
-        int tl = tbeg + (blockIdx.x >> 3);
-        if constexpr (kPairPipe) {
-            // unrolled by two so both register sets have static names
-            if (tl < tend) issue(RA, ma, tl);
-            while (tl < tend) {
-                run(RA, ma, tl, 0, RB, mb);
-                tl += tstep;
-                if (tl >= tend) break;
-                run(RB, mb, tl, 1, RA, ma);
-                tl += tstep;
-            }
-        } else {
-            for (int b = 0; tl < tend; tl += tstep, b ^= 1) {
-                issue(RA, ma, tl);
-                run(RA, ma, tl, b, RB, mb);
-            }
+        // unrolled by three so the register sets have static names; one round past the last
+        // slice runs the last round's second products
+        Regs RA, RB, RC;
+        int4 ma = make_int4(0, 0, 0, 0), mb = ma, mcc = ma;
+        const int end = eb < ee ? ee + kWaves : eb;
+        int sl = eb + wave;
+        if (eb < ee) issue(RA, ma, sl);
+        while (sl - wave < end) {
+            round(RC, mcc, RA, ma, RB, mb, sl);
+            sl += kWaves;
+            if (sl - wave >= end) break;
+            round(RA, ma, RB, mb, RC, mcc, sl);
+            sl += kWaves;
+            if (sl - wave >= end) break;
+            round(RB, mb, RC, mcc, RA, ma, sl);
+            sl += kWaves;
         }
     }
     block_sum3(p[0], p[1], p[2], sm);
     block_sum3(p[3], p[4], p[5], sm);
     pair_reduce(p, a.blk_part, a.pair_blk, &a.ctl->counter, a.my_part, a.pair_part, sm, &s_last);
+}
+
+// The first product of a pair launch on its own, stored: yout = A (xin / nrm) with the slice code
+// of a single launch, so yout is bitwise the w1 the pair launch kept on chip.  No prologue, no
+// partials (csr_pair_first_product).
+template <class S, int KB>
+__global__ __launch_bounds__(kThreads) void csr_pair_first_kernel(CsrArgs<S> a, const S* xin, S* yout, double nrm) {
+    __shared__ __align__(16) S xw_all[kWaves][kSliceWin];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int sl = blockIdx.x * kWaves + wave; sl < a.nslices; sl += gridDim.x * kWaves) {
+        SliceRegs<S, KB, false> R;
+        const int4 mc = ld_uniform(a.slice_meta, sl);
+        slice_issue<S, KB, false>(a, xin, sl, mc, R);
+        double z0 = 0.0, z1 = 0.0, z2 = 0.0;
+        slice_compute<S, true, KB, false>(a, xin, yout, nrm, R, mc, sl, xw_all[wave], z0, z1, z2);
+    }
 }
 
 // Start of a peer-exchange session (begin(), after the x0 norm partial): x0's halo rows and the
@@ -1436,7 +1448,7 @@ void csr_release(eigsol_csr* A) {
     if (A->val) (void)hipFree(A->val);
     if (A->tile_meta) (void)hipFree(A->tile_meta);
     if (A->tile_win) (void)hipFree(A->tile_win);
-    for (void* q : {(void*)A->slice_meta, A->sval, (void*)A->scol8, (void*)A->scol32, (void*)A->slen, (void*)A->pair_meta})
+    for (void* q : {(void*)A->slice_meta, A->sval, (void*)A->scol8, (void*)A->scol32, (void*)A->slen})
         if (q) (void)hipFree(q);
     if (A->send_idx) (void)hipFree(A->send_idx);
     if (A->send_buf) (void)hipFree(A->send_buf);
@@ -1640,30 +1652,18 @@ static bool build_slices(const int32_t* rowptr, const int32_t* col, const void* 
     return true;
 }
 
-// Tiles of the pair kernel: per tile of kPairT slices the rows its windows read [lo, hi) and the
-// slices [h0, h1) holding them (the tile's own and its halo slices).  False when some slice
-// gathers or a tile's span does not fit the kernel's LDS array (the matrix keeps single launches).
-static bool build_pair_tiles(const SliceLayout& L, int64_t nrows, std::vector<int32_t>& tm) {
+// The pair kernel's rule, per slice: a window slice whose window lies inside the rows and holds
+// the slice's own rows, so that it reaches at most kPairReach slices to either side (what the
+// kernel's ring and its one-round lag allow).  False when some slice gathers (the matrix keeps
+// single launches).
+static bool pair_eligible(const SliceLayout& L, int64_t nrows) {
     const int64_t ns = (int64_t)L.meta.size() / 4;
     if (ns == 0 || L.any_gather) return false;
-    const int64_t nt = (ns + kPairT - 1) / kPairT;
-    tm.assign((size_t)(4 * nt), 0);
-    for (int64_t t = 0; t < nt; ++t) {
-        const int64_t s0 = t * kPairT, s1 = std::min<int64_t>(ns, s0 + kPairT);
-        int64_t lo = s0 * kSliceRows, hi = std::min<int64_t>(nrows, s1 * kSliceRows);
-        for (int64_t sl = s0; sl < s1; ++sl) {
-            const int64_t w0 = L.meta[4 * sl + 1], wl = (L.meta[4 * sl + 2] >> 9) & 0x1ff;
-            if (w0 < 0) return false;
-            lo = std::min(lo, w0);
-            hi = std::max(hi, w0 + wl);
-        }
-        if (lo < 0 || hi > nrows) return false;
-        const int64_t h0 = std::min(s0, lo / kSliceRows), h1 = std::max(s1, (hi + kSliceRows - 1) / kSliceRows);
-        if ((s0 - h0) + (h1 - s1) > kPairHalo || (h1 - h0) * kSliceRows > kPairSpan) return false;
-        tm[4 * t] = (int32_t)h0;
-        tm[4 * t + 1] = (int32_t)h1;
-        tm[4 * t + 2] = (int32_t)lo;
-        tm[4 * t + 3] = (int32_t)hi;
+    for (int64_t sl = 0; sl < ns; ++sl) {
+        const int64_t w0 = L.meta[4 * sl + 1], wl = (L.meta[4 * sl + 2] >> 9) & 0x1ff;
+        const int64_t r0 = sl * kSliceRows, r1 = std::min<int64_t>(nrows, r0 + kSliceRows);
+        if (w0 < 0 || w0 + wl > nrows || w0 > r0 || w0 + wl < r1) return false;
+        if (r0 - w0 > kPairReach * kSliceRows || w0 + wl - r0 > (kPairReach + 1) * kSliceRows) return false;
     }
     return true;
 }
@@ -1804,16 +1804,8 @@ int csr_upload(eigsol_ctx* ctx, int dtype, int64_t nrows, int64_t ncols, int64_t
             return fail(EIGSOL_E_HIP, std::string("eigsol_csr_create: slice upload: ") + hipGetErrorString(e));
         }
         // pair path: decided here, once; square single-GPU f64 matrices of window slices only
-        std::vector<int32_t> ptm;
-        if (dtype == EIGSOL_F64 && nrows == ncols && xoff == 0 && !A->slice_gather && build_pair_tiles(SL, nrows, ptm)) {
-            if ((e = upl((void**)&A->pair_meta, ptm.data(), ptm.size() * 4)) != hipSuccess ||
-                (e = hipStreamSynchronize(s)) != hipSuccess) {
-                cleanup();
-                return fail(EIGSOL_E_HIP, std::string("eigsol_csr_create: pair tile upload: ") + hipGetErrorString(e));
-            }
-            A->pair_ntiles = (int32_t)(ptm.size() / 4);
+        if (dtype == EIGSOL_F64 && nrows == ncols && xoff == 0 && !A->slice_gather && pair_eligible(SL, nrows))
             A->pair_ok = 1;
-        }
     }
     int rcb = build_bins(A, rowptr, col_use, val_use);
     if (rcb == EIGSOL_OK && !A->binned) rcb = build_col_blocks(A, rowptr, col_use, val_use);
@@ -2199,8 +2191,6 @@ static CsrArgs<S> make_args(const eigsol_csr* A, int64_t xlen) {
     a.cend = A->nchunks;
     a.cont = 0;
     a.pair_mode = 0;
-    a.pair_ntiles = A->pair_ntiles;
-    a.pair_meta = (const int4*)A->pair_meta;
     a.pair_part = nullptr;
     a.pair_blk = nullptr;
     return a;
@@ -2330,18 +2320,19 @@ static const void* pair_kernel_ptr(const eigsol_csr* A) {
 const void* csr_pair_kernel_ptr(const eigsol_csr* A) { return A->pair_ok ? pair_kernel_ptr(A) : nullptr; }
 
 int csr_pair_grid(eigsol_csr* A, int* grid) {
-    return resident_grid(A->ctx, pair_kernel_ptr(A), A->pair_ntiles, grid, kPairBlocksPerCU);
+    return resident_grid(A->ctx, pair_kernel_ptr(A), (A->nslices + kWaves - 1) / kWaves, grid, kPairBlocksPerCU);
 }
 
-// One launch of a session on the pair carry: pair != 0 runs reference launches t and t + 1 (xin ->
-// out1 -> out2), else one single launch xin -> out1 of the slice kernel with the pair prologue.
-int csr_pair_launch(eigsol_csr* A, int64_t xlen, const void* xin, void* out1, void* out2, PowerCtl* ctl,
-                    void* part1, void* part2, void* blk1, void* blk2, void* trace, int parity, int grid, int pair) {
+// One launch of a session on the pair carry: pair != 0 runs reference launches t and t + 1 and
+// stores the second product only (xin -> out), else one single launch xin -> out of the slice
+// kernel with the pair prologue.
+int csr_pair_launch(eigsol_csr* A, int64_t xlen, const void* xin, void* out, PowerCtl* ctl, void* part1,
+                    void* part2, void* blk1, void* blk2, void* trace, int parity, int grid, int pair) {
     if (!A->pair_ok) return fail(EIGSOL_E_INVALID, "pair launch: the matrix is not eligible");
     CsrArgs<double> a = make_args<double>(A, xlen);
     // the slice kernel reads buf[parity ^ 1] and writes buf[parity]
-    a.buf0 = (double*)(parity ? const_cast<void*>(xin) : out1);
-    a.buf1 = (double*)(parity ? out1 : const_cast<void*>(xin));
+    a.buf0 = (double*)(parity ? const_cast<void*>(xin) : out);
+    a.buf1 = (double*)(parity ? out : const_cast<void*>(xin));
     a.ctl = ctl;
     a.rank_part = (const part4*)part1;
     a.nranks = 1;
@@ -2354,13 +2345,30 @@ int csr_pair_launch(eigsol_csr* A, int64_t xlen, const void* xin, void* out1, vo
     if (!pair) return launch_csr<double>(A, a, true, parity, grid, false);
     hipStream_t s = A->ctx->stream;
     const double* xi = (const double*)xin;
-    double* o1 = (double*)out1;
-    double* o2 = (double*)out2;
+    double* o = (double*)out;
     switch (A->slice_kb) {
-        case 4: hipLaunchKernelGGL((csr_pair_kernel<double, 4>), dim3(grid), dim3(kThreads), 0, s, a, parity, xi, o1, o2); break;
-        case 8: hipLaunchKernelGGL((csr_pair_kernel<double, 8>), dim3(grid), dim3(kThreads), 0, s, a, parity, xi, o1, o2); break;
-        case 12: hipLaunchKernelGGL((csr_pair_kernel<double, 12>), dim3(grid), dim3(kThreads), 0, s, a, parity, xi, o1, o2); break;
-        default: hipLaunchKernelGGL((csr_pair_kernel<double, 16>), dim3(grid), dim3(kThreads), 0, s, a, parity, xi, o1, o2); break;
+        case 4: hipLaunchKernelGGL((csr_pair_kernel<double, 4>), dim3(grid), dim3(kThreads), 0, s, a, parity, xi, o); break;
+        case 8: hipLaunchKernelGGL((csr_pair_kernel<double, 8>), dim3(grid), dim3(kThreads), 0, s, a, parity, xi, o); break;
+        case 12: hipLaunchKernelGGL((csr_pair_kernel<double, 12>), dim3(grid), dim3(kThreads), 0, s, a, parity, xi, o); break;
+        default: hipLaunchKernelGGL((csr_pair_kernel<double, 16>), dim3(grid), dim3(kThreads), 0, s, a, parity, xi, o); break;
+    }
+    EIGSOL_HIP(hipGetLastError());
+    return EIGSOL_OK;
+}
+
+// The first product of a pair launch again (eigsol_power_finish, a stop that returns it):
+// out = A (xin / nrm); touches neither the control block nor any partial.
+int csr_pair_first_product(eigsol_csr* A, int64_t xlen, const void* xin, void* out, double nrm, int grid) {
+    if (!A->pair_ok) return fail(EIGSOL_E_INVALID, "pair first product: the matrix is not eligible");
+    const CsrArgs<double> a = make_args<double>(A, xlen);
+    hipStream_t s = A->ctx->stream;
+    const double* xi = (const double*)xin;
+    double* o = (double*)out;
+    switch (A->slice_kb) {
+        case 4: hipLaunchKernelGGL((csr_pair_first_kernel<double, 4>), dim3(grid), dim3(kThreads), 0, s, a, xi, o, nrm); break;
+        case 8: hipLaunchKernelGGL((csr_pair_first_kernel<double, 8>), dim3(grid), dim3(kThreads), 0, s, a, xi, o, nrm); break;
+        case 12: hipLaunchKernelGGL((csr_pair_first_kernel<double, 12>), dim3(grid), dim3(kThreads), 0, s, a, xi, o, nrm); break;
+        default: hipLaunchKernelGGL((csr_pair_first_kernel<double, 16>), dim3(grid), dim3(kThreads), 0, s, a, xi, o, nrm); break;
     }
     EIGSOL_HIP(hipGetLastError());
     return EIGSOL_OK;

@@ -166,6 +166,7 @@ struct alignas(64) PowerCtl {
     int32_t fault;           // row-sharded peer exchange: a wait for a peer timed out (host raises)
     int32_t pad_;
     PowerCarry st[2];
+    double final_in_norm;    // pair path, final_parity 8 + b: x_final's iterate is A (B[(b + 2) % 3] / final_in_norm)
 };
 
 // Reference termination logic of powerMethodImpl (power_method.hpp:68-96) evaluated by the fused
@@ -316,11 +317,9 @@ struct eigsol_csr {
     uint8_t* slen = nullptr;       // device, per row (ragged slices)
     int32_t nseg = 1;              // stream segments (see kSliceSegShift): element offsets of each
     int64_t seg_val[16] = {0}, seg_c8[16] = {0}, seg_c32[16] = {0};
-    // pair path (csr_pair_kernel): eligible when square, f64, xoff == 0, every slice a window slice
-    // and every tile's span fits the kernel's LDS array; decided at upload
+    // pair path (csr_pair_kernel): eligible when square, f64, xoff == 0 and every slice a window
+    // slice whose window lies inside the rows; decided at upload
     int32_t pair_ok = 0;
-    int32_t pair_ntiles = 0;
-    int32_t* pair_meta = nullptr;  // device, 4 ints per tile
     // Row-sharded (multi-GPU) layout: this rank owns global rows [row_begin, row_begin + nrows);
     // local columns are [own rows | ghosts grouped by owner rank, ascending global index].
     int dist = 0;

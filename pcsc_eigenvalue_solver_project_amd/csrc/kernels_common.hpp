@@ -396,18 +396,26 @@ __device__ __forceinline__ T ldg_stream(const T* base, uint32_t i) {
 // them, part2 = {||w2||^2, (s w1)^H w2}, so
 //     rho_{t+1} = (s w1)^H w2 / (s^2 ||w1||^2),   ||y_{t+1}|| = ||w2|| / (s ||w1||)
 // and the next input is w2 / ||w2||.  y_v lives in vector buffer (v + 3) % 3 (x0 in buffer 2), so
-// a pair never overwrites an iterate a stopping decision can still return.
+// a pair never overwrites an iterate a stopping decision can still return.  A pair launch stores
+// only w2: w1, the iterate y_v of its first half, stays on chip.  Only a stop at launch v + 2 returns
+// it, and that stop is decided in a prologue, before the deciding launch writes anything, so the
+// pair's input y_{v-1} is still intact in buffer (v + 2) % 3: the prologue then records
+// final_parity = kPairRecompute + (v + 3) % 3 and final_in_norm = ||y_{v-1}||, and
+// eigsol_power_finish recomputes y_v = A (y_{v-1} / ||y_{v-1}||) into y_v's own buffer with the
+// single launch's slice code (bitwise what a single launch stores).
 //
 // This prologue serves every launch of a session on the pair path, single launches included
 // (this_pair == false), so the two kinds interleave freely on one carry.  It first applies
 // power_decide to the deferred launch of a preceding pair (carry.pad != 0), then to its own first
 // launch, in order: ctl->launches, ntrace, the trace, iters and converged take the single path's
 // values, and work past the stopping launch is discarded.  A decision that stops at launch v
-// returns y_{v-2} / ||y_{v-2}||: final_parity = kPairCode + (v + 1) % 3.
+// returns y_{v-2} / ||y_{v-2}||: final_parity = kPairCode + (v + 1) % 3, or kPairRecompute +
+// (v + 1) % 3 when y_{v-2} is the unstored first half of the preceding pair.
 // Carry: rho = the last Rayleigh quotient, nrm = the norm of this launch's input buffer,
 // t = the last reference launch this launch runs, pad = 0 (single) or kPairFlag | (e + 1024).
 constexpr int32_t kPairFlag = 1 << 16;
 constexpr int32_t kPairCode = 4;
+constexpr int32_t kPairRecompute = 8;
 template <class S>
 __device__ __forceinline__ void pair_prologue(PowerCtl* ctl, const part4* part1, const part4* part2,
                                               int parity, S* trace, Prologue* out, bool this_pair) {
@@ -422,10 +430,12 @@ __device__ __forceinline__ void pair_prologue(PowerCtl* ctl, const part4* part1,
             const part4 p1 = part1[0];
             bool fin = false;
             int32_t fcode = 0;
-            double fnorm = 0.0, rho_re = in.rho_re, rho_im = in.rho_im, nrm = 0.0, g = 0.0;
+            double fnorm = 0.0, fin_norm = 0.0, rho_re = in.rho_re, rho_im = in.rho_im, nrm = 0.0, g = 0.0;
             PowerDecision d;
             // one reference launch v: the single path's bookkeeping
-            auto apply = [&](int32_t v, double nv, double rr, double ri, double pre, double pim, double fn) {
+            // first_half: y_{v-2} is the preceding pair's w1, computed from an input of norm in.nrm
+            auto apply = [&](int32_t v, double nv, double rr, double ri, double pre, double pim, double fn,
+                             bool first_half) {
                 d = power_decide(v, ctl->max_iter, ctl->tol, cplx_, nv, rr, ri, pre, pim);
                 if (w0) {
                     ctl->launches = v + 1;
@@ -434,20 +444,21 @@ __device__ __forceinline__ void pair_prologue(PowerCtl* ctl, const part4* part1,
                 }
                 if (d.done) {
                     fin = true;
-                    fcode = kPairCode + (v + 1) % 3;
+                    fcode = (first_half ? kPairRecompute : kPairCode) + (v + 1) % 3;
                     fnorm = fn;
+                    fin_norm = first_half ? in.nrm : 0.0;
                 }
             };
             if (!(in.pad & kPairFlag)) {
                 nrm = sqrt(p1.a);
-                apply(t, nrm, p1.b, p1.c, in.rho_re, in.rho_im, in.nrm);
+                apply(t, nrm, p1.b, p1.c, in.rho_re, in.rho_im, in.nrm, false);
                 rho_re = p1.b;
                 rho_im = p1.c;
                 g = nrm;
             } else {
                 const double sp = ldexp(1.0, -((in.pad & 0xffff) - 1024));
                 const double n1 = sqrt(p1.a);
-                apply(t - 1, n1, p1.b, p1.c, in.rho_re, in.rho_im, in.nrm);
+                apply(t - 1, n1, p1.b, p1.c, in.rho_re, in.rho_im, in.nrm, false);
                 if (!fin) {   // n1 > 0 here
                     const part4 p2 = part2[0];
                     const double den = sp * sp * p1.a;
@@ -455,7 +466,7 @@ __device__ __forceinline__ void pair_prologue(PowerCtl* ctl, const part4* part1,
                     rho_im = p2.c / den;
                     nrm = sqrt(p2.a);
                     g = nrm / (sp * n1);
-                    apply(t, g, rho_re, rho_im, p1.b, p1.c, n1);
+                    apply(t, g, rho_re, rho_im, p1.b, p1.c, n1, true);
                 }
             }
             // growth of the last product from a unit input: the scale of this launch's second product
@@ -476,6 +487,7 @@ __device__ __forceinline__ void pair_prologue(PowerCtl* ctl, const part4* part1,
                     ctl->converged = d.converged ? 1 : 0;
                     ctl->final_parity = fcode;
                     ctl->final_norm = fnorm;
+                    ctl->final_in_norm = fin_norm;
                     __hip_atomic_store(&ctl->done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }

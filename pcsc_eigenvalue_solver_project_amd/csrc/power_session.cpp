@@ -27,8 +27,9 @@ int csr_power_launch(eigsol_csr* A, int64_t xlen, void* buf0, void* buf1, PowerC
                      int parity, int grid, const dev::PeerArgs* peer = nullptr, int part = -1);
 const void* csr_pair_kernel_ptr(const eigsol_csr* A);
 int csr_pair_grid(eigsol_csr* A, int* grid);
-int csr_pair_launch(eigsol_csr* A, int64_t xlen, const void* xin, void* out1, void* out2, PowerCtl* ctl,
-                    void* part1, void* part2, void* blk1, void* blk2, void* trace, int parity, int grid, int pair);
+int csr_pair_launch(eigsol_csr* A, int64_t xlen, const void* xin, void* out, PowerCtl* ctl, void* part1,
+                    void* part2, void* blk1, void* blk2, void* trace, int parity, int grid, int pair);
+int csr_pair_first_product(eigsol_csr* A, int64_t xlen, const void* xin, void* out, double nrm, int grid);
 int64_t csr_bin_split_row(const eigsol_csr* A);
 int dist_exchange_part(eigsol_csr* A, void* y, void* rank_part, int part, const std::vector<int64_t>& split,
                        hipStream_t comm_st, hipEvent_t* ev);
@@ -556,12 +557,13 @@ int eigsol_power_step(eigsol_power* s, int32_t nsteps) {
     if (s->trivial) return EIGSOL_OK;
     EIGSOL_HIP(hipSetDevice(s->ctx->device));
     if (s->pair) {
-        // nsteps reference launches: pair launches, single ones for launch 0 and an odd remainder
+        // nsteps reference launches: pair launches, single ones for launch 0 and an odd remainder;
+        // a pair leaves the buffer of its first product, buf[vt % 3], as it is
         for (int32_t left = nsteps; left > 0;) {
             const int two = (s->vt > 0 && left >= 2) ? 1 : 0;
-            EIGSOL_TRY(csr_pair_launch(s->csr, s->nbuf, s->buf[(s->vt + 2) % 3], s->buf[s->vt % 3],
-                                       s->buf[(s->vt + 1) % 3], s->ctl, s->rank_part, s->pair_part, s->blk_part,
-                                       s->pair_blk, s->trace, s->parity, two ? s->pair_grid : s->grid, two));
+            EIGSOL_TRY(csr_pair_launch(s->csr, s->nbuf, s->buf[(s->vt + 2) % 3], s->buf[(s->vt + two) % 3], s->ctl,
+                                       s->rank_part, s->pair_part, s->blk_part, s->pair_blk, s->trace, s->parity,
+                                       two ? s->pair_grid : s->grid, two));
             s->parity ^= 1;
             s->vt += 1 + two;
             s->launches += 1 + two;
@@ -615,7 +617,7 @@ int eigsol_power_finish(eigsol_power* s, void* lambda_out, void* x_out, int x_ou
     const size_t sb = scalar_bytes(s->dtype);
     double lam[2] = {0.0, 0.0};
     int parity = 1;
-    double fnorm = 0.0;
+    double fnorm = 0.0, fin_norm = 0.0;
     int32_t it = 0, conv = 0;
     if (s->trivial) {
         // maxIterations <= 0: lambda = 0, x = normalised x0, 0 iterations (power_method.hpp:61-68)
@@ -655,6 +657,7 @@ int eigsol_power_finish(eigsol_power* s, void* lambda_out, void* x_out, int x_ou
         lam[1] = s->host_ctl->lam_im;
         parity = s->host_ctl->final_parity;
         fnorm = s->host_ctl->final_norm;
+        fin_norm = s->host_ctl->final_in_norm;
         it = s->host_ctl->iters;
         conv = s->host_ctl->converged;
     }
@@ -663,13 +666,17 @@ int eigsol_power_finish(eigsol_power* s, void* lambda_out, void* x_out, int x_ou
     if (converged) *converged = conv;
     if (x_out) {
         // final_parity 2 + j: solve j of a multi-solve launch (the triangular factor's buffer aux[j])
-        // pair path: final_parity 4 + b names buf[b] (pair_prologue); scratch below: the next buffer
+        // pair path: final_parity 4 + b names buf[b] (pair_prologue); scratch below: the next buffer.
+        // 8 + b: buf[b] is the unstored first product of the last pair, computed here from that
+        // pair's input buf[(b + 2) % 3] (which stays as it is, so a second finish() does the same)
         void* src;
         void* scratch;
         if (s->pair) {
-            const int b = parity >= 4 ? parity - 4 : parity;
+            const int b = parity >= 8 ? parity - 8 : parity >= 4 ? parity - 4 : parity;
             src = s->buf[b];
             scratch = s->buf[(b + 1) % 3];
+            if (parity >= 8)
+                EIGSOL_TRY(csr_pair_first_product(s->csr, s->nbuf, s->buf[(b + 2) % 3], src, fin_norm, s->grid));
         } else {
             src = parity >= 2 ? shift_aux(s->shift, parity - 2)
                               : static_cast<char*>(s->buf[parity]) + (size_t)s->xoff * sb;
