@@ -637,6 +637,19 @@ struct SylvesterResult {
     bool converged = false;              // both Schur factorisations converged (the solvers throw otherwise)
 };
 
+// Principal matrix square root (sqrtm, solvers.hpp; no counterpart in the reference): through the Schur form on
+// the device (eigsol_sqrtm_dense).  A real S keeps a real root wherever one exists; where A has a negative real
+// eigenvalue the root is complex and comes in Xc, as schur returns a real or a complex form by its scalar type.
+template <typename S>
+struct SqrtmResult {
+    using Complex = std::complex<decltype(std::abs(S{}))>;   // the complex type over S's real type
+    DenseMatrix<S> X;                    // n x n: the root in A's scalar type; empty where isComplex
+    DenseMatrix<Complex> Xc;             // n x n: the root of a real A with a negative real eigenvalue; else empty
+    bool isComplex = false;              // the root is in Xc
+    int perturbed = 0;                   // blocks of the triangular stage in which a pivot below smin was replaced by smin
+    bool converged = false;              // the Schur factorisation converged (sqrtm throws otherwise)
+};
+
 // Thin singular value decomposition (svd / svdvals, solvers.hpp; no counterpart in the reference): block
 // one-sided Jacobi on the device (eigsol_svd_dense).
 struct SvdOptions {

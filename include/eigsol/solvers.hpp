@@ -821,6 +821,57 @@ SylvesterResult<S> solve_lyapunov(const DenseMatrix<S>& A, const DenseMatrix<S>&
     return detail::sylvester_run<S>("solve_lyapunov", A, nullptr, Q, opts);
 }
 
+// ------------------------------------------------------------------------------------------- sqrtm
+// Principal square root X of a square A (eigsol_sqrtm_dense; scipy.linalg.sqrtm): X X = A with every eigenvalue of
+// X in the closed right half plane, through the Schur form on the device: schur's pipeline, the blocked
+// triangular square root, the back-transformation on the matrix cores.  A real A keeps a real root wherever one
+// exists.  Where the library reports a negative real eigenvalue (no real root), the call runs again on A cast to
+// complex and the root comes in Xc with isComplex set; that costs a second Schur factorisation.
+// opts.maxIterations bounds the sweeps; opts.vectors and opts.sort are not read.  Throws if the factorisation does
+// not converge.  float and std::complex<float> run on their fp64 promotion; the root is rounded back.
+template <ScalarConcept S>
+SqrtmResult<S> sqrtm(const DenseMatrix<S>& A, const SchurOptions& opts = {}) {
+    const std::int64_t n = A.rows();
+    if (n != A.cols()) throw std::runtime_error("sqrtm: matrix must be square");
+    if (n == 0) throw std::runtime_error("sqrtm: matrix has zero size");
+    if constexpr (PromotedScalar<S>) {
+        using D = device_scalar_t<S>;
+        SqrtmResult<D> rd = sqrtm<D>(detail::convert_dense<D>(A), opts);
+        SqrtmResult<S> rs;
+        if (rd.isComplex) rs.Xc = detail::convert_dense<typename SqrtmResult<S>::Complex>(rd.Xc);
+        else rs.X = detail::convert_dense<S>(rd.X);
+        rs.isComplex = rd.isComplex;
+        rs.perturbed = rd.perturbed;
+        rs.converged = rd.converged;
+        return rs;
+    } else if constexpr (!DeviceScalar<S>) {
+        throw std::runtime_error("sqrtm: scalar type not supported by the device path (double, std::complex<double>)");
+    } else {
+        SqrtmResult<S> res;
+        eigsol_solver_options o{};
+        o.max_iterations = opts.maxIterations;
+        res.X = DenseMatrix<S>(n, n);
+        std::int32_t pert = 0, conv = 0, cx = 0;
+        detail::check(eigsol_sqrtm_dense(detail::ctx(), detail::dtype_of<S>(), n, A.data(), &o, res.X.data(), &pert, &conv, &cx), "sqrtm");
+        if (!conv) throw std::runtime_error("sqrtm: the Schur factorisation did not converge");
+        if constexpr (std::is_floating_point_v<S>) {
+            if (cx) {
+                using Z = typename SqrtmResult<S>::Complex;
+                SqrtmResult<Z> rc = sqrtm<Z>(detail::convert_dense<Z>(A), opts);
+                res.X = DenseMatrix<S>();
+                res.Xc = std::move(rc.X);
+                res.isComplex = true;
+                res.perturbed = rc.perturbed;
+                res.converged = rc.converged;
+                return res;
+            }
+        }
+        res.perturbed = pert;
+        res.converged = true;
+        return res;
+    }
+}
+
 // ------------------------------------------------------------------------------------------- svd
 // Thin singular value decomposition A = U diag(s) V^H of a dense m x n matrix (eigsol_svd_dense: block one-sided
 // Jacobi on the fp64 matrix cores).  S = double and std::complex<double>.  svdvals returns the bits of svd's s.

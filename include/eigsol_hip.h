@@ -759,6 +759,48 @@ int eigsol_lyapunov_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_c
                           const eigsol_solver_options* opts, void* X_out, int32_t* perturbed, int32_t* converged);
 int eigsol_sylvester_stage_times(eigsol_ctx* ctx, double* ms5);
 
+/* ---------------------------------------------------------------- principal matrix square root (dense)
+ * Through the Schur form on the device (csrc/sqrtm.hip).  The reference has no such solver; the routines
+ * correspond to scipy.linalg.sqrtm.  All matrices are column-major host arrays of EIGSOL_F64 or EIGSOL_C128.
+ *
+ * eigsol_trsqrt_dense: the triangular stage alone, U_out = T^(1/2), U^2 = T with every eigenvalue of U in the
+ * closed right half plane.  T (n x n) is upper triangular (C128) or real quasi-triangular (F64) whose 2 x 2
+ * diagonal blocks have complex eigenvalues (any such block, not only eigsol_schur_dense's standard form).  The
+ * host checks before the upload and fails with EIGSOL_E_INVALID on: a non-zero below the sub-diagonal, a
+ * non-zero complex sub-diagonal entry, two consecutive non-zero real sub-diagonal entries, a real 2 x 2 block
+ * with real eigenvalues, and a negative real 1 x 1 block (no real root: pass T as C128).  T is cut into the
+ * blocks of eigsol_trsyl_dense; one launch takes the root of every diagonal block (in LDS: the scalar and
+ * 2 x 2 roots, then the small Sylvester systems U_gg Y + Y U_hh = rhs along the super-diagonals), and each block
+ * super-diagonal is two launches: the sums over earlier blocks on the fp64 matrix cores and the block solves
+ * U_ii Y + Y U_jj = F_ij of eigsol_trsyl_dense.  No atomics: two calls give the same bits.  U is real for real
+ * T, the entrywise principal root for diagonal T (a complex entry on the negative real axis, with an imaginary
+ * part of either zero, goes to the positive imaginary axis), and T scaled by 4^e gives U scaled by 2^e exactly.
+ * A pivot below smin = max(eps max|U_gg|, 2^-1022 / eps) is replaced by smin; *perturbed counts the blocks in
+ * which that happened: 0 means the root was computed as posed, a positive value that T has a (nearly) repeated
+ * eigenvalue at 0 and U solves a nearby problem or does not exist.  There is no overflow scaling.
+ *
+ * eigsol_sqrtm_dense: X_out = A^(1/2) (n x n): A = Z T Z^H by the pipeline of eigsol_schur_dense, the triangular
+ * stage, X = Z U Z^H on the matrix cores; between the upload and the download everything stays on the device.
+ * A real A whose real Schur form has a negative 1 x 1 block has no real square root: the call then returns
+ * EIGSOL_OK with *needs_complex = 1 (*converged = 1, *perturbed = 0) and leaves X_out untouched; the caller
+ * passes A as EIGSOL_C128, which costs a second Schur factorisation.  A zero 1 x 1 block is not negative.
+ * *needs_complex = 0 otherwise.  EIGSOL_C128 storage of a matrix whose entries are all real (what such a caller
+ * sends): a diagonal entry of the complex T left of the imaginary axis whose imaginary part is at most
+ * n eps ||A||_F in modulus is a real eigenvalue up to the factorisation's backward error, and its imaginary part
+ * is set to +0, so that its root lies on the positive imaginary axis whatever sign the rounding left (what
+ * scipy.linalg.sqrtm returns through rsf2csf).  opts->max_iterations bounds the sweeps of the Schur factorisation (null opts:
+ * 1000); if it does not converge, *converged = 0, X_out is not written and the call returns EIGSOL_OK.
+ * Status: EIGSOL_E_INVALID (null pointers, negative order, unknown dtype, max_iterations < 1),
+ * EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD; an order above eigsol_schur_dense's), EIGSOL_E_SOLVER (a
+ * non-finite entry, found on the host before the upload).  n == 0: EIGSOL_OK, nothing written but the flags.
+ * Out of scope: funm, logm, expm, signm, non-principal roots, rsf2csf, a condition or error estimate.
+ * eigsol_sqrtm_stage_times: the context's last eigsol_sqrtm_dense call by stream events, 4 doubles in ms: the
+ * Schur factorisation, the triangular stage, the transform with the copy to the host, and their sum. */
+int eigsol_trsqrt_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* T_colmajor, void* U_out, int32_t* perturbed);
+int eigsol_sqrtm_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor, const eigsol_solver_options* opts,
+                       void* X_out, int32_t* perturbed, int32_t* converged, int32_t* needs_complex);
+int eigsol_sqrtm_stage_times(eigsol_ctx* ctx, double* ms4);
+
 /* ---------------------------------------------------------------- singular value decomposition (dense)
  * eigsol_svd_dense: the thin singular value decomposition A = U diag(s) V^H of a real (EIGSOL_F64) or
  * complex (EIGSOL_C128) dense m x n matrix, k = min(m, n) (csrc/svd.hip).  The reference has no such solver.

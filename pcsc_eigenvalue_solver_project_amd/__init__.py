@@ -31,6 +31,7 @@ __all__ = [
     "cholesky", "geigh_stage_times", "EigResult", "eig", "eig_stage_times", "SchurResult", "schur", "schur_stage_times",
     "OrdSchurResult", "ordschur", "ordschur_stats",
     "SylvesterResult", "solve_sylvester", "solve_continuous_lyapunov", "trsyl", "sylvester_stage_times",
+    "SqrtmResult", "sqrtm", "trsqrt", "sqrtm_stage_times",
     "SvdResult", "svd", "svdvals", "svd_stage_times",
     "SvdsOptions", "SvdsResult", "svds", "svds_stage_times", "dense_mv_h",
 ]
@@ -1198,6 +1199,72 @@ def sylvester_stage_times(ctx: Context) -> dict:
     ms = (C.c_double * 5)()
     call("eigsol_sylvester_stage_times", ctx.handle, ms)
     return {k: ms[i] * 1e-3 for i, k in enumerate(("schur_a", "schur_b", "transform_in", "triangular", "transform_out"))}
+
+
+@dataclass
+class SqrtmResult:
+    """Result of :func:`sqrtm`: ``X`` n x n, Fortran order, float64 for a real A without negative real
+    eigenvalues, else complex128; ``perturbed`` the number of blocks of the triangular stage in which a pivot
+    below ``smin`` was replaced by it (0: the root was computed as posed; positive: A has a (nearly) repeated
+    eigenvalue at 0 and X solves a nearby problem, or no root exists); ``converged`` the Schur factorisation
+    converged (a result is only returned when it did)."""
+
+    X: np.ndarray
+    perturbed: int
+    converged: bool
+
+
+def _sqrtm_operand(A, who: str) -> np.ndarray:
+    A = _square_dense(A, who)
+    if not np.issubdtype(A.dtype, np.inexact):
+        A = A.astype(np.float64)
+    return np.asfortranarray(A)
+
+
+def sqrtm(ctx: Context, A, opts: SolverOptions = SolverOptions()) -> SqrtmResult:
+    """Principal square root of a square matrix on the device (``eigsol_sqrtm_dense``; SciPy's ``sqrtm``):
+    ``X @ X = A`` with every eigenvalue of X in the closed right half plane.  A = Z T Z^H by :func:`schur`'s
+    pipeline, U = T^(1/2) by the blocked recurrence of :func:`trsqrt`, X = Z U Z^H on the matrix cores.  A real
+    A keeps a real X whenever one exists (no negative real eigenvalue); otherwise the library reports that the
+    real Schur form has a negative 1 x 1 block, and the call runs again on A cast to complex128 and returns a
+    complex X, which costs a second Schur factorisation; a negative real eigenvalue's root is then on the positive
+    imaginary axis, as SciPy's.  float32 and long double input is refused with
+    ``EIGSOL_E_UNSUPPORTED``, a matrix that is not square with status 1, a non-finite entry with
+    ``EIGSOL_E_SOLVER``.  Raises :class:`EigSolError` if the Schur factorisation does not converge."""
+    A = _sqrtm_operand(A, "sqrtm")
+    n = A.shape[0]
+    o = SolverOptionsC(int(opts.maxIterations), float(opts.tolerance))
+    while True:
+        X = np.zeros((n, n), dtype=A.dtype, order="F")
+        pert, conv, cx = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        call("eigsol_sqrtm_dense", ctx.handle, _dtype_code(A.dtype), n, _ptr(A), C.byref(o), _ptr(X), C.byref(pert),
+             C.byref(conv), C.byref(cx))
+        if not conv.value:
+            raise EigSolError(EIGSOL_E_SOLVER, "sqrtm: the Schur factorisation did not converge")
+        if not cx.value:
+            return SqrtmResult(X, int(pert.value), True)
+        A = np.asfortranarray(A, dtype=np.complex128)
+
+
+def trsqrt(ctx: Context, T):
+    """The triangular stage alone (``eigsol_trsqrt_dense``): ``U @ U = T`` for an upper triangular (complex) or
+    real quasi-triangular T whose 2 x 2 diagonal blocks have complex eigenvalues.  Anything else, and a real T
+    with a negative 1 x 1 block (pass it as complex), raises ``EIGSOL_E_INVALID``.  Returns ``(U, perturbed)``, U
+    in Fortran order and T's dtype."""
+    T = _sqrtm_operand(T, "trsqrt")
+    n = T.shape[0]
+    U = np.zeros((n, n), dtype=T.dtype, order="F")
+    pert = C.c_int32(0)
+    call("eigsol_trsqrt_dense", ctx.handle, _dtype_code(T.dtype), n, _ptr(T), _ptr(U), C.byref(pert))
+    return U, int(pert.value)
+
+
+def sqrtm_stage_times(ctx: Context) -> dict:
+    """The context's last ``eigsol_sqrtm_dense`` call by stream events, in seconds (a :func:`sqrtm` that went
+    to complex: its second call)."""
+    ms = (C.c_double * 4)()
+    call("eigsol_sqrtm_stage_times", ctx.handle, ms)
+    return {k: ms[i] * 1e-3 for i, k in enumerate(("schur", "triangular", "transform", "total"))}
 
 
 @dataclass

@@ -191,6 +191,9 @@ SIGNATURES = {
     "eigsol_sylvester_dense": [_vp, C.c_int, _i64, _i64, _vp, _vp, _vp, C.POINTER(SolverOptionsC), _vp, _pi32, _pi32],
     "eigsol_lyapunov_dense": [_vp, C.c_int, _i64, _vp, _vp, C.POINTER(SolverOptionsC), _vp, _pi32, _pi32],
     "eigsol_sylvester_stage_times": [_vp, _pd],
+    "eigsol_trsqrt_dense": [_vp, C.c_int, _i64, _vp, _vp, _pi32],
+    "eigsol_sqrtm_dense": [_vp, C.c_int, _i64, _vp, C.POINTER(SolverOptionsC), _vp, _pi32, _pi32, _pi32],
+    "eigsol_sqrtm_stage_times": [_vp, _pd],
     "eigsol_svd_dense": [_vp, C.c_int, _i64, _i64, _vp, C.POINTER(SvdOptionsC), _pd, _vp, _vp, _pi32, _pi64],
     "eigsol_svd_stage_times": [_vp, _pd],
     "eigsol_csr_adjoint": [_vp, _ppv],

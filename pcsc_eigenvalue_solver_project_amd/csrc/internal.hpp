@@ -284,6 +284,9 @@ struct eigsol_ctx {
     // (eigsol_sylvester_stage_times): Schur of A, Schur of B, transforms in, triangular stage, transforms
     // out with the copies
     double sylvester_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    // the last eigsol_sqrtm_dense call's stages in ms (eigsol_sqrtm_stage_times): the Schur factorisation, the
+    // triangular square root, the transform with the copy to the host, and their sum
+    double sqrtm_ms[4] = {0.0, 0.0, 0.0, 0.0};
     // the last eigsol_ordschur_dense / eigsol_schur_sorted_dense call's reordering (eigsol_ordschur_stats): its
     // time in ms by stream events; rounds that did work, windows that did work, swaps
     double ordschur_ms = 0.0;
