@@ -650,6 +650,15 @@ struct SqrtmResult {
     bool converged = false;              // the Schur factorisation converged (sqrtm throws otherwise)
 };
 
+// Matrix exponential (expm, solvers.hpp; no counterpart in the reference): Higham's 2005 scaling and squaring on
+// the device (eigsol_expm_dense).
+template <typename S>
+struct ExpmResult {
+    DenseMatrix<S> X;                    // n x n: exp(A) in A's scalar type
+    int degree = 0;                      // of the Pade approximant: 3, 5, 7, 9 or 13
+    int squarings = 0;
+};
+
 // Thin singular value decomposition (svd / svdvals, solvers.hpp; no counterpart in the reference): block
 // one-sided Jacobi on the device (eigsol_svd_dense).
 struct SvdOptions {

@@ -872,6 +872,57 @@ SqrtmResult<S> sqrtm(const DenseMatrix<S>& A, const SchurOptions& opts = {}) {
     }
 }
 
+// ------------------------------------------------------------------------------------ solve, expm
+// X with A X = B by LU with partial pivoting on the device (eigsol_solve_dense): the blocked factorisation of the
+// shifted solves and a blocked substitution with all columns of B.  Throws where a pivot is exactly zero; the
+// message names its column.  float and std::complex<float> run on their fp64 promotion; X is rounded back.
+template <ScalarConcept S>
+DenseMatrix<S> solve(const DenseMatrix<S>& A, const DenseMatrix<S>& B) {
+    const std::int64_t n = A.rows();
+    if (n != A.cols()) throw std::runtime_error("solve: matrix must be square");
+    if (B.rows() != n) throw std::runtime_error("solve: size mismatch between A and B");
+    if (n == 0 || B.cols() == 0) throw std::runtime_error("solve: matrix has zero size");
+    if constexpr (PromotedScalar<S>) {
+        using D = device_scalar_t<S>;
+        return detail::convert_dense<S>(solve<D>(detail::convert_dense<D>(A), detail::convert_dense<D>(B)));
+    } else if constexpr (!DeviceScalar<S>) {
+        throw std::runtime_error("solve: scalar type not supported by the device path (double, std::complex<double>)");
+    } else {
+        DenseMatrix<S> X(n, B.cols());
+        detail::check(eigsol_solve_dense(detail::ctx(), detail::dtype_of<S>(), n, B.cols(), A.data(), B.data(), X.data()), "solve");
+        return X;
+    }
+}
+
+// exp(A) of a square A (eigsol_expm_dense; scipy.linalg.expm): Higham's 2005 scaling and squaring on the device.
+// The 1-norm decides the degree of the Pade approximant and the squarings; a real A gives a real X.  Throws on a
+// non-finite entry and on a result that overflows.  float and std::complex<float> run on their fp64 promotion.
+template <ScalarConcept S>
+ExpmResult<S> expm(const DenseMatrix<S>& A) {
+    const std::int64_t n = A.rows();
+    if (n != A.cols()) throw std::runtime_error("expm: matrix must be square");
+    if (n == 0) throw std::runtime_error("expm: matrix has zero size");
+    if constexpr (PromotedScalar<S>) {
+        using D = device_scalar_t<S>;
+        ExpmResult<D> rd = expm<D>(detail::convert_dense<D>(A));
+        ExpmResult<S> rs;
+        rs.X = detail::convert_dense<S>(rd.X);
+        rs.degree = rd.degree;
+        rs.squarings = rd.squarings;
+        return rs;
+    } else if constexpr (!DeviceScalar<S>) {
+        throw std::runtime_error("expm: scalar type not supported by the device path (double, std::complex<double>)");
+    } else {
+        ExpmResult<S> res;
+        res.X = DenseMatrix<S>(n, n);
+        std::int32_t m = 0, s = 0;
+        detail::check(eigsol_expm_dense(detail::ctx(), detail::dtype_of<S>(), n, A.data(), res.X.data(), &m, &s), "expm");
+        res.degree = m;
+        res.squarings = s;
+        return res;
+    }
+}
+
 // ------------------------------------------------------------------------------------------- svd
 // Thin singular value decomposition A = U diag(s) V^H of a dense m x n matrix (eigsol_svd_dense: block one-sided
 // Jacobi on the fp64 matrix cores).  S = double and std::complex<double>.  svdvals returns the bits of svd's s.

@@ -801,6 +801,45 @@ int eigsol_sqrtm_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colm
                        void* X_out, int32_t* perturbed, int32_t* converged, int32_t* needs_complex);
 int eigsol_sqrtm_stage_times(eigsol_ctx* ctx, double* ms4);
 
+/* ---------------------------------------------------------------- product, solve and exponential (dense)
+ * Column-major host arrays of EIGSOL_F64 or EIGSOL_C128 in and out; the reference has no such routines.
+ *
+ * eigsol_gemm_dense: C_out (m x n) = A (m x k) B (k x n) on the fp64 matrix cores (csrc/gemm.hip): a workgroup
+ * owns a 128 x 128 (complex: 128 x 64) tile of C, stages slices of 16 of K through LDS and keeps the tile in
+ * registers; C is written once.  One lane sums an entry in ascending k: no split-K, no atomics, two calls
+ * give the same bits.  Any m, n, k >= 0 (k == 0: C = 0).
+ *
+ * eigsol_solve_dense: X_out (n x nrhs) = A^-1 B by LU with partial pivoting, the blocked factorisation of the
+ * shifted solves (csrc/dense_lu.hip), and a blocked substitution with all right-hand sides: the diagonal blocks by
+ * substitution, the rest on the matrix cores.  X_out may be B.  An exactly zero pivot fails with EIGSOL_E_SOLVER and
+ * the message names its column (0-based); nothing is written then.  No condition estimate, no refinement.
+ *
+ * eigsol_expm_dense: X_out = exp(A) (n x n) by Higham's 2005 scaling and squaring (csrc/expm.hip;
+ * scipy.linalg.expm without the 2009 norm estimates): alpha = ||A||_1 on the device, eigsol_expm_plan's degree and
+ * squarings (returned in *degree and *squarings, either may be null), the [m/m] Pade approximant of 2^-s A by
+ * three to six products and one LU solve with n right-hand sides, s squarings.  Real A gives real X; A = 0
+ * gives exactly I.  A strongly non-normal A is scaled by its norm alone and may be squared more often than SciPy
+ * squares it.  EIGSOL_E_SOLVER: a non-finite entry (found on the host before the upload), a 1-norm that
+ * overflows, or a non-finite result ("result overflows"; X_out then holds it).
+ * eigsol_expm_stage_times: the context's last eigsol_expm_dense call by stream events, 6 doubles in ms: the
+ * upload with the norm, the Pade products, the LU factorisation, the substitution, the squarings, and the whole
+ * call: these five, the pass that looks for a non-finite entry and the copy to the host.
+ * eigsol_expm_plan (host only): the first degree m of 3, 5, 7, 9, 13 with alpha <= theta_m (Higham's Table 2.3)
+ * and s = 0; beyond theta_13 m = 13 and s is the smallest integer with alpha 2^-s <= theta_13.  EIGSOL_E_INVALID
+ * for a negative or non-finite alpha.
+ * Status of the three device entries: EIGSOL_E_INVALID (null pointers, a negative size, unknown dtype),
+ * EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD; an order whose matrix does not fit).  An empty result: EIGSOL_OK.
+ * Out of scope: logm, funm, signm, the action of exp(A) on a vector, Frechet derivatives, condition estimates,
+ * batches. */
+int eigsol_gemm_dense(eigsol_ctx* ctx, int dtype, int64_t m, int64_t n, int64_t k, const void* A_colmajor,
+                      const void* B_colmajor, void* C_out);
+int eigsol_solve_dense(eigsol_ctx* ctx, int dtype, int64_t n, int64_t nrhs, const void* A_colmajor, const void* B_colmajor,
+                       void* X_out);
+int eigsol_expm_plan(double alpha, int32_t* degree, int32_t* squarings);
+int eigsol_expm_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor, void* X_out, int32_t* degree,
+                      int32_t* squarings);
+int eigsol_expm_stage_times(eigsol_ctx* ctx, double* ms6);
+
 /* ---------------------------------------------------------------- singular value decomposition (dense)
  * eigsol_svd_dense: the thin singular value decomposition A = U diag(s) V^H of a real (EIGSOL_F64) or
  * complex (EIGSOL_C128) dense m x n matrix, k = min(m, n) (csrc/svd.hip).  The reference has no such solver.

@@ -32,6 +32,7 @@ __all__ = [
     "OrdSchurResult", "ordschur", "ordschur_stats",
     "SylvesterResult", "solve_sylvester", "solve_continuous_lyapunov", "trsyl", "sylvester_stage_times",
     "SqrtmResult", "sqrtm", "trsqrt", "sqrtm_stage_times",
+    "matmul", "solve", "ExpmResult", "expm", "expm_stage_times", "expm_plan",
     "SvdResult", "svd", "svdvals", "svd_stage_times",
     "SvdsOptions", "SvdsResult", "svds", "svds_stage_times", "dense_mv_h",
 ]
@@ -1265,6 +1266,87 @@ def sqrtm_stage_times(ctx: Context) -> dict:
     ms = (C.c_double * 4)()
     call("eigsol_sqrtm_stage_times", ctx.handle, ms)
     return {k: ms[i] * 1e-3 for i, k in enumerate(("schur", "triangular", "transform", "total"))}
+
+
+# ------------------------------------------------------------------------------- matmul, solve, expm
+def _dense_operand(A) -> np.ndarray:
+    A = np.asarray(A)
+    if not np.issubdtype(A.dtype, np.inexact):
+        A = A.astype(np.float64)
+    return A
+
+
+def matmul(ctx: Context, A, B) -> np.ndarray:
+    """``A @ B`` for host matrices on the fp64 matrix cores (``eigsol_gemm_dense``; float64 / complex128, a real
+    and a complex operand give a complex product): an LDS-tiled MFMA kernel that sums every entry in ascending k,
+    so two calls return the same bits.  The result is in Fortran order."""
+    A, B = _dense_operand(A), _dense_operand(B)
+    if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[0]:
+        raise EigSolError(EIGSOL_E_SIZE_MISMATCH, f"matmul: shapes {A.shape} and {B.shape} do not match")
+    dt = np.result_type(A.dtype, B.dtype)
+    code = _dtype_code(dt)
+    Af, Bf = np.asfortranarray(A, dtype=dt), np.asfortranarray(B, dtype=dt)
+    m, k = A.shape
+    n = B.shape[1]
+    Cm = np.zeros((m, n), dtype=dt, order="F")
+    call("eigsol_gemm_dense", ctx.handle, code, m, n, k, _ptr(Af), _ptr(Bf), _ptr(Cm))
+    return Cm
+
+
+def solve(ctx: Context, A, B) -> np.ndarray:
+    """``X`` with ``A @ X = B`` by LU with partial pivoting on the device (``eigsol_solve_dense``; float64 /
+    complex128).  ``B`` is a vector (n) or a matrix (n x nrhs); X has its shape, a matrix in Fortran order.  Raises
+    ``EigSolError`` (``EIGSOL_E_SOLVER``) naming the column of the first exactly zero pivot when A is singular."""
+    A = _dense_operand(_square_dense(A, "solve"))
+    B = _dense_operand(B)
+    n = A.shape[0]
+    if B.ndim not in (1, 2) or B.shape[0] != n:
+        raise EigSolError(EIGSOL_E_SIZE_MISMATCH, f"solve: B has shape {B.shape}, A has order {n}")
+    dt = np.result_type(A.dtype, B.dtype)
+    code = _dtype_code(dt)
+    Af = np.asfortranarray(A, dtype=dt)
+    X = np.array(B.reshape(n, -1), dtype=dt, order="F")
+    call("eigsol_solve_dense", ctx.handle, code, n, X.shape[1], _ptr(Af), _ptr(X), _ptr(X))
+    return X[:, 0].copy() if B.ndim == 1 else X
+
+
+@dataclass
+class ExpmResult:
+    """Result of :func:`expm`: ``X`` n x n, Fortran order, float64 for real input and else complex128; ``degree``
+    of the Pade approximant (3, 5, 7, 9 or 13) and the number of ``squarings``."""
+
+    X: np.ndarray
+    degree: int
+    squarings: int
+
+
+def expm(ctx: Context, A) -> ExpmResult:
+    """Matrix exponential on the device (``eigsol_expm_dense``; SciPy's ``expm``) by Higham's 2005 scaling and
+    squaring: the 1-norm decides the degree and the squarings (:func:`expm_plan`), the Pade approximant of the
+    scaled matrix takes three to six products on the matrix cores and one LU solve, then the squarings.  Integer
+    input is cast to float64; float32 and long double input is refused with ``EIGSOL_E_UNSUPPORTED``, a matrix that
+    is not square with status 1, a non-finite entry and a result that overflows with ``EIGSOL_E_SOLVER``."""
+    A = np.asfortranarray(_dense_operand(_square_dense(A, "expm")))
+    n = A.shape[0]
+    X = np.zeros((n, n), dtype=A.dtype, order="F")
+    m, s = C.c_int32(0), C.c_int32(0)
+    call("eigsol_expm_dense", ctx.handle, _dtype_code(A.dtype), n, _ptr(A), _ptr(X), C.byref(m), C.byref(s))
+    return ExpmResult(X, int(m.value), int(s.value))
+
+
+def expm_stage_times(ctx: Context) -> dict:
+    """The context's last ``eigsol_expm_dense`` call by stream events, in seconds."""
+    ms = (C.c_double * 6)()
+    call("eigsol_expm_stage_times", ctx.handle, ms)
+    return {k: ms[i] * 1e-3 for i, k in enumerate(("norm", "pade", "factor", "substitution", "squarings", "total"))}
+
+
+def expm_plan(alpha: float):
+    """Host only (``eigsol_expm_plan``): ``(degree, squarings)`` that :func:`expm` uses for a matrix of 1-norm
+    ``alpha``."""
+    m, s = C.c_int32(0), C.c_int32(0)
+    call("eigsol_expm_plan", float(alpha), C.byref(m), C.byref(s))
+    return int(m.value), int(s.value)
 
 
 @dataclass

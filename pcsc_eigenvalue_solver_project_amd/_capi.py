@@ -194,6 +194,11 @@ SIGNATURES = {
     "eigsol_trsqrt_dense": [_vp, C.c_int, _i64, _vp, _vp, _pi32],
     "eigsol_sqrtm_dense": [_vp, C.c_int, _i64, _vp, C.POINTER(SolverOptionsC), _vp, _pi32, _pi32, _pi32],
     "eigsol_sqrtm_stage_times": [_vp, _pd],
+    "eigsol_gemm_dense": [_vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _vp],
+    "eigsol_solve_dense": [_vp, C.c_int, _i64, _i64, _vp, _vp, _vp],
+    "eigsol_expm_plan": [C.c_double, _pi32, _pi32],
+    "eigsol_expm_dense": [_vp, C.c_int, _i64, _vp, _vp, _pi32, _pi32],
+    "eigsol_expm_stage_times": [_vp, _pd],
     "eigsol_svd_dense": [_vp, C.c_int, _i64, _i64, _vp, C.POINTER(SvdOptionsC), _pd, _vp, _vp, _pi32, _pi64],
     "eigsol_svd_stage_times": [_vp, _pd],
     "eigsol_csr_adjoint": [_vp, _ppv],

@@ -15,6 +15,8 @@
 #include <string>
 #include <vector>
 
+#include "dense_lu.hpp"
+#include "gemm.hpp"
 #include "mfma_rankk.hpp"
 #include "scratch.hpp"
 #include "shift_factor.hpp"
@@ -124,6 +126,64 @@ __global__ __launch_bounds__(256) void lu_trsm_kernel(S* a, int64_t n, int64_t k
         if (j < kb) {   // kb < NB only for the last panel
 #pragma unroll
             for (int i = j + 1; i < NB; ++i) x[i] = sub(x[i], mul(l11[i + j * NB], x[j]));
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i)
+        if (i < kb) col[i] = x[i];
+}
+
+// ------------------------------------------------------------------ matrix right-hand sides (dense_getrs)
+// all n interchanges (rows k <-> piv[k], k ascending) on the n x nrhs matrix B; one thread per column
+template <class S>
+__global__ __launch_bounds__(256) void getrs_laswp_kernel(S* B, int64_t ldb, int64_t nrhs, int64_t n, const int32_t* piv) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= nrhs) return;
+    S* col = B + c * ldb;
+    for (int64_t r = 0; r < n; ++r) {
+        const int64_t p = piv[r];
+        if (p != r) {
+            const S t = col[r];
+            col[r] = col[p];
+            col[p] = t;
+        }
+    }
+}
+
+// B_k <- T^-1 B_k for the kb rows of B from k0: T the factor's diagonal block at k0 (LDS), its unit lower
+// triangle (kUpper = false) or its upper triangle (kUpper = true); one thread per column of B, by substitution
+// in the column order of lu_trsm_kernel: backward stable whatever the block holds
+template <class S, int NB, bool kUpper>
+__global__ __launch_bounds__(256) void getrs_trsm_kernel(const S* lu, int64_t n, int64_t k0, int kb, S* B, int64_t ldb,
+                                                         int64_t nrhs) {
+    __shared__ S t[NB * NB];
+    for (int e = threadIdx.x; e < kb * kb; e += 256) {
+        const int i = e % kb, j = e / kb;
+        t[i + j * NB] = lu[(k0 + i) + (k0 + j) * n];
+    }
+    __syncthreads();
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= nrhs) return;
+    S* col = B + c * ldb + k0;
+    S x[NB];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) x[i] = i < kb ? col[i] : s_zero<S>();
+    if constexpr (!kUpper) {
+#pragma unroll
+        for (int j = 0; j < NB - 1; ++j) {
+            if (j < kb) {   // kb < NB only for the last block row
+#pragma unroll
+                for (int i = j + 1; i < NB; ++i) x[i] = sub(x[i], mul(t[i + j * NB], x[j]));
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = NB - 1; j >= 0; --j) {
+            if (j < kb) {
+                x[j] = sdiv(x[j], t[j + j * NB]);
+#pragma unroll
+                for (int i = 0; i < j; ++i) x[i] = sub(x[i], mul(t[i + j * NB], x[j]));
+            }
         }
     }
 #pragma unroll
@@ -922,17 +982,7 @@ static int64_t kDenseSingleMax() {
 constexpr double kDenseBlockCondMax = 1e6;
 
 template <class S>
-static int dense_lu_factor(const ShiftFactor* f, DenseFactor& d, bool from_sparse) {
-    hipStream_t st = f->ctx->stream;
-    const int64_t n = f->n;
-    S* a = static_cast<S*>(d.lu);
-    DevBuf pivots;
-    EIGSOL_TRY(pivots.alloc(n * sizeof(int32_t)));
-    int32_t* piv = pivots.as<int32_t>();
-    EIGSOL_HIP(hipMalloc(&d.zero_pivot, sizeof(int32_t)));
-    EIGSOL_HIP(hipMemsetAsync(d.zero_pivot, 0xff, sizeof(int32_t), st));
-    hipLaunchKernelGGL((dev::shift_diag_kernel<S>), dim3((n + 255) / 256), dim3(256), 0, st, a, n,
-                       make_sigma<S>(f->sig_re, f->sig_im));
+void dense_getrf(hipStream_t st, S* a, int64_t n, int32_t* piv, int32_t* zero_pivot) {
     // right-looking blocked LU with partial pivoting (LAPACK getrf order): per panel of NB columns,
     // column-by-column pivoting and rank-1 updates inside the panel, the panel's interchanges on
     // the other columns, U12 = L11^-1 A12, and A22 -= L21 U12 on the fp64 matrix cores
@@ -941,8 +991,7 @@ static int dense_lu_factor(const ShiftFactor* f, DenseFactor& d, bool from_spars
         const int kb = (int)std::min<int64_t>(NB, n - k0);
         const int64_t c1 = k0 + kb;
         for (int64_t k = k0; k < c1; ++k) {
-            hipLaunchKernelGGL((dev::lu_pivot_kernel<S>), dim3(1), dim3(1024), 0, st, a, n, k, k0, c1, piv,
-                               d.zero_pivot);
+            hipLaunchKernelGGL((dev::lu_pivot_kernel<S>), dim3(1), dim3(1024), 0, st, a, n, k, k0, c1, piv, zero_pivot);
             const int64_t m = n - k - 1, w = c1 - k - 1;
             if (m > 0 && w > 0)
                 hipLaunchKernelGGL((dev::lu_update_kernel<S>), dim3((m * w + 255) / 256), dim3(256), 0, st, a, n, k, c1);
@@ -956,6 +1005,21 @@ static int dense_lu_factor(const ShiftFactor* f, DenseFactor& d, bool from_spars
                                   a + c1 + c1 * n, n);
         }
     }
+}
+
+template <class S>
+static int dense_lu_factor(const ShiftFactor* f, DenseFactor& d, bool from_sparse) {
+    hipStream_t st = f->ctx->stream;
+    const int64_t n = f->n;
+    S* a = static_cast<S*>(d.lu);
+    DevBuf pivots;
+    EIGSOL_TRY(pivots.alloc(n * sizeof(int32_t)));
+    int32_t* piv = pivots.as<int32_t>();
+    EIGSOL_HIP(hipMalloc(&d.zero_pivot, sizeof(int32_t)));
+    EIGSOL_HIP(hipMemsetAsync(d.zero_pivot, 0xff, sizeof(int32_t), st));
+    hipLaunchKernelGGL((dev::shift_diag_kernel<S>), dim3((n + 255) / 256), dim3(256), 0, st, a, n,
+                       make_sigma<S>(f->sig_re, f->sig_im));
+    dense_getrf<S>(st, a, n, piv, d.zero_pivot);
     EIGSOL_HIP(hipGetLastError());
     std::vector<int32_t> hp(n);
     int32_t zp = -1;
@@ -1134,4 +1198,74 @@ int dense_launch(ShiftFactor* f, bool iter, const void* b, void* y, const ShiftI
     return by_dtype(f->dtype, [&](auto tag) { return dense_launch_t<decltype(tag)>(f, iter, b, y, it); });
 }
 
+// ------------------------------------------------------------------ matrix right-hand sides
+// The diagonal blocks are solved by substitution and not multiplied by their inverses (see dense_lu_factor on
+// dense_trsv2_kernel: partial pivoting bounds |l_ij|, not inv(L_kk)), so the solve is backward stable whatever
+// the factor holds.  2 ceil(n / NB) - 1 rank-NB updates on the matrix cores carry the n^2 nrhs flops.
+template <class S>
+void dense_getrs(hipStream_t st, const S* lu, int64_t n, const int32_t* piv, S* B, int64_t ldb, int64_t nrhs) {
+    constexpr int NB = dev::RankKMax<S>::value;
+    if (n <= 0 || nrhs <= 0) return;
+    const dim3 cols((unsigned)((nrhs + 255) / 256));
+    hipLaunchKernelGGL((dev::getrs_laswp_kernel<S>), cols, dim3(256), 0, st, B, ldb, nrhs, n, piv);
+    for (int64_t k0 = 0; k0 < n; k0 += NB) {   // L Y = P B
+        const int kb = (int)std::min<int64_t>(NB, n - k0);
+        const int64_t c1 = k0 + kb;
+        hipLaunchKernelGGL((dev::getrs_trsm_kernel<S, NB, false>), cols, dim3(256), 0, st, lu, n, k0, kb, B, ldb, nrhs);
+        if (n - c1 > 0) rankk_update<S, true>(st, (int)(n - c1), (int)nrhs, kb, -1.0, lu + c1 + k0 * n, n, B + k0, ldb, B + c1, ldb);
+    }
+    for (int64_t k0 = ((n - 1) / NB) * NB; k0 >= 0; k0 -= NB) {   // U X = Y
+        const int kb = (int)std::min<int64_t>(NB, n - k0);
+        hipLaunchKernelGGL((dev::getrs_trsm_kernel<S, NB, true>), cols, dim3(256), 0, st, lu, n, k0, kb, B, ldb, nrhs);
+        if (k0 > 0) rankk_update<S, true>(st, (int)k0, (int)nrhs, kb, -1.0, lu + k0 * n, n, B + k0, ldb, B, ldb);
+    }
+}
+
+template void dense_getrf<double>(hipStream_t, double*, int64_t, int32_t*, int32_t*);
+template void dense_getrf<cplx>(hipStream_t, cplx*, int64_t, int32_t*, int32_t*);
+template void dense_getrs<double>(hipStream_t, const double*, int64_t, const int32_t*, double*, int64_t, int64_t);
+template void dense_getrs<cplx>(hipStream_t, const cplx*, int64_t, const int32_t*, cplx*, int64_t, int64_t);
+
+namespace {
+
+template <class S>
+int solve_host(eigsol_ctx* ctx, int64_t n, int64_t nrhs, const void* A_host, const void* B_host, void* X_out) {
+    hipStream_t st = ctx->stream;
+    DevBuf dA, dB, dpiv, dzp;
+    EIGSOL_TRY(dA.alloc((size_t)n * n * sizeof(S)));
+    EIGSOL_TRY(dB.alloc((size_t)n * nrhs * sizeof(S)));
+    EIGSOL_TRY(dpiv.alloc((size_t)n * sizeof(int32_t)));
+    EIGSOL_TRY(dzp.alloc(sizeof(int32_t)));
+    EIGSOL_HIP(hipMemcpyAsync(dA.p, A_host, (size_t)n * n * sizeof(S), hipMemcpyHostToDevice, st));
+    EIGSOL_HIP(hipMemcpyAsync(dB.p, B_host, (size_t)n * nrhs * sizeof(S), hipMemcpyHostToDevice, st));
+    EIGSOL_HIP(hipMemsetAsync(dzp.p, 0xff, sizeof(int32_t), st));
+    dense_getrf<S>(st, dA.as<S>(), n, dpiv.as<int32_t>(), dzp.as<int32_t>());
+    EIGSOL_HIP(hipGetLastError());
+    int32_t zp = -1;
+    EIGSOL_HIP(hipMemcpyAsync(&zp, dzp.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    EIGSOL_HIP(hipStreamSynchronize(st));
+    if (zp >= 0)
+        return fail(EIGSOL_E_SOLVER, "eigsol_solve_dense: the matrix is singular: the pivot of column " + std::to_string(zp) + " is zero");
+    dense_getrs<S>(st, dA.as<S>(), n, dpiv.as<int32_t>(), dB.as<S>(), n, nrhs);
+    EIGSOL_HIP(hipGetLastError());
+    EIGSOL_HIP(hipMemcpyAsync(X_out, dB.p, (size_t)n * nrhs * sizeof(S), hipMemcpyDeviceToHost, st));
+    EIGSOL_HIP(hipStreamSynchronize(st));
+    return EIGSOL_OK;
+}
+
+}  // namespace
 }  // namespace eigsol
+
+using namespace eigsol;
+
+extern "C" int eigsol_solve_dense(eigsol_ctx* ctx, int dtype, int64_t n, int64_t nrhs, const void* A_colmajor,
+                                  const void* B_colmajor, void* X_out) {
+    const char* who = "eigsol_solve_dense";
+    if (n < 0 || nrhs < 0) return fail(EIGSOL_E_INVALID, std::string(who) + ": negative size");
+    if (!ctx) return fail(EIGSOL_E_INVALID, std::string(who) + ": null context");
+    EIGSOL_TRY(dense_fn_check(who, ctx, dtype, std::max(n, nrhs)));
+    if (n == 0 || nrhs == 0) return EIGSOL_OK;
+    if (!A_colmajor || !B_colmajor || !X_out) return fail(EIGSOL_E_INVALID, std::string(who) + ": null pointer");
+    return dtype == EIGSOL_C128 ? solve_host<cplx>(ctx, n, nrhs, A_colmajor, B_colmajor, X_out)
+                                : solve_host<double>(ctx, n, nrhs, A_colmajor, B_colmajor, X_out);
+}

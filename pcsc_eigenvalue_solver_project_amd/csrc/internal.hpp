@@ -287,6 +287,10 @@ struct eigsol_ctx {
     // the last eigsol_sqrtm_dense call's stages in ms (eigsol_sqrtm_stage_times): the Schur factorisation, the
     // triangular square root, the transform with the copy to the host, and their sum
     double sqrtm_ms[4] = {0.0, 0.0, 0.0, 0.0};
+    // the last eigsol_expm_dense call's stages in ms (eigsol_expm_stage_times): the upload with the norm, the Pade
+    // products, the LU factorisation, the substitution, the squarings, and the whole call (these five, the
+    // finiteness pass and the copy to the host)
+    double expm_ms[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     // the last eigsol_ordschur_dense / eigsol_schur_sorted_dense call's reordering (eigsol_ordschur_stats): its
     // time in ms by stream events; rounds that did work, windows that did work, swaps
     double ordschur_ms = 0.0;
