@@ -650,6 +650,21 @@ struct SqrtmResult {
     bool converged = false;              // the Schur factorisation converged (sqrtm throws otherwise)
 };
 
+// Principal matrix logarithm (logm, solvers.hpp; no counterpart in the reference): inverse scaling and squaring on
+// the Schur form on the device (eigsol_logm_dense).  A real S keeps a real logarithm wherever one exists; where A
+// has a negative real eigenvalue the logarithm is complex and comes in Xc, as in SqrtmResult.
+template <typename S>
+struct LogmResult {
+    using Complex = std::complex<decltype(std::abs(S{}))>;   // the complex type over S's real type
+    DenseMatrix<S> X;                    // n x n: the logarithm in A's scalar type; empty where isComplex
+    DenseMatrix<Complex> Xc;             // n x n: the logarithm of a real A with a negative real eigenvalue; else empty
+    bool isComplex = false;              // the logarithm is in Xc
+    int roots = 0;                       // square roots taken of the triangular factor
+    int degree = 0;                      // of the Pade approximant, 1 to 7; 0 where A is the identity
+    int perturbed = 0;                   // the sum of the root stages' counts (SqrtmResult::perturbed)
+    bool converged = false;              // the Schur factorisation converged (logm throws otherwise)
+};
+
 // Matrix exponential (expm, solvers.hpp; no counterpart in the reference): Higham's 2005 scaling and squaring on
 // the device (eigsol_expm_dense).
 template <typename S>

@@ -872,6 +872,65 @@ SqrtmResult<S> sqrtm(const DenseMatrix<S>& A, const SchurOptions& opts = {}) {
     }
 }
 
+// ------------------------------------------------------------------------------------------- logm
+// Principal logarithm X of a square A (eigsol_logm_dense; scipy.linalg.logm): exp(X) = A with the imaginary part of
+// every eigenvalue of X in (-pi, pi], through the Schur form on the device: schur's pipeline, the inverse scaling
+// and squaring logarithm of the triangular factor, the back-transformation on the matrix cores.  A real A keeps a
+// real logarithm wherever one exists.  Where the library reports a negative real eigenvalue, the call runs again on A
+// cast to complex and the logarithm comes in Xc with isComplex set; that costs a second Schur factorisation.
+// opts.maxIterations bounds the sweeps; opts.vectors and opts.sort are not read.  Throws if the factorisation does
+// not converge or A is singular.  float and std::complex<float> run on their fp64 promotion; X is rounded back.
+template <ScalarConcept S>
+LogmResult<S> logm(const DenseMatrix<S>& A, const SchurOptions& opts = {}) {
+    const std::int64_t n = A.rows();
+    if (n != A.cols()) throw std::runtime_error("logm: matrix must be square");
+    if (n == 0) throw std::runtime_error("logm: matrix has zero size");
+    if constexpr (PromotedScalar<S>) {
+        using D = device_scalar_t<S>;
+        LogmResult<D> rd = logm<D>(detail::convert_dense<D>(A), opts);
+        LogmResult<S> rs;
+        if (rd.isComplex) rs.Xc = detail::convert_dense<typename LogmResult<S>::Complex>(rd.Xc);
+        else rs.X = detail::convert_dense<S>(rd.X);
+        rs.isComplex = rd.isComplex;
+        rs.roots = rd.roots;
+        rs.degree = rd.degree;
+        rs.perturbed = rd.perturbed;
+        rs.converged = rd.converged;
+        return rs;
+    } else if constexpr (!DeviceScalar<S>) {
+        throw std::runtime_error("logm: scalar type not supported by the device path (double, std::complex<double>)");
+    } else {
+        LogmResult<S> res;
+        eigsol_solver_options o{};
+        o.max_iterations = opts.maxIterations;
+        res.X = DenseMatrix<S>(n, n);
+        std::int32_t roots = 0, degree = 0, pert = 0, conv = 0, cx = 0;
+        detail::check(eigsol_logm_dense(detail::ctx(), detail::dtype_of<S>(), n, A.data(), &o, res.X.data(), &roots, &degree, &pert,
+                                        &conv, &cx),
+                      "logm");
+        if (!conv) throw std::runtime_error("logm: the Schur factorisation did not converge");
+        if constexpr (std::is_floating_point_v<S>) {
+            if (cx) {
+                using Z = typename LogmResult<S>::Complex;
+                LogmResult<Z> rc = logm<Z>(detail::convert_dense<Z>(A), opts);
+                res.X = DenseMatrix<S>();
+                res.Xc = std::move(rc.X);
+                res.isComplex = true;
+                res.roots = rc.roots;
+                res.degree = rc.degree;
+                res.perturbed = rc.perturbed;
+                res.converged = rc.converged;
+                return res;
+            }
+        }
+        res.roots = roots;
+        res.degree = degree;
+        res.perturbed = pert;
+        res.converged = true;
+        return res;
+    }
+}
+
 // ------------------------------------------------------------------------------------ solve, expm
 // X with A X = B by LU with partial pivoting on the device (eigsol_solve_dense): the blocked factorisation of the
 // shifted solves and a blocked substitution with all columns of B.  Throws where a pivot is exactly zero; the

@@ -793,7 +793,7 @@ int eigsol_sylvester_stage_times(eigsol_ctx* ctx, double* ms5);
  * Status: EIGSOL_E_INVALID (null pointers, negative order, unknown dtype, max_iterations < 1),
  * EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD; an order above eigsol_schur_dense's), EIGSOL_E_SOLVER (a
  * non-finite entry, found on the host before the upload).  n == 0: EIGSOL_OK, nothing written but the flags.
- * Out of scope: funm, logm, expm, signm, non-principal roots, rsf2csf, a condition or error estimate.
+ * Out of scope: funm, signm, non-principal roots, rsf2csf, a condition or error estimate.
  * eigsol_sqrtm_stage_times: the context's last eigsol_sqrtm_dense call by stream events, 4 doubles in ms: the
  * Schur factorisation, the triangular stage, the transform with the copy to the host, and their sum. */
 int eigsol_trsqrt_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* T_colmajor, void* U_out, int32_t* perturbed);
@@ -829,7 +829,7 @@ int eigsol_sqrtm_stage_times(eigsol_ctx* ctx, double* ms4);
  * for a negative or non-finite alpha.
  * Status of the three device entries: EIGSOL_E_INVALID (null pointers, a negative size, unknown dtype),
  * EIGSOL_E_UNSUPPORTED (F32 / C64 / DD / CDD; an order whose matrix does not fit).  An empty result: EIGSOL_OK.
- * Out of scope: logm, funm, signm, the action of exp(A) on a vector, Frechet derivatives, condition estimates,
+ * Out of scope: funm, signm, the action of exp(A) on a vector, Frechet derivatives, condition estimates,
  * batches. */
 int eigsol_gemm_dense(eigsol_ctx* ctx, int dtype, int64_t m, int64_t n, int64_t k, const void* A_colmajor,
                       const void* B_colmajor, void* C_out);
@@ -839,6 +839,57 @@ int eigsol_expm_plan(double alpha, int32_t* degree, int32_t* squarings);
 int eigsol_expm_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor, void* X_out, int32_t* degree,
                       int32_t* squarings);
 int eigsol_expm_stage_times(eigsol_ctx* ctx, double* ms6);
+
+/* ---------------------------------------------------------------- principal matrix logarithm (dense)
+ * Through the Schur form on the device (csrc/logm.hip): the Schur-Pade inverse scaling and squaring method (Higham,
+ * Functions of Matrices, Alg. 11.9, with the bounds theta_1 .. theta_7 of Al-Mohy and Higham (2012) applied to the
+ * 1-norm).  The reference has no such solver; the routines correspond to scipy.linalg.logm.  All matrices are
+ * column-major host arrays of EIGSOL_F64 or EIGSOL_C128.
+ *
+ * eigsol_trlogm_dense: the triangular stage alone, L_out = log T, the principal logarithm: exp(L) = T and every
+ * eigenvalue of L has its imaginary part in (-pi, pi].  T as for eigsol_trsqrt_dense, with the same host checks
+ * (EIGSOL_E_INVALID: a non-zero below the sub-diagonal, a non-zero complex sub-diagonal entry, two consecutive
+ * non-zero real sub-diagonal entries, a real 2 x 2 block with real eigenvalues, a negative real 1 x 1 block: pass T
+ * as C128); a zero 1 x 1 diagonal block (T is singular) fails with EIGSOL_E_SOLVER and the message names its row
+ * (0-based).  The stage keeps T's three inner diagonals, takes square roots of T in place with the kernels of
+ * eigsol_trsqrt_dense, and after each forms R = T^(1/2^s) - I and ||R||_1 (one host wait of 8 bytes per root);
+ * eigsol_logm_plan decides from the norm whether to stop; more than 64 roots fail with EIGSOL_E_SOLVER.  Then the
+ * [m / m] Pade approximant of log(I + R) through its partial fractions sum_j alpha_j (I + beta_j R)^-1 R (alpha, beta:
+ * the m-point Gauss-Legendre rule on [0, 1]): the m block triangular systems are solved together, one launch that
+ * inverts the diagonal blocks I + beta_j R_ii (condition at most 1.81, as ||R||_1 <= 0.288) and one launch per block
+ * super-diagonal on the fp64 matrix cores, with no host wait between them (their scratch, m n^2 scalars, is allocated
+ * first); L = 2^s sum_j alpha_j X_j.  L's diagonal blocks are
+ * recomputed from T itself: log t for a 1 x 1 block (C128: ln|t| + i atan2(im, re), an imaginary part of -0.0
+ * counting as +0.0, so both zeros on the negative real axis give +i pi), ln|lambda| I + (atan2(mu, a) / mu)(B - a I)
+ * for a real 2 x 2 block with eigenvalues a +- i mu; and the super-diagonal entry between two 1 x 1 blocks by Al-Mohy
+ * and Higham's formula (2012, eq. 5.6).  L has exact zeros below the quasi-triangle, is real for real T, the
+ * entrywise principal logarithm for diagonal T, and exactly 0 with *roots = 0 and *degree = 0 for T = I.  No
+ * atomics: two calls give the same bits.  *roots, *degree (1 .. 7) and *perturbed (the sum of the root stages'
+ * counts, see eigsol_trsqrt_dense) may be null.
+ *
+ * eigsol_logm_dense: X_out = log A (n x n): A = Z T Z^H by the pipeline of eigsol_schur_dense, the triangular
+ * stage, X = Z L Z^H on the matrix cores.  A real A whose real Schur form has a negative 1 x 1 block has no real
+ * logarithm: the call then returns EIGSOL_OK with *needs_complex = 1 (*converged = 1) and leaves X_out untouched;
+ * the caller passes A as EIGSOL_C128, which costs a second Schur factorisation.  For EIGSOL_C128 storage of a matrix
+ * whose entries are all real, the real negative eigenvalues are put on the axis with imaginary part +0 as in
+ * eigsol_sqrtm_dense, so that their logarithms have imaginary part +pi (scipy.linalg.logm's branch).  A singular A
+ * (an exactly zero 1 x 1 block of T) fails with EIGSOL_E_SOLVER.  opts->max_iterations bounds the sweeps of the
+ * Schur factorisation (null opts: 1000); if it does not converge, *converged = 0, X_out is not written and the call
+ * returns EIGSOL_OK.  Status otherwise as eigsol_sqrtm_dense.  n == 0: EIGSOL_OK, nothing written but the flags.
+ * eigsol_logm_plan (host only): *degree for ||R||_1 = norm: 0 (another root) while norm > theta_7 = 0.288; else
+ * with j1 = min{m : norm <= theta_m} and j2 = min{m : norm / 2 <= theta_m}, j1 if j1 - j2 <= 1 or tried != 0 (the
+ * test was reached before), else 0.  EIGSOL_E_INVALID for a negative or non-finite norm.
+ * eigsol_logm_stage_times: the context's last eigsol_logm_dense call by stream events, 5 doubles in ms: the Schur
+ * factorisation, the root loop, the Pade stage, the transform with the copy to the host, and their sum.
+ * Out of scope: the alpha_p norm estimates of the 2012 algorithm, the cancellation-free recomputation of R's
+ * diagonal, degrees above 7, funm, signm and fractional powers, Frechet derivatives and condition estimates. */
+int eigsol_trlogm_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* T_colmajor, void* L_out, int32_t* roots,
+                        int32_t* degree, int32_t* perturbed);
+int eigsol_logm_dense(eigsol_ctx* ctx, int dtype, int64_t n, const void* A_colmajor, const eigsol_solver_options* opts,
+                      void* X_out, int32_t* roots, int32_t* degree, int32_t* perturbed, int32_t* converged,
+                      int32_t* needs_complex);
+int eigsol_logm_plan(double norm, int32_t tried, int32_t* degree);
+int eigsol_logm_stage_times(eigsol_ctx* ctx, double* ms5);
 
 /* ---------------------------------------------------------------- singular value decomposition (dense)
  * eigsol_svd_dense: the thin singular value decomposition A = U diag(s) V^H of a real (EIGSOL_F64) or

@@ -32,6 +32,7 @@ __all__ = [
     "OrdSchurResult", "ordschur", "ordschur_stats",
     "SylvesterResult", "solve_sylvester", "solve_continuous_lyapunov", "trsyl", "sylvester_stage_times",
     "SqrtmResult", "sqrtm", "trsqrt", "sqrtm_stage_times",
+    "LogmResult", "logm", "trlogm", "logm_stage_times", "logm_plan",
     "matmul", "solve", "ExpmResult", "expm", "expm_stage_times", "expm_plan",
     "SvdResult", "svd", "svdvals", "svd_stage_times",
     "SvdsOptions", "SvdsResult", "svds", "svds_stage_times", "dense_mv_h",
@@ -1266,6 +1267,76 @@ def sqrtm_stage_times(ctx: Context) -> dict:
     ms = (C.c_double * 4)()
     call("eigsol_sqrtm_stage_times", ctx.handle, ms)
     return {k: ms[i] * 1e-3 for i, k in enumerate(("schur", "triangular", "transform", "total"))}
+
+
+# ------------------------------------------------------------------------------- logm
+@dataclass
+class LogmResult:
+    """Result of :func:`logm`: ``X`` n x n, Fortran order, float64 for a real A without negative real eigenvalues,
+    else complex128; ``roots`` the number of square roots taken of the triangular factor and ``degree`` of the Pade
+    approximant (1 to 7; 0 where A is the identity); ``perturbed`` the sum of the root stages' counts (see
+    :class:`SqrtmResult`; 0: every root was computed as posed); ``converged`` the Schur factorisation converged (a
+    result is only returned when it did)."""
+
+    X: np.ndarray
+    roots: int
+    degree: int
+    perturbed: int
+    converged: bool
+
+
+def logm(ctx: Context, A, opts: SolverOptions = SolverOptions()) -> LogmResult:
+    """Principal logarithm of a square matrix on the device (``eigsol_logm_dense``; SciPy's ``logm``):
+    ``exp(X) = A`` with the imaginary part of every eigenvalue of X in (-pi, pi].  A = Z T Z^H by :func:`schur`'s
+    pipeline, L = log T by the inverse scaling and squaring of :func:`trlogm`, X = Z L Z^H on the matrix cores.  A
+    real A keeps a real X whenever one exists (no negative real eigenvalue); otherwise the call runs again on A cast
+    to complex128, which costs a second Schur factorisation, and a negative real eigenvalue's logarithm has
+    imaginary part +pi, as SciPy's.  A singular A (a zero on the diagonal of T) and a non-finite entry raise
+    :class:`EigSolError` with ``EIGSOL_E_SOLVER``; float32 and long double input is refused with
+    ``EIGSOL_E_UNSUPPORTED``, a matrix that is not square with status 1."""
+    A = _sqrtm_operand(A, "logm")
+    n = A.shape[0]
+    o = SolverOptionsC(int(opts.maxIterations), float(opts.tolerance))
+    while True:
+        X = np.zeros((n, n), dtype=A.dtype, order="F")
+        s, m, pert, conv, cx = (C.c_int32(0) for _ in range(5))
+        call("eigsol_logm_dense", ctx.handle, _dtype_code(A.dtype), n, _ptr(A), C.byref(o), _ptr(X), C.byref(s), C.byref(m),
+             C.byref(pert), C.byref(conv), C.byref(cx))
+        if not conv.value:
+            raise EigSolError(EIGSOL_E_SOLVER, "logm: the Schur factorisation did not converge")
+        if not cx.value:
+            return LogmResult(X, int(s.value), int(m.value), int(pert.value), True)
+        A = np.asfortranarray(A, dtype=np.complex128)
+
+
+def trlogm(ctx: Context, T):
+    """The triangular stage alone (``eigsol_trlogm_dense``): ``L = log T`` for an upper triangular (complex) or
+    real quasi-triangular T whose 2 x 2 diagonal blocks have complex eigenvalues.  Anything else, and a real T
+    with a negative 1 x 1 block (pass it as complex), raises ``EIGSOL_E_INVALID``; a zero diagonal entry raises
+    ``EIGSOL_E_SOLVER`` and names the row.  Returns ``(L, roots, degree, perturbed)``, L in Fortran order and T's
+    dtype."""
+    T = _sqrtm_operand(T, "trlogm")
+    n = T.shape[0]
+    L = np.zeros((n, n), dtype=T.dtype, order="F")
+    s, m, pert = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    call("eigsol_trlogm_dense", ctx.handle, _dtype_code(T.dtype), n, _ptr(T), _ptr(L), C.byref(s), C.byref(m), C.byref(pert))
+    return L, int(s.value), int(m.value), int(pert.value)
+
+
+def logm_stage_times(ctx: Context) -> dict:
+    """The context's last ``eigsol_logm_dense`` call by stream events, in seconds (a :func:`logm` that went to
+    complex: its second call)."""
+    ms = (C.c_double * 5)()
+    call("eigsol_logm_stage_times", ctx.handle, ms)
+    return {k: ms[i] * 1e-3 for i, k in enumerate(("schur", "roots", "pade", "transform", "total"))}
+
+
+def logm_plan(norm: float, tried: bool = False) -> int:
+    """Host only (``eigsol_logm_plan``): the Pade degree with which the root loop of :func:`logm` stops at
+    ||T^(1/2^s) - I||_1 = ``norm``, or 0: another root.  ``tried``: the loop has been below theta_7 before."""
+    m = C.c_int32(0)
+    call("eigsol_logm_plan", float(norm), 1 if tried else 0, C.byref(m))
+    return int(m.value)
 
 
 # ------------------------------------------------------------------------------- matmul, solve, expm

@@ -199,6 +199,10 @@ SIGNATURES = {
     "eigsol_expm_plan": [C.c_double, _pi32, _pi32],
     "eigsol_expm_dense": [_vp, C.c_int, _i64, _vp, _vp, _pi32, _pi32],
     "eigsol_expm_stage_times": [_vp, _pd],
+    "eigsol_logm_plan": [C.c_double, C.c_int32, _pi32],
+    "eigsol_trlogm_dense": [_vp, C.c_int, _i64, _vp, _vp, _pi32, _pi32, _pi32],
+    "eigsol_logm_dense": [_vp, C.c_int, _i64, _vp, C.POINTER(SolverOptionsC), _vp, _pi32, _pi32, _pi32, _pi32, _pi32],
+    "eigsol_logm_stage_times": [_vp, _pd],
     "eigsol_svd_dense": [_vp, C.c_int, _i64, _i64, _vp, C.POINTER(SvdOptionsC), _pd, _vp, _vp, _pi32, _pi64],
     "eigsol_svd_stage_times": [_vp, _pd],
     "eigsol_csr_adjoint": [_vp, _ppv],

@@ -291,6 +291,9 @@ struct eigsol_ctx {
     // products, the LU factorisation, the substitution, the squarings, and the whole call (these five, the
     // finiteness pass and the copy to the host)
     double expm_ms[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    // the last eigsol_logm_dense call's stages in ms (eigsol_logm_stage_times): the Schur factorisation, the root
+    // loop with its norms, the Pade stage, the transform with the copy to the host, and their sum
+    double logm_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     // the last eigsol_ordschur_dense / eigsol_schur_sorted_dense call's reordering (eigsol_ordschur_stats): its
     // time in ms by stream events; rounds that did work, windows that did work, swaps
     double ordschur_ms = 0.0;

@@ -44,6 +44,7 @@
 
 #include "schur.hpp"
 #include "small_sqrt.hpp"
+#include "sqrtm.hpp"
 #include "sylvester.hpp"
 
 namespace eigsol {
@@ -207,11 +208,9 @@ __global__ __launch_bounds__(256) void sqrtm_real_axis(cplx* T, int64_t n, doubl
 
 }  // namespace dev
 
-namespace {
-
 // U <- U^(1/2) in place for the (quasi-)triangular device matrix U (leading dimension n) with the starts rs,
 // stream-ordered, no host wait.  `work` receives the starts and the flags; *d_pert (device) the number of
-// perturbed blocks.
+// perturbed blocks.  Declared in sqrtm.hpp: logm.hip takes its roots with it.
 template <class S>
 int trsqrt_device(hipStream_t st, int64_t n, S* U, const std::vector<int>& rs, DevBuf& work, int* d_pert) {
     const int p = (int)rs.size() - 1;
@@ -233,6 +232,11 @@ int trsqrt_device(hipStream_t st, int64_t n, S* U, const std::vector<int>& rs, D
     EIGSOL_HIP(hipGetLastError());
     return EIGSOL_OK;
 }
+
+template int trsqrt_device<double>(hipStream_t, int64_t, double*, const std::vector<int>&, DevBuf&, int*);
+template int trsqrt_device<cplx>(hipStream_t, int64_t, cplx*, const std::vector<int>&, DevBuf&, int*);
+
+namespace {
 
 template <class S>
 int trsqrt_host(eigsol_ctx* ctx, int64_t n, const void* T_host, void* U_out, int32_t* perturbed) {
